@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — simulated Farkle games/sec on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5,6}] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input.  `--config` picks the BASELINE.json workload
 (default 2 = configs[1], the configuration the metric is quoted on):
@@ -19,9 +19,13 @@ reference's scaling table is likewise one command per worker count, run_tourname
 tallies locally and ONE int64 SUM reduce of the tally to rank 0 at the end of the job (RCCL over xGMI), inside the timed
 region, plays the role of OutcomeCounter.absorb (run_tournament.py:197-213).
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel (fk_play_kernel): the path is integer VALU work,
-so the bound is the vector-ALU issue roof, not HBM or MFMA; `cpu_baseline` is the CPU oracle (a C port of the
-reference's algorithm, test infrastructure) timed on the host's cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline fields (`value`,
+`ms_per_step`, ...).  `--dump-outputs DIR` writes what the last timed step returned (and the reduced tally) as DIR/<name>.npy.
+`--full` adds what takes work of its own after the timed steps: the conservation check of the reduced tally, `roofline`
+for the dominant kernel (fk_play_kernel; the path is integer VALU work, so the bound is the vector-ALU issue roof, not HBM
+or MFMA; the in-kernel clock stamps are on for its measured clock), `cpu_baseline`, the CPU oracle (a C port of the
+reference's algorithm, test infrastructure) timed on the host's cores on a bounded sample of the same workload and
+checked against the GPU, and, for config 2, the comparisons with the reference.
 """
 from __future__ import annotations
 
@@ -123,7 +127,8 @@ def _cpu_threads() -> int:
 
 # ---------------------------------------------------------------------------------------------------------------
 # workloads: every one exposes  local_shape, step(eng, index, rank, world) -> (local tally, games played by THIS rank),
-# games_per_step(world), verify(total, steps, world), sample(eng) -> (rows, k, games) for W, cpu_baseline(eng)
+# games_per_step(world), last_outputs (what the last step's engine calls returned), verify(total, steps, world),
+# sample(eng) -> (rows, k, games) for W, cpu_baseline(eng)
 # ---------------------------------------------------------------------------------------------------------------
 class Tournament:
     """BASELINE configs[1] / configs[2]: one (grid, k, root) cell, every rank plays its own shuffle range per step."""
@@ -148,6 +153,7 @@ class Tournament:
             nxt = (next_index * world + rank) * self.shuffles
             eng.hint_next(nxt, nxt + self.shuffles)
         res = eng.tournament(self.table, self.k, self.root, first, first + self.shuffles)
+        self.last_outputs = {"tally": res["tally"][0]}  # [S][26]: the per-strategy tally of the step's one batch
         return res["tally"][0], self.shuffles * self.gps, add_timing({}, eng.timing())
 
     def verify(self, tot: np.ndarray, games: int) -> None:
@@ -232,6 +238,7 @@ class KSweep:
                 out[i] = eng.tournament(self.table, k, self.root, lo, hi)["tally"][0]
                 games += (hi - lo) * (self.S // k)
                 add_timing(timing, {**eng.timing(), "per_k": {k: eng.timing()}})
+        self.last_outputs = {"tally": out}  # [len(ks)][S][26]: this rank's part of every k's tally
         return out, games, timing
 
     def verify(self, tot: np.ndarray, games: int) -> None:
@@ -332,8 +339,15 @@ class H2H:
         for b in range(rank, len(self.blocks), world):
             out[b] = [res[b][key] for key in ("games_attempted", "games_completed", "games_safety_limit", "wins_seat1", "wins_seat2")]
         self.last_attempts = np.array([r["games_attempted"] for r in res], dtype=np.int64)
+        self.last_results = res  # every block's result: every rank receives all of them
         timing = add_timing({}, eng.timing()) if len(range(rank, len(self.blocks), world)) else {}
         return out, int(out[:, 0].sum()), timing
+
+    @property
+    def last_outputs(self) -> dict:
+        """[blocks][5]: attempted, completed and safety-limit games, wins of seat 1 and of seat 2 of every block of the last step."""
+        keys = ("games_attempted", "games_completed", "games_safety_limit", "wins_seat1", "wins_seat2")
+        return {"blocks": np.array([[r[key] for key in keys] for r in self.last_results], dtype=np.int64)}
 
     def verify(self, tot: np.ndarray, games: int) -> None:
         assert (tot[:, 0] == tot[:, 1] + tot[:, 2]).all() and (tot[:, 1] == tot[:, 3] + tot[:, 4]).all()
@@ -474,8 +488,13 @@ def main() -> None:
     ap.add_argument("--config", type=int, default=2, choices=(2, 3, 4, 5, 6))
     ap.add_argument("--shuffles", type=int, default=0, help="configs 2/3: shuffles per rank per step (default: the BASELINE size)")
     ap.add_argument("--games", type=int, default=0, help="configs 4 / 6: games per k per step; config 5: completed games per pair")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the tally, measure W and the roofline (in-kernel clock stamps on) and time the CPU "
+                         "oracle; without it the run only times the steps and prints the headline fields")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU-oracle leg")
     ap.add_argument("--dump-tally", type=Path, default=None, help="rank 0 saves the reduced tally here (.npy; tests)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned (and the reduced tally) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {2: 20, 3: 2, 4: 1, 5: 1, 6: 1}[args.config]
@@ -552,11 +571,12 @@ def main() -> None:
     wl = make_workload(args)
     eng = make_engine(local_rank)
     info = eng.device_info()
-    try:  # every game-kernel workgroup stamps s_memtime / s_memrealtime at its first and last instruction (two scalar reads and one
-        # (FK_BENCH_CLOCK_STAMPS=0 turns them off: the A/B of profiles/r06_ab_clock_stamps.json — their cost inside the timed steps)
-        eng.set_option("clock_stamps", 0 if os.environ.get("FK_BENCH_CLOCK_STAMPS") == "0" else 1)  # 32-byte store per workgroup and launch): the clock the fractions below are also priced at
-    except Exception:
-        pass  # (the CPU test stub has no such option)
+    if args.full:
+        try:  # every game-kernel workgroup stamps s_memtime / s_memrealtime at its first and last instruction (two scalar reads and one
+            # (FK_BENCH_CLOCK_STAMPS=0 turns them off: the A/B of profiles/r06_ab_clock_stamps.json — their cost inside the timed steps)
+            eng.set_option("clock_stamps", 0 if os.environ.get("FK_BENCH_CLOCK_STAMPS") == "0" else 1)  # 32-byte store per workgroup and launch): the clock the fractions below are also priced at
+        except Exception:
+            pass  # (the CPU test stub has no such option)
     dev = torch.device("cuda", local_rank) if have_gpu else torch.device("cpu")
     red_dev = dev if data_group is not None else torch.device("cpu")  # where the tally reduction runs
 
@@ -681,138 +701,13 @@ def main() -> None:
 
     if rank == 0:
         tot = total.cpu().numpy()
-        wl.verify(tot, played if wl.config != 5 else total_games)
+        if args.full:
+            wl.verify(tot, played if wl.config != 5 else total_games)
         if args.dump_tally is not None:
             np.save(args.dump_tally, tot)
+        if args.dump_outputs is not None:
+            dump_outputs(args.dump_outputs, {**wl.last_outputs, "tally_sum": tot})
 
-        # live per-game work (R, T of SURVEY section 8d) from the rows of a launch of the same workload
-        rows, k_s, sample_desc = wl.sample(eng)
-        wpg = dict(rows) if isinstance(rows, dict) else work_per_game(rows, k_s)
-        del rows
-        wpg["sample"] = sample_desc
-        # dominant kernel: average launch duration and games per launch over the last engine call of every timed step
-        launches = max(int(t.get("play_launches", 0)), 1)
-        kernel_ms = t.get("play_ms", 0.0) / launches
-        games_per_launch = t.get("games", 0) / launches
-        kernel_games_per_s = games_per_launch / max(kernel_ms * 1e-3, 1e-12)
-        # VALU roof: CUs x 4 SIMD x 32 lanes/clk x clock (MI355X_MICROARCH.md: wave64 issues over 2 cycles on a SIMD-32)
-        peak_ops = info["compute_units"] * 4 * 32 * info["clock_mhz"] * 1e6
-        achieved_ops = kernel_games_per_s * wpg["ops_per_game"]
-        hbm_bpg = wl.hbm_bytes_per_game()
-        # HBM bytes per launch from the PMC passes of the same launch shape (rocprofv3 cannot run inside this process):
-        # profiles/r*_hbm_traffic.json carries the commit it was taken at; dropped when that is not an ancestor's kernel
-        def kernel_of(shape: dict, k_seats: int) -> str:
-            """fk_play_hc_kernel launches are recognisable by their LDS size: 16 bytes per seat and lane (+ the 12 656-byte table
-            image), or 32 with the cold records in LDS (csrc/fk_play_hc.h); everything else is fk_play_kernel."""
-            block, lds = shape.get("play_block"), shape.get("play_lds_bytes")
-            hc = bool(block) and lds in (block * 16 * k_seats, block * 16 * k_seats + 12656, block * 32 * k_seats)
-            return "fk_play_hc_kernel" if hc else "fk_play_kernel"
-
-        dominant = kernel_of(t, int(wl.k)) if isinstance(getattr(wl, "k", None), int) else "fk_play_kernel"  # (sweep / H2H lines: per_k / k = 2)
-        def traffic_for(kernel: str, k_seats: int | None = None):
-            """HBM bytes per launch of `kernel` from the newest PMC stamp of this workload (per player count for the sweep), or None
-            when the kernel sources have changed since it was taken."""
-            suffix = f"config{wl.config}" + (f"_k{k_seats}" if k_seats is not None else "")
-            for tpath in sorted((ROOT / "profiles").glob(f"r*_hbm_traffic_{suffix}.json"), reverse=True):
-                rec = json.loads(tpath.read_text())
-                if rec.get("kernel_source_sha256") == kernel_source_sha():
-                    return rec["kernels"].get(kernel, {}).get("hbm_bytes_corrected")
-                break
-            return None
-
-        def mix_for(kernel: str, shape: dict, k_seats: int, frac: float):
-            """Static instruction mix of the instance's roll loop priced with the two measured issue classes (tools/isa_mix.py ->
-            profiles/r*_isa_mix.json, valid while the kernel sources are the ones it was taken on): `ceiling_frac` is the fraction of the
-            NOMINAL peak a SIMD issuing this mix back to back would reach, `frac_of_mix_ceiling` = frac / that.  None when unknown."""
-            for mpath in sorted((ROOT / "profiles").glob("r*_isa_mix.json"), reverse=True):
-                doc = json.loads(mpath.read_text())
-                if doc.get("kernel_source_sha256") != kernel_source_sha():
-                    break
-                block, mixed = shape.get("play_block"), shape.get("play_mixed_flags")
-                hits = []
-                for name, rec in doc["instances"].items():
-                    a = [int(x) for x in name[name.index("<") + 1:-1].split(",")]
-                    if not name.startswith(kernel + "<") or a[0] != block:
-                        continue
-                    if kernel == "fk_play_kernel":  # <BLOCK, LEAN, WPE, MIXED, GS, BLK, KC>
-                        ok = a[1] == 1 and a[3] == mixed and a[4] == 0 and a[5] == (1 if wl.config == 5 else 0) and a[6] == (2 if k_seats == 2 else 0)
-                    else:  # <BLOCK, MIXED, LT, KI, WPE, PKR, CL, NS, CR, IL>: KI seats in registers (0 = the cold-in-LDS instance of k <= 4)
-                        ki = 0 if k_seats <= 4 else k_seats if k_seats <= 8 else 10 if k_seats <= 10 else 12
-                        ok = a[1] == mixed and a[3] == ki
-                    if ok:
-                        hits.append((name, rec))
-                if len(hits) == 1:
-                    name, rec = hits[0]
-                    return {"instance": name, "source": f"profiles/{mpath.name} (static mix of the roll loop; classes: profiles/r05_valu_issue_rates.txt)",
-                            **{key: rec[key] for key in ("valu_static", "full_rate", "half_rate", "mean_issue_cycles", "ceiling_frac")},
-                            "frac_of_mix_ceiling": frac / rec["ceiling_frac"]}
-                break
-            return None
-
-        traffic = traffic_for(dominant)
-        roofline = {
-            "bound": "valu", "kernel": dominant,
-            "achieved": achieved_ops / 1e12, "peak": peak_ops / 1e12, "unit": "Tlane-op/s (int32)", "frac": achieved_ops / peak_ops,
-            "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC, separate pass; null when the kernel sources changed since)",
-            "kernel_ms": kernel_ms, "games_per_launch": games_per_launch, "kernel_games_per_s": kernel_games_per_s, **wpg,
-            # ONE number, stated once: kernel_ms is the mean duration of the game kernel over the launches of the TIMED steps only (HIP
-            # events on the engine's stream).  A rocprofv3 --stats average of this command also counts the warm-up steps (clock still
-            # ramping), the statistics launch that measures W and the CPU-baseline parity launch: compare with its rows for the timed
-            # launches, not with its mean (round 5: 9.31 ms average over nine launches against 8.88 ms here for the same kernel).
-            "kernel_ms_is": "mean over the launches of the timed steps (HIP events); a rocprofv3 average of this command also includes warm-up, statistics and parity launches",
-            "kernel_ms_min": t.get("play_ms_min"), "kernel_ms_max": t.get("play_ms_max"), "timed_launches": t.get("play_launches"),
-            "hbm": {"achieved": kernel_games_per_s * hbm_bpg / 1e9, "peak": 8000.0, "unit": "GB/s",
-                    "frac": kernel_games_per_s * hbm_bpg / 8e12, "bytes_per_game": hbm_bpg},
-            # permutations: every launch (they run on the main stream, in front of the previous game kernel when pipelined);
-            # seat seeding: only the launches that were NOT seeded on the side stream behind the previous game kernel
-            "seed_kernel_ms": t.get("seed_ms", 0.0) / max(launches - int(t.get("prefetched_chunks", 0)), 1),
-            "perm_kernel_ms": t.get("perm_ms", 0.0) / max(launches, 1),
-            "launches_seeded_behind_the_previous_kernel": int(t.get("prefetched_chunks", 0)),
-            "launch": {k2: t.get(k2) for k2 in ("play_block", "play_grid", "play_lds_bytes", "play_mixed_flags")},
-        }
-        roofline["mix"] = mix_for(dominant, t, int(wl.k) if isinstance(getattr(wl, "k", None), int) else 2, roofline["frac"])
-
-        def with_clock(rec: dict, tt: dict) -> None:
-            """`frac` stays defined against the NOMINAL clock (as every round before); next to it the clock the game kernels
-            really held (in-kernel s_memtime / s_memrealtime, median over workgroups, mean over the timed launches) and the fraction of
-            the peak at THAT clock — the chip lowers its clock under load (MI355X_MICROARCH.md, DVFS give-back)."""
-            if tt.get("clock_n"):
-                mhz = tt["clock_sum"] / tt["clock_n"]
-                rec["clock_mhz_measured"] = mhz
-                rec["frac_at_measured_clock"] = rec["frac"] * info["clock_mhz"] / mhz
-            if tt.get("tail_n"):  # how long the last launch of a call took to drain behind its longest games
-                rec["launch_tail_ms"] = tt["tail_ms_sum"] / tt["tail_n"]
-
-        with_clock(roofline, t)
-        if "per_k" in wpg:  # config 4: one roofline record per player count (kernel time, W and fraction of each k's launches)
-            per_k = []
-            for k2, w2 in wpg.pop("per_k").items():
-                tk = (t.get("per_k") or {}).get(k2, {})
-                n_l = max(int(tk.get("play_launches", 0)), 1)
-                ms = tk.get("play_ms", 0.0) / n_l
-                gpl = tk.get("games", 0) / n_l
-                rate = gpl / max(ms * 1e-3, 1e-12)
-                per_k.append({"k": int(k2), "kernel": kernel_of(tk, int(k2)), "kernel_ms": ms,
-                              "games_per_launch": gpl, "kernel_games_per_s": rate, **w2,
-                              "frac": rate * w2["ops_per_game"] / peak_ops, "traffic": traffic_for(kernel_of(tk, int(k2)), int(k2)),
-                              "launch": {k3: tk.get(k3) for k3 in ("play_block", "play_grid", "play_lds_bytes", "play_mixed_flags")}})
-                per_k[-1]["mix"] = mix_for(per_k[-1]["kernel"], tk, int(k2), per_k[-1]["frac"])
-                with_clock(per_k[-1], tk)
-            roofline["per_k"] = per_k
-            # The line's headline record is ONE kernel's, whole: the player count furthest below its roofline (every field — kernel, time,
-            # games, W, achieved, frac, clock, traffic, launch, hbm — from that k's launches; round 4 mixed the mean fraction with the worst
-            # k's kernel fields).  The mean over the player counts stands beside it under its own name.
-            worst = min(per_k, key=lambda r: r["frac"])
-            roofline["frac_mean_over_k"] = float(np.mean([r["frac"] for r in per_k]))
-            hbm_k = 32 * worst["k"] + 2 * worst["k"] + 4
-            roofline.update({key: worst[key] for key in worst if key != "k"})
-            roofline.update({"kernel_note": f"slowest player count of the sweep: k = {worst['k']} (every headline field is that k's; mean over k in frac_mean_over_k)",
-                             "achieved": worst["frac"] * peak_ops / 1e12,
-                             "hbm": {"achieved": worst["kernel_games_per_s"] * hbm_k / 1e9, "peak": 8000.0, "unit": "GB/s",
-                                     "frac": worst["kernel_games_per_s"] * hbm_k / 8e12, "bytes_per_game": hbm_k}})
-        cpu = None
-        if not args.no_cpu_baseline and n_gpus == 1:  # the CPU leg runs on rank 0 of the single-GPU run only
-            cpu = wl.cpu_baseline(eng)
         line = {
             "metric": METRIC if wl.config in (2,) else (f"{METRIC} [variant: BASELINE config {wl.config}]" if wl.config != 6 else
                                                           f"{METRIC} [variant: sweep over the reference's production player counts]"),
@@ -829,33 +724,186 @@ def main() -> None:
                         ("torch.distributed.run" if distributed else "single process"),
             "config": {**wl.describe(n_gpus), "device": info["name"], "arch": info["arch"], "compute_units": info["compute_units"],
                        "clock_mhz": info["clock_mhz"]},
-            "roofline": roofline, "cpu_baseline": cpu,
         }
+        if args.full:
+            line.update(full_report(args, wl, eng, info, t, value, n_gpus))
         if wl.config == 5:
             line["attempts_per_s"] = played / elapsed
             line["value_note"] = "completed games required by the schedule per second; attempts (incl. safety-limit games) in attempts_per_s"
-        if wl.config == 2:
-            # not `vs_baseline` (BASELINE.json publishes nothing for this exact config): the reference's own report of the
-            # k=2 tournament path on its 80-strategy grid, Ryzen 7 3700X, 12 workers = 1 142.9 games/s
-            line["vs_reference_published_12_workers"] = value / 1142.9
-            # the Python reference itself timed on this same workload in the build container (oracle/time_reference.py; the
-            # reference cannot travel to the GPU box, so this is a committed fixture, not a measurement of this run)
-            fixture = ROOT / "tests" / "golden" / "reference_cpu_timing.json"
-            if fixture.exists():
-                ref = json.loads(fixture.read_text())
-                line["reference_python_fixture"] = {
-                    "tournament_loop_games_per_s_1_process": ref["tournament_loop_1_process"]["games_per_s"],
-                    "tournament_loop_games_per_s_8_processes": ref["tournament_loop_8_processes"]["games_per_s"],
-                    "where": ref["host"]["note"]}
-            e2e = sorted((ROOT / "profiles").glob("r*_farkle_run_end_to_end.json"))
-            if e2e:  # the latest committed measurement of `farkle run` end to end (rows off / on), not of this run
-                line["farkle_run_end_to_end_fixture"] = {"file": f"profiles/{e2e[-1].name}", **json.loads(e2e[-1].read_text())}
         os.write(json_fd, (json.dumps(line) + "\n").encode("utf-8"))
     eng.close()
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
 
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, arrays: dict) -> None:
+    """Every array as out_dir/<name>.npy in float64 (the counts stay exact below 2^53).  An array beyond its equal share of DUMP_BYTES
+    keeps a fixed, seeded sample of its elements in their original order (<name>.npy, flat) and their flat indices (<name>_index.npy)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // (2 * len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share // 8, replace=False))
+            np.save(out_dir / f"{name}_index.npy", idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}.npy", a)
+
+
+def full_report(args, wl, eng, info: dict, t: dict, value: float, n_gpus: int) -> dict:
+    """What a `--full` run adds to the line after the timed steps: the roofline of the dominant kernel (its kernel times are the
+    timed steps' HIP events, W is measured on a launch of its own), the CPU oracle timed on a sample of the same workload and checked
+    against the GPU, and for config 2 the comparisons with the reference.  None of it runs inside the timed steps."""
+    # live per-game work (R, T of SURVEY section 8d) from the rows of a launch of the same workload
+    rows, k_s, sample_desc = wl.sample(eng)
+    wpg = dict(rows) if isinstance(rows, dict) else work_per_game(rows, k_s)
+    del rows
+    wpg["sample"] = sample_desc
+    # dominant kernel: average launch duration and games per launch over the last engine call of every timed step
+    launches = max(int(t.get("play_launches", 0)), 1)
+    kernel_ms = t.get("play_ms", 0.0) / launches
+    games_per_launch = t.get("games", 0) / launches
+    kernel_games_per_s = games_per_launch / max(kernel_ms * 1e-3, 1e-12)
+    # VALU roof: CUs x 4 SIMD x 32 lanes/clk x clock (MI355X_MICROARCH.md: wave64 issues over 2 cycles on a SIMD-32)
+    peak_ops = info["compute_units"] * 4 * 32 * info["clock_mhz"] * 1e6
+    achieved_ops = kernel_games_per_s * wpg["ops_per_game"]
+    hbm_bpg = wl.hbm_bytes_per_game()
+    # HBM bytes per launch from the PMC passes of the same launch shape (rocprofv3 cannot run inside this process):
+    # profiles/r*_hbm_traffic.json carries the commit it was taken at; dropped when that is not an ancestor's kernel
+    def kernel_of(shape: dict, k_seats: int) -> str:
+        """fk_play_hc_kernel launches are recognisable by their LDS size: 16 bytes per seat and lane (+ the 12 656-byte table
+        image), or 32 with the cold records in LDS (csrc/fk_play_hc.h); everything else is fk_play_kernel."""
+        block, lds = shape.get("play_block"), shape.get("play_lds_bytes")
+        hc = bool(block) and lds in (block * 16 * k_seats, block * 16 * k_seats + 12656, block * 32 * k_seats)
+        return "fk_play_hc_kernel" if hc else "fk_play_kernel"
+
+    dominant = kernel_of(t, int(wl.k)) if isinstance(getattr(wl, "k", None), int) else "fk_play_kernel"  # (sweep / H2H lines: per_k / k = 2)
+    def traffic_for(kernel: str, k_seats: int | None = None):
+        """HBM bytes per launch of `kernel` from the newest PMC stamp of this workload (per player count for the sweep), or None
+        when the kernel sources have changed since it was taken."""
+        suffix = f"config{wl.config}" + (f"_k{k_seats}" if k_seats is not None else "")
+        for tpath in sorted((ROOT / "profiles").glob(f"r*_hbm_traffic_{suffix}.json"), reverse=True):
+            rec = json.loads(tpath.read_text())
+            if rec.get("kernel_source_sha256") == kernel_source_sha():
+                return rec["kernels"].get(kernel, {}).get("hbm_bytes_corrected")
+            break
+        return None
+
+    def mix_for(kernel: str, shape: dict, k_seats: int, frac: float):
+        """Static instruction mix of the instance's roll loop priced with the two measured issue classes (tools/isa_mix.py ->
+        profiles/r*_isa_mix.json, valid while the kernel sources are the ones it was taken on): `ceiling_frac` is the fraction of the
+        NOMINAL peak a SIMD issuing this mix back to back would reach, `frac_of_mix_ceiling` = frac / that.  None when unknown."""
+        for mpath in sorted((ROOT / "profiles").glob("r*_isa_mix.json"), reverse=True):
+            doc = json.loads(mpath.read_text())
+            if doc.get("kernel_source_sha256") != kernel_source_sha():
+                break
+            block, mixed = shape.get("play_block"), shape.get("play_mixed_flags")
+            hits = []
+            for name, rec in doc["instances"].items():
+                a = [int(x) for x in name[name.index("<") + 1:-1].split(",")]
+                if not name.startswith(kernel + "<") or a[0] != block:
+                    continue
+                if kernel == "fk_play_kernel":  # <BLOCK, LEAN, WPE, MIXED, GS, BLK, KC>
+                    ok = a[1] == 1 and a[3] == mixed and a[4] == 0 and a[5] == (1 if wl.config == 5 else 0) and a[6] == (2 if k_seats == 2 else 0)
+                else:  # <BLOCK, MIXED, LT, KI, WPE, PKR, CL, NS, CR, IL>: KI seats in registers (0 = the cold-in-LDS instance of k <= 4)
+                    ki = 0 if k_seats <= 4 else k_seats if k_seats <= 8 else 10 if k_seats <= 10 else 12
+                    ok = a[1] == mixed and a[3] == ki
+                if ok:
+                    hits.append((name, rec))
+            if len(hits) == 1:
+                name, rec = hits[0]
+                return {"instance": name, "source": f"profiles/{mpath.name} (static mix of the roll loop; classes: profiles/r05_valu_issue_rates.txt)",
+                        **{key: rec[key] for key in ("valu_static", "full_rate", "half_rate", "mean_issue_cycles", "ceiling_frac")},
+                        "frac_of_mix_ceiling": frac / rec["ceiling_frac"]}
+            break
+        return None
+
+    traffic = traffic_for(dominant)
+    roofline = {
+        "bound": "valu", "kernel": dominant,
+        "achieved": achieved_ops / 1e12, "peak": peak_ops / 1e12, "unit": "Tlane-op/s (int32)", "frac": achieved_ops / peak_ops,
+        "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC, separate pass; null when the kernel sources changed since)",
+        "kernel_ms": kernel_ms, "games_per_launch": games_per_launch, "kernel_games_per_s": kernel_games_per_s, **wpg,
+        # ONE number, stated once: kernel_ms is the mean duration of the game kernel over the launches of the TIMED steps only (HIP
+        # events on the engine's stream).  A rocprofv3 --stats average of this command also counts the warm-up steps (clock still
+        # ramping), the statistics launch that measures W and the CPU-baseline parity launch: compare with its rows for the timed
+        # launches, not with its mean (round 5: 9.31 ms average over nine launches against 8.88 ms here for the same kernel).
+        "kernel_ms_is": "mean over the launches of the timed steps (HIP events); a rocprofv3 average of this command also includes warm-up, statistics and parity launches",
+        "kernel_ms_min": t.get("play_ms_min"), "kernel_ms_max": t.get("play_ms_max"), "timed_launches": t.get("play_launches"),
+        "hbm": {"achieved": kernel_games_per_s * hbm_bpg / 1e9, "peak": 8000.0, "unit": "GB/s",
+                "frac": kernel_games_per_s * hbm_bpg / 8e12, "bytes_per_game": hbm_bpg},
+        # permutations: every launch (they run on the main stream, in front of the previous game kernel when pipelined);
+        # seat seeding: only the launches that were NOT seeded on the side stream behind the previous game kernel
+        "seed_kernel_ms": t.get("seed_ms", 0.0) / max(launches - int(t.get("prefetched_chunks", 0)), 1),
+        "perm_kernel_ms": t.get("perm_ms", 0.0) / max(launches, 1),
+        "launches_seeded_behind_the_previous_kernel": int(t.get("prefetched_chunks", 0)),
+        "launch": {k2: t.get(k2) for k2 in ("play_block", "play_grid", "play_lds_bytes", "play_mixed_flags")},
+    }
+    roofline["mix"] = mix_for(dominant, t, int(wl.k) if isinstance(getattr(wl, "k", None), int) else 2, roofline["frac"])
+
+    def with_clock(rec: dict, tt: dict) -> None:
+        """`frac` stays defined against the NOMINAL clock (as every round before); next to it the clock the game kernels
+        really held (in-kernel s_memtime / s_memrealtime, median over workgroups, mean over the timed launches) and the fraction of
+        the peak at THAT clock — the chip lowers its clock under load (MI355X_MICROARCH.md, DVFS give-back)."""
+        if tt.get("clock_n"):
+            mhz = tt["clock_sum"] / tt["clock_n"]
+            rec["clock_mhz_measured"] = mhz
+            rec["frac_at_measured_clock"] = rec["frac"] * info["clock_mhz"] / mhz
+        if tt.get("tail_n"):  # how long the last launch of a call took to drain behind its longest games
+            rec["launch_tail_ms"] = tt["tail_ms_sum"] / tt["tail_n"]
+
+    with_clock(roofline, t)
+    if "per_k" in wpg:  # config 4: one roofline record per player count (kernel time, W and fraction of each k's launches)
+        per_k = []
+        for k2, w2 in wpg.pop("per_k").items():
+            tk = (t.get("per_k") or {}).get(k2, {})
+            n_l = max(int(tk.get("play_launches", 0)), 1)
+            ms = tk.get("play_ms", 0.0) / n_l
+            gpl = tk.get("games", 0) / n_l
+            rate = gpl / max(ms * 1e-3, 1e-12)
+            per_k.append({"k": int(k2), "kernel": kernel_of(tk, int(k2)), "kernel_ms": ms,
+                          "games_per_launch": gpl, "kernel_games_per_s": rate, **w2,
+                          "frac": rate * w2["ops_per_game"] / peak_ops, "traffic": traffic_for(kernel_of(tk, int(k2)), int(k2)),
+                          "launch": {k3: tk.get(k3) for k3 in ("play_block", "play_grid", "play_lds_bytes", "play_mixed_flags")}})
+            per_k[-1]["mix"] = mix_for(per_k[-1]["kernel"], tk, int(k2), per_k[-1]["frac"])
+            with_clock(per_k[-1], tk)
+        roofline["per_k"] = per_k
+        # The line's headline record is ONE kernel's, whole: the player count furthest below its roofline (every field — kernel, time,
+        # games, W, achieved, frac, clock, traffic, launch, hbm — from that k's launches; round 4 mixed the mean fraction with the worst
+        # k's kernel fields).  The mean over the player counts stands beside it under its own name.
+        worst = min(per_k, key=lambda r: r["frac"])
+        roofline["frac_mean_over_k"] = float(np.mean([r["frac"] for r in per_k]))
+        hbm_k = 32 * worst["k"] + 2 * worst["k"] + 4
+        roofline.update({key: worst[key] for key in worst if key != "k"})
+        roofline.update({"kernel_note": f"slowest player count of the sweep: k = {worst['k']} (every headline field is that k's; mean over k in frac_mean_over_k)",
+                         "achieved": worst["frac"] * peak_ops / 1e12,
+                         "hbm": {"achieved": worst["kernel_games_per_s"] * hbm_k / 1e9, "peak": 8000.0, "unit": "GB/s",
+                                 "frac": worst["kernel_games_per_s"] * hbm_k / 8e12, "bytes_per_game": hbm_k}})
+    cpu = None
+    if not args.no_cpu_baseline and n_gpus == 1:  # the CPU leg runs on rank 0 of the single-GPU run only
+        cpu = wl.cpu_baseline(eng)
+    out = {"roofline": roofline, "cpu_baseline": cpu}
+    if wl.config == 2:
+        # not `vs_baseline` (BASELINE.json publishes nothing for this exact config): the reference's own report of the
+        # k=2 tournament path on its 80-strategy grid, Ryzen 7 3700X, 12 workers = 1 142.9 games/s (BASELINE.md section 1)
+        out["vs_reference_published_12_workers"] = value / 1142.9
+        # the Python reference itself timed on this same workload in the build container (oracle/time_reference.py; the
+        # reference cannot travel to the GPU box, so this is a committed fixture, not a measurement of this run)
+        fixture = ROOT / "tests" / "golden" / "reference_cpu_timing.json"
+        if fixture.exists():
+            ref = json.loads(fixture.read_text())
+            out["reference_python_fixture"] = {
+                "tournament_loop_games_per_s_1_process": ref["tournament_loop_1_process"]["games_per_s"],
+                "tournament_loop_games_per_s_8_processes": ref["tournament_loop_8_processes"]["games_per_s"],
+                "where": ref["host"]["note"]}
+        e2e = sorted((ROOT / "profiles").glob("r*_farkle_run_end_to_end.json"))
+        if e2e:  # the latest committed measurement of `farkle run` end to end (rows off / on), not of this run
+            out["farkle_run_end_to_end_fixture"] = {"file": f"profiles/{e2e[-1].name}", **json.loads(e2e[-1].read_text())}
+    return out
 
 def kernel_source_sha() -> str:
     """sha256 over the CODE of the device sources (kernels + per-roll device functions; comments and white space left out, so that

@@ -58,7 +58,7 @@ def test_bench_single_process_and_rank_failure_propagates(tmp_path):
 
 @pytest.mark.parametrize("config,extra", [(3, ("--shuffles", "3")), (4, ("--games", "3000")), (5, ("--games", "200")), (6, ("--games", "1500"))])
 def test_bench_other_baseline_configs_two_ranks(config, extra):
-    line = _run_bench("--gpus", "2", "--config", str(config), *extra, "--steps", "1", "--warmup", "0", "--no-cpu-baseline", timeout=900)
+    line = _run_bench("--gpus", "2", "--config", str(config), *extra, "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", timeout=900)
     assert line["n_gpus"] == 2 and (f"config {config}" in line["metric"] or (config == 6 and "production player counts" in line["metric"]))
     assert line["scaling"] == ("weak" if config == 3 else "strong")
     assert line["roofline"]["ops_per_game"] > 0 and line["value"] > 0
@@ -68,6 +68,39 @@ def test_bench_other_baseline_configs_two_ranks(config, extra):
         worst = min(per_k, key=lambda r: r["frac"])
         assert all(line["roofline"][key] == worst[key] for key in ("frac", "kernel", "kernel_ms", "games_per_launch", "ops_per_game"))
         assert line["roofline"]["frac_mean_over_k"] == pytest.approx(np.mean([r["frac"] for r in per_k]))
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline fields only; --dump-outputs writes the last timed step's tally and the reduced
+    tally as float64, the same arrays on every run with the same arguments."""
+    import golden_util as gu
+    import pyoracle as po
+
+    lines = []
+    for run in ("a", "b"):
+        lines.append(_run_bench("--shuffles", "50", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run)))
+    line = lines[0]
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in line, key
+    assert line["steps"] == 2 and line["unit"] == "games/s" and line["higher_is_better"] is True and line["dtype"] == "int32"
+    assert "roofline" not in line and "cpu_baseline" not in line
+    assert line["value"] == pytest.approx(2 * 50 * 32 / (line["ms_per_step"] * 2e-3), rel=1e-6)
+    table = gu.strategies_from_tuples(gu.load("grid_vectors.json")["g64"], po.STRATEGY_DTYPE)
+    # timed steps 1 and 2 (after one warm-up step) = shuffles [50, 150); the last one = shuffles [100, 150)
+    want = {"tally": po.tournament(table, 2, 42, 100, 150)["tally"][0], "tally_sum": po.tournament(table, 2, 42, 50, 100)["tally"][0]}
+    want["tally_sum"] = want["tally_sum"] + want["tally"]
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["tally.npy", "tally_sum.npy"]
+    for name, ref in want.items():
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, ref.astype(np.float64)), name
+        assert np.array_equal(got, np.load(tmp_path / "b" / f"{name}.npy")), name
+
+
+def test_bench_full_adds_roofline_and_cpu_baseline():
+    line = _run_bench("--shuffles", "2000", "--steps", "1", "--warmup", "0", "--full")
+    assert line["roofline"]["ops_per_game"] > 0 and line["roofline"]["kernel"] == "fk_play_kernel"
+    assert line["cpu_baseline"]["parity"].startswith("GPU tally == oracle tally")
+    assert line["vs_reference_published_12_workers"] > 0
 
 
 def test_bench_under_torch_distributed_run_like_the_driver(tmp_path):

@@ -85,7 +85,7 @@ def run(out_path: str) -> None:
             env["FARKLE_HIP_LIB"] = str(lib)
         tests = subprocess.run([sys.executable, "-m", "pytest", "tests/test_hot_cold_gpu.py", "-x", "-q", "-m", "gpu"], cwd=ROOT, env=env,
                                capture_output=True, text=True) if name != "shipped_again" else None  # every hot / cold instance family against the oracle
-        bench = subprocess.run([sys.executable, "bench.py", "--config", "6", "--steps", "2", "--warmup", "1"], cwd=ROOT, env=env, capture_output=True, text=True)
+        bench = subprocess.run([sys.executable, "bench.py", "--config", "6", "--steps", "2", "--warmup", "1", "--full"], cwd=ROOT, env=env, capture_output=True, text=True)
         line = json.loads(bench.stdout.strip().splitlines()[-1])
         per_k = {str(e["k"]): {"kernel_ms": e.get("kernel_ms"), "frac": e.get("frac")} for e in line.get("roofline", {}).get("per_k", [])} if isinstance(line.get("roofline", {}).get("per_k"), list) else line.get("roofline")
         results["variants"][name] = {"library": str(lib) if lib else "farkle_ii_amd/libfarkle_hip.so", "parity_tests": None if tests is None else tests.stdout.strip().splitlines()[-1],
