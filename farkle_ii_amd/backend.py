@@ -109,7 +109,8 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
 _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_get_timing", "fk_set_option",
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_lags", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
-            "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds"]
+            "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
+            "fk_last_play_instance"]
 _libs: dict = {}
 
 
@@ -126,6 +127,8 @@ def load_library(variant: str | None = None) -> C.CDLL:
             getattr(lib, name)  # AttributeError if a declared symbol is not exported
         lib.fk_last_error.restype = C.c_char_p
         lib.fk_last_error.argtypes = [C.c_void_p]
+        lib.fk_last_play_instance.restype = C.c_char_p
+        lib.fk_last_play_instance.argtypes = [C.c_void_p]
         lib.fk_destroy.restype = None
         lib.fk_destroy.argtypes = [C.c_void_p]
         _libs[variant] = lib
@@ -284,6 +287,11 @@ class Engine:
         t = _Timing()
         self._check(self._lib.fk_get_timing(self._ctx, C.byref(t)))
         return {f: getattr(t, f) for f, _ in _Timing._fields_}
+
+    def last_play_instance(self) -> str:
+        """``fk_last_play_instance``: the game-kernel template instance the last tournament / game-list / H2H call launched last
+        (after a replay: the replay's), e.g. ``fk_play_kernel<768, true, 6, 49152u, false, false, 2>``; ``""`` when it launched none."""
+        return (self._lib.fk_last_play_instance(self._ctx) or b"").decode()
 
     # -- hot path ------------------------------------------------------------------------
     def tournament(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,

@@ -82,6 +82,7 @@ struct fk_ctx {
     hipDeviceProp_t prop{};
     std::string err;
     fk_timing timing{};
+    std::string play_instance; // the game-kernel instance of the call's last launch (fk_last_play_instance)
     hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; // see TimerSlot
     int32_t *err_host = nullptr;    // pinned: the error record of a call's last game kernel (read with the tally)
     hipEvent_t main_idle = nullptr; // recorded on the main stream in front of a game kernel: what a side-stream preparation waits for
@@ -326,6 +327,7 @@ SeedPool seed_prefix(uint32_t purpose, uint64_t root_seed, uint64_t k) {
 struct LaunchPlan {
     int block = 0, grid = 0, cus = 1;
     mutable int launched_grid = 0; // the grid after the occupancy clamp of the launch
+    mutable const char *instance = nullptr; // the kernel instance the launch ran, as the compiler spells its template (fk_last_play_instance)
     size_t lds = 0;
     bool lds_tally = false;
     bool lean = false; // 10-dword seat records (increment + strategy re-read from HBM/L2 each turn, 16-bit score / 50)
@@ -527,6 +529,13 @@ hipError_t launch_play_u(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) 
     // a persistent grid: blocks beyond the resident ones would only queue behind them
     const int grid = std::min(p.grid, occ_blocks * p.cus);
     p.launched_grid = grid;
+    static const std::string instance = [] {
+        char b[96];
+        snprintf(b, sizeof(b), "fk_play_kernel<%d, %s, %d, %uu, %s, %s, %d>", BLOCK, LEAN ? "true" : "false", WPE, MIXED,
+                 GS ? "true" : "false", BLK ? "true" : "false", KC);
+        return std::string(b);
+    }();
+    p.instance = instance.c_str();
     hipLaunchKernelGGL((fk_play_kernel<BLOCK, LEAN, WPE, MIXED, GS, BLK, KC>), dim3((unsigned)grid), dim3(BLOCK), lds, s, a);
     return hipGetLastError();
 }
@@ -564,6 +573,13 @@ hipError_t launch_play_hc_u(const LaunchPlan &p, const PlayArgs &a, hipStream_t 
     }
     const int grid = std::min(p.grid, occ_blocks * p.cus);
     p.launched_grid = grid;
+    static const std::string instance = [] {
+        char b[96];
+        snprintf(b, sizeof(b), "fk_play_hc_kernel<%d, %uu, %s, %d, %d, %s, %s, %d>", BLOCK, MIXED, LT ? "true" : "false", KI, WPE,
+                 PKR ? "true" : "false", CL ? "true" : "false", NS);
+        return std::string(b);
+    }();
+    p.instance = instance.c_str();
     hipLaunchKernelGGL((fk_play_hc_kernel<BLOCK, MIXED, LT, KI, WPE, PKR, CL, NS>), dim3((unsigned)grid), dim3(BLOCK), p.lds, s, a);
     return hipGetLastError();
 }
@@ -860,6 +876,7 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
         hipError_t e = launch_play(lp, pa, c->stream);
         t.stop();
         HIPCHK(c, e);
+        c->play_instance = lp.instance ? lp.instance : "";
         c->timing.play_grid = lp.launched_grid;
         c->timing.play_mixed_flags = lp.mixed_flags == MIXED_NONE ? (int32_t)MIXED_NONE
                                      : (lp.mixed_flags & ~MIXED_RB_FAV) == 0u ? (int32_t)MIXED_RB_FAV : (int32_t)MIXED_ALL;
@@ -1312,6 +1329,8 @@ void fk_destroy(fk_ctx *c) {
 
 const char *fk_last_error(fk_ctx *c) { return c ? c->err.c_str() : "null context"; }
 
+const char *fk_last_play_instance(fk_ctx *c) { return c ? c->play_instance.c_str() : ""; }
+
 int fk_get_device_info(fk_ctx *c, fk_device_info *out) {
     if (!c || !out) return FK_ERR_ARG;
     memset(out, 0, sizeof(*out));
@@ -1660,6 +1679,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
     HIPCHK(c, hipSetDevice(c->device));
     c->timing = fk_timing{};
+    c->play_instance.clear();
     c->pending.clear();
     c->letters.clear(); // (a failed call may have left some)
     c->mail_used = 0;
@@ -2082,6 +2102,7 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     }
     HIPCHK(c, hipSetDevice(c->device));
     c->timing = fk_timing{};
+    c->play_instance.clear();
     c->pending.clear();
     c->letters.clear(); // (a failed call may have left some)
     c->mail_used = 0;
@@ -2172,6 +2193,7 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
     if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
     HIPCHK(c, hipSetDevice(c->device));
     c->timing = fk_timing{};
+    c->play_instance.clear();
     c->pending.clear();
     c->letters.clear(); // (a failed call may have left some)
     c->mail_used = 0;

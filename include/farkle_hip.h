@@ -132,6 +132,10 @@ void fk_destroy(fk_ctx *ctx);
 const char *fk_last_error(fk_ctx *ctx);
 int fk_get_device_info(fk_ctx *ctx, fk_device_info *out);
 int fk_get_timing(fk_ctx *ctx, fk_timing *out);
+/* The game-kernel instance of the last launch of the last fk_tournament_run* / fk_play_games / fk_h2h_run* call on this context — after
+ * a replay (out-of-memory, counter guard) the replay's — as the compiler spells its template, e.g.
+ * "fk_play_hc_kernel<768, 65280u, true, 12, 3, false, false, 12>"; "" when that call launched none.  Valid until the next call. */
+const char *fk_last_play_instance(fk_ctx *ctx);
 /* Page-locked host memory for the caller-owned output buffers (rows above all: 60 bytes per k=2 game).  A buffer from here is
  * copied to by one DMA per chunk at PCIe rate, while the next chunk plays; any other host pointer works too (staged by the HIP
  * runtime, about a third of the rate, the host thread waits).  Free with fk_host_free before fk_destroy.  The pages are anonymous

@@ -353,20 +353,23 @@ def test_resident_tally_accumulates_on_the_device_and_reduces_through_rccl(eng):
         eng.set_option("resident_tally", 0)
 
 
-@pytest.mark.parametrize("S,k", [(8, 2), (64, 2), (96, 3), (1290, 2), (5160, 4), (7140, 5)])
+@pytest.mark.parametrize("S,k", [(8, 2), (64, 2), (96, 3), (1290, 2), (5160, 4), (7140, 5), (16386, 2), (32770, 2), (65534, 2)])
 def test_permutation_kernels_agree_with_numpy_semantics(eng, po, S, k):
     """Generator.permutation through the three device paths — one-kernel Fisher-Yates, draws + serial swap chains, draws +
     the chain-free kernel (bucket sort + pointer jumping), the draws by a thread or by a wave per shuffle — against the oracle's
-    restatement of NumPy's loop, permutations and tallies; shuffle counts that leave partial blocks and partial 8-draw groups."""
+    restatement of NumPy's loop, permutations and tallies; shuffle counts that leave partial blocks and partial 8-draw groups.
+    16 386 / 32 770 / 65 534 strategies (k = 2): the masked draws of a shuffle change bit length between the bounds 16 383 / 16 384 and
+    32 767 / 32 768, and 65 534 is the largest table the ABI takes; at these sizes the chain-free kernel's LDS does not fit, so split
+    modes 1 and 2 both run the swap chains."""
     table = _random_valid_table(S, S) if (S <= 96 or S > 5160) else _default_table()[:S]  # 7 140: the reference's largest documented grid
-    n_sh = {8: 300, 64: 521, 96: 77, 1290: 70, 5160: 37, 7140: 260}[S]
+    n_sh = {8: 300, 64: 521, 96: 77, 1290: 70, 5160: 37, 7140: 260, 16386: 5, 32770: 4, 65534: 3}[S]
     ref = po.tournament(table.view(po.STRATEGY_DTYPE), k, 21, 1000, 1000 + n_sh, want_perms=True, max_rounds=3, n_threads=16)
     try:
         for mode in (0, 1, 2, -1):
             eng.set_option("perm_split", mode)
             # the draws of the two split paths: by one thread per shuffle (0) or by a whole wave (1: jump-ahead by 64 + the rejection
             # scan iterated to its fixed point, csrc/fk_perm_wave.h) — the same 16-bit draws in the same groups
-            for draw_by_wave in ((0, 1) if mode in (1, 2) else (-1,)):
+            for draw_by_wave in ((0, 1) if mode >= 0 else (-1,)):
                 eng.set_option("perm_draw_wave", draw_by_wave)
                 try:
                     got = eng.tournament(table, k, 21, 1000, 1000 + n_sh, want_perms=True, max_rounds=3)
