@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -107,7 +107,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
 
 
 _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_get_timing", "fk_set_option",
-            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_lags", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
+            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance"]
@@ -419,6 +419,71 @@ class Engine:
             C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
             _p(tally), _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail)))
         return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh}
+
+    def tournament_matchups(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, lags, strategy_ids,
+                            max_players: int, shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                            overrides: np.ndarray | None = None) -> dict:
+        """``tournament_lags`` + the per-game records of the RNG diagnostics' matchup family (``fk_tournament_run_matchups``), in
+        coordinate order: ``matchups = {"digest": uint64 [n], "seats": uint16 [n][k] (table indices in ascending-ID order),
+        "rounds": uint16 [n]}``."""
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        lags = np.ascontiguousarray(list(lags), dtype=np.int32)
+        ids = np.ascontiguousarray(strategy_ids, dtype=np.int32)
+        S = len(table)
+        if len(ids) != S or len(np.unique(ids)) != S:
+            raise ValueError("strategy_ids must hold one unique ID per strategy of the table")
+        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
+        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
+        n_batches = (n_sh + spb - 1) // spb
+        n_games = n_sh * (S // k if k > 0 else 0)
+        tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+        m = min(int(lags.max()) if len(lags) else 0, n_sh)
+        sums = np.zeros((S, len(lags), LAG_COLS), dtype=np.int64)
+        head = np.zeros((max(m, 1), S), dtype=np.uint16)
+        tail = np.zeros((max(m, 1), S), dtype=np.uint16)
+        digest = np.zeros(max(n_games, 1), dtype=np.uint64)
+        seats = np.zeros((max(n_games, 1), max(k, 1)), dtype=np.uint16)
+        rounds = np.zeros(max(n_games, 1), dtype=np.uint16)
+        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        self._check(self._lib.fk_tournament_run_matchups(
+            self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
+            C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
+            _p(tally), _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail), _p(ids), C.c_int32(max_players),
+            _p(digest), _p(seats), _p(rounds)))
+        return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh,
+                "matchups": {"digest": digest[:n_games], "seats": seats[:n_games], "rounds": rounds[:n_games]}}
+
+    def matchup_reduce(self, records: dict, k: int, lags, cap: int | None) -> dict:
+        """``fk_matchup_reduce`` over the records of a whole (root, k) in coordinate order: counts, histogram (``[min(lags) + 66]``
+        groups per bin code) and the eligible groups of least priority — the first ``cap`` (``None`` / <= 0: all) plus every group
+        tied with the last one kept — with their counts and per-lag sums ``[M][n_lags][6]`` (layout of ``rng_matchups.host_reduce``)."""
+        lags_a = np.ascontiguousarray(list(lags), dtype=np.int32)
+        digest = np.ascontiguousarray(records["digest"], dtype=np.uint64)
+        seats = np.ascontiguousarray(np.asarray(records["seats"], dtype=np.uint16).reshape(-1, k))
+        rounds = np.ascontiguousarray(records["rounds"], dtype=np.uint16)
+        n = len(digest)
+        minimum = int(lags_a.min()) + 2 if len(lags_a) else 2
+        cap_v = int(cap) if cap is not None and int(cap) > 0 else 0
+        capacity = cap_v + 64 if cap_v else n // minimum + 1
+        while True:
+            counts = np.zeros(4, dtype=np.int64)
+            hist = np.zeros(minimum + 64, dtype=np.uint64)
+            out_d = np.zeros(max(capacity, 1), dtype=np.uint64)
+            out_s = np.zeros((max(capacity, 1), k), dtype=np.uint16)
+            out_c = np.zeros(max(capacity, 1), dtype=np.int64)
+            out_x = np.zeros((max(capacity, 1), len(lags_a), 6), dtype=np.int64)
+            rc = self._lib.fk_matchup_reduce(self._ctx, C.c_int32(k), C.c_int64(n), _p(digest), _p(seats), _p(rounds), _p(lags_a),
+                                             C.c_int32(len(lags_a)), C.c_int64(cap_v), C.c_int64(capacity), _p(counts), _p(hist),
+                                             _p(out_d), _p(out_s), _p(out_c), _p(out_x))
+            if rc == FK_ERR_ARG and counts[3] > capacity:  # more priority ties than the slack: once more with room for all
+                capacity = int(counts[3])
+                continue
+            self._check(rc)
+            break
+        M = int(counts[3])
+        return {"k": int(k), "lags": tuple(int(v) for v in lags_a), "observations": int(counts[0]), "candidate_groups": int(counts[1]),
+                "eligible_groups": int(counts[2]), "histogram": hist, "digest": out_d[:M], "seats": out_s[:M], "count": out_c[:M],
+                "sums": out_x[:M]}
 
     def get_option(self, name: str) -> int:
         """``fk_get_option``: an option's value or a figure of the last call (``last_budget``, ``oom_replays``, the effective ``comm_timeout_ms``)."""

@@ -39,6 +39,11 @@ def build_parser() -> argparse.ArgumentParser:
                           "and the autocorrelation rows computed from them, from device accumulators, without rows.  The series spans every "
                           "shuffle of the run and is held in memory until the end: an interrupted --rng-lag-sums run cannot resume (the next "
                           "invocation asks for --force), and a run completed without it must be replayed with --force")
+    run.add_argument("--rng-matchup-lags", action="store_true",
+                     help="--rng-lag-sums plus the RNG diagnostics' MATCHUP family: per game a digest of the sorted seat tuple and "
+                          "n_rounds, grouped on the device; per player count <k>p_rng_matchup_groups.parquet (its top "
+                          "analysis.rng_max_matchup_groups eligible groups with their lag sums, counts and histogram), after the last "
+                          "player count rng_matchup_lag_stats.parquet and rng_group_selection.json at the results root")
     run.add_argument("--sidecars", action="store_true",
                      help="Write <artifact>.sidecar.json (producer contract + SHA-256 / size of the artifact) beside every output")
     run.add_argument("--code-identity", metavar="COMMIT[:DIRTY_SHA256[:POLICY]]",
@@ -110,6 +115,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.all_player_batch_dir = args.all_player_batches
     if args.rng_lag_sums:
         cfg.sim.rng_lag_sums = True
+    if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
+        cfg.sim.rng_lag_sums = cfg.sim.rng_matchup_lags = True
     _maybe_init_distributed()
     if int(os.environ.get("WORLD_SIZE", "1")) > 1 and os.environ.get("FK_TALLY_REDUCE", "rccl") == "rccl":
         # The per-group tally reduction through the C-ABI's own RCCL communicator (fk_comm_init / fk_reduce_tally): the default

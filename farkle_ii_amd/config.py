@@ -63,6 +63,7 @@ class SimConfig:
     sidecars: bool = False  # this engine's option: per-artifact <name>.sidecar.json (sidecars.py; contract version 2)
     all_player_batch_dir: Path | None = None  # this engine's option: all-player batch metrics without rows (all_player.py)
     rng_lag_sums: bool = False  # this engine's option: lag sufficient statistics of the RNG diagnostics' strategy family (rng_lags.py)
+    rng_matchup_lags: bool = False  # this engine's option: the RNG diagnostics' matchup family + group selection (rng_matchups.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
     mp_start_method: str | None = None
@@ -165,6 +166,36 @@ class AppConfig:
         if not lags or any(v < 1 for v in lags) or tuple(sorted(set(lags))) != lags:
             raise ValueError("analysis.rng_diagnostic_lags must be unique increasing positive integers")
         return lags
+
+    def rng_max_matchup_groups(self) -> int | None:
+        """``analysis.rng_max_matchup_groups`` (config.py:333, validated like :1928-1932): ``None`` or a positive integer."""
+        cap = (self.opaque.get("analysis") or {}).get("rng_max_matchup_groups", 100_000)
+        if cap is not None and (isinstance(cap, bool) or not isinstance(cap, int) or cap < 1):
+            raise ValueError("analysis.rng_max_matchup_groups must be positive when configured")
+        return cap
+
+    def rng_diagnostic_partitions(self) -> int:
+        """``analysis.rng_diagnostic_partitions`` (config.py:337, validated like :1940-1947); echoed in the selection report."""
+        parts = (self.opaque.get("analysis") or {}).get("rng_diagnostic_partitions", 32)
+        if isinstance(parts, bool) or not isinstance(parts, int) or parts < 1 or parts > 256:
+            raise ValueError("analysis.rng_diagnostic_partitions must be in [1, 256]")
+        return parts
+
+    def combine_max_players(self) -> int:
+        """``combine.max_players`` (config.py:356): the number of ``P#_strategy`` columns the matchup key is padded to."""
+        mp = (self.opaque.get("combine") or {}).get("max_players", 12)
+        if isinstance(mp, bool) or not isinstance(mp, int) or mp < 1:
+            raise ValueError("combine.max_players must be a positive integer")
+        return mp
+
+    def rng_matchup_groups_path(self, n: int) -> Path:
+        return self.n_dir(n) / f"{n}p_rng_matchup_groups.parquet"
+
+    def rng_matchup_stats_path(self) -> Path:
+        return self.results_root / "rng_matchup_lag_stats.parquet"
+
+    def rng_group_selection_path(self) -> Path:
+        return self.results_root / "rng_group_selection.json"
 
     def rng_lag_sums_path(self, n: int) -> Path:
         return self.n_dir(n) / f"{n}p_rng_lag_sums.parquet"

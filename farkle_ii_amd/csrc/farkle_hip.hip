@@ -8,6 +8,7 @@
 #include "fk_shard_writer.h" // host side: column images -> row-shard Parquet files
 #include "fk_perm_wave.h"    // device side: a shuffle's Fisher-Yates draws by a whole wave (small launches)
 #include "fk_row_columns_seats.h" // device side: column images with one thread per (game, seat)
+#include "fk_matchups.h"      // device side: RNG-diagnostics matchup family (key post-pass, grouped lag reduce)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -128,6 +129,9 @@ struct fk_ctx {
     DevBuf clk;                // [grid][4] stamps of the last game kernel
     int clk_grid = 0;
     DevBuf lag_v, lag_out, lag_lags, lag_edge, lag_tmp; // fk_tournament_run_lags: value matrix, sums, lag list, head / tail rows
+    DevBuf m_ids, m_dig, m_seat, m_rnd;  // fk_tournament_run_matchups: strategy IDs, one chunk's game records
+    DevBuf mr[36];                       // fk_matchup_reduce: records, sort keys / values, segments, selection, hipcub scratch
+    uint64_t matchup_sort_mask = ~0ull;  // option "matchup_sort_key_mask": the bits of the digest the reduce sorts by (tests)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
     int32_t columns_by_seat = -1; // column images: -1 one thread per (game, seat) up to sixteen seats, per game beyond; 0 per game; 1 per (game, seat)
@@ -1298,8 +1302,10 @@ void fk_destroy(fk_ctx *c) {
     release(c->comm_buf);
     if (c->prep_stream) (void)hipStreamSynchronize(c->prep_stream);
     for (DevBuf *b : {&c->strat, &c->recs, &c->rec0, &c->tally, &c->rows, &c->ov, &c->seatlist, &c->coords, &c->inv, &c->slow, &c->digest, &c->score_lut,
-                      &c->discard_lut, &c->block_out, &c->stats, &c->ratios, &c->cold, &c->clk, &c->lds_tables, &c->acc, &c->rows_alt, &c->ids, &c->lag_v, &c->lag_out, &c->lag_lags, &c->lag_edge, &c->lag_tmp})
+                      &c->discard_lut, &c->block_out, &c->stats, &c->ratios, &c->cold, &c->clk, &c->lds_tables, &c->acc, &c->rows_alt, &c->ids, &c->lag_v, &c->lag_out, &c->lag_lags, &c->lag_edge, &c->lag_tmp,
+                      &c->m_ids, &c->m_dig, &c->m_seat, &c->m_rnd})
         release(*b);
+    for (DevBuf &b : c->mr) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
@@ -1473,6 +1479,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "columns_by_seat") c->columns_by_seat = (int32_t)value;
     else if (n == "pipeline") c->pipeline = (int32_t)value;
     else if (n == "uniform_flags") c->uniform_flags_opt = (int32_t)value;
+    else if (n == "matchup_sort_key_mask") c->matchup_sort_mask = (uint64_t)value;
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
             return fail(c, FK_ERR_ARG, "block must be 0, 64, 128, 256, 512, 768 (lean records only) or 1024");
@@ -1567,12 +1574,41 @@ struct LagReq { // fk_tournament_run_lags: host pointers of the request
     int32_t n_lags, max_lag;
     int64_t *sums;
     uint16_t *head, *tail;
+    // fk_tournament_run_matchups (null otherwise): the caller's strategy IDs, max_players, and the per-game records of the range
+    const int32_t *ids = nullptr;
+    int32_t max_players = 0;
+    uint64_t *m_digest = nullptr;
+    uint16_t *m_seats = nullptr, *m_rounds = nullptr;
 };
 
 static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                                uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
                                int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
                                int64_t *seat_stats, const LagReq *lag, double *seat_ratios = nullptr);
+
+extern "C++" { // (this part of the file lies inside the C-ABI's extern "C" block)
+template <int K>
+static void launch_matchup_keys_k(fk_ctx *c, const uint32_t *recs, const uint16_t *perm, uint32_t slots, uint32_t S, uint32_t gps,
+                                  uint32_t n_games, uint32_t max_players) {
+    hipLaunchKernelGGL(fkm::fk_matchup_keys_kernel<K>, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, recs, perm, slots, S, gps, n_games,
+                       static_cast<const int32_t *>(c->m_ids.p), max_players, static_cast<unsigned long long *>(c->m_dig.p),
+                       static_cast<uint16_t *>(c->m_seat.p), static_cast<uint16_t *>(c->m_rnd.p));
+}
+} // extern "C++"
+
+// the key post-pass of one chunk: one instance per seat count (the sorting network is unrolled over K)
+static int launch_matchup_keys(fk_ctx *c, uint32_t k, const uint32_t *recs, const uint16_t *perm, uint32_t slots, uint32_t S, uint32_t gps,
+                               uint32_t n_games, uint32_t max_players) {
+    switch (k) {
+#define FKM_CASE(K) case K: launch_matchup_keys_k<K>(c, recs, perm, slots, S, gps, n_games, max_players); break;
+        FKM_CASE(1) FKM_CASE(2) FKM_CASE(3) FKM_CASE(4) FKM_CASE(5) FKM_CASE(6) FKM_CASE(7) FKM_CASE(8)
+        FKM_CASE(9) FKM_CASE(10) FKM_CASE(11) FKM_CASE(12) FKM_CASE(13) FKM_CASE(14) FKM_CASE(15) FKM_CASE(16)
+#undef FKM_CASE
+    default: return fail(c, FK_ERR_ARG, "matchup records: k = %u has no key-kernel instance", k);
+    }
+    HIPCHK(c, hipGetLastError());
+    return FK_OK;
+}
 
 static int tournament_call(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
@@ -1614,6 +1650,181 @@ int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, 
     return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
                            tally, nullptr, nullptr, nullptr, &req);
 }
+
+int fk_tournament_run_matchups(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                               uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
+                               const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
+                               uint16_t *edge_head, uint16_t *edge_tail, const int32_t *strategy_ids, int32_t max_players,
+                               uint64_t *m_digest, uint16_t *m_seats, uint16_t *m_rounds) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_ids || !m_digest || !m_seats || !m_rounds) return fail(c, FK_ERR_ARG, "strategy_ids, m_digest, m_seats, m_rounds are required");
+    if (k < 1 || k > (int32_t)fkm::MAX_K) return fail(c, FK_ERR_ARG, "matchup records are made for 1 .. %u seats, got %d", fkm::MAX_K, (int)k);
+    if (max_players < k || max_players > (int32_t)fkm::MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "max_players must be in [k, %u] (one BLAKE2b block), got %d", fkm::MAX_PLAYERS, (int)max_players);
+    if (!lags || !lag_sums || !edge_head || !edge_tail || n_lags < 1 || n_lags > FK_MAX_LAGS)
+        return fail(c, FK_ERR_ARG, "lags, lag_sums, edge_head, edge_tail are required; 1 <= n_lags <= %d", FK_MAX_LAGS);
+    for (int32_t i = 0; i < n_lags; ++i)
+        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
+            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers (rng_diagnostic_lags, config.py:1933-1939)");
+    if (max_rounds > 32767) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: max_rounds must be <= 32767");
+    for (int32_t i = 0; i < n_ov; ++i)
+        if (ov && ov[i].max_rounds > 32767u) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: override max_rounds must be <= 32767");
+    LagReq req{lags, n_lags, lags[n_lags - 1], lag_sums, edge_head, edge_tail};
+    req.ids = strategy_ids;
+    req.max_players = max_players;
+    req.m_digest = m_digest;
+    req.m_seats = m_seats;
+    req.m_rounds = m_rounds;
+    return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
+                           tally, nullptr, nullptr, nullptr, &req);
+}
+
+// hipcub device-wide primitives: size query, the context's scratch buffer, the call
+#define FKM_CUB(FN, ...)                                                     \
+    do {                                                                     \
+        size_t tb_ = 0;                                                      \
+        HIPCHK(c, FN(nullptr, tb_, __VA_ARGS__));                            \
+        if ((rc = ensure(c, c->mr[35], std::max<size_t>(tb_, 1)))) return rc; \
+        tb_ = c->mr[35].cap;                                                 \
+        HIPCHK(c, FN(c->mr[35].p, tb_, __VA_ARGS__));                        \
+    } while (0)
+
+int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *digest, const uint16_t *seats, const uint16_t *rounds,
+                      const int32_t *lags, int32_t n_lags, int64_t cap, int64_t out_capacity, int64_t *counts, uint64_t *histogram,
+                      uint64_t *out_digest, uint16_t *out_seats, int64_t *out_count, int64_t *out_sums) {
+    if (!c) return FK_ERR_ARG;
+    if (!counts || !histogram || !lags || (n_obs > 0 && (!digest || !seats || !rounds)))
+        return fail(c, FK_ERR_ARG, "counts, histogram, lags and (for n_obs > 0) the records are required");
+    if (k < 1 || k > (int32_t)fkm::MAX_K) return fail(c, FK_ERR_ARG, "k must be in [1, %u]", fkm::MAX_K);
+    if (n_obs < 0 || n_obs > (int64_t)0x7fffffff) return fail(c, FK_ERR_ARG, "n_obs must be in [0, 2^31)");
+    if (n_lags < 1 || n_lags > FK_MAX_LAGS) return fail(c, FK_ERR_ARG, "1 <= n_lags <= %d", FK_MAX_LAGS);
+    for (int32_t i = 0; i < n_lags; ++i)
+        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
+            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers");
+    HIPCHK(c, hipSetDevice(c->device));
+    const uint32_t n = (uint32_t)n_obs, K = (uint32_t)k, minimum = (uint32_t)lags[0] + 2u, H = minimum + 64u;
+    for (int i = 0; i < 4; ++i) counts[i] = 0;
+    std::fill(histogram, histogram + H, 0ull);
+    counts[0] = n_obs;
+    if (n == 0) return FK_OK;
+    int rc = 0;
+    const size_t sizes[] = {8ul * n, 2ul * n * K, 2ul * n, 8ul * n, 8ul * n, 4ul * n, 4ul * n, 8ul * n, 2ul * n * K, 2ul * n, 4ul * n, 4ul * n,
+                            4ul * n, 4ul * n, 1ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n};
+    for (int i = 0; i < 21; ++i)
+        if ((rc = ensure(c, c->mr[i], sizes[i]))) return rc;
+    auto U64 = [&](int i) { return static_cast<unsigned long long *>(c->mr[i].p); };
+    auto U32 = [&](int i) { return static_cast<uint32_t *>(c->mr[i].p); };
+    auto U16 = [&](int i) { return static_cast<uint16_t *>(c->mr[i].p); };
+    const hipStream_t st = c->stream;
+    const dim3 bn((n + 255u) / 256u), b256(256);
+    HIPCHK(c, hipMemcpyAsync(c->mr[0].p, digest, 8ul * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->mr[1].p, seats, 2ul * n * K, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->mr[2].p, rounds, 2ul * n, hipMemcpyHostToDevice, st));
+    // 1. stable radix sort by the (masked) digest: coordinate order is kept inside every run of equal keys
+    hipLaunchKernelGGL(fkm::fkm_key_init, bn, b256, 0, st, U64(0), (unsigned long long)c->matchup_sort_mask, n, U64(3), U32(5));
+    HIPCHK(c, hipGetLastError());
+    FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(3), U64(4), U32(5), U32(6), (int)n, 0, 64, st);
+    hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, U32(6), U64(0), U16(1), U16(2), n, K, U64(7), U16(8), U16(9));
+    // 2. runs of equal sort key that hold more than one tuple (digest collisions): a stable LSD sort of only those elements by
+    //    tuple column k-1 .. 0, then by run, puts every tuple of a run together, each still in coordinate order
+    hipLaunchKernelGGL(fkm::fkm_run_heads, bn, b256, 0, st, U64(4), U16(8), n, K, U32(10), U32(12));
+    FKM_CUB(hipcub::DeviceScan::InclusiveSum, U32(10), U32(11), (int)n, st);
+    HIPCHK(c, hipMemsetAsync(c->mr[13].p, 0, 4ul * n, st));
+    hipLaunchKernelGGL(fkm::fkm_mark_mixed, bn, b256, 0, st, U32(11), U32(12), n, U32(13));
+    hipLaunchKernelGGL(fkm::fkm_mixed_flags, bn, b256, 0, st, U32(11), U32(13), n, static_cast<uint8_t *>(c->mr[14].p));
+    HIPCHK(c, hipGetLastError());
+    if ((rc = ensure(c, c->mr[34], 16))) return rc;
+    uint32_t *d_num = U32(34);
+    FKM_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(c->mr[14].p), U32(15), d_num,
+            (int)n, st);
+    uint32_t m = 0;
+    HIPCHK(c, hipMemcpyAsync(&m, d_num, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (m > 0) {
+        const dim3 bm((m + 255u) / 256u);
+        HIPCHK(c, hipMemcpyAsync(c->mr[18].p, c->mr[15].p, 4ul * m, hipMemcpyDeviceToDevice, st)); // values: positions, ascending
+        int a = 18, b = 19;
+        for (int32_t col = k; col >= 0; --col) { // col = k - 1 .. 0, then the run (col == k is applied LAST: the primary key)
+            const uint32_t key_col = col == 0 ? K : (uint32_t)(col - 1);
+            hipLaunchKernelGGL(fkm::fkm_mixed_keys, bm, b256, 0, st, U32(a), U16(8), U32(11), m, K, key_col, U32(16));
+            HIPCHK(c, hipGetLastError());
+            FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U32(16), U32(17), U32(a), U32(b), (int)m, 0, key_col == K ? 32 : 16, st);
+            std::swap(a, b);
+        }
+        HIPCHK(c, hipMemcpyAsync(c->mr[20].p, c->mr[6].p, 4ul * n, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(fkm::fkm_mixed_apply, bm, b256, 0, st, U32(15), U32(a), U32(20), m, U32(6));
+        hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, U32(6), U64(0), U16(1), U16(2), n, K, U64(7), U16(8), U16(9));
+        HIPCHK(c, hipGetLastError());
+    }
+    // 3. segments = groups (the tuple changes), their starts, counts, eligibility, priorities, histogram bins
+    hipLaunchKernelGGL(fkm::fkm_seg_heads, bn, b256, 0, st, U16(8), n, K, U32(10));
+    FKM_CUB(hipcub::DeviceScan::InclusiveSum, U32(10), U32(11), (int)n, st);
+    uint32_t G = 0;
+    HIPCHK(c, hipMemcpyAsync(&G, U32(11) + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    const size_t gsizes[] = {4ul * (G + 1), 1ul * G, 8ul * G, 4ul * G, 4ul * H, 4ul * G, 4ul * G, 8ul * G};
+    for (int i = 0; i < 8; ++i)
+        if ((rc = ensure(c, c->mr[21 + i], gsizes[i]))) return rc;
+    hipLaunchKernelGGL(fkm::fkm_seg_starts, bn, b256, 0, st, U32(10), U32(11), n, U32(21));
+    const dim3 bg((G + 255u) / 256u);
+    hipLaunchKernelGGL(fkm::fkm_seg_info, bg, b256, 0, st, U32(21), U64(7), G, K, minimum, static_cast<uint8_t *>(c->mr[22].p), U64(23),
+                       static_cast<int32_t *>(c->mr[24].p));
+    HIPCHK(c, hipGetLastError());
+    FKM_CUB(hipcub::DeviceHistogram::HistogramEven, static_cast<const int32_t *>(c->mr[24].p), U32(25), (int)(H + 1), 0, (int)H, (int)G, st);
+    // 4. selection: the eligible groups by priority (radix sort); the first `cap` and every group tied with the last one kept
+    FKM_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(c->mr[22].p), U32(26), d_num,
+            (int)G, st);
+    uint32_t E = 0;
+    std::vector<uint32_t> hist32(H);
+    HIPCHK(c, hipMemcpyAsync(&E, d_num, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hist32.data(), c->mr[25].p, 4ul * H, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (uint32_t i = 0; i < H; ++i) histogram[i] = hist32[i];
+    counts[1] = G;
+    counts[2] = E;
+    uint64_t M = E;
+    if (E > 0) {
+        const dim3 be((E + 255u) / 256u);
+        hipLaunchKernelGGL(fkm::fkm_gather_u64, be, b256, 0, st, U32(26), U64(23), E, U64(4));
+        HIPCHK(c, hipGetLastError());
+        FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(4), U64(28), U32(26), U32(27), (int)E, 0, 64, st);
+        if (cap > 0 && (uint64_t)cap < E) {
+            M = (uint64_t)cap;
+            unsigned long long last = 0;
+            HIPCHK(c, hipMemcpyAsync(&last, U64(28) + (M - 1), 8, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            std::vector<unsigned long long> more(4096);
+            while (M < E) { // ties on the 64-bit priority: the host breaks them by the rest of the tuple
+                const uint64_t take = std::min<uint64_t>(more.size(), E - M);
+                HIPCHK(c, hipMemcpy(more.data(), U64(28) + M, 8 * take, hipMemcpyDeviceToHost));
+                uint64_t j = 0;
+                while (j < take && more[j] == last) ++j;
+                M += j;
+                if (j < take) break;
+            }
+        }
+    }
+    counts[3] = (int64_t)M;
+    if ((int64_t)M > out_capacity) return fail(c, FK_ERR_ARG, "fk_matchup_reduce: %llu groups selected, out_capacity is %lld", (unsigned long long)M, (long long)out_capacity);
+    if (M == 0) return FK_OK;
+    if (!out_digest || !out_seats || !out_count || !out_sums) return fail(c, FK_ERR_ARG, "the output arrays are required");
+    const size_t osizes[] = {8ul * M, 2ul * M * K, 8ul * M, 8ul * M * n_lags * fkm::SUM_COLS, 4ul * n_lags};
+    for (int i = 0; i < 5; ++i)
+        if ((rc = ensure(c, c->mr[29 + i], osizes[i]))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->mr[33].p, lags, 4ul * n_lags, hipMemcpyHostToDevice, st));
+    // 5. the lag sums of the selected groups: one wave per group
+    hipLaunchKernelGGL(fkm::fkm_group_sums, dim3((unsigned)((M * 64 + 255) / 256)), b256, 0, st, U32(27), (uint32_t)M, U32(21), U64(7), U16(8),
+                       U16(9), K, static_cast<const int32_t *>(c->mr[33].p), (uint32_t)n_lags, U64(29), U16(30),
+                       static_cast<long long *>(c->mr[31].p), static_cast<long long *>(c->mr[32].p));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_digest, c->mr[29].p, osizes[0], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_seats, c->mr[30].p, osizes[1], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_count, c->mr[31].p, osizes[2], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_sums, c->mr[32].p, osizes[3], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return FK_OK;
+}
+#undef FKM_CUB
 
 static int tournament_call(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
@@ -1736,7 +1947,8 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     // chunk planning: whole shuffles per chunk inside the workspace budget
     const size_t bytes_per_shuffle = (size_t)S * 2 + (size_t)gps * (game_workspace_bytes(k, plan.gs || want_state, want_recs, rows != nullptr) +
                                                                     (seat_stats ? (size_t)k * 32 : 0)) // + the exposure digests
-                                     + (lag ? (size_t)S * 2 : 0);                                        // + the lag value matrix row
+                                     + (lag ? (size_t)S * 2 : 0)                                         // + the lag value matrix row
+                                     + (lag && lag->m_digest ? (size_t)gps * (10 + 2 * (size_t)k) : 0);  // + the matchup records
     // (column images are larger than AoS rows: the workspace figure above counts 4 + 28 k bytes per game)
     uint64_t chunk_sh = std::max<uint64_t>(1, (uint64_t)workspace_budget(c) / bytes_per_shuffle);
     chunk_sh = std::min<uint64_t>(chunk_sh, (uint64_t)0x7fffffff / gps);
@@ -1760,6 +1972,13 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         if ((rc = ensure(c, c->lag_tmp, (size_t)std::max<uint32_t>(L, 1) * (size_t)S * 2))) return rc;
         HIPCHK(c, hipMemsetAsync(c->lag_out.p, 0, lag_sum_bytes, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->lag_lags.p, lag->lags, sizeof(int32_t) * (size_t)lag->n_lags, hipMemcpyHostToDevice, c->stream));
+    }
+    if (lag && lag->m_digest) { // matchup records of one chunk (copied to the caller's arrays behind it)
+        if ((rc = ensure(c, c->m_ids, sizeof(int32_t) * (size_t)S))) return rc;
+        if ((rc = ensure(c, c->m_dig, (size_t)chunk_sh * gps * 8))) return rc;
+        if ((rc = ensure(c, c->m_seat, (size_t)chunk_sh * gps * 2 * (size_t)k))) return rc;
+        if ((rc = ensure(c, c->m_rnd, (size_t)chunk_sh * gps * 2))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->m_ids.p, lag->ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
 
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
@@ -1956,6 +2175,15 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                                rows_per_seg, static_cast<const int32_t *>(c->lag_lags.p), (uint32_t)lag->n_lags,
                                static_cast<long long *>(c->lag_out.p));
             HIPCHK(c, hipGetLastError());
+            if (lag->m_digest) {
+                rc = launch_matchup_keys(c, (uint32_t)k, static_cast<const uint32_t *>(c->recs.p), static_cast<const uint16_t *>(CSET(c).perm.p),
+                                         slots, (uint32_t)S, gps, n_games, (uint32_t)lag->max_players);
+                if (rc) return rc;
+                const size_t g0 = (size_t)done * gps;
+                HIPCHK(c, hipMemcpyAsync(lag->m_digest + g0, c->m_dig.p, (size_t)n_games * 8, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(lag->m_seats + g0 * k, c->m_seat.p, (size_t)n_games * 2 * k, hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(c, hipMemcpyAsync(lag->m_rounds + g0, c->m_rnd.p, (size_t)n_games * 2, hipMemcpyDeviceToHost, c->stream));
+            }
             uint16_t *edge = static_cast<uint16_t *>(c->lag_edge.p);
             if (head_filled < edge_rows) { // the first rows of the call's range (they may span chunks shorter than the largest lag)
                 const uint32_t take = std::min<uint32_t>(edge_rows - head_filled, n_sh);

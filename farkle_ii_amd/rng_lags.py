@@ -11,8 +11,7 @@ that straddle the cut from ``a``'s last and ``b``'s first ``max(lags)`` observat
 batches each) combine this way, in range order.  :func:`strategy_lag_rows` turns a summary into the rows ``_rows_for_online_group``
 writes (:2110-2160) with ``_OnlineMetric.result``'s arithmetic (:2066-2076).
 
-The MATCHUP family of the same module (one group per sorted seat tuple, O(games) groups) has no pre-aggregation; it keeps reading
-rows (``farkle run`` rows mode)."""
+The MATCHUP family of the same module (one group per sorted seat tuple) is ``rng_matchups.py``."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -141,11 +140,11 @@ STATS_NOTE = ("Zero-centered approximate descriptive reference band only; values
               "refute independence")  # _EXPECTED_NOTE, rng_diagnostics.py:80-83
 
 
-def lag_stats_table(summary: LagSummary, strategy_ids: Sequence[int], k: int):
-    """The strategy-level rows in the reference's ``_stats_schema`` (rng_diagnostics.py:2079-2098)."""
+def stats_schema():
+    """The reference's ``_stats_schema`` (rng_diagnostics.py:2079-2098)."""
     import pyarrow as pa
 
-    schema = pa.schema([
+    return pa.schema([
         pa.field("summary_level", pa.string(), nullable=False), pa.field("strategy", pa.int32()), pa.field("matchup_id", pa.uint64()),
         pa.field("matchup", pa.string()), pa.field("participant_strategy_ids", pa.list_(pa.int32())),
         pa.field("n_players", pa.int16(), nullable=False), pa.field("observations", pa.int64(), nullable=False),
@@ -155,4 +154,10 @@ def lag_stats_table(summary: LagSummary, strategy_ids: Sequence[int], k: int):
         pa.field("zero_centered_descriptive_reference_band_lower", pa.float64()),
         pa.field("zero_centered_descriptive_reference_band_upper", pa.float64()),
         pa.field("sequence_order", pa.string(), nullable=False), pa.field("note", pa.string(), nullable=False)])
-    return pa.Table.from_pylist(strategy_lag_rows(summary, strategy_ids, k, note=STATS_NOTE), schema=schema)
+
+
+def lag_stats_table(summary: LagSummary, strategy_ids: Sequence[int], k: int):
+    """The strategy-level rows in the reference's ``_stats_schema`` (rng_diagnostics.py:2079-2098)."""
+    import pyarrow as pa
+
+    return pa.Table.from_pylist(strategy_lag_rows(summary, strategy_ids, k, note=STATS_NOTE), schema=stats_schema())

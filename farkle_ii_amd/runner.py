@@ -559,11 +559,13 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                    resume: bool, checkpoint_metadata: "Mapping[str, Any] | Callable[[], Mapping[str, Any]]", oracle_game_profile: GameProfile | None = None,
                    all_player_dir: Path | None = None, sidecars: "_Sidecars | None" = None,
                    rng_lags: Sequence[int] | None = None, defer_final_checkpoint: bool = False, packed_table: np.ndarray | None = None,
-                   defer_tail: list | None = None) -> dict:
+                   defer_tail: list | None = None, rng_matchups: int | None = None) -> dict:
     """Play every deterministic batch not yet owned by the checkpoint and persist the aggregates.  ``defer_final_checkpoint``: the final
     checkpoint's file write may still be in flight on return — the caller joins ``result["checkpoint_written"]`` before reading the file.  ``rng_lags``: also accumulate the lag
     sufficient statistics of the RNG diagnostics' strategy family over the WHOLE shuffle range (``fk_tournament_run_lags``; launch
-    groups and ranks are contiguous ranges that merge in order, rng_lags.LagSummary) — returned as ``result["lag_summary"]``."""
+    groups and ranks are contiguous ranges that merge in order, rng_lags.LagSummary) — returned as ``result["lag_summary"]``.
+    ``rng_matchups`` (= ``combine.max_players``; needs ``rng_lags``): the same calls also return the per-game records of the matchup
+    family (``fk_tournament_run_matchups``), gathered to rank 0 in range order — ``result["matchup_records"]``."""
     rank, world = _rank_world()
     _trace(f"{n_players}p run_tournament")
     eng = get_engine()
@@ -652,6 +654,9 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
     pending = [b for b in range(n_batches) if b not in done_batches]
     shard_identities: dict[str, tuple[int, str]] = {}
     lag_total = None
+    matchup_parts: list = []
+    if rng_matchups and not rng_lags:
+        raise ValueError("the matchup family is played in the lag mode: rng_matchups needs rng_lags")
     if rng_lags:
         if done_batches:  # a strategy's series runs over every shuffle of the root: a partial replay cannot rebuild it
             raise ValueError("lag statistics need the whole shuffle range of the run; this checkpoint already owns batches: use --force")
@@ -747,6 +752,11 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                 for piece in parts:
                     if piece is not None:
                         lag_total = piece if lag_total is None else lag_total.merge(piece)
+        if rng_matchups:  # the group's per-game records in rank order = coordinate order (contiguous whole batches per rank)
+            rec = res["matchups"] if hi > lo else None
+            recs = gather_objects(rec, dst=0) if world > 1 else [rec]
+            if rank == 0:
+                matchup_parts.extend(r for r in recs if r is not None)
         group = reduce_tally(local, dst=0)
         group_stats = reduce_tally(local_stats, dst=0) if local_stats is not None else None  # integer sums, like the tally
         # the float64 sums: a deterministic batch is played whole by ONE rank (the others hold +0.0 = all-zero bits), so the int64 SUM of
@@ -845,6 +855,9 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             if g["slot"] is not None:
                 eng._pinned_columns["jobs"][g["slot"]] = shard_job
             return {"res": res, "shard_job": shard_job}
+        elif rng_matchups:
+            res = eng.tournament_matchups(table, k, cfg.sim.seed, lo, hi, rng_lags, np.asarray(ids, dtype=np.int32), rng_matchups,
+                                          shuffles_per_batch=batch_arg, target_score=target, max_rounds=max_rounds, overrides=ov)
         elif rng_lags:
             res = eng.tournament_lags(table, k, cfg.sim.seed, lo, hi, rng_lags, shuffles_per_batch=batch_arg, target_score=target,
                                       max_rounds=max_rounds, overrides=ov)
@@ -1017,7 +1030,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
       if awaiting_post is not None:
           previous, awaiting_post = awaiting_post, None
           post(*previous)
-      if not (defer_tail is not None and world == 1):
+      if not (defer_tail is not None and world == 1) or rng_matchups:  # (the matchup reduce below is an engine call: never deferred)
           while in_flight:
               finish(**in_flight.popleft())
     finally:
@@ -1047,6 +1060,11 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                     sidecars.write("shard_manifest", manifest)
         barrier()
         result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total)
+        if rng_matchups and rank == 0:  # the grouped reduce of the whole (root, k), on this thread's engine
+            from .rng_matchups import concat_records, effective_cap
+
+            records = concat_records(matchup_parts, k)
+            result["matchup_reduce"] = eng.matchup_reduce(records, k, rng_lags, effective_cap(cfg.rng_max_matchup_groups()))
         return result
 
     if last_groups:  # (only with defer_tail, one process): the caller runs it — run_multi on its publisher thread, under the next count
@@ -1076,6 +1094,9 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if cfg.sim.rng_lag_sums and not (cfg.rng_lag_sums_path(n).exists() and cfg.rng_lag_stats_path(n).exists()):
             raise ValueError(f"{n}p is already complete without {cfg.rng_lag_sums_path(n).name}: --rng-lag-sums needs every shuffle of the "
                              "run; use --force to replay it with the lag statistics")
+        if cfg.sim.rng_matchup_lags and not cfg.rng_matchup_groups_path(n).exists():
+            raise ValueError(f"{n}p is already complete without {cfg.rng_matchup_groups_path(n).name}: --rng-matchup-lags needs every "
+                             "game of the run; use --force to replay it with the matchup records")
         LOGGER.info("Simulation already complete; preserving published outputs for %sp", n)
         return plan.required_games
     plan_path = n_dir / "simulation_workload_plan.json"
@@ -1093,7 +1114,7 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
     if rank == 0:
         if force:
             for path in (ckpt_path, n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), simulation_done_path(cfg, n),
-                         cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n)):
+                         cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n)):
                 path.unlink(missing_ok=True)
                 path.with_name(path.name + ".sidecar.json").unlink(missing_ok=True)
             for d in (row_dir, metric_chunk_dir, all_player_dir):
@@ -1143,7 +1164,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             resume=not force, checkpoint_metadata=lambda: {"strategy_manifest_sha": shared.manifest_sha},
                             oracle_game_profile=oracle_game_profile, all_player_dir=all_player_dir, sidecars=sidecars,
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
-                            packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None)
+                            packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
+                            rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None)
     finally:
         if published is not None:
             published.result()  # the inputs are on disk (or their error is raised) before the summaries and the stamp name them
@@ -1165,6 +1187,47 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
     return plan.required_games
 
 
+def _matchup_max_players(cfg: AppConfig, n: int) -> int:
+    """``combine.max_players``, the width of the matchup key: it must seat every player count of the run."""
+    mp = cfg.combine_max_players()
+    cfg.rng_max_matchup_groups(), cfg.rng_diagnostic_partitions()  # (validated before anything plays)
+    if mp < max(int(v) for v in [*cfg.sim.n_players_list, n]):
+        raise ValueError(f"combine.max_players = {mp} is smaller than the largest player count of n_players_list")
+    return mp
+
+
+def _publish_rng_matchups(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], result: dict) -> None:
+    """``<n>p_rng_matchup_groups.parquet`` (this player count's top-cap eligible matchup groups, its counts and histogram), and once
+    every player count of the run has its file, the root's selection across them: ``rng_matchup_lag_stats.parquet`` and
+    ``rng_group_selection.json`` (rng_matchups.select)."""
+    import json
+
+    import pyarrow.parquet as pq
+
+    from . import rng_matchups as rm
+
+    lags = cfg.rng_diagnostic_lags()
+    cap = rm.effective_cap(cfg.rng_max_matchup_groups())
+    mp = _matchup_max_players(cfg, n)
+    ids = np.asarray([int(s.strategy_id) for s in strategies], dtype=np.int32)
+    groups = rm.MatchupGroups.from_reduce(result["matchup_reduce"], ids, mp, cap)
+    groups.extra = {"root_seed": int(cfg.sim.seed), "n_strategies": len(ids), "n_shuffles": int(result["lag_summary"].n)}
+    _write_parquet_atomic(groups.to_table(), cfg.rng_matchup_groups_path(n))
+    counts, _ = _filter_player_counts(list(cfg.sim.n_players_list), len(ids))
+    paths = [cfg.rng_matchup_groups_path(int(v)) for v in counts]
+    if not all(p.exists() for p in paths):
+        return
+    per_k = [rm.MatchupGroups.from_table(pq.read_table(p)) for p in paths]
+    if any(g.extra.get("root_seed") != int(cfg.sim.seed) or tuple(g.lags) != tuple(lags) or g.max_players != mp for g in per_k):
+        raise ValueError("the per-player-count matchup files of this root were written with other settings: replay them with --force")
+    strategies_family = [rm.StrategyFamily(g.k, int(g.extra["n_strategies"]), int(g.extra["n_shuffles"])) for g in per_k]
+    rows, report = rm.select(per_k, strategies_family, lags, cap, cfg.rng_diagnostic_partitions())
+    _write_parquet_atomic(rm.stats_table(rows), cfg.rng_matchup_stats_path())
+    tmp = cfg.rng_group_selection_path().with_suffix(".json.tmp")
+    tmp.write_text(json.dumps(report, indent=2, sort_keys=False) + "\n", encoding="utf-8")
+    os.replace(tmp, cfg.rng_group_selection_path())
+
+
 def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], plan: TournamentWorkloadPlan, result: dict, grid_size: int,
                      ckpt_path: Path, n_dir: Path, sidecars: "_Sidecars", oracle_game_profile: GameProfile | None) -> None:
     """What follows the last launch of a player count on rank 0: lag tables, summary / metrics parquets, the completion stamp."""
@@ -1178,6 +1241,8 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
 
         _write_parquet_atomic(lag_sums_table(result["lag_summary"], ids, cfg.sim.seed, n), cfg.rng_lag_sums_path(n))
         _write_parquet_atomic(lag_stats_table(result["lag_summary"], ids, n), cfg.rng_lag_stats_path(n))
+    if cfg.sim.rng_matchup_lags and result.get("matchup_reduce") is not None:
+        _publish_rng_matchups(cfg, n, strategies, result)
     # (A) summary parquet, (B) expanded metrics parquet — column order, types and values as in runner.py:1612-1712, built column by
     # column from the tally (the per-strategy dict loop cost 25 us per strategy and table: 140 ms of a 330-ms config-3 run).  Rows in
     # the reference's order: strategies sorted by the STRING of their id, those without an attempted exposure left out.
@@ -1249,14 +1314,16 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
     outputs: list[Path] = [ckpt_path, n_dir / "simulation_workload_plan.json"]  # the order of simulation/runner.py:1714-1727
     for extra in (n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), cfg.strategy_manifest_root_path(),
                   cfg.simulation_row_dir(n), cfg.metric_chunk_dir(n), cfg.all_player_batch_dir(n),
-                  cfg.rng_lag_sums_path(n) if cfg.sim.rng_lag_sums else None, cfg.rng_lag_stats_path(n) if cfg.sim.rng_lag_sums else None):
+                  cfg.rng_lag_sums_path(n) if cfg.sim.rng_lag_sums else None, cfg.rng_lag_stats_path(n) if cfg.sim.rng_lag_sums else None,
+                  cfg.rng_matchup_groups_path(n) if cfg.sim.rng_matchup_lags else None):
         if extra is not None and Path(extra).exists():
             outputs.append(Path(extra))
     if sidecars.v3 is not None:
         # the authenticated completion (write_simulation_done -> write_v3_stage_completion, release_identity.py:1227-1284): the reference's
         # output inventory only — every entry has a contract-v3 sidecar, shard directories stand as their sealed manifests; this engine's
         # extra outputs (all-player batches, lag statistics) are not part of the stage the reference's consumers authenticate
-        reference_outputs = [p for p in outputs if p not in (cfg.all_player_batch_dir(n), cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n))]
+        reference_outputs = [p for p in outputs if p not in (cfg.all_player_batch_dir(n), cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n),
+                                                             cfg.rng_matchup_groups_path(n))]
         sidecars.v3.write_completion(done_path, sc.completion_output_files(reference_outputs, done_path))
         return
     engine_config_sha = config_hash(cfg)

@@ -295,12 +295,40 @@ int fk_tournament_hint_next(fk_ctx *ctx, uint64_t shuffle_begin, uint64_t shuffl
  *               shuffles of the range, strategy-minor.  Two ranges that follow each other (launch groups, ranks: contiguous whole
  *               batches per rank) combine on the host: sums add, plus the pairs that straddle the cut, which need exactly the
  *               tail of the earlier and the head of the later range (farkle_ii_amd/rng_lags.py: LagSummary.merge).
- * The matchup family of the same module (one group per seat TUPLE, O(games) groups) has no pre-aggregation and keeps reading rows.
+ * The matchup family of the same module is fk_tournament_run_matchups + fk_matchup_reduce below.
  * Requires max_rounds (and every override) <= 32767. */
 int fk_tournament_run_lags(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
                            int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags,
                            int64_t *lag_sums, uint16_t *edge_head, uint16_t *edge_tail);
+
+/* fk_tournament_run_lags (same outputs) + one record per game for the MATCHUP family of the RNG diagnostics
+ * (analysis/rng_diagnostics.py: group key _extract_batch_arrays :1092-1150, digest _matchup_ids :1173-1185).  Records are in
+ * coordinate order (shuffle-major, game within shuffle), game g of the range at index g:
+ *   m_digest   uint64 [n_games]: blake2b(int32 LE [k, sorted seat strategy IDs, -1 padding to max_players], digest_size=8,
+ *              person=b"farkle-m"), read little-endian
+ *   m_seats    uint16 [n_games][k]: the seats' TABLE indices, ordered by ascending strategy_ids[index]
+ *   m_rounds   uint16 [n_games]: n_rounds (15 bits; safety-limit games included)
+ *   strategy_ids  int32 [S], unique: the IDs the digest and the order use; 1 <= k <= 16, k <= max_players <= 31. */
+int fk_tournament_run_matchups(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                               uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                               int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags,
+                               int64_t *lag_sums, uint16_t *edge_head, uint16_t *edge_tail, const int32_t *strategy_ids, int32_t max_players,
+                               uint64_t *m_digest, uint16_t *m_seats, uint16_t *m_rounds);
+
+/* The matchup groups of one (root, k): the records of fk_tournament_run_matchups of the WHOLE range, in coordinate order
+ * (n_obs < 2^31).  Groups are equal seat tuples; a group's series is its n_rounds in record order.
+ *   counts      int64 [4]: observations, candidate groups, eligible groups (count >= lags[0] + 2), returned groups M
+ *   histogram   uint64 [lags[0] + 2 + 64]: groups per _observation_histogram_bin code (rng_diagnostics.py:1568)
+ *   cap         > 0: return the `cap` eligible groups of least priority (_priority :1281, group_type 1) and every group whose
+ *               priority equals the last one's (the caller breaks such ties by the rest of the tuple); <= 0: every eligible group
+ *   out_*       [out_capacity] groups in ascending priority: digest, m_seats tuple (uint16 [k]), count, and per lag the int64 sums
+ *               out_sums [M][n_lags][6]: pairs, sum x, sum y, sum x^2, sum y^2, sum xy (x = observation i - lag, y = i)
+ * M > out_capacity returns FK_ERR_ARG with counts[3] = M.  Option "matchup_sort_key_mask" (tests): the digest bits the sort uses;
+ * groups stay exact (digest-collision runs are split by tuple). */
+int fk_matchup_reduce(fk_ctx *ctx, int32_t k, int64_t n_obs, const uint64_t *digest, const uint16_t *seats, const uint16_t *rounds,
+                      const int32_t *lags, int32_t n_lags, int64_t cap, int64_t out_capacity, int64_t *counts, uint64_t *histogram,
+                      uint64_t *out_digest, uint16_t *out_seats, int64_t *out_count, int64_t *out_sums);
 
 /* Explicit game list: game g seats strategies table[seat_strategy[g*k+i]] with streams coords[g](seat i).
  * rows: n_games * (4+28k) bytes (required). */
