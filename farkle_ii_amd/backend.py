@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -107,7 +107,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
 
 
 _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_get_timing", "fk_set_option",
-            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
+            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance"]
@@ -337,6 +337,50 @@ class Engine:
         return {"tally": tally[:n_batches], "rows": rows, "perms": perms,
                 "seat_stats": None if stats is None else stats[:n_batches],
                 "seat_ratio_sums": None if ratios is None else ratios[:n_batches]}
+
+    def tournament_game_stats(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
+                              shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                              overrides: np.ndarray | None = None, rare_target_score: int = 10_000, want_seat_stats: bool = False,
+                              spill_capacity: int = 4096) -> dict:
+        """``tournament`` + the game-stats stage's sufficient statistics of the range (``fk_tournament_run_game_stats``), with the
+        all-player arrays of ``tournament(..., want_seat_stats=True)`` from the same launch when ``want_seat_stats``.  ``game_stats``
+        holds int64 ``strategy_counts [S][4]``, ``strategy_rounds [S][R + 1]`` (R = max(max_rounds, every override)),
+        ``strategy_runner`` / ``strategy_spread [S][M]`` (margin / 50), ``game_counts [4]``, ``game_rounds [R + 1]``, ``game_runner [M]``:
+        the device's spill entries already merged (``game_stats.merge_spills``)."""
+        from .game_stats import DEVICE_MARGIN_BINS, DEVICE_ROUNDS_BINS, merge_spills
+
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        S = len(table)
+        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
+        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
+        n_batches = (n_sh + spb - 1) // spb
+        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        R = max([int(max_rounds)] + [int(v) for v in ov["max_rounds"]])
+        rb, mb = min(R + 1, DEVICE_ROUNDS_BINS), DEVICE_MARGIN_BINS
+        capacity = max(int(spill_capacity), 0)
+        while True:
+            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            stats = np.zeros((max(n_batches, 1), S, SEAT_STAT_COLS), dtype=np.int64) if want_seat_stats else None
+            ratios = np.zeros((max(n_batches, 1), S, SEAT_RATIO_COLS), dtype=np.float64) if want_seat_stats else None
+            g = {"strategy_counts": np.zeros((S, 4), np.int64), "strategy_rounds": np.zeros((S, rb), np.int64),
+                 "strategy_runner": np.zeros((S, mb), np.int64), "strategy_spread": np.zeros((S, mb), np.int64),
+                 "game_counts": np.zeros(4, np.int64), "game_rounds": np.zeros(rb, np.int64), "game_runner": np.zeros(mb, np.int64)}
+            spill = np.zeros((max(capacity, 1), 3), dtype=np.int32)
+            spilled = C.c_int64(0)
+            rc = self._lib.fk_tournament_run_game_stats(
+                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
+                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
+                _p(tally), None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
+                _p(g["strategy_counts"]), _p(g["strategy_rounds"]), _p(g["strategy_runner"]), _p(g["strategy_spread"]),
+                _p(g["game_counts"]), _p(g["game_rounds"]), _p(g["game_runner"]), C.c_int64(capacity), C.byref(spilled), _p(spill))
+            if rc == FK_ERR_ARG and spilled.value > capacity:  # more values outside the windows than room: once more with room for all
+                capacity = int(spilled.value)
+                continue
+            self._check(rc)
+            break
+        return {"tally": tally[:n_batches], "seat_stats": None if stats is None else stats[:n_batches],
+                "seat_ratio_sums": None if ratios is None else ratios[:n_batches], "spilled": int(spilled.value),
+                "game_stats": merge_spills(g, spill[:spilled.value], R + 1)}
 
     def tournament_columns(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, strategy_ids,
                            shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,

@@ -44,6 +44,12 @@ def build_parser() -> argparse.ArgumentParser:
                           "n_rounds, grouped on the device; per player count <k>p_rng_matchup_groups.parquet (its top "
                           "analysis.rng_max_matchup_groups eligible groups with their lag sums, counts and histogram), after the last "
                           "player count rng_matchup_lag_stats.parquet and rng_group_selection.json at the results root")
+    run.add_argument("--game-stats", action="store_true",
+                     help="Write the game-stats stage's tables from device histograms, without rows: per player count "
+                          "<k>p_game_stats.parquet (per-strategy and per-k game length, runner-up margin, score spread and close-game "
+                          "rates) and <k>p_game_stats_sums.parquet (the exact histograms), after the last player count "
+                          "game_stats_rare_event_summary.parquet at the results root (analysis.game_stats_margin_thresholds, "
+                          "analysis.rare_event_target_score).  Not resumable: an interrupted run asks for --force")
     run.add_argument("--sidecars", action="store_true",
                      help="Write <artifact>.sidecar.json (producer contract + SHA-256 / size of the artifact) beside every output")
     run.add_argument("--code-identity", metavar="COMMIT[:DIRTY_SHA256[:POLICY]]",
@@ -115,6 +121,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.all_player_batch_dir = args.all_player_batches
     if args.rng_lag_sums:
         cfg.sim.rng_lag_sums = True
+    if args.game_stats:
+        cfg.sim.game_stats = True
     if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
         cfg.sim.rng_lag_sums = cfg.sim.rng_matchup_lags = True
     _maybe_init_distributed()

@@ -64,6 +64,7 @@ class SimConfig:
     all_player_batch_dir: Path | None = None  # this engine's option: all-player batch metrics without rows (all_player.py)
     rng_lag_sums: bool = False  # this engine's option: lag sufficient statistics of the RNG diagnostics' strategy family (rng_lags.py)
     rng_matchup_lags: bool = False  # this engine's option: the RNG diagnostics' matchup family + group selection (rng_matchups.py)
+    game_stats: bool = False  # this engine's option: the game-stats stage's per-k tables and rare-event summary without rows (game_stats.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
     mp_start_method: str | None = None
@@ -166,6 +167,37 @@ class AppConfig:
         if not lags or any(v < 1 for v in lags) or tuple(sorted(set(lags))) != lags:
             raise ValueError("analysis.rng_diagnostic_lags must be unique increasing positive integers")
         return lags
+
+    def game_stats_margin_thresholds(self) -> tuple[int, ...]:
+        """``analysis.game_stats_margin_thresholds`` (config.py:323, default (500, 1000)): integers, one column pair each."""
+        raw = (self.opaque.get("analysis") or {}).get("game_stats_margin_thresholds", (500, 1000))
+        if isinstance(raw, (str, bytes)) or not hasattr(raw, "__iter__"):
+            raise ValueError("analysis.game_stats_margin_thresholds must be a list of integers")
+        values = tuple(raw)
+        if any(isinstance(v, bool) or not isinstance(v, int) for v in values):
+            raise ValueError("analysis.game_stats_margin_thresholds must be a list of integers")
+        return tuple(int(v) for v in values)
+
+    def rare_event_target_score(self) -> int:
+        """``analysis.rare_event_target_score`` (config.py:325, default 10 000).  The quantile-resolved rare-event thresholds
+        (``rare_event_margin_quantile`` / ``rare_event_target_rate``) need the per-game rows: they are refused here."""
+        analysis = self.opaque.get("analysis") or {}
+        for key in ("rare_event_margin_quantile", "rare_event_target_rate"):
+            if analysis.get(key) is not None:
+                raise ValueError(f"analysis.{key} resolves its threshold from per-game rows: --game-stats supports fixed thresholds only")
+        value = analysis.get("rare_event_target_score", 10_000)
+        if isinstance(value, bool) or not isinstance(value, int) or not -(2 ** 31) <= value < 2 ** 31:
+            raise ValueError("analysis.rare_event_target_score must be a 32-bit integer")
+        return int(value)
+
+    def game_stats_path(self, n: int) -> Path:
+        return self.n_dir(n) / f"{n}p_game_stats.parquet"
+
+    def game_stats_sums_path(self, n: int) -> Path:
+        return self.n_dir(n) / f"{n}p_game_stats_sums.parquet"
+
+    def game_stats_rare_summary_path(self) -> Path:
+        return self.results_root / "game_stats_rare_event_summary.parquet"
 
     def rng_max_matchup_groups(self) -> int | None:
         """``analysis.rng_max_matchup_groups`` (config.py:333, validated like :1928-1932): ``None`` or a positive integer."""

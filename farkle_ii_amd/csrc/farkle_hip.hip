@@ -9,6 +9,7 @@
 #include "fk_perm_wave.h"    // device side: a shuffle's Fisher-Yates draws by a whole wave (small launches)
 #include "fk_row_columns_seats.h" // device side: column images with one thread per (game, seat)
 #include "fk_matchups.h"      // device side: RNG-diagnostics matchup family (key post-pass, grouped lag reduce)
+#include "fk_game_stats.h"    // device side: game-stats stage (game-record pass, per-strategy LDS histogram gather)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -68,6 +69,17 @@ struct ChunkSet {
     bool side = false; // prepared on the side stream: its event intervals include waiting behind a game kernel
     ChunkDesc desc;
     SeedArgs sa{}; // the prepared chunk's buffers as the kernels see them
+};
+
+// fk_tournament_run_game_stats: host pointers of the request (histogram rows of rounds_bins / margin_bins int64 each)
+struct GameStatsReq {
+    int64_t rare_target;
+    uint32_t rounds_bins, margin_bins;
+    int64_t *s_counts, *s_rounds, *s_runner, *s_spread; // [S][4], [S][rounds_bins], [S][margin_bins] x 2
+    int64_t *g_counts, *g_rounds, *g_runner;           // [4], [rounds_bins], [margin_bins]
+    int64_t spill_capacity;
+    int64_t *spill_count; // entries the call produced (also when they did not fit)
+    int32_t *spill;       // [spill_capacity][3]
 };
 
 struct fk_ctx {
@@ -132,6 +144,9 @@ struct fk_ctx {
     DevBuf m_ids, m_dig, m_seat, m_rnd;  // fk_tournament_run_matchups: strategy IDs, one chunk's game records
     DevBuf mr[36];                       // fk_matchup_reduce: records, sort keys / values, segments, selection, hipcub scratch
     uint64_t matchup_sort_mask = ~0ull;  // option "matchup_sort_key_mask": the bits of the digest the reduce sorts by (tests)
+    DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
+    int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
+    const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
     int32_t columns_by_seat = -1; // column images: -1 one thread per (game, seat) up to sixteen seats, per game beyond; 0 per game; 1 per (game, seat)
@@ -1480,6 +1495,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "pipeline") c->pipeline = (int32_t)value;
     else if (n == "uniform_flags") c->uniform_flags_opt = (int32_t)value;
     else if (n == "matchup_sort_key_mask") c->matchup_sort_mask = (uint64_t)value;
+    else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
             return fail(c, FK_ERR_ARG, "block must be 0, 64, 128, 256, 512, 768 (lean records only) or 1024");
@@ -1631,6 +1647,30 @@ int fk_tournament_run_all_player(fk_ctx *c, const fk_strategy *strategies, int32
     if (!seat_stats || !seat_ratio_sums) return fail(c, FK_ERR_ARG, "seat_stats and seat_ratio_sums are required");
     return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
                            tally, rows, perms, seat_stats, nullptr, seat_ratio_sums);
+}
+
+int fk_tournament_run_game_stats(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                 int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                                 int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
+                                 int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
+                                 int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
+                                 int64_t spill_capacity, int64_t *spill_count, int32_t *spill) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_counts || !strategy_rounds || !strategy_runner || !strategy_spread || !game_counts || !game_rounds || !game_runner || !spill_count)
+        return fail(c, FK_ERR_ARG, "the game-stat outputs and spill_count are required");
+    if (seat_ratio_sums && !seat_stats) return fail(c, FK_ERR_ARG, "seat_ratio_sums needs seat_stats");
+    if (rounds_bins < 1 || rounds_bins > (int32_t)fkg::MAX_ROUNDS_BINS || margin_bins < 1 || margin_bins > (int32_t)fkg::MAX_MARGIN_BINS)
+        return fail(c, FK_ERR_ARG, "rounds_bins must be in [1, %u] and margin_bins in [1, %u]", fkg::MAX_ROUNDS_BINS, fkg::MAX_MARGIN_BINS);
+    if (spill_capacity < 0 || (spill_capacity > 0 && !spill)) return fail(c, FK_ERR_ARG, "spill_capacity must be >= 0, with a spill buffer when > 0");
+    *spill_count = 0;
+    const GameStatsReq req{rare_target_score, (uint32_t)rounds_bins, (uint32_t)margin_bins, strategy_counts, strategy_rounds, strategy_runner,
+                           strategy_spread, game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill};
+    c->gstats = &req;
+    const int rc = tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov,
+                                   n_ov, tally, rows, perms, seat_stats, nullptr, seat_ratio_sums);
+    c->gstats = nullptr;
+    return rc;
 }
 
 int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
@@ -1929,7 +1969,8 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k * 16);
         if (rc) return rc;
     }
-    const bool want_state = rows != nullptr || seat_stats != nullptr;
+    const GameStatsReq *gst = c->gstats; // fk_tournament_run_game_stats (null otherwise)
+    const bool want_state = rows != nullptr || seat_stats != nullptr || gst != nullptr;
     const bool want_recs = !plan.lds_tally || want_state || lag != nullptr;
     const size_t stats_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_SEAT_STAT_COLS;
     if (seat_stats) {
@@ -1948,7 +1989,8 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     const size_t bytes_per_shuffle = (size_t)S * 2 + (size_t)gps * (game_workspace_bytes(k, plan.gs || want_state, want_recs, rows != nullptr) +
                                                                     (seat_stats ? (size_t)k * 32 : 0)) // + the exposure digests
                                      + (lag ? (size_t)S * 2 : 0)                                         // + the lag value matrix row
-                                     + (lag && lag->m_digest ? (size_t)gps * (10 + 2 * (size_t)k) : 0);  // + the matchup records
+                                     + (lag && lag->m_digest ? (size_t)gps * (10 + 2 * (size_t)k) : 0)   // + the matchup records
+                                     + (gst ? (size_t)gps * 16 : 0);                                      // + the game-stat records
     // (column images are larger than AoS rows: the workspace figure above counts 4 + 28 k bytes per game)
     uint64_t chunk_sh = std::max<uint64_t>(1, (uint64_t)workspace_budget(c) / bytes_per_shuffle);
     chunk_sh = std::min<uint64_t>(chunk_sh, (uint64_t)0x7fffffff / gps);
@@ -1979,6 +2021,23 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         if ((rc = ensure(c, c->m_seat, (size_t)chunk_sh * gps * 2 * (size_t)k))) return rc;
         if ((rc = ensure(c, c->m_rnd, (size_t)chunk_sh * gps * 2))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->m_ids.p, lag->ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
+    }
+
+    // game statistics (fk_tournament_run_game_stats): g_out = u64 [S][4] counts | [S][rb] rounds | [S][mb] runner-up | [S][mb] spread |
+    // [4] game counts | [rb] game rounds | [mb] game runner-up | spill count, then the spill entries (int32 [cap][3])
+    const uint32_t g_rb = gst ? gst->rounds_bins : 0u, g_mb = gst ? gst->margin_bins : 0u;
+    const uint32_t g_wr = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(g_rb, c->game_stats_window) : g_rb;
+    const uint32_t g_wm = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(g_mb, c->game_stats_window) : g_mb;
+    const size_t g_sc = 0, g_sr = g_sc + (size_t)S * fkg::N_COUNTS, g_sru = g_sr + (size_t)S * g_rb, g_ssp = g_sru + (size_t)S * g_mb,
+                 g_gc = g_ssp + (size_t)S * g_mb, g_gr = g_gc + fkg::N_COUNTS, g_gru = g_gr + g_rb, g_cnt = g_gru + g_mb, g_u64 = g_cnt + 1;
+    fkg::Spill g_spill{};
+    if (gst) {
+        if ((rc = ensure(c, c->g_rec, (size_t)chunk_sh * gps * 16))) return rc;
+        if ((rc = ensure(c, c->g_out, g_u64 * 8 + (size_t)std::max<int64_t>(gst->spill_capacity, 1) * 12))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->g_out.p, 0, g_u64 * 8, c->stream));
+        g_spill.count = static_cast<unsigned long long *>(c->g_out.p) + g_cnt;
+        g_spill.entries = reinterpret_cast<int32_t *>(static_cast<unsigned long long *>(c->g_out.p) + g_u64);
+        g_spill.cap = (uint64_t)gst->spill_capacity;
     }
 
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
@@ -2129,12 +2188,32 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             hipLaunchKernelGGL(fk_invert_sched_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
                                static_cast<const uint32_t *>(CSET(c).order.p), n_games, static_cast<uint32_t *>(c->inv.p));
         }
-        if (seat_stats) {
+        if (seat_stats || gst) {
             rc = ensure(c, CSET(c).draws, (size_t)perm_blocks * S * slots * 2); // the draws buffer is free again: inverse permutations
             if (rc) return rc;
             const uint32_t cells = perm_blocks * (uint32_t)S * slots;
             hipLaunchKernelGGL(fk_invert_perm_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, c->stream,
                                static_cast<const uint16_t *>(CSET(c).perm.p), (uint32_t)S, slots, n_sh, static_cast<uint16_t *>(CSET(c).draws.p));
+        }
+        if (gst) {
+            // phase 1, game-major: one 16-byte record per game + the game-level histograms; phase 2 gathers them per strategy
+            unsigned long long *o = static_cast<unsigned long long *>(c->g_out.p);
+            const uint32_t rec_grid = std::max<uint32_t>(1u, std::min<uint32_t>((n_games + 255u) / 256u, 2048u));
+            hipLaunchKernelGGL(fkg::fk_game_record_kernel, dim3(rec_grid), dim3(256), (size_t)(g_wr + g_wm + fkg::N_COUNTS) * 4, c->stream,
+                               static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
+                               scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr, n_games, gps, n_sh, (uint32_t)k, gst->rare_target,
+                               g_wr, g_wm, static_cast<uint4 *>(c->g_rec.p), o + g_gc, o + g_gr, o + g_gru, g_spill);
+            // (strategy, segment) workgroups: enough of them to fill the chip, at least 256 shuffles (one per lane) per segment
+            const uint32_t want_seg = std::max<uint32_t>(1u, (2048u + (uint32_t)S - 1u) / (uint32_t)S);
+            const uint32_t rows_per_seg = std::max<uint32_t>(256u, (n_sh + want_seg - 1u) / want_seg);
+            const uint32_t n_seg = (n_sh + rows_per_seg - 1u) / rows_per_seg;
+            hipLaunchKernelGGL(fkg::fk_game_stats_gather_kernel, dim3((uint32_t)S, n_seg), dim3(256), (size_t)(g_wr + 2 * g_wm + fkg::N_COUNTS) * 4,
+                               c->stream, static_cast<const uint4 *>(c->g_rec.p), static_cast<const uint16_t *>(CSET(c).draws.p), slots,
+                               (uint32_t)S, (uint32_t)k, gps, n_sh, rows_per_seg, g_wr, g_wm, g_rb, g_mb, o + g_sc, o + g_sr, o + g_sru, o + g_ssp,
+                               g_spill);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (seat_stats) {
             const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
             const uint32_t nb = (uint32_t)((done + n_sh - 1) / shuffles_per_batch) - first_batch + 1u;
             const uint32_t s_blocks = ((uint32_t)S + 255u) / 256u;
@@ -2297,6 +2376,16 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     if (seat_stats) HIPCHK(c, hipMemcpyAsync(seat_stats, c->stats.p, stats_bytes, hipMemcpyDeviceToHost, c->stream));
     if (seat_ratios) HIPCHK(c, hipMemcpyAsync(seat_ratios, c->ratios.p, ratio_bytes, hipMemcpyDeviceToHost, c->stream));
+    int64_t g_spilled = 0;
+    if (gst) {
+        const uint8_t *o = static_cast<const uint8_t *>(c->g_out.p);
+        const std::pair<int64_t *, std::pair<size_t, size_t>> parts[] = {
+            {gst->s_counts, {g_sc, (size_t)S * fkg::N_COUNTS}}, {gst->s_rounds, {g_sr, (size_t)S * g_rb}}, {gst->s_runner, {g_sru, (size_t)S * g_mb}},
+            {gst->s_spread, {g_ssp, (size_t)S * g_mb}}, {gst->g_counts, {g_gc, fkg::N_COUNTS}}, {gst->g_rounds, {g_gr, g_rb}},
+            {gst->g_runner, {g_gru, g_mb}}, {&g_spilled, {g_cnt, 1}}};
+        for (const auto &pt : parts)
+            HIPCHK(c, hipMemcpyAsync(pt.first, o + pt.second.first * 8, pt.second.second * 8, hipMemcpyDeviceToHost, c->stream));
+    }
     if (lag) {
         const size_t edge_bytes = (size_t)edge_rows * (size_t)S * 2;
         HIPCHK(c, hipMemcpyAsync(lag->sums, c->lag_out.p, lag_sum_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2310,6 +2399,14 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         const int rc_t = finish_timers(c);
         if (rc) return rc;
         if (rc_t) return rc_t;
+    }
+    if (gst) { // the exact values outside the histogram windows
+        *gst->spill_count = g_spilled;
+        if (g_spilled > gst->spill_capacity)
+            return fail(c, FK_ERR_ARG, "game statistics: the spill list needs %lld entries, spill_capacity is %lld", (long long)g_spilled,
+                        (long long)gst->spill_capacity);
+        if (g_spilled)
+            HIPCHK(c, hipMemcpy(gst->spill, static_cast<const unsigned long long *>(c->g_out.p) + g_u64, (size_t)g_spilled * 12, hipMemcpyDeviceToHost));
     }
     HIPCHK(c, hipEventElapsedTime(&c->timing.total_ms, t0, t1));
     return FK_OK;

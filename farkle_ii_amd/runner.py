@@ -559,13 +559,15 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                    resume: bool, checkpoint_metadata: "Mapping[str, Any] | Callable[[], Mapping[str, Any]]", oracle_game_profile: GameProfile | None = None,
                    all_player_dir: Path | None = None, sidecars: "_Sidecars | None" = None,
                    rng_lags: Sequence[int] | None = None, defer_final_checkpoint: bool = False, packed_table: np.ndarray | None = None,
-                   defer_tail: list | None = None, rng_matchups: int | None = None) -> dict:
+                   defer_tail: list | None = None, rng_matchups: int | None = None, game_stats: bool = False) -> dict:
     """Play every deterministic batch not yet owned by the checkpoint and persist the aggregates.  ``defer_final_checkpoint``: the final
     checkpoint's file write may still be in flight on return — the caller joins ``result["checkpoint_written"]`` before reading the file.  ``rng_lags``: also accumulate the lag
     sufficient statistics of the RNG diagnostics' strategy family over the WHOLE shuffle range (``fk_tournament_run_lags``; launch
     groups and ranks are contiguous ranges that merge in order, rng_lags.LagSummary) — returned as ``result["lag_summary"]``.
     ``rng_matchups`` (= ``combine.max_players``; needs ``rng_lags``): the same calls also return the per-game records of the matchup
-    family (``fk_tournament_run_matchups``), gathered to rank 0 in range order — ``result["matchup_records"]``."""
+    family (``fk_tournament_run_matchups``), gathered to rank 0 in range order — ``result["matchup_records"]``.  ``game_stats``: the
+    game-stats stage's histograms of the WHOLE range (``fk_tournament_run_game_stats``, on the same launch as the all-player batches),
+    summed on rank 0 — ``result["game_stats"]`` (game_stats.GameStatsSummary)."""
     rank, world = _rank_world()
     _trace(f"{n_players}p run_tournament")
     eng = get_engine()
@@ -662,6 +664,15 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             raise ValueError("lag statistics need the whole shuffle range of the run; this checkpoint already owns batches: use --force")
         if row_dir is not None or all_player_dir is not None:
             raise ValueError("--rng-lag-sums runs without rows / all-player batches (one post-pass per launch): run them separately")
+    gs_total = None
+    rare_target = None
+    if game_stats:
+        if done_batches:  # the histograms are held in memory until the run's end: a partial replay cannot rebuild them
+            raise ValueError("game statistics need every shuffle of the run; this checkpoint already owns batches: use --force")
+        if row_dir is not None or rng_lags:
+            raise ValueError("--game-stats runs without rows / lag statistics (one post-pass per launch): run them separately")
+        rare_target = cfg.rare_event_target_score()
+        cfg.game_stats_margin_thresholds()  # (validated before anything plays)
     target = oracle_game_profile.default_target_score if oracle_game_profile else 10_000
     max_rounds = oracle_game_profile.default_max_rounds if oracle_game_profile else 200
     ov = oracle_game_profile.tournament_overrides() if oracle_game_profile else None
@@ -738,7 +749,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
 
     def finish(b0, b1, lo, hi, j, local, local_stats, local_ratios, row_records, fragments, res, shard_job, per_batch) -> None:
         """What follows a launch group's engine call: its shards' manifest lines, the reduction over ranks, chunk files, checkpoint."""
-        nonlocal total, games_done, lag_total, batches_since_save, last_save
+        nonlocal total, games_done, lag_total, gs_total, batches_since_save, last_save
         if shard_job is not None:
             row_records = shard_job.result()
             if callable(row_records):  # the per-shard manifest lines: built here, not on the shard thread (its host threads would idle)
@@ -752,6 +763,15 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                 for piece in parts:
                     if piece is not None:
                         lag_total = piece if lag_total is None else lag_total.merge(piece)
+        if game_stats:  # whole batches per rank: the histograms add in any order
+            from .game_stats import GameStatsSummary
+
+            part = GameStatsSummary.from_engine(res, k) if res is not None and hi > lo else None
+            parts = gather_objects(part, dst=0) if world > 1 else [part]
+            if rank == 0:
+                for piece in parts:
+                    if piece is not None:
+                        gs_total = piece if gs_total is None else gs_total.merge(piece)
         if rng_matchups:  # the group's per-game records in rank order = coordinate order (contiguous whole batches per rank)
             rec = res["matchups"] if hi > lo else None
             recs = gather_objects(rec, dst=0) if world > 1 else [rec]
@@ -858,6 +878,10 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
         elif rng_matchups:
             res = eng.tournament_matchups(table, k, cfg.sim.seed, lo, hi, rng_lags, np.asarray(ids, dtype=np.int32), rng_matchups,
                                           shuffles_per_batch=batch_arg, target_score=target, max_rounds=max_rounds, overrides=ov)
+        elif game_stats:
+            res = eng.tournament_game_stats(table, k, cfg.sim.seed, lo, hi, shuffles_per_batch=batch_arg, target_score=target,
+                                            max_rounds=max_rounds, overrides=ov, rare_target_score=rare_target,
+                                            want_seat_stats=bool(g["extra"].get("want_seat_stats")))
         elif rng_lags:
             res = eng.tournament_lags(table, k, cfg.sim.seed, lo, hi, rng_lags, shuffles_per_batch=batch_arg, target_score=target,
                                       max_rounds=max_rounds, overrides=ov)
@@ -1059,7 +1083,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                 elif manifest is not None:
                     sidecars.write("shard_manifest", manifest)
         barrier()
-        result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total)
+        result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total, game_stats=gs_total)
         if rng_matchups and rank == 0:  # the grouped reduce of the whole (root, k), on this thread's engine
             from .rng_matchups import concat_records, effective_cap
 
@@ -1094,6 +1118,9 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if cfg.sim.rng_lag_sums and not (cfg.rng_lag_sums_path(n).exists() and cfg.rng_lag_stats_path(n).exists()):
             raise ValueError(f"{n}p is already complete without {cfg.rng_lag_sums_path(n).name}: --rng-lag-sums needs every shuffle of the "
                              "run; use --force to replay it with the lag statistics")
+        if cfg.sim.game_stats and not cfg.game_stats_sums_path(n).exists():
+            raise ValueError(f"{n}p is already complete without {cfg.game_stats_sums_path(n).name}: --game-stats needs every game of "
+                             "the run; use --force to replay it with the game statistics")
         if cfg.sim.rng_matchup_lags and not cfg.rng_matchup_groups_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.rng_matchup_groups_path(n).name}: --rng-matchup-lags needs every "
                              "game of the run; use --force to replay it with the matchup records")
@@ -1114,7 +1141,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
     if rank == 0:
         if force:
             for path in (ckpt_path, n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), simulation_done_path(cfg, n),
-                         cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n)):
+                         cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n), cfg.game_stats_path(n),
+                         cfg.game_stats_sums_path(n)):
                 path.unlink(missing_ok=True)
                 path.with_name(path.name + ".sidecar.json").unlink(missing_ok=True)
             for d in (row_dir, metric_chunk_dir, all_player_dir):
@@ -1165,7 +1193,7 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             oracle_game_profile=oracle_game_profile, all_player_dir=all_player_dir, sidecars=sidecars,
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
                             packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
-                            rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None)
+                            rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats)
     finally:
         if published is not None:
             published.result()  # the inputs are on disk (or their error is raised) before the summaries and the stamp name them
@@ -1228,6 +1256,39 @@ def _publish_rng_matchups(cfg: AppConfig, n: int, strategies: list[ThresholdStra
     os.replace(tmp, cfg.rng_group_selection_path())
 
 
+def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], result: dict) -> None:
+    """``<n>p_game_stats.parquet`` (the reference's per-k table) and ``<n>p_game_stats_sums.parquet`` (its exact histograms), and once
+    every player count of the run has its sums file, the root's ``game_stats_rare_event_summary.parquet`` across them."""
+    import pyarrow.parquet as pq
+
+    from . import game_stats as gs
+
+    thresholds = cfg.game_stats_margin_thresholds()
+    rare_target = cfg.rare_event_target_score()
+    ids = np.asarray([int(s.strategy_id) for s in strategies], dtype=np.int64)
+    summary = result["game_stats"]
+    table = gs.game_stats_table(summary, ids, n, thresholds)
+    if table is not None:
+        _write_parquet_atomic(table, cfg.game_stats_path(n))
+    settings = {b"root_seed": str(int(cfg.sim.seed)).encode(), b"rare_target_score": str(rare_target).encode()}
+    _write_parquet_atomic(summary.sums_table(ids).replace_schema_metadata(settings), cfg.game_stats_sums_path(n))
+    counts, _ = _filter_player_counts(list(cfg.sim.n_players_list), len(ids))
+    paths = {int(v): cfg.game_stats_sums_path(int(v)) for v in counts}
+    if not all(p.exists() for p in paths.values()):
+        return
+    per_k = {}
+    for v, p in paths.items():
+        t = pq.read_table(p)
+        if {key: (t.schema.metadata or {}).get(key) for key in settings} != settings:
+            raise ValueError("the per-player-count game-stat files of this root were written with other settings: replay them with --force")
+        per_k[v] = gs.GameStatsSummary.from_sums_table(t, ids, v)
+    rare = gs.rare_event_summary_table(per_k, ids, thresholds)
+    if rare is None:  # no flagged game in the root: the reference writes no file either
+        cfg.game_stats_rare_summary_path().unlink(missing_ok=True)
+    else:
+        _write_parquet_atomic(rare, cfg.game_stats_rare_summary_path())
+
+
 def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], plan: TournamentWorkloadPlan, result: dict, grid_size: int,
                      ckpt_path: Path, n_dir: Path, sidecars: "_Sidecars", oracle_game_profile: GameProfile | None) -> None:
     """What follows the last launch of a player count on rank 0: lag tables, summary / metrics parquets, the completion stamp."""
@@ -1243,6 +1304,8 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
         _write_parquet_atomic(lag_stats_table(result["lag_summary"], ids, n), cfg.rng_lag_stats_path(n))
     if cfg.sim.rng_matchup_lags and result.get("matchup_reduce") is not None:
         _publish_rng_matchups(cfg, n, strategies, result)
+    if cfg.sim.game_stats and result.get("game_stats") is not None:
+        _publish_game_stats(cfg, n, strategies, result)
     # (A) summary parquet, (B) expanded metrics parquet — column order, types and values as in runner.py:1612-1712, built column by
     # column from the tally (the per-strategy dict loop cost 25 us per strategy and table: 140 ms of a 330-ms config-3 run).  Rows in
     # the reference's order: strategies sorted by the STRING of their id, those without an attempted exposure left out.

@@ -330,6 +330,31 @@ int fk_matchup_reduce(fk_ctx *ctx, int32_t k, int64_t n_obs, const uint64_t *dig
                       const int32_t *lags, int32_t n_lags, int64_t cap, int64_t out_capacity, int64_t *counts, uint64_t *histogram,
                       uint64_t *out_digest, uint16_t *out_seats, int64_t *out_count, int64_t *out_sums);
 
+/* fk_tournament_run_all_player (seat_stats / seat_ratio_sums nullable: pass both, only seat_stats, or neither) + the sufficient
+ * statistics of the reference's game-stats stage for this range (analysis/game_stats.py: _compute_k_game_stats :840-1220, margins
+ * _compute_margin_arrays :3378-3406, rare-event summary sums _build_rare_event_summary_shard :2715-2880).  All outputs int64,
+ * overwritten; margins are in units of 50 points (seat scores are multiples of 50):
+ *   strategy_counts   [S][4]  over the strategy's seat exposures: attempted, completed, safety-limit, games where at least two seats
+ *                             have score >= rare_target_score (analysis.rare_event_target_score)
+ *   strategy_rounds   [S][rounds_bins]  n_rounds histogram of its exposures
+ *   strategy_runner / strategy_spread   [S][margin_bins]  (max - second max) / 50 and (max - min) / 50 of the game's seat scores,
+ *                             over its COMPLETED exposures of games with k >= 2
+ *   game_counts [4], game_rounds [rounds_bins], game_runner [margin_bins]   the same over the range's games
+ * Nothing is clamped: a value beyond its histogram (n_rounds >= rounds_bins, margin / 50 >= margin_bins) is an entry of
+ *   spill   int32 [spill_capacity][3]: strategy table index (-1: the game level), kind (0 n_rounds, 1 runner-up, 2 spread), value
+ * *spill_count = the entries the call produced; more than spill_capacity returns FK_ERR_ARG (call again with that capacity).
+ * 1 <= rounds_bins <= 4096, 1 <= margin_bins <= 2048.  Option "game_stats_window" (tests): > 0 narrows both device windows to that
+ * many bins, so that values spill; results are the same.  Per workgroup the device gathers one strategy's exposures over a segment
+ * of shuffles into LDS histograms (farkle_ii_amd/csrc/fk_game_stats.h); farkle_ii_amd/game_stats.py builds the reference's tables. */
+int fk_tournament_run_game_stats(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch,
+                                 int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov,
+                                 int64_t *tally, void *rows, int32_t *perms, int64_t *seat_stats, double *seat_ratio_sums,
+                                 int32_t rare_target_score, int32_t rounds_bins, int32_t margin_bins, int64_t *strategy_counts,
+                                 int64_t *strategy_rounds, int64_t *strategy_runner, int64_t *strategy_spread, int64_t *game_counts,
+                                 int64_t *game_rounds, int64_t *game_runner, int64_t spill_capacity, int64_t *spill_count,
+                                 int32_t *spill);
+
 /* Explicit game list: game g seats strategies table[seat_strategy[g*k+i]] with streams coords[g](seat i).
  * rows: n_games * (4+28k) bytes (required). */
 int fk_play_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
