@@ -207,12 +207,62 @@ __host__ __device__ inline uint32_t mulhi32(uint32_t a, uint32_t b) {
 //                 words that are generated but not consumed only cause a harmless, exact detour through the
 //                 sequential path; words that are not generated are the constant 1 (24 >= 16, never detours).
 // STRIDE = width of one face's count field in the result: 4 (nibbles, the SWAR scorer's input) or 3 (the 18-bit key
-// of the score table, SCORE_LUT below; a count is at most 6).
+// of the score table, SCORE_LUT below; a count is at most 6; no faces): STRIDE 3 is roll_key_fast.
+// roll_key_fast (STRIDE 3): the key is a sum of one term per die, so the dice need not be in draw order.  The m = n - has_buf dice
+// drawn now take the first m words of lo0 hi0 lo1 hi1 lo2 hi2, the buffered die takes the sixth slot, and every slot without a die holds
+// the word 1 (face 1, low product word 6: never a detour).  The key of all six slots is then exact but for 6 - n extra counts in the
+// face-1 field (at most 6 counts in a field: no carry between fields), taken off at the end.  No per-die "is this die rolled" bit,
+// and no per-die choice between the two word alignments.  A drawn word that is not rolled (the high half of the last output when m
+// is odd: the next roll's buffered die) is replaced by 1 in its own draw's region.
+__device__ inline uint32_t roll_key_fast(Rng &r, uint32_t n, bool &detour) {
+    const uint32_t hb = r.has_buf, m = n - hb;
+    const uint32_t need = (m + 1u) >> 1; // new 64-bit outputs, 0..3
+    uint32_t s0 = 1, s1 = 1, s2 = 1, s3 = 1, s4 = 1, s5 = 1, last_hi = r.buf;
+    if (need > 0u) {
+        const uint64_t o = pcg_next64_plain(r);
+        last_hi = (uint32_t)(o >> 32);
+        s0 = (uint32_t)o;
+        s1 = m > 1u ? last_hi : 1u;
+    }
+    if (need > 1u) {
+        const uint64_t o = pcg_next64_plain(r);
+        last_hi = (uint32_t)(o >> 32);
+        s2 = (uint32_t)o;
+        s3 = m > 3u ? last_hi : 1u;
+    }
+    if (need > 2u) {
+        const uint64_t o = pcg_next64_plain(r);
+        last_hi = (uint32_t)(o >> 32);
+        s4 = (uint32_t)o;
+        s5 = m > 5u ? last_hi : 1u;
+    }
+    uint32_t s5b = hb ? r.buf : s5; // hb = 1: m <= 5, so s5 is 1 and the slot is free
+    // the words, not their products, leave the regions: unpinned, the compiler moves the x6 products into the regions and selects
+    // both halves of a product where one word select does
+    asm("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(s4), "+v"(s5b));
+    const uint32_t w[6] = {s0, s1, s2, s3, s4, s5b};
+    uint32_t key = n - 6u, minleft = 0xffffffffu;
+#pragma unroll
+    for (uint32_t i = 0; i < 6; ++i) {
+        const uint64_t pw = (uint64_t)w[i] * 6u; // face - 1 = high word; rejection iff low word < 4
+        key += 1u << (3u * (uint32_t)(pw >> 32));
+        minleft = min(minleft, (uint32_t)pw);
+    }
+    r.has_buf = (n + hb) & 1u;
+    r.buf = last_hi;
+    detour = minleft < 4u; // rare: exactly the rejections among the rolled dice
+#ifdef FK_FORCE_DETOUR
+    detour = detour || ((((uint32_t)(r.lo >> 17)) & (uint32_t)(FK_FORCE_DETOUR - 1)) == 0u); // see roll_counts_fast
+#endif
+    return key;
+}
+
 // roll_counts_fast: the converged part.  `detour` = some low product word fell below the rejection bound: the caller restores the
 // generator it started from and replays the roll with roll_counts_sequential (roll_counts below does both; the game kernels
 // restore from the seat record in LDS instead of keeping a copy of the state in registers).
 template <uint32_t STRIDE = 4>
 __device__ inline uint32_t roll_counts_fast(Rng &r, uint32_t n, bool &detour, uint32_t *faces_out = nullptr) {
+    if (STRIDE == 3u) return roll_key_fast(r, n, detour); // the score-table key: no faces
     const uint32_t hb = r.has_buf, buf_in = r.buf;
     const uint32_t need = (n - hb + 1u) >> 1; // new 64-bit outputs: ceil((n - has_buf) / 2), 0..3
     uint32_t lo0 = 1, hi0 = 1, lo1 = 1, hi1 = 1, lo2 = 1, hi2 = 1, last_hi = r.buf;
@@ -245,12 +295,11 @@ __device__ inline uint32_t roll_counts_fast(Rng &r, uint32_t n, bool &detour, ui
     uint32_t counts = 0, faces = 0, minleft = 0xffffffffu;
 #pragma unroll
     for (uint32_t i = 0; i < 6; ++i) {
-        // one v_mad_u64_u32 per die: field shift from the high word, rejection test on the low word.
-        //   STRIDE 4: 24w -> 4*face = hi & 28, low word 4 * (6w mod 2^30);   STRIDE 3: 6w -> face = hi, 3*face = hi + 2*hi
-        const uint64_t pw = (uint64_t)w[i] * (STRIDE == 4u ? 24u : 6u);
+        // one v_mad_u64_u32 per die: 24w -> 4*face = hi & 28 (the field shift), low word 4 * (6w mod 2^30) (the rejection test)
+        const uint64_t pw = (uint64_t)w[i] * 24u;
         const uint32_t hiw = (uint32_t)(pw >> 32);
-        const uint32_t fsh = (STRIDE == 4u) ? (hiw & 28u) : (hiw + 2u * hiw);
-        const uint32_t face = (STRIDE == 4u) ? (fsh >> 2) : hiw;
+        const uint32_t fsh = hiw & 28u;
+        const uint32_t face = fsh >> 2;
         const uint32_t on = (onbits >> i) & 1u;
         counts += on << fsh;
         const uint32_t left = (uint32_t)pw;
@@ -259,7 +308,7 @@ __device__ inline uint32_t roll_counts_fast(Rng &r, uint32_t n, bool &detour, ui
     }
     r.has_buf = (n + hb) & 1u;
     r.buf = last_hi;
-    detour = minleft < (STRIDE == 4u ? 16u : 4u); // rare (STRIDE 4: a superset of the rejections)
+    detour = minleft < 16u; // rare: a superset of the rejections
 #ifdef FK_FORCE_DETOUR
     // Test builds only (tests/test_detour_gpu.py): a real rejection happens once in ~2^30 dice, so the kernels' detour — generator re-read
     // from the seat record / hot planes, the roll replayed sequentially — would never run in a parity test.  Here every
