@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_bootstrap.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -110,7 +110,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap"]
 _libs: dict = {}
 
 
@@ -694,6 +694,51 @@ class Engine:
         raw = np.zeros((n, 4), dtype=np.uint64) if want_raw else None
         self._check(self._lib.fk_debug_dice(self._ctx, C.c_int64(n), _p(coords), C.c_int32(len(sizes)), _p(sizes), _p(faces), _p(raw)))
         return faces, raw
+
+    def debug_bounded_draws(self, coords: np.ndarray, bound: int, n_draws: int) -> np.ndarray:
+        """``fk_debug_bounded_draws``: uint32 ``[n][n_draws]`` = ``Generator(PCG64DXSM(coords[i])).integers(0, bound, size=n_draws)`` by
+        the bootstrap's own device draw function (1 <= bound <= 2**32 - 1)."""
+        coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
+        out = np.zeros((len(coords), int(n_draws)), dtype=np.uint32)
+        self._check(self._lib.fk_debug_bounded_draws(self._ctx, C.c_int64(len(coords)), _p(coords), C.c_uint64(int(bound)),
+                                                     C.c_int32(int(n_draws)), _p(out)))
+        return out
+
+    def performance_bootstrap(self, root_seed: int, ks, wins, exposures, replicate_begin: int, replicate_end: int, top_n: int,
+                              delta: float, controls=(), want_scores: bool = True, contrast_sum: np.ndarray | None = None,
+                              contrast_square_sum: np.ndarray | None = None) -> dict:
+        """``fk_performance_bootstrap``: the joint deterministic-batch bootstrap of replicates ``[replicate_begin, replicate_end)``.
+        ``wins[i]`` / ``exposures[i]``: int64 ``[B_i][S]`` of player count ``ks[i]``, eligible batches only, columns in ascending
+        strategy id; ``controls``: column indices.  Returns ``scores`` (float64 ``[R][S]`` or None), int64 ``rank_sum``,
+        ``rank_square_sum``, ``top_counts``, ``shortlist_counts`` of THIS range and float64 ``contrast_sum`` /
+        ``contrast_square_sum`` ``[C][S]`` continued from the arrays passed in (zeros when omitted)."""
+        ks = [int(v) for v in ks]
+        if len(ks) != len(wins) or len(ks) != len(exposures) or not ks:
+            raise ValueError("one wins and one exposures matrix per player count")
+        W = [np.ascontiguousarray(m, dtype=np.int64) for m in wins]
+        E = [np.ascontiguousarray(m, dtype=np.int64) for m in exposures]
+        S = int(W[0].shape[1]) if W[0].ndim == 2 else -1
+        for w, e in zip(W, E):
+            if w.ndim != 2 or w.shape != e.shape or w.shape[1] != S:
+                raise ValueError("every matrix is [batches][S] with one S")
+        n_k = len(ks)
+        R = max(int(replicate_end) - int(replicate_begin), 0)
+        ctrl = np.ascontiguousarray(list(controls), dtype=np.int32)
+        n_ctrl = len(ctrl)
+        scores = np.zeros((R, S), dtype=np.float64) if want_scores else None
+        counters = [np.zeros(S, dtype=np.int64) for _ in range(4)]
+        csum = np.zeros((n_ctrl, S), np.float64) if contrast_sum is None else np.array(contrast_sum, dtype=np.float64, order="C").reshape(n_ctrl, S)
+        csq = np.zeros((n_ctrl, S), np.float64) if contrast_square_sum is None else np.array(contrast_square_sum, dtype=np.float64, order="C").reshape(n_ctrl, S)
+        k_arr = np.asarray(ks, dtype=np.int32)
+        b_arr = np.asarray([len(m) for m in W], dtype=np.int64)
+        w_ptr = (C.c_void_p * n_k)(*[m.ctypes.data for m in W])
+        e_ptr = (C.c_void_p * n_k)(*[m.ctypes.data for m in E])
+        self._check(self._lib.fk_performance_bootstrap(
+            self._ctx, C.c_uint64(int(root_seed)), C.c_int32(n_k), _p(k_arr), _p(b_arr), w_ptr, e_ptr, C.c_int32(S),
+            C.c_int64(int(replicate_begin)), C.c_int64(int(replicate_end)), C.c_int32(int(top_n)), C.c_double(float(delta)), C.c_int32(n_ctrl),
+            _p(ctrl) if n_ctrl else None, _p(scores), *[_p(a) for a in counters], _p(csum) if n_ctrl else None, _p(csq) if n_ctrl else None))
+        return {"scores": scores, "rank_sum": counters[0], "rank_square_sum": counters[1], "top_counts": counters[2],
+                "shortlist_counts": counters[3], "contrast_sum": csum, "contrast_square_sum": csq}
 
     def debug_dice_state(self, state: np.ndarray, sizes):
         state = np.ascontiguousarray(state, dtype=np.uint64).reshape(-1, 6)

@@ -50,6 +50,12 @@ def build_parser() -> argparse.ArgumentParser:
                           "rates) and <k>p_game_stats_sums.parquet (the exact histograms), after the last player count "
                           "game_stats_rare_event_summary.parquet at the results root (analysis.game_stats_margin_thresholds, "
                           "analysis.rare_event_target_score).  Not resumable: an interrupted run asks for --force")
+    run.add_argument("--performance-bootstrap", action="store_true",
+                     help="Write the performance stage's joint deterministic-batch bootstrap from the device: per player count "
+                          "analysis/03_metrics/by_k/<k>p/performance_batch_matrix.npy (wins / exposures per batch and strategy), after the "
+                          "last player count across_k/performance_bootstrap.parquet and across_k/performance_control_contrasts.parquet "
+                          "(screening.bootstrap_replicates, delta_across_k, candidate_contribution_size, controls).  May be combined "
+                          "with --all-player-batches (the same statistics launch).  Not resumable: an interrupted run asks for --force")
     run.add_argument("--sidecars", action="store_true",
                      help="Write <artifact>.sidecar.json (producer contract + SHA-256 / size of the artifact) beside every output")
     run.add_argument("--code-identity", metavar="COMMIT[:DIRTY_SHA256[:POLICY]]",
@@ -123,6 +129,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.rng_lag_sums = True
     if args.game_stats:
         cfg.sim.game_stats = True
+    if args.performance_bootstrap:
+        cfg.sim.performance_bootstrap = True
     if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
         cfg.sim.rng_lag_sums = cfg.sim.rng_matchup_lags = True
     _maybe_init_distributed()
@@ -151,7 +159,7 @@ def main(argv: Sequence[str] | None = None) -> None:
     LOGGER.info("Dispatching run command: seed=%s n_players_list=%s results_dir=%s", cfg.sim.seed, cfg.sim.n_players_list,
                 cfg.results_root)
     try:
-        if len(cfg.sim.n_players_list) > 1:
+        if len(cfg.sim.n_players_list) > 1 or cfg.sim.performance_bootstrap:  # (the bootstrap follows the sweep's last player count)
             out = runner.run_multi(cfg, force=args.force)
         else:
             out = {cfg.sim.n_players_list[0]: runner.run_single_n(cfg, cfg.sim.n_players_list[0], force=args.force)}

@@ -65,6 +65,7 @@ class SimConfig:
     rng_lag_sums: bool = False  # this engine's option: lag sufficient statistics of the RNG diagnostics' strategy family (rng_lags.py)
     rng_matchup_lags: bool = False  # this engine's option: the RNG diagnostics' matchup family + group selection (rng_matchups.py)
     game_stats: bool = False  # this engine's option: the game-stats stage's per-k tables and rare-event summary without rows (game_stats.py)
+    performance_bootstrap: bool = False  # this engine's option: the performance stage's batch matrices + joint batch bootstrap (performance_bootstrap.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
     mp_start_method: str | None = None
@@ -189,6 +190,22 @@ class AppConfig:
         if isinstance(value, bool) or not isinstance(value, int) or not -(2 ** 31) <= value < 2 ** 31:
             raise ValueError("analysis.rare_event_target_score must be a 32-bit integer")
         return int(value)
+
+    def metrics_stage_dir(self) -> Path:
+        """The reference's metrics stage directory in its default stage layout (config.py:798-802: ``analysis/03_metrics``)."""
+        return self.results_root / self.io.analysis_subdir / "03_metrics"
+
+    def performance_batch_matrix_path(self, n: int) -> Path:
+        """config.py:981-984: ``by_k/<k>p/performance_batch_matrix.npy``."""
+        return self.metrics_stage_dir() / "by_k" / f"{n}p" / "performance_batch_matrix.npy"
+
+    def performance_bootstrap_path(self) -> Path:
+        """config.py:1001-1004."""
+        return self.metrics_stage_dir() / "across_k" / "performance_bootstrap.parquet"
+
+    def performance_control_contrasts_path(self) -> Path:
+        """config.py:1006-1009."""
+        return self.metrics_stage_dir() / "across_k" / "performance_control_contrasts.parquet"
 
     def game_stats_path(self, n: int) -> Path:
         return self.n_dir(n) / f"{n}p_game_stats.parquet"

@@ -10,6 +10,7 @@
 #include "fk_row_columns_seats.h" // device side: column images with one thread per (game, seat)
 #include "fk_matchups.h"      // device side: RNG-diagnostics matchup family (key post-pass, grouped lag reduce)
 #include "fk_game_stats.h"    // device side: game-stats stage (game-record pass, per-strategy LDS histogram gather)
+#include "fk_bootstrap.h"     // device side: performance stage's joint batch bootstrap (draws, integer product, ranks, contrasts)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -147,6 +148,8 @@ struct fk_ctx {
     DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
     const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
+    DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
+    int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
     int32_t columns_by_seat = -1; // column images: -1 one thread per (game, seat) up to sixteen seats, per game beyond; 0 per game; 1 per (game, seat)
@@ -1321,6 +1324,7 @@ void fk_destroy(fk_ctx *c) {
                       &c->m_ids, &c->m_dig, &c->m_seat, &c->m_rnd})
         release(*b);
     for (DevBuf &b : c->mr) release(b);
+    for (DevBuf &b : c->boot) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
@@ -1496,6 +1500,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "uniform_flags") c->uniform_flags_opt = (int32_t)value;
     else if (n == "matchup_sort_key_mask") c->matchup_sort_mask = (uint64_t)value;
     else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
+    else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
             return fail(c, FK_ERR_ARG, "block must be 0, 64, 128, 256, 512, 768 (lean records only) or 1024");
@@ -3152,6 +3157,133 @@ int fk_debug_dice_keys(fk_ctx *c, int64_t n, const uint64_t *state, int32_t n_ca
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(keys, c->dbg[2].p, (size_t)n * n_calls * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(state_out, c->dbg[4].p, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+int fk_debug_bounded_draws(fk_ctx *c, int64_t n, const fk_coord *coords, uint64_t bound, int32_t n_draws, uint32_t *out) {
+    if (!c) return FK_ERR_ARG;
+    if (n < 0 || n_draws < 0 || !coords || !out) return fail(c, FK_ERR_ARG, "bad arguments");
+    if (bound < 1 || bound > 0xffffffffull) return fail(c, FK_ERR_ARG, "bound must be in [1, 2^32 - 1]");
+    if (n == 0 || n_draws == 0) return FK_OK;
+    if ((uint64_t)n * (uint64_t)n_draws > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 draws in one probe");
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
+    if ((rc = ensure(c, c->dbg[2], (size_t)n * n_draws * 4))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fkb::fk_boot_draws_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n,
+                       static_cast<const fk_coord *>(c->coords.p), (uint32_t)bound, (uint32_t)n_draws, static_cast<uint32_t *>(c->dbg[2].p));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, c->dbg[2].p, (size_t)n * n_draws * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+int fk_performance_bootstrap(fk_ctx *c, uint64_t root_seed, int32_t n_k, const int32_t *ks, const int64_t *batch_counts,
+                             const int64_t *const *wins, const int64_t *const *exposures, int32_t S, int64_t replicate_begin,
+                             int64_t replicate_end, int32_t top_n, double delta, int32_t n_controls, const int32_t *controls,
+                             double *scores, int64_t *rank_sum, int64_t *rank_square_sum, int64_t *top_counts, int64_t *shortlist_counts,
+                             double *contrast_sum, double *contrast_square_sum) {
+    if (!c) return FK_ERR_ARG;
+    if (n_k < 1 || n_k > 64 || !ks || !batch_counts || !wins || !exposures) return fail(c, FK_ERR_ARG, "1 to 64 player counts with their matrices are required");
+    if (S < 1 || S > (1 << 24)) return fail(c, FK_ERR_ARG, "S must be in [1, 2^24]");
+    if (replicate_begin < 0 || replicate_end < replicate_begin) return fail(c, FK_ERR_ARG, "bad replicate range");
+    if (top_n < 0 || top_n > S) return fail(c, FK_ERR_ARG, "top_n must be in [0, S]");
+    if (!(delta == delta)) return fail(c, FK_ERR_ARG, "delta is NaN");
+    if (!rank_sum || !rank_square_sum || !top_counts || !shortlist_counts) return fail(c, FK_ERR_ARG, "the four counter outputs are required");
+    if (n_controls < 0 || (n_controls > 0 && (!controls || !contrast_sum || !contrast_square_sum)))
+        return fail(c, FK_ERR_ARG, "controls need their index list and both accumulators");
+    for (int32_t i = 0; i < n_controls; ++i)
+        if (controls[i] < 0 || controls[i] >= S) return fail(c, FK_ERR_ARG, "control %d: column %d outside [0, S)", i, controls[i]);
+    std::vector<fkb::KDesc> kd((size_t)n_k);
+    uint64_t sum_B = 0;
+    for (int32_t i = 0; i < n_k; ++i) {
+        if (ks[i] < 1) return fail(c, FK_ERR_ARG, "player count %d: k = %d", i, ks[i]);
+        if (batch_counts[i] < 1 || batch_counts[i] > 0xffffffffll || !wins[i] || !exposures[i])
+            return fail(c, FK_ERR_ARG, "player count %d needs 1 to 2^32 - 1 eligible batches and both matrices", ks[i]);
+        kd[(size_t)i] = {(uint64_t)ks[i], (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)ks[i]};
+        sum_B += (uint64_t)batch_counts[i];
+        if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
+        // exactness of the int64 totals: every value in [0, 2^63 / B_k)
+        const uint64_t limit = ((uint64_t)1 << 63) / (uint64_t)batch_counts[i];
+        const size_t cells = (size_t)batch_counts[i] * (size_t)S;
+        uint64_t seen = 0, top = 0; // OR of all values (a negative one sets the top bit); their maximum, looked for only when the OR is large
+        for (const int64_t *m : {wins[i], exposures[i]})
+            for (size_t j = 0; j < cells; ++j) seen |= (uint64_t)m[j];
+        if (seen >= limit)
+            for (const int64_t *m : {wins[i], exposures[i]})
+                for (size_t j = 0; j < cells; ++j) top = std::max(top, (uint64_t)m[j]);
+        if (top >= limit) return fail(c, FK_ERR_ARG, "player count %d: a negative count, or one whose resampled total can pass 2^63", ks[i]);
+    }
+    const int64_t n_rep = replicate_end - replicate_begin;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    // resident for the call: both stacked matrices, the descriptors, the counters and the contrast accumulators
+    const size_t mat_bytes = (size_t)sum_B * (size_t)S * 8;
+    const size_t counter_bytes = (size_t)4 * S * 8, contrast_bytes = (size_t)2 * n_controls * S * 8;
+    if ((rc = ensure(c, c->boot[0], mat_bytes))) return rc;
+    if ((rc = ensure(c, c->boot[1], mat_bytes))) return rc;
+    if ((rc = ensure(c, c->boot[2], kd.size() * sizeof(fkb::KDesc)))) return rc;
+    if ((rc = ensure(c, c->boot[5], counter_bytes))) return rc;
+    if ((rc = ensure(c, c->boot[6], contrast_bytes + (size_t)n_controls * 4))) return rc;
+    if ((rc = ensure(c, c->boot[7], 4))) return rc;
+    for (int which = 0; which < 2; ++which)
+        for (int32_t i = 0; i < n_k; ++i)
+            HIPCHK(c, hipMemcpyAsync(static_cast<int64_t *>(c->boot[which].p) + (size_t)kd[(size_t)i].row0 * (size_t)S, (which ? exposures : wins)[i],
+                                     (size_t)kd[(size_t)i].B * (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->boot[2].p, kd.data(), kd.size() * sizeof(fkb::KDesc), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->boot[5].p, 0, counter_bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->boot[7].p, 0, 4, c->stream));
+    double *d_contrast = static_cast<double *>(c->boot[6].p);
+    int32_t *d_controls = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(c->boot[6].p) + contrast_bytes);
+    if (n_controls) {
+        HIPCHK(c, hipMemcpyAsync(d_contrast, contrast_sum, contrast_bytes / 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_contrast + (size_t)n_controls * S, contrast_square_sum, contrast_bytes / 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_controls, controls, (size_t)n_controls * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    // the replicate range in blocks sized from the workspace budget: per replicate one multiplicity row and one score row
+    const size_t per_rep = (size_t)sum_B * 4 + (size_t)S * 8;
+    int64_t block = std::max<int64_t>((int64_t)(workspace_budget(c) / 2 / (int64_t)per_rep), 1);
+    block = std::min<int64_t>(block, 4096);
+    if (c->bootstrap_block > 0) block = std::min(block, c->bootstrap_block);
+    block = std::min<int64_t>(std::max<int64_t>(block / fkb::RB * fkb::RB, fkb::RB), (n_rep + fkb::RB - 1) / fkb::RB * fkb::RB);
+    if (n_rep > 0) {
+        if ((rc = ensure(c, c->boot[3], (size_t)block * sum_B * 4))) return rc;
+        if ((rc = ensure(c, c->boot[4], (size_t)block * S * 8))) return rc;
+    }
+    const fkb::KDesc *d_kd = static_cast<const fkb::KDesc *>(c->boot[2].p);
+    uint32_t *d_counts = static_cast<uint32_t *>(c->boot[3].p);
+    double *d_scores = static_cast<double *>(c->boot[4].p);
+    int32_t *d_bad = static_cast<int32_t *>(c->boot[7].p);
+    const unsigned s_tiles = (unsigned)((S + fkb::TS - 1) / fkb::TS);
+    for (int64_t b0 = 0; b0 < n_rep; b0 += block) {
+        const uint32_t nr = (uint32_t)std::min<int64_t>(block, n_rep - b0), nr_pad = (nr + fkb::RB - 1) / fkb::RB * fkb::RB;
+        HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)nr_pad * sum_B * 4, c->stream));
+        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_k + 63) / 64), dim3(64), 0, c->stream, root_seed,
+                           (uint64_t)(replicate_begin + b0), nr, (uint32_t)n_k, d_kd, (uint32_t)sum_B, d_counts);
+        hipLaunchKernelGGL(fkb::fk_boot_score_kernel, dim3(s_tiles, nr_pad / fkb::RB), dim3(fkb::TS), 0, c->stream,
+                           static_cast<const int64_t *>(c->boot[0].p), static_cast<const int64_t *>(c->boot[1].p), d_counts, d_kd,
+                           (uint32_t)n_k, (uint32_t)sum_B, (uint32_t)S, nr, d_scores, d_bad);
+        hipLaunchKernelGGL(fkb::fk_boot_rank_kernel, dim3(s_tiles, (nr + fkb::RC - 1) / fkb::RC), dim3(fkb::TS), 0, c->stream, d_scores,
+                           (uint32_t)S, nr, (uint32_t)top_n, delta, static_cast<unsigned long long *>(c->boot[5].p));
+        if (n_controls)
+            hipLaunchKernelGGL(fkb::fk_boot_contrast_kernel, dim3((unsigned)(((size_t)n_controls * S + 255) / 256)), dim3(256), 0, c->stream,
+                               d_scores, (uint32_t)S, nr, d_controls, (uint32_t)n_controls, d_contrast);
+        HIPCHK(c, hipGetLastError());
+        if (scores) HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * S, d_scores, (size_t)nr * S * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    int32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, FK_ERR_ARG, "joint batch resampling produced zero complete-support exposure");
+    int64_t *outs[4] = {rank_sum, rank_square_sum, top_counts, shortlist_counts};
+    for (int i = 0; i < 4; ++i)
+        HIPCHK(c, hipMemcpyAsync(outs[i], static_cast<uint8_t *>(c->boot[5].p) + (size_t)i * S * 8, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_controls) {
+        HIPCHK(c, hipMemcpyAsync(contrast_sum, d_contrast, contrast_bytes / 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(contrast_square_sum, d_contrast + (size_t)n_controls * S, contrast_bytes / 2, hipMemcpyDeviceToHost, c->stream));
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }

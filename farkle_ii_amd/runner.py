@@ -39,13 +39,15 @@ from .distributed import barrier, gather_objects, reduce_tally, shard_shuffle_ra
 from .engine import get_engine
 from .game_profile import GameProfile
 from .all_player import all_player_batch_table
-from .backend import COL_ATTEMPTED, COL_COMPLETED, COL_SAFETY, COL_SQ_SUMS, COL_SUMS, COL_WINS, SEAT_RATIO_COLS, SEAT_STAT_COLS
+from .backend import COL_ATTEMPTED, COL_COMPLETED, COL_SAFETY, COL_SQ_SUMS, COL_SUMS, COL_WINS, SEAT_RATIO_COLS, SEAT_STAT_COLS, SEAT_STAT_NAMES
 from .rows import OUTCOME_SCHEMA_VERSION, TOURNAMENT_METHOD_VERSION, raw_simulation_schema_for
 from .strategies import (STRATEGY_TUPLE_FIELDS, FavorDiceOrScore, ThresholdStrategy, generate_strategy_grid,
                          prepare_public_helper_strategies, strategy_tuple)
 from .workload_planner import TournamentWorkloadPlan, WorkloadCapExceeded, plan_tournament_workload, write_workload_plan
 
 LOGGER = logging.getLogger(__name__)
+_BOOT_STAT_NAMES = ("wins", "exposures", "completed_exposures", "safety_limit_exposures")  # what the performance bootstrap keeps per batch
+_BOOT_STAT_COLUMNS = [SEAT_STAT_NAMES.index(name) for name in _BOOT_STAT_NAMES]
 MAX_GAMES_PER_LAUNCH = 200_000_000  # checkpoint cadence on the GPU: a launch group is at most this many games
 ROWS_ASYNC = os.environ.get("FK_ROWS_ASYNC", "1") != "0"  # (A/B switch: the images' last copy awaited by the shard job / by the engine call)
 ROWS_PIPELINE = os.environ.get("FK_ROWS_PIPELINE", "0") != "0"  # (A/B switch: a launch group's engine part on the launcher thread / in line)
@@ -559,7 +561,8 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                    resume: bool, checkpoint_metadata: "Mapping[str, Any] | Callable[[], Mapping[str, Any]]", oracle_game_profile: GameProfile | None = None,
                    all_player_dir: Path | None = None, sidecars: "_Sidecars | None" = None,
                    rng_lags: Sequence[int] | None = None, defer_final_checkpoint: bool = False, packed_table: np.ndarray | None = None,
-                   defer_tail: list | None = None, rng_matchups: int | None = None, game_stats: bool = False) -> dict:
+                   defer_tail: list | None = None, rng_matchups: int | None = None, game_stats: bool = False,
+                   performance_bootstrap: bool = False) -> dict:
     """Play every deterministic batch not yet owned by the checkpoint and persist the aggregates.  ``defer_final_checkpoint``: the final
     checkpoint's file write may still be in flight on return — the caller joins ``result["checkpoint_written"]`` before reading the file.  ``rng_lags``: also accumulate the lag
     sufficient statistics of the RNG diagnostics' strategy family over the WHOLE shuffle range (``fk_tournament_run_lags``; launch
@@ -567,7 +570,9 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
     ``rng_matchups`` (= ``combine.max_players``; needs ``rng_lags``): the same calls also return the per-game records of the matchup
     family (``fk_tournament_run_matchups``), gathered to rank 0 in range order — ``result["matchup_records"]``.  ``game_stats``: the
     game-stats stage's histograms of the WHOLE range (``fk_tournament_run_game_stats``, on the same launch as the all-player batches),
-    summed on rank 0 — ``result["game_stats"]`` (game_stats.GameStatsSummary)."""
+    summed on rank 0 — ``result["game_stats"]`` (game_stats.GameStatsSummary).  ``performance_bootstrap``: keep the wins / exposures of
+    every deterministic batch (the stats launch of the all-player batches) — ``result["performance_matrix"]`` on rank 0
+    (performance_bootstrap.BatchMatrix)."""
     rank, world = _rank_world()
     _trace(f"{n_players}p run_tournament")
     eng = get_engine()
@@ -664,6 +669,14 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             raise ValueError("lag statistics need the whole shuffle range of the run; this checkpoint already owns batches: use --force")
         if row_dir is not None or all_player_dir is not None:
             raise ValueError("--rng-lag-sums runs without rows / all-player batches (one post-pass per launch): run them separately")
+    want_stats = all_player_dir is not None or performance_bootstrap  # the launch with the all-seat statistics
+    boot_counts: dict[int, np.ndarray] = {}  # batch -> [S][4] wins, exposures, completed, safety-limit exposures (rank 0)
+    if performance_bootstrap:
+        if done_batches:  # the batch statistics are held in memory until the run's end: a partial replay cannot rebuild them
+            raise ValueError("the performance bootstrap needs the statistics of every deterministic batch; this checkpoint already owns "
+                             "batches: use --force")
+        if row_dir is not None or rng_lags:
+            raise ValueError("--performance-bootstrap runs without rows / lag statistics (one post-pass per launch): run them separately")
     gs_total = None
     rare_target = None
     if game_stats:
@@ -796,6 +809,8 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             chunk_lines, all_player_records = [], []
             lists = fragments.result() if fragments is not None else None
             for n, b in enumerate(range(b0, b1)):
+                if performance_bootstrap:
+                    boot_counts[b] = np.ascontiguousarray(group_stats[n][:, _BOOT_STAT_COLUMNS])
                 if all_player_dir is not None:
                     ap = all_player_batch_table(group_stats[n], ids, cfg.sim.seed, k, b, group_ratios[n])
                     name = f"all_player_batch_{b + 1:06d}.parquet"
@@ -908,7 +923,8 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             local[first:first + len(res["tally"])] = res["tally"]
             if local_stats is not None:
                 local_stats[first:first + len(res["seat_stats"])] = res["seat_stats"]
-                local_ratios[first:first + len(res["seat_ratio_sums"])] = res["seat_ratio_sums"]
+                if local_ratios is not None:
+                    local_ratios[first:first + len(res["seat_ratio_sums"])] = res["seat_ratio_sums"]
             if played["shard_job"] is not None:  # (laid out in the prelude, submitted by the engine part)
                 shard_job = played["shard_job"]
             elif want_rows:  # AoS rows (more than 64 seats, lag or all-player runs, an engine without column images): Arrow in writer processes
@@ -943,11 +959,11 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
           lo, hi = shard_shuffle_range(b0 * spb, min(b1 * spb, plan.required_shuffles), rank, world, batch_size=spb)
           # Per-batch tallies are only needed for the metric chunk files; without them the group is one tally, which the
           # engine keeps in LDS when the table is small.
-          per_batch = metric_chunk_dir is not None or all_player_dir is not None
+          per_batch = metric_chunk_dir is not None or want_stats
           g: dict[str, Any] = dict(
               index=n_groups + (1 if awaiting_post is not None else 0), b0=b0, b1=b1, lo=lo, hi=hi, j=j, per_batch=per_batch,
               local=np.zeros((b1 - b0 if per_batch else 1, S, 26), dtype=np.int64),
-              local_stats=np.zeros((b1 - b0, S, SEAT_STAT_COLS), dtype=np.int64) if all_player_dir is not None else None,
+              local_stats=np.zeros((b1 - b0, S, SEAT_STAT_COLS), dtype=np.int64) if want_stats else None,
               local_ratios=np.zeros((b1 - b0, S, SEAT_RATIO_COLS), dtype=np.float64) if all_player_dir is not None else None,
               row_records=[],  # (shuffle index, manifest line, shard bytes, shard sha256)
               fragments=None, hint=None, use_columns=False, async_rows=False, pinned_rows=None, slot=None, extra={}, write=None, tasks=None,
@@ -969,8 +985,10 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                                                  batch_size=spb)
                   if hi2 > lo2:
                       g["hint"] = (lo2, hi2)
-              if all_player_dir is not None:
+              if want_stats:
                   g["extra"]["want_seat_stats"] = True
+                  if all_player_dir is None and not game_stats:  # (only the all-player table reads the four float ratio sums)
+                      g["extra"]["want_seat_ratios"] = False
               g["use_columns"] = columns_mode
               if columns_mode:
                   need = (hi - lo) * image_bytes
@@ -1084,6 +1102,12 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                     sidecars.write("shard_manifest", manifest)
         barrier()
         result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total, game_stats=gs_total)
+        if performance_bootstrap and rank == 0:
+            from .performance_bootstrap import BatchMatrix
+
+            batch_ids = sorted(boot_counts)
+            result["performance_matrix"] = BatchMatrix.from_seat_stats(np.stack([boot_counts[b] for b in batch_ids]), ids, cfg.sim.seed, k,
+                                                                       batch_ids, columns=_BOOT_STAT_NAMES)
         if rng_matchups and rank == 0:  # the grouped reduce of the whole (root, k), on this thread's engine
             from .rng_matchups import concat_records, effective_cap
 
@@ -1121,6 +1145,9 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if cfg.sim.game_stats and not cfg.game_stats_sums_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.game_stats_sums_path(n).name}: --game-stats needs every game of "
                              "the run; use --force to replay it with the game statistics")
+        if cfg.sim.performance_bootstrap and not cfg.performance_batch_matrix_path(n).exists():
+            raise ValueError(f"{n}p is already complete without {cfg.performance_batch_matrix_path(n).name}: --performance-bootstrap needs "
+                             "the statistics of every deterministic batch; use --force to replay it")
         if cfg.sim.rng_matchup_lags and not cfg.rng_matchup_groups_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.rng_matchup_groups_path(n).name}: --rng-matchup-lags needs every "
                              "game of the run; use --force to replay it with the matchup records")
@@ -1142,7 +1169,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if force:
             for path in (ckpt_path, n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), simulation_done_path(cfg, n),
                          cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n), cfg.game_stats_path(n),
-                         cfg.game_stats_sums_path(n)):
+                         cfg.game_stats_sums_path(n), cfg.performance_batch_matrix_path(n), cfg.performance_bootstrap_path(),
+                         cfg.performance_control_contrasts_path()):
                 path.unlink(missing_ok=True)
                 path.with_name(path.name + ".sidecar.json").unlink(missing_ok=True)
             for d in (row_dir, metric_chunk_dir, all_player_dir):
@@ -1193,7 +1221,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             oracle_game_profile=oracle_game_profile, all_player_dir=all_player_dir, sidecars=sidecars,
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
                             packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
-                            rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats)
+                            rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats,
+                            performance_bootstrap=cfg.sim.performance_bootstrap)
     finally:
         if published is not None:
             published.result()  # the inputs are on disk (or their error is raised) before the summaries and the stamp name them
@@ -1289,6 +1318,35 @@ def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrate
         _write_parquet_atomic(rare, cfg.game_stats_rare_summary_path())
 
 
+def _check_performance_bootstrap(cfg: AppConfig, strategies: list[ThresholdStrategy]) -> None:
+    """What ``--performance-bootstrap`` cannot serve is refused before anything plays."""
+    sc = cfg.screening
+    if sc.delta_across_k is None:
+        raise ValueError("screening.delta_across_k is required for shortlist resampling")
+    if isinstance(sc.bootstrap_replicates, bool) or int(sc.bootstrap_replicates) < 1:
+        raise ValueError("screening.bootstrap_replicates must be a positive integer")
+    if int(sc.candidate_contribution_size) < 1:
+        raise ValueError("screening.candidate_contribution_size must be a positive integer")
+    known = {int(s.strategy_id) for s in strategies}
+    missing = sorted(set(int(c) for c in sc.controls).difference(known))
+    if missing:
+        raise ValueError(f"declared controls lack complete k support: {missing}")
+
+
+def _publish_performance_bootstrap(cfg: AppConfig, counts: Sequence[int]) -> None:
+    """After the last player count, on the launching thread of rank 0 (the engine serves one call at a time): the joint batch bootstrap
+    over the batch matrices of the root — ``performance_bootstrap.parquet`` and ``performance_control_contrasts.parquet``."""
+    from . import performance_bootstrap as pb
+
+    matrices = {int(k): pb.BatchMatrix.load(cfg.performance_batch_matrix_path(int(k)), int(k)) for k in counts}
+    sc = cfg.screening
+    boot, contrasts = pb.performance_bootstrap_tables(get_engine(), matrices, sorted(matrices), int(sc.bootstrap_replicates),
+                                                      int(sc.candidate_contribution_size), sc.delta_across_k, sc.controls)
+    for table, path in ((boot, cfg.performance_bootstrap_path()), (contrasts, cfg.performance_control_contrasts_path())):
+        path.parent.mkdir(parents=True, exist_ok=True)
+        _write_parquet_atomic(table, path)
+
+
 def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], plan: TournamentWorkloadPlan, result: dict, grid_size: int,
                      ckpt_path: Path, n_dir: Path, sidecars: "_Sidecars", oracle_game_profile: GameProfile | None) -> None:
     """What follows the last launch of a player count on rank 0: lag tables, summary / metrics parquets, the completion stamp."""
@@ -1306,6 +1364,8 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
         _publish_rng_matchups(cfg, n, strategies, result)
     if cfg.sim.game_stats and result.get("game_stats") is not None:
         _publish_game_stats(cfg, n, strategies, result)
+    if cfg.sim.performance_bootstrap and result.get("performance_matrix") is not None:
+        result["performance_matrix"].save(cfg.performance_batch_matrix_path(n))  # (the frames follow the LAST player count: run_multi)
     # (A) summary parquet, (B) expanded metrics parquet — column order, types and values as in runner.py:1612-1712, built column by
     # column from the tally (the per-strategy dict loop cost 25 us per strategy and table: 140 ms of a 330-ms config-3 run).  Rows in
     # the reference's order: strategies sorted by the STRING of their id, those without an attempted exposure left out.
@@ -1407,6 +1467,8 @@ def run_multi(cfg: AppConfig, player_counts: Sequence[int] | None = None, *, for
     strategies, grid_size = _resolve_strategies(cfg, None)
     valid, _ = _filter_player_counts(counts, grid_size)
     results: dict[int, int] = {}
+    if cfg.sim.performance_bootstrap:
+        _check_performance_bootstrap(cfg, strategies)
     # A player count's publishing tail (summary tables, completion stamp: 10 - 20 ms of Python on the 5 160-strategy grid; in rows mode
     # also the count's last launch groups, whose shards are still being written) runs on its own thread under the NEXT player counts'
     # engine calls (ctypes drops the GIL for their duration).  The tails run in order on that one thread; the launching thread joins a
@@ -1448,6 +1510,8 @@ def run_multi(cfg: AppConfig, player_counts: Sequence[int] | None = None, *, for
             for t, thread, label in _TRACE:
                 print(f"[fk trace] {(t - t0) * 1e3:9.2f} ms  {thread:24s} {label}", file=sys.stderr)
             _TRACE.clear()
+    if cfg.sim.performance_bootstrap and valid and _rank_world()[0] == 0:  # the matrices of every count are reduced on rank 0
+        _publish_performance_bootstrap(cfg, valid)
     return results
 
 

@@ -450,6 +450,38 @@ int fk_debug_dice_state(fk_ctx *ctx, int64_t n, const uint64_t *state, int32_t n
 int fk_debug_dice_keys(fk_ctx *ctx, int64_t n, const uint64_t *state, int32_t n_calls, const int32_t *sizes, uint32_t *keys,
                        uint64_t *state_out);
 
+/* The device's bounded draw (farkle_ii_amd/csrc/fk_bootstrap.h: bounded_draw, the function fk_performance_bootstrap resamples
+ * with): out[i * n_draws + j] = draw j of Generator(PCG64DXSM(coords[i])).integers(0, bound, size = n_draws), i.e. numpy's
+ * buffered_bounded_lemire_uint32 on the buffered 32-bit stream (low half of a 64-bit output first).  1 <= bound <= 2^32 - 1; bound 1
+ * draws nothing from the stream (every result 0).  A bound such as 2^31 + 1 rejects about half the draws, which no batch count does. */
+int fk_debug_bounded_draws(fk_ctx *ctx, int64_t n, const fk_coord *coords, uint64_t bound, int32_t n_draws, uint32_t *out);
+
+/* The performance stage's joint deterministic-batch bootstrap (analysis/performance.py: _BootstrapRangeWriter.__call__ :838-928,
+ * _reduce_bootstrap_ranges :1013-1111; _joint_batch_resampling :715-833) for replicates [replicate_begin, replicate_end).
+ * Inputs: n_k player counts in the caller's (ascending) order; per player count i its k = ks[i], its ELIGIBLE batches
+ * batch_counts[i] (the caller has projected to complete-support strategies and dropped every batch in which one of them has no
+ * exposure, :861-868) and two row-major int64 [batch_counts[i]][S] matrices wins[i] / exposures[i] (raw_wins,
+ * raw_player_game_exposures); S strategy columns in ascending strategy id; top_n in [0, S]; delta (screening.delta_across_k);
+ * n_controls column indices.  Per replicate r and player count: stream (purpose 400, root_seed, k, replicate_index r), B_k draws
+ * in [0, B_k) (B_k = 1 draws nothing), exact int64 resampled totals, score[r][s] = (sum over k of (double)wins / (double)exposures
+ * - 1.0 / k) / n_k as separate IEEE operations, in the given order of player counts.
+ * Outputs (caller-owned host memory):
+ *   scores               float64 [replicate_end - replicate_begin][S], nullable: the payload of the range writer's .npy
+ *   rank_sum, rank_square_sum, top_counts, shortlist_counts   int64 [S], required, overwritten: over the call's replicates, rank =
+ *                        position in lexsort((strategies, -score)) from 1 (ties: ascending column), top = rank <= top_n,
+ *                        shortlist = score >= max(score) - delta
+ *   contrast_sum, contrast_square_sum   float64 [n_controls][S], IN / OUT: the call continues the sums it is given with
+ *                        d = score[r][s] - score[r][controls[c]]; sum += d; square_sum += d * d, replicate by replicate in ascending
+ *                        order, so a range split over several calls gives the bits of one call.  Nullable when n_controls = 0.
+ * A resampled exposure total <= 0 (the reference's ValueError), a negative count or one whose total could pass 2^63 returns
+ * FK_ERR_ARG.  Option "bootstrap_block" > 0 caps the replicates of one device block (default: from the workspace budget); results do
+ * not depend on it. */
+int fk_performance_bootstrap(fk_ctx *ctx, uint64_t root_seed, int32_t n_k, const int32_t *ks, const int64_t *batch_counts,
+                             const int64_t *const *wins, const int64_t *const *exposures, int32_t S, int64_t replicate_begin,
+                             int64_t replicate_end, int32_t top_n, double delta, int32_t n_controls, const int32_t *controls,
+                             double *scores, int64_t *rank_sum, int64_t *rank_square_sum, int64_t *top_counts, int64_t *shortlist_counts,
+                             double *contrast_sum, double *contrast_square_sum);
+
 #ifdef __cplusplus
 }
 #endif
