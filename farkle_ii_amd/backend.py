@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_bootstrap.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -110,7 +110,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap"]
 _libs: dict = {}
 
 
@@ -739,6 +739,49 @@ class Engine:
             _p(ctrl) if n_ctrl else None, _p(scores), *[_p(a) for a in counters], _p(csum) if n_ctrl else None, _p(csq) if n_ctrl else None))
         return {"scores": scores, "rank_sum": counters[0], "rank_square_sum": counters[1], "top_counts": counters[2],
                 "shortlist_counts": counters[3], "contrast_sum": csum, "contrast_square_sum": csq}
+
+    def root_stability_bootstrap(self, roots, ks, wins, exposures, weights, replicate_begin: int, replicate_end: int, top_n: int,
+                                 observed=None, expected=None, observed_across=None, expected_across=None,
+                                 want_membership: bool = False) -> dict:
+        """``fk_root_stability_bootstrap``: the two-root stability stage's bootstrap families for replicates ``[replicate_begin,
+        replicate_end)``.  ``wins[c]`` / ``exposures[c]``: int64 ``[B_c][S]`` of cell ``c`` in (root, k) order — ``roots[0]``'s player
+        counts ``ks``, then ``roots[1]``'s — eligible batches only; ``weights``: one per player count.  ``observed`` / ``expected``
+        ``[n_k][S]`` and ``observed_across`` / ``expected_across`` ``[S]`` come as a group or not at all (top-N family only).
+        Returns int64 ``top_counts`` ``[2][S]``, float64 ``maxima`` ``[R]`` (None without the group) and uint8 ``membership``
+        ``[R][2][S]`` (None unless asked for)."""
+        ks = [int(v) for v in ks]
+        n_k = len(ks)
+        if not n_k or len(wins) != 2 * n_k or len(exposures) != 2 * n_k or len(list(weights)) != n_k or len(list(roots)) != 2:
+            raise ValueError("two roots, one weight per player count and one wins / exposures matrix per (root, player count) cell")
+        W = [np.ascontiguousarray(m, dtype=np.int64) for m in wins]
+        E = [np.ascontiguousarray(m, dtype=np.int64) for m in exposures]
+        S = int(W[0].shape[1]) if W[0].ndim == 2 else -1
+        for w, e in zip(W, E):
+            if w.ndim != 2 or w.shape != e.shape or w.shape[1] != S:
+                raise ValueError("every matrix is [batches][S] with one S")
+        group = [observed, expected, observed_across, expected_across]
+        if sum(v is not None for v in group) not in (0, 4):
+            raise ValueError("observed / expected by k and across k come as a group of four")
+        joint = observed is not None
+        if joint:
+            group = [np.ascontiguousarray(v, dtype=np.float64) for v in group]
+            if group[0].shape != (n_k, S) or group[1].shape != (n_k, S) or group[2].shape != (S,) or group[3].shape != (S,):
+                raise ValueError("observed / expected are [n_k][S], observed_across / expected_across [S]")
+        R = max(int(replicate_end) - int(replicate_begin), 0)
+        root_arr = np.asarray([int(r) for r in roots], dtype=np.uint64)
+        k_arr = np.asarray(ks, dtype=np.int32)
+        b_arr = np.asarray([len(m) for m in W], dtype=np.int64)
+        w_arr = np.asarray([float(w) for w in weights], dtype=np.float64)
+        w_ptr = (C.c_void_p * (2 * n_k))(*[m.ctypes.data for m in W])
+        e_ptr = (C.c_void_p * (2 * n_k))(*[m.ctypes.data for m in E])
+        top_counts = np.zeros((2, S), dtype=np.int64)
+        maxima = np.zeros(R, dtype=np.float64) if joint else None
+        membership = np.zeros((R, 2, S), dtype=np.uint8) if want_membership else None
+        self._check(self._lib.fk_root_stability_bootstrap(
+            self._ctx, _p(root_arr), C.c_int32(n_k), _p(k_arr), _p(b_arr), w_ptr, e_ptr, C.c_int32(S), _p(w_arr),
+            C.c_int64(int(replicate_begin)), C.c_int64(int(replicate_end)), C.c_int32(int(top_n)), *[_p(v) if joint else None for v in group],
+            _p(top_counts), _p(maxima), _p(membership)))
+        return {"top_counts": top_counts, "maxima": maxima, "membership": membership}
 
     def debug_dice_state(self, state: np.ndarray, sizes):
         state = np.ascontiguousarray(state, dtype=np.uint64).reshape(-1, 6)

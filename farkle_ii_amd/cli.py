@@ -1,10 +1,11 @@
-"""``farkle`` command line for the simulation path: ``run`` and ``time``.
+"""``farkle`` command line for the simulation path: ``run``, ``time`` and ``root-stability``.
 
 Mirrors ``src/farkle/cli/main.py`` (:53-140 parser, :325-464 dispatch) for the two commands on this path; the
 analysis/orchestration commands of the reference are out of scope and are rejected with a clear message.
 
     python -m farkle_ii_amd --config configs/fast.yaml --set sim.n_players_list=[2] --set sim.seed_list=[42] run --metrics
     python -m farkle_ii_amd time --players 2 --n-games 1000 --seed 42
+    python -m farkle_ii_amd --config cfg.yaml root-stability --root-results data/results_seed_11 --root-results data/results_seed_23
     torchrun --nproc-per-node 8 -m farkle_ii_amd --config cfg.yaml run      (one process per GPU, RCCL tally reduce)
 """
 from __future__ import annotations
@@ -71,6 +72,15 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--n-games", dest="n_games", type=int, default=1000, help="Number of games to run (default: 1000)")
     t.add_argument("--jobs", type=int, default=1, help="Parallel jobs (accepted for compatibility)")
     t.add_argument("--seed", type=int, default=42, help="Seed (default: 42)")
+    rs = sub.add_parser("root-stability", help="The two-root stability stage's bootstrap families from two roots' batch matrices")
+    rs.add_argument("--root-results", action="append", default=[], type=Path, metavar="DIR",
+                    help="Results root of one `farkle run --performance-bootstrap` (its analysis/03_metrics/by_k/<k>p/"
+                         "performance_batch_matrix.npy for every player count of sim.n_players_list); exactly two, of different roots")
+    rs.add_argument("--out", type=Path, metavar="DIR",
+                    help="Write root_bootstrap_top_n_inclusion.parquet, root_discrepancies.parquet and root_joint_discrepancy.parquet under "
+                         "DIR/root_stability/ (default: roots_<a>_<b> beside the first results root).  Settings: "
+                         "screening.bootstrap_replicates, candidate_contribution_size, practical_delta_by_k, delta_across_k, "
+                         "robustness.delta_seed_stability, robustness.joint_discrepancy_alpha, k_aggregation")
     for name in _OUT_OF_SCOPE:
         sub.add_parser(name, help="(reference command outside the simulation path)")
     return parser
@@ -107,6 +117,10 @@ def main(argv: Sequence[str] | None = None) -> None:
 
     cfg = load_app_config(args.config, seed_list_len=None) if args.config is not None else AppConfig()
     cfg = apply_dot_overrides(cfg, list(args.overrides or []))
+    if args.command == "root-stability":
+        written = runner.run_root_stability(cfg, args.root_results, out=args.out)
+        print({name: str(path) for name, path in written.items()})
+        return
     if cfg.sim.seed_list is not None and len(cfg.sim.seed_list) != 1:
         raise ValueError(f"sim.seed_list must contain exactly 1 seeds, got {cfg.sim.seed_list!r}")
     cfg.sim.populate_seed_list(1)

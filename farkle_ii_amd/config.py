@@ -207,6 +207,25 @@ class AppConfig:
         """config.py:1006-1009."""
         return self.metrics_stage_dir() / "across_k" / "performance_control_contrasts.parquet"
 
+    def root_stability_settings(self) -> dict:
+        """What the two-root stability stage reads beside ``screening``: ``robustness.delta_seed_stability`` (config.py:201, default
+        0.03), ``robustness.joint_discrepancy_alpha`` (:202, default 0.05) and ``k_aggregation`` (:222-226, default ``equal-k``); both
+        sections are carried opaquely, the reference's defaults apply to what they do not set."""
+        robustness = self.opaque.get("robustness") or {}
+        aggregation = self.opaque.get("k_aggregation") or {}
+        threshold = float(robustness.get("delta_seed_stability", 0.03))
+        alpha = float(robustness.get("joint_discrepancy_alpha", 0.05))
+        if not threshold > 0.0:
+            raise ValueError("robustness.delta_seed_stability must be positive")
+        if not 0.0 < alpha < 1.0:
+            raise ValueError("robustness.joint_discrepancy_alpha must be in (0, 1)")
+        method = str(aggregation.get("method", "equal-k"))
+        if method not in ("equal-k", "declared-mapping"):
+            raise ValueError("k_aggregation.method must be equal-k or declared-mapping")
+        declared = aggregation.get("k_weights")
+        return {"delta_seed_stability": threshold, "joint_discrepancy_alpha": alpha, "k_aggregation_method": method,
+                "declared_k_weights": None if declared is None else {int(k): float(v) for k, v in dict(declared).items()}}
+
     def game_stats_path(self, n: int) -> Path:
         return self.n_dir(n) / f"{n}p_game_stats.parquet"
 

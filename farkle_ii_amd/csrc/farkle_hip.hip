@@ -11,6 +11,7 @@
 #include "fk_matchups.h"      // device side: RNG-diagnostics matchup family (key post-pass, grouped lag reduce)
 #include "fk_game_stats.h"    // device side: game-stats stage (game-record pass, per-strategy LDS histogram gather)
 #include "fk_bootstrap.h"     // device side: performance stage's joint batch bootstrap (draws, integer product, ranks, contrasts)
+#include "fk_root_stability.h" // device side: two-root stability stage's bootstrap families (rates of both roots, maxima, top-N membership)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -19,6 +20,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <memory>
 #include <mutex>
 #include <sys/mman.h>
@@ -148,6 +150,7 @@ struct fk_ctx {
     DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
     const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
+    DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
@@ -1234,6 +1237,19 @@ int comm_wait_stream(fk_ctx *c, const char *what, double t0) {
 
 } // namespace
 
+// Exactness of a cell's resampled int64 totals: every value of both [B][S] matrices in [0, 2^63 / B)
+static bool boot_totals_exact(const int64_t *wins, const int64_t *exposures, uint64_t B, size_t S) {
+    const uint64_t limit = ((uint64_t)1 << 63) / B;
+    const size_t cells = (size_t)B * S;
+    uint64_t seen = 0, top = 0; // OR of all values (a negative one sets the top bit); their maximum, looked for only when the OR is large
+    for (const int64_t *m : {wins, exposures})
+        for (size_t j = 0; j < cells; ++j) seen |= (uint64_t)m[j];
+    if (seen >= limit)
+        for (const int64_t *m : {wins, exposures})
+            for (size_t j = 0; j < cells; ++j) top = std::max(top, (uint64_t)m[j]);
+    return top < limit;
+}
+
 extern "C" {
 
 void fk_destroy(fk_ctx *c);
@@ -1325,6 +1341,7 @@ void fk_destroy(fk_ctx *c) {
         release(*b);
     for (DevBuf &b : c->mr) release(b);
     for (DevBuf &b : c->boot) release(b);
+    for (DevBuf &b : c->rootb) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
@@ -3202,19 +3219,11 @@ int fk_performance_bootstrap(fk_ctx *c, uint64_t root_seed, int32_t n_k, const i
         if (ks[i] < 1) return fail(c, FK_ERR_ARG, "player count %d: k = %d", i, ks[i]);
         if (batch_counts[i] < 1 || batch_counts[i] > 0xffffffffll || !wins[i] || !exposures[i])
             return fail(c, FK_ERR_ARG, "player count %d needs 1 to 2^32 - 1 eligible batches and both matrices", ks[i]);
-        kd[(size_t)i] = {(uint64_t)ks[i], (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)ks[i]};
+        kd[(size_t)i] = {root_seed, (uint64_t)ks[i], (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)ks[i]};
         sum_B += (uint64_t)batch_counts[i];
         if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
-        // exactness of the int64 totals: every value in [0, 2^63 / B_k)
-        const uint64_t limit = ((uint64_t)1 << 63) / (uint64_t)batch_counts[i];
-        const size_t cells = (size_t)batch_counts[i] * (size_t)S;
-        uint64_t seen = 0, top = 0; // OR of all values (a negative one sets the top bit); their maximum, looked for only when the OR is large
-        for (const int64_t *m : {wins[i], exposures[i]})
-            for (size_t j = 0; j < cells; ++j) seen |= (uint64_t)m[j];
-        if (seen >= limit)
-            for (const int64_t *m : {wins[i], exposures[i]})
-                for (size_t j = 0; j < cells; ++j) top = std::max(top, (uint64_t)m[j]);
-        if (top >= limit) return fail(c, FK_ERR_ARG, "player count %d: a negative count, or one whose resampled total can pass 2^63", ks[i]);
+        if (!boot_totals_exact(wins[i], exposures[i], (uint64_t)batch_counts[i], (size_t)S))
+            return fail(c, FK_ERR_ARG, "player count %d: a negative count, or one whose resampled total can pass 2^63", ks[i]);
     }
     const int64_t n_rep = replicate_end - replicate_begin;
     HIPCHK(c, hipSetDevice(c->device));
@@ -3260,7 +3269,7 @@ int fk_performance_bootstrap(fk_ctx *c, uint64_t root_seed, int32_t n_k, const i
     for (int64_t b0 = 0; b0 < n_rep; b0 += block) {
         const uint32_t nr = (uint32_t)std::min<int64_t>(block, n_rep - b0), nr_pad = (nr + fkb::RB - 1) / fkb::RB * fkb::RB;
         HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)nr_pad * sum_B * 4, c->stream));
-        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_k + 63) / 64), dim3(64), 0, c->stream, root_seed,
+        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_k + 63) / 64), dim3(64), 0, c->stream, fkb::PURPOSE_BOOTSTRAP,
                            (uint64_t)(replicate_begin + b0), nr, (uint32_t)n_k, d_kd, (uint32_t)sum_B, d_counts);
         hipLaunchKernelGGL(fkb::fk_boot_score_kernel, dim3(s_tiles, nr_pad / fkb::RB), dim3(fkb::TS), 0, c->stream,
                            static_cast<const int64_t *>(c->boot[0].p), static_cast<const int64_t *>(c->boot[1].p), d_counts, d_kd,
@@ -3285,6 +3294,137 @@ int fk_performance_bootstrap(fk_ctx *c, uint64_t root_seed, int32_t n_k, const i
         HIPCHK(c, hipMemcpyAsync(contrast_square_sum, d_contrast + (size_t)n_controls * S, contrast_bytes / 2, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+int fk_root_stability_bootstrap(fk_ctx *c, const uint64_t *roots, int32_t n_k, const int32_t *ks, const int64_t *batch_counts,
+                                const int64_t *const *wins, const int64_t *const *exposures, int32_t S, const double *weights,
+                                int64_t replicate_begin, int64_t replicate_end, int32_t top_n, const double *observed,
+                                const double *expected, const double *observed_across, const double *expected_across,
+                                int64_t *top_counts, double *maxima, uint8_t *membership) {
+    if (!c) return FK_ERR_ARG;
+    if (!roots || roots[0] >= roots[1]) return fail(c, FK_ERR_ARG, "two roots (a, b) with a < b are required");
+    if (n_k < 1 || n_k > 64 || !ks || !batch_counts || !wins || !exposures || !weights)
+        return fail(c, FK_ERR_ARG, "1 to 64 player counts with their weights and the matrices of both roots are required");
+    if (S < 1 || S > (1 << 24)) return fail(c, FK_ERR_ARG, "S must be in [1, 2^24]");
+    if (replicate_begin < 0 || replicate_end < replicate_begin) return fail(c, FK_ERR_ARG, "bad replicate range");
+    if (top_n < 0 || top_n > S) return fail(c, FK_ERR_ARG, "top_n must be in [0, S]");
+    if (!top_counts) return fail(c, FK_ERR_ARG, "top_counts is required");
+    const int given = (observed ? 1 : 0) + (expected ? 1 : 0) + (observed_across ? 1 : 0) + (expected_across ? 1 : 0);
+    if (given != 0 && given != 4) return fail(c, FK_ERR_ARG, "observed / expected by k and across k come as a group of four");
+    const bool joint = given == 4;
+    if (joint && !maxima) return fail(c, FK_ERR_ARG, "the joint family needs the maxima output");
+    for (int32_t i = 0; i < n_k; ++i) {
+        if (ks[i] < 1) return fail(c, FK_ERR_ARG, "player count %d: k = %d", i, ks[i]);
+        if (!std::isfinite(weights[i])) return fail(c, FK_ERR_ARG, "player count %d: its weight is not finite", ks[i]);
+    }
+    if (joint) { // expected may be NaN or <= 0 (the column is no estimand); a non-finite observed would poison a maximum
+        for (size_t j = 0; j < (size_t)n_k * (size_t)S; ++j)
+            if (!std::isfinite(observed[j])) return fail(c, FK_ERR_ARG, "player count %d: observed is not finite", ks[j / (size_t)S]);
+        for (size_t j = 0; j < (size_t)S; ++j)
+            if (!std::isfinite(observed_across[j])) return fail(c, FK_ERR_ARG, "across k: observed is not finite");
+    }
+    const int32_t n_cells = 2 * n_k;
+    std::vector<fkb::KDesc> kd((size_t)n_cells);
+    uint64_t sum_B = 0;
+    for (int32_t i = 0; i < n_cells; ++i) {
+        const int32_t k = ks[i % n_k];
+        const unsigned long long root = (unsigned long long)roots[i / n_k];
+        if (batch_counts[i] < 1 || batch_counts[i] > 0xffffffffll || !wins[i] || !exposures[i])
+            return fail(c, FK_ERR_ARG, "root %llu, player count %d needs 1 to 2^32 - 1 eligible batches and both matrices", root, k);
+        kd[(size_t)i] = {roots[i / n_k], (uint64_t)k, (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)k};
+        sum_B += (uint64_t)batch_counts[i];
+        if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
+        if (!boot_totals_exact(wins[i], exposures[i], (uint64_t)batch_counts[i], (size_t)S))
+            return fail(c, FK_ERR_ARG, "root %llu, player count %d: a negative count, or one whose resampled total can pass 2^63", root, k);
+    }
+    const int64_t n_rep = replicate_end - replicate_begin;
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc;
+    // resident for the call: both stacked matrices, the descriptors, weights | observed | expected | across, the counters of both roots
+    const size_t mat_bytes = (size_t)sum_B * (size_t)S * 8;
+    const size_t by_k = (size_t)n_k * (size_t)S;
+    const size_t par_doubles = (size_t)n_k + (joint ? 2 * by_k + 2 * (size_t)S : 0);
+    const size_t counter_bytes = (size_t)2 * 4 * S * 8; // the rank kernel's four counters per root
+    if ((rc = ensure(c, c->boot[0], mat_bytes))) return rc;
+    if ((rc = ensure(c, c->boot[1], mat_bytes))) return rc;
+    if ((rc = ensure(c, c->boot[2], kd.size() * sizeof(fkb::KDesc)))) return rc;
+    if ((rc = ensure(c, c->boot[7], 4))) return rc;
+    if ((rc = ensure(c, c->rootb[0], par_doubles * 8))) return rc;
+    if ((rc = ensure(c, c->rootb[3], counter_bytes))) return rc;
+    for (int which = 0; which < 2; ++which)
+        for (int32_t i = 0; i < n_cells; ++i)
+            HIPCHK(c, hipMemcpyAsync(static_cast<int64_t *>(c->boot[which].p) + (size_t)kd[(size_t)i].row0 * (size_t)S, (which ? exposures : wins)[i],
+                                     (size_t)kd[(size_t)i].B * (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->boot[2].p, kd.data(), kd.size() * sizeof(fkb::KDesc), hipMemcpyHostToDevice, c->stream));
+    double *d_weights = static_cast<double *>(c->rootb[0].p);
+    double *d_observed = d_weights + n_k, *d_expected = d_observed + by_k, *d_observed_across = d_expected + by_k, *d_expected_across = d_observed_across + S;
+    HIPCHK(c, hipMemcpyAsync(d_weights, weights, (size_t)n_k * 8, hipMemcpyHostToDevice, c->stream));
+    if (joint) {
+        HIPCHK(c, hipMemcpyAsync(d_observed, observed, by_k * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_expected, expected, by_k * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_observed_across, observed_across, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_expected_across, expected_across, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(c->rootb[3].p, 0, counter_bytes, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->boot[7].p, 0, 4, c->stream));
+    // the replicate range in blocks sized from the workspace budget: per replicate one multiplicity row, one score row per root, one
+    // maximum and (when asked for) one membership row per root.  Counts are integers and maxima per replicate: no carried state.
+    const size_t per_rep = (size_t)sum_B * 4 + (size_t)2 * S * 8 + 8 + (membership ? (size_t)2 * S : 0);
+    int64_t block = std::max<int64_t>((int64_t)(workspace_budget(c) / 2 / (int64_t)per_rep), 1);
+    block = std::min<int64_t>(block, 4096);
+    if (c->bootstrap_block > 0) block = std::min(block, c->bootstrap_block);
+    block = std::min<int64_t>(std::max<int64_t>(block / fkr::RRB * fkr::RRB, fkr::RRB), (n_rep + fkr::RRB - 1) / fkr::RRB * fkr::RRB);
+    if (n_rep > 0) {
+        if ((rc = ensure(c, c->boot[3], (size_t)block * sum_B * 4))) return rc;
+        if ((rc = ensure(c, c->boot[4], (size_t)block * 2 * S * 8))) return rc;
+        if ((rc = ensure(c, c->rootb[1], (size_t)block * 8))) return rc;
+        if (membership && (rc = ensure(c, c->rootb[2], (size_t)block * 2 * S))) return rc;
+    }
+    const fkb::KDesc *d_kd = static_cast<const fkb::KDesc *>(c->boot[2].p);
+    const int64_t *d_W = static_cast<const int64_t *>(c->boot[0].p), *d_E = static_cast<const int64_t *>(c->boot[1].p);
+    uint32_t *d_counts = static_cast<uint32_t *>(c->boot[3].p);
+    double *d_scores = static_cast<double *>(c->boot[4].p);
+    unsigned long long *d_maxima = static_cast<unsigned long long *>(c->rootb[1].p);
+    uint8_t *d_member = static_cast<uint8_t *>(c->rootb[2].p);
+    unsigned long long *d_counters = static_cast<unsigned long long *>(c->rootb[3].p);
+    int32_t *d_bad = static_cast<int32_t *>(c->boot[7].p);
+    const unsigned s_tiles = (unsigned)((S + fkb::TS - 1) / fkb::TS);
+    for (int64_t b0 = 0; b0 < n_rep; b0 += block) {
+        const uint32_t nr = (uint32_t)std::min<int64_t>(block, n_rep - b0), nr_pad = (nr + fkr::RRB - 1) / fkr::RRB * fkr::RRB;
+        HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)nr_pad * sum_B * 4, c->stream));
+        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_cells + 63) / 64), dim3(64), 0, c->stream,
+                           fkb::PURPOSE_ROOT_STABILITY_BOOTSTRAP, (uint64_t)(replicate_begin + b0), nr, (uint32_t)n_cells, d_kd, (uint32_t)sum_B,
+                           d_counts);
+        const dim3 rates_grid(s_tiles, nr_pad / fkr::RRB);
+        if (joint) {
+            HIPCHK(c, hipMemsetAsync(d_maxima, 0, (size_t)nr_pad * 8, c->stream));
+            hipLaunchKernelGGL(fkr::fk_root_rates_kernel<true>, rates_grid, dim3(fkb::TS), 0, c->stream, d_W, d_E, d_counts, d_kd, (uint32_t)n_k,
+                               (uint32_t)sum_B, (uint32_t)S, nr, d_weights, d_observed, d_expected, d_observed_across, d_expected_across,
+                               d_scores, d_maxima, d_bad);
+        } else {
+            hipLaunchKernelGGL(fkr::fk_root_rates_kernel<false>, rates_grid, dim3(fkb::TS), 0, c->stream, d_W, d_E, d_counts, d_kd, (uint32_t)n_k,
+                               (uint32_t)sum_B, (uint32_t)S, nr, d_weights, nullptr, nullptr, nullptr, nullptr, d_scores, nullptr, d_bad);
+        }
+        for (int root = 0; root < 2; ++root) // the rank kernel's top-n counter (third of four) is this root's inclusion count
+            hipLaunchKernelGGL(fkb::fk_boot_rank_kernel, dim3(s_tiles, (nr + fkb::RC - 1) / fkb::RC), dim3(fkb::TS), 0, c->stream,
+                               d_scores + (size_t)root * nr * S, (uint32_t)S, nr, (uint32_t)top_n, 0.0, d_counters + (size_t)root * 4 * S);
+        if (membership)
+            hipLaunchKernelGGL(fkr::fk_root_member_kernel, dim3(s_tiles, 2 * nr), dim3(fkb::TS), 0, c->stream, d_scores, (uint32_t)S, nr,
+                               (uint32_t)top_n, d_member);
+        HIPCHK(c, hipGetLastError());
+        if (joint) HIPCHK(c, hipMemcpyAsync(maxima + b0, d_maxima, (size_t)nr * 8, hipMemcpyDeviceToHost, c->stream));
+        if (membership) HIPCHK(c, hipMemcpyAsync(membership + (size_t)b0 * 2 * S, d_member, (size_t)nr * 2 * S, hipMemcpyDeviceToHost, c->stream));
+    }
+    int32_t bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (bad) return fail(c, FK_ERR_ARG, "root bootstrap produced zero complete-support exposure");
+    for (int root = 0; root < 2; ++root)
+        HIPCHK(c, hipMemcpyAsync(top_counts + (size_t)root * S, d_counters + ((size_t)root * 4 + 2) * S, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!joint && maxima)
+        for (int64_t r = 0; r < n_rep; ++r) maxima[r] = 0.0;
     return FK_OK;
 }
 

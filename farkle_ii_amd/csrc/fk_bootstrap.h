@@ -6,7 +6,8 @@
 // (BOOTSTRAP = 400, root, k, replicate_index = r); B_k bounded draws in [0, B_k) resample the k's eligible batches; the resampled
 // integer totals give score[r][s] = mean over k of (wins / exposures - 1 / k); every replicate is ranked and reduced.
 //
-//   fk_boot_counts_kernel    one lane per (replicate, player count) stream: SeedSequence -> PCG64DXSM -> B_k Lemire draws on the
+//   fk_boot_counts_kernel    one lane per (replicate, cell) stream (a cell: a player count here, a (root, player count) of
+//                            fk_root_stability.h; the purpose is a launch argument): SeedSequence -> PCG64DXSM -> B_k Lemire draws on the
 //                            buffered 32-bit stream (a rejected draw shifts every later one: a stream is sequential), counted into
 //                            the stream's own multiplicity row counts[replicate][batch] (zeroed before the launch).
 //   fk_boot_score_kernel     the hot path: [R x B] . [B x S] in exact 64-bit integers.  Strategy on the lane (matrix rows are read
@@ -30,9 +31,12 @@ constexpr uint32_t BT = 64;  // batches per LDS tile of multiplicities
 constexpr uint32_t TS = 256; // strategies per workgroup
 constexpr uint32_t RC = 8;   // replicates per workgroup of the rank kernel
 constexpr uint32_t JT = 2048; // keys per LDS tile of the rank kernel
-constexpr uint32_t PURPOSE_BOOTSTRAP = 400;
+constexpr uint32_t PURPOSE_BOOTSTRAP = 400;                // RandomPurpose.BOOTSTRAP
+constexpr uint32_t PURPOSE_ROOT_STABILITY_BOOTSTRAP = 401; // RandomPurpose.ROOT_STABILITY_BOOTSTRAP (fk_root_stability.h)
 
+// One resampled cell: a player count of the performance stage's root, or a (root, player count) of the two-root stability stage.
 struct KDesc {
+    uint64_t root;  // the coordinate's root_seed
     uint64_t k;     // player count (the coordinate's k)
     uint32_t B;     // eligible batches
     uint32_t row0;  // first row of this player count in the stacked matrices = its offset in a replicate's multiplicity row
@@ -68,8 +72,8 @@ __device__ inline uint32_t bounded_draw(Rng &r, uint32_t bound) {
     return (uint32_t)(m >> 32);
 }
 
-// counts: [n_rep_padded][sum_B] uint32, zero on entry; stream t = (replicate r0 + t / n_k, player count t % n_k)
-__global__ __launch_bounds__(64) void fk_boot_counts_kernel(uint64_t root_seed, uint64_t r0, uint32_t n_rep, uint32_t n_k, const KDesc *kd,
+// counts: [n_rep_padded][sum_B] uint32, zero on entry; stream t = (replicate r0 + t / n_k, cell t % n_k) of the caller's purpose
+__global__ __launch_bounds__(64) void fk_boot_counts_kernel(uint32_t purpose, uint64_t r0, uint32_t n_rep, uint32_t n_k, const KDesc *kd,
                                                              uint32_t sum_B, uint32_t *counts) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_rep * n_k) return;
@@ -81,8 +85,8 @@ __global__ __launch_bounds__(64) void fk_boot_counts_kernel(uint64_t root_seed, 
         return;
     }
     fk_coord c{};
-    c.purpose = PURPOSE_BOOTSTRAP;
-    c.root_seed = root_seed;
+    c.purpose = purpose;
+    c.root_seed = d.root;
     c.k = d.k;
     c.replicate_index = r0 + rr;
     Rng r;
@@ -104,6 +108,36 @@ __global__ __launch_bounds__(64) void fk_boot_draws_kernel(int64_t n, const fk_c
     for (uint32_t j = 0; j < n_draws; ++j) o[j] = bounded_draw(r, bound);
 }
 
+// One cell's resampled totals of NR replicates (rr0 ...) for the lane's strategy column sr: w[r] += counts[r][b] * W[b][sr], e likewise, in
+// exact 64-bit integers over the cell's batches.  The multiplicities of BT batches pass through LDS (cnt) and are read as uniform
+// ds_read_b128; every lane of the workgroup calls this together.
+template <uint32_t NR>
+__device__ inline void cell_totals(const int64_t *W, const int64_t *E, const uint32_t *counts, const KDesc &d, uint32_t sum_B, uint32_t S,
+                                   uint32_t sr, uint32_t rr0, uint4 (*cnt)[NR / 4], uint64_t (&w)[NR], uint64_t (&e)[NR]) {
+    for (uint32_t b0 = 0; b0 < d.B; b0 += BT) {
+        const uint32_t nb = min(BT, d.B - b0);
+        __syncthreads();
+        for (uint32_t i = threadIdx.x; i < BT * NR; i += TS) {
+            const uint32_t r = i / BT, b = i - r * BT; // consecutive lanes read consecutive batches of one replicate
+            const uint32_t v = b < nb ? counts[(size_t)(rr0 + r) * sum_B + d.row0 + b0 + b] : 0u;
+            reinterpret_cast<uint32_t *>(&cnt[b][0])[r] = v;
+        }
+        __syncthreads();
+        const int64_t *wp = W + (size_t)(d.row0 + b0) * S + sr, *ep = E + (size_t)(d.row0 + b0) * S + sr;
+        for (uint32_t b = 0; b < nb; ++b) {
+            const uint64_t wv = (uint64_t)wp[(size_t)b * S], ev = (uint64_t)ep[(size_t)b * S];
+#pragma unroll
+            for (uint32_t q = 0; q < NR / 4; ++q) {
+                const uint4 c4 = cnt[b][q];
+                w[4 * q + 0] += (uint64_t)c4.x * wv, e[4 * q + 0] += (uint64_t)c4.x * ev;
+                w[4 * q + 1] += (uint64_t)c4.y * wv, e[4 * q + 1] += (uint64_t)c4.y * ev;
+                w[4 * q + 2] += (uint64_t)c4.z * wv, e[4 * q + 2] += (uint64_t)c4.z * ev;
+                w[4 * q + 3] += (uint64_t)c4.w * wv, e[4 * q + 3] += (uint64_t)c4.w * ev;
+            }
+        }
+    }
+}
+
 // grid = (ceil(S / TS), n_rep_padded / RB), block = TS.  W / E: the stacked [sum_B][S] matrices.  scores: [n_rep_padded][S].
 // *bad is set when a resampled exposure total is <= 0 (the reference's ValueError).
 __global__ __launch_bounds__(TS) void fk_boot_score_kernel(const int64_t *W, const int64_t *E, const uint32_t *counts, const KDesc *kd, uint32_t n_k,
@@ -122,28 +156,7 @@ __global__ __launch_bounds__(TS) void fk_boot_score_kernel(const int64_t *W, con
         uint64_t w[RB], e[RB];
 #pragma unroll
         for (uint32_t r = 0; r < RB; ++r) w[r] = 0, e[r] = 0;
-        for (uint32_t b0 = 0; b0 < d.B; b0 += BT) {
-            const uint32_t nb = min(BT, d.B - b0);
-            __syncthreads();
-            for (uint32_t i = threadIdx.x; i < BT * RB; i += TS) {
-                const uint32_t r = i / BT, b = i - r * BT; // consecutive lanes read consecutive batches of one replicate
-                const uint32_t v = b < nb ? counts[(size_t)(rr0 + r) * sum_B + d.row0 + b0 + b] : 0u;
-                reinterpret_cast<uint32_t *>(&cnt[b][0])[r] = v;
-            }
-            __syncthreads();
-            const int64_t *wp = W + (size_t)(d.row0 + b0) * S + sr, *ep = E + (size_t)(d.row0 + b0) * S + sr;
-            for (uint32_t b = 0; b < nb; ++b) {
-                const uint64_t wv = (uint64_t)wp[(size_t)b * S], ev = (uint64_t)ep[(size_t)b * S];
-#pragma unroll
-                for (uint32_t q = 0; q < RB / 4; ++q) {
-                    const uint4 c4 = cnt[b][q];
-                    w[4 * q + 0] += (uint64_t)c4.x * wv, e[4 * q + 0] += (uint64_t)c4.x * ev;
-                    w[4 * q + 1] += (uint64_t)c4.y * wv, e[4 * q + 1] += (uint64_t)c4.y * ev;
-                    w[4 * q + 2] += (uint64_t)c4.z * wv, e[4 * q + 2] += (uint64_t)c4.z * ev;
-                    w[4 * q + 3] += (uint64_t)c4.w * wv, e[4 * q + 3] += (uint64_t)c4.w * ev;
-                }
-            }
-        }
+        cell_totals<RB>(W, E, counts, d, sum_B, S, sr, rr0, cnt, w, e);
 #pragma unroll
         for (uint32_t r = 0; r < RB; ++r) {
             const long long tw = (long long)w[r], te = (long long)e[r];

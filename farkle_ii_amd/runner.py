@@ -1347,6 +1347,61 @@ def _publish_performance_bootstrap(cfg: AppConfig, counts: Sequence[int]) -> Non
         _write_parquet_atomic(table, path)
 
 
+ROOT_STABILITY_FILES = {"root_bootstrap_top_n_inclusion": "root_bootstrap_top_n_inclusion.parquet",
+                        "root_discrepancies": "root_discrepancies.parquet", "root_joint_discrepancy": "root_joint_discrepancy.parquet"}
+
+
+def run_root_stability(cfg: AppConfig, root_results: Sequence, out: Path | None = None, range_size: int | None = None) -> dict:
+    """``farkle root-stability``: the two-root stability stage's bootstrap families over the batch matrices two
+    ``farkle run --performance-bootstrap`` trees left (``<results>/analysis/03_metrics/by_k/<k>p/performance_batch_matrix.npy`` for every
+    player count of ``sim.n_players_list``): ``root_bootstrap_top_n_inclusion.parquet``, ``root_discrepancies.parquet`` and
+    ``root_joint_discrepancy.parquet`` under ``<out>/root_stability/``.  Returns ``{frame name: path}``."""
+    from . import root_stability as rs
+
+    directories = [Path(d) for d in root_results]
+    if len(directories) != 2:
+        raise ValueError(f"two-root stability requires exactly two roots: pass --root-results twice, got {len(directories)}")
+    if directories[0].resolve() == directories[1].resolve():
+        raise ValueError(f"two-root stability requires exactly two roots: both --root-results name {directories[0]}")
+    sc = cfg.screening
+    if sc.practical_delta_by_k is None:
+        raise ValueError("screening.practical_delta_by_k is required")
+    if sc.delta_across_k is None:
+        raise ValueError("screening.delta_across_k is required")
+    if isinstance(sc.bootstrap_replicates, bool) or int(sc.bootstrap_replicates) < 1:
+        raise ValueError("screening.bootstrap_replicates must be a positive integer")
+    if int(sc.candidate_contribution_size) < 1:
+        raise ValueError("screening.candidate_contribution_size must be a positive integer")
+    settings = cfg.root_stability_settings()
+    required = sorted({int(k) for k in cfg.sim.n_players_list})
+    loaded = []
+    for directory in directories:
+        matrices = {}
+        for k in required:
+            path = directory / cfg.io.analysis_subdir / "03_metrics" / "by_k" / f"{k}p" / "performance_batch_matrix.npy"
+            if not path.exists():
+                raise ValueError(f"two-root inputs must cover every root/k cell; missing: {path} (a `farkle run --performance-bootstrap` "
+                                 f"tree of {k} players)")
+            matrices[k] = rs.BatchMatrix.load(path, k)
+        roots = sorted({int(m.root_seed) for m in matrices.values()})
+        if len(roots) != 1:
+            raise ValueError(f"{directory} holds batch matrices of several roots: {roots}")
+        loaded.append((roots[0], matrices))
+    if loaded[0][0] == loaded[1][0]:
+        raise ValueError(f"two-root stability requires exactly two roots: both --root-results hold root {loaded[0][0]}")
+    loaded.sort(key=lambda item: item[0])
+    cells = rs.check_cells({(root, k): m for root, matrices in loaded for k, m in matrices.items()}, [root for root, _ in loaded], required)
+    tables = rs.root_stability_tables(get_engine(), cells, int(sc.bootstrap_replicates), int(sc.candidate_contribution_size),
+                                      sc.practical_delta_by_k, sc.delta_across_k, range_size=range_size, **settings)
+    target = (Path(out) if out is not None else directories[0].parent / f"roots_{cells.roots[0]}_{cells.roots[1]}") / "root_stability"
+    target.mkdir(parents=True, exist_ok=True)
+    written = {}
+    for name, table in tables.items():
+        written[name] = target / ROOT_STABILITY_FILES[name]
+        _write_parquet_atomic(table, written[name])
+    return written
+
+
 def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], plan: TournamentWorkloadPlan, result: dict, grid_size: int,
                      ckpt_path: Path, n_dir: Path, sidecars: "_Sidecars", oracle_game_profile: GameProfile | None) -> None:
     """What follows the last launch of a player count on rank 0: lag tables, summary / metrics parquets, the completion stamp."""

@@ -482,6 +482,36 @@ int fk_performance_bootstrap(fk_ctx *ctx, uint64_t root_seed, int32_t n_k, const
                              double *scores, int64_t *rank_sum, int64_t *rank_square_sum, int64_t *top_counts, int64_t *shortlist_counts,
                              double *contrast_sum, double *contrast_square_sum);
 
+/* The two-root stability stage's bootstrap families (analysis/root_stability.py: _RootTopNRangeWriter.__call__ :816-906 and
+ * _JointDiscrepancyRangeWriter.__call__ :1201-1311, reduced by _root_bootstrap_top_n_inclusion :909-992 and
+ * _joint_discrepancy_bootstrap :1314-1426) for replicates [replicate_begin, replicate_end).
+ * Inputs: roots[2] = (a, b), a < b; n_k player counts ks[] in the caller's (ascending) order with their weights[] (_k_weights
+ * :501-513); 2 * n_k cells in (root, k) order — root a's player counts, then root b's — each with its ELIGIBLE batches
+ * batch_counts[cell] (every batch in which each strategy has an exposure) and two row-major int64 [batch_counts[cell]][S] matrices
+ * wins[cell] / exposures[cell]; S strategy columns in ascending strategy id, the same for every cell; top_n in [0, S].
+ * observed / expected: float64 [n_k][S] (raw_difference / expected_mcse of the by-k discrepancy rows), observed_across /
+ * expected_across: float64 [S]; the four are nullable AS A GROUP (top-N family only).  observed must be finite; a column whose
+ * expected is NaN or <= 0 is no estimand.
+ * Per replicate r and cell: stream (purpose 401, root, k, replicate_index r), B draws in [0, B) (B = 1 draws nothing), exact int64
+ * resampled totals, rate = (double)wins / (double)exposures - 1.0 / k.  Both families use the same streams.
+ * Outputs (caller-owned host memory):
+ *   top_counts   int64 [2][S], required, overwritten: per root the replicates in which the column is among the first top_n of
+ *                lexsort((strategies, -score)), score = 0.0 then score += weights[i] * rate for each player count in order
+ *   maxima       float64 [replicate_end - replicate_begin], required with the group of four: per replicate the maximum of
+ *                |(rate_a - rate_b - observed[k]) / expected[k]| over the valid columns of every k and
+ *                |(sum_k weights[k] * (rate_a - rate_b) - observed_across) / expected_across| over the valid columns (the sum runs
+ *                0 + t_1 + t_2 ... left to right); 0.0 when nothing is valid.  Without the group it is filled with 0.0 when given.
+ *   membership   uint8 [replicate_end - replicate_begin][2][S], nullable: the payload of the top-N range writer's .npy
+ * Every operation is a separate IEEE operation.  Counts are integers and maxima are per replicate, so a range split over several
+ * calls or device blocks gives the bits of one call.  Bad shapes, roots not ascending, a non-finite weight or observed, a resampled
+ * exposure total <= 0 (the reference's ValueError), a negative count or one whose total could pass 2^63 return FK_ERR_ARG.  Option
+ * "bootstrap_block" as for fk_performance_bootstrap. */
+int fk_root_stability_bootstrap(fk_ctx *ctx, const uint64_t *roots, int32_t n_k, const int32_t *ks, const int64_t *batch_counts,
+                                const int64_t *const *wins, const int64_t *const *exposures, int32_t S, const double *weights,
+                                int64_t replicate_begin, int64_t replicate_end, int32_t top_n, const double *observed,
+                                const double *expected, const double *observed_across, const double *expected_across,
+                                int64_t *top_counts, double *maxima, uint8_t *membership);
+
 #ifdef __cplusplus
 }
 #endif
