@@ -617,10 +617,15 @@ __host__ __device__ inline uint32_t discard_key(const DiscardQuery &q) {
            (smart_one ? (uint32_t)SF_SMART_ONE : 0u) | (q.rb ? (uint32_t)SF_REQUIRE_BOTH : 0u) | (q.fav ? (uint32_t)SF_FAVOR_SCORE : 0u);
 }
 
+// The entry's byte: the choice (d5 | d1 << 2) in the low nibble; above it "a five was returned" and "a one was returned" (round 8), the
+// increments of the smart-discard use counters ready-made.  Every reader of the choice masks the low nibble.
+constexpr uint32_t DCH_ANY5_SHIFT = 4, DCH_ANY1_SHIFT = 5;
+
 __host__ __device__ inline uint8_t discard_lut_entry(uint32_t key) {
     const uint32_t so = (key >> 2) & 3u, r7 = (key >> DKEY_R7_SHIFT) & 7u;
-    return (uint8_t)discard_choice(key & 3u, (key & SF_SMART_ONE) ? so : 0u, (key >> DKEY_VMIN_SHIFT) & 7u, (key >> DKEY_CMIN_SHIFT) & 7u,
-                                   r7 < 7u ? r7 : 15u, (key & SF_REQUIRE_BOTH) != 0u, (key & SF_FAVOR_SCORE) != 0u);
+    const uint32_t ch = discard_choice(key & 3u, (key & SF_SMART_ONE) ? so : 0u, (key >> DKEY_VMIN_SHIFT) & 7u, (key >> DKEY_CMIN_SHIFT) & 7u,
+                                       r7 < 7u ? r7 : 15u, (key & SF_REQUIRE_BOTH) != 0u, (key & SF_FAVOR_SCORE) != 0u);
+    return (uint8_t)(ch | ((ch & 3u) ? 1u << DCH_ANY5_SHIFT : 0u) | ((ch & 12u) ? 1u << DCH_ANY1_SHIFT : 0u));
 }
 
 __host__ __device__ inline RollResult apply_discards(const RawScore raw, uint32_t choice) {
@@ -721,9 +726,11 @@ __host__ __device__ inline Roll50 default_score_lut50_decoded(const uint32_t *lu
 // entry (high half), the strategy's share is three of its flag bits, the two thresholds are clamped sums shifted into their fields:
 //     vmin = consider_score ? clamp(pre50 + raw50 - thr50 + 1, 0, 7) : 0        cmin = consider_dice ? clamp(dthr - (n - used) + 1, 0, 5) : 0
 // (tests/native/device_header_host_check.hip runs it against the loop form of the rule on every multiset x flag set x threshold).
-__host__ __device__ inline Roll50 default_score_lut50(const uint32_t *lut, const uint8_t *dlut, uint32_t key, int32_t n, int32_t pre50,
-                                                      const Strat50 &s) {
+// The two gathers of that path: the roll's score entry and the discard table's byte for it (0 where no discard is considered).
+__host__ __device__ inline uint32_t discard_lookup50(const uint32_t *lut, const uint8_t *dlut, uint32_t key, int32_t n, int32_t pre50,
+                                                     const Strat50 &s, uint32_t &e_out) {
     const uint32_t e = lut[key];
+    e_out = e;
     const int32_t raw50 = (int32_t)(e & 63u), used = (int32_t)((e >> 6) & 7u);
     const bool eligible = s.has(SF_SMART_FIVE) & ((e & SE_SINGLES) != 0u) & (used != n); // scoring.py:433
     uint32_t choice = 0u;
@@ -736,8 +743,14 @@ __host__ __device__ inline Roll50 default_score_lut50(const uint32_t *lut, const
         const uint32_t cpart = s.has(SF_CONSIDER_DICE) ? (uint32_t)(c + 1) << DKEY_CMIN_SHIFT : 0u;
         choice = dlut[(e >> 16) | (s.bits & SF_DISCARD_KEY_BITS) | vpart | cpart];
     }
-    const int32_t d5 = (int32_t)(choice & 3u), d1 = (int32_t)((choice >> 2) & 3u);
-    return Roll50{raw50 - d5 - 2 * d1, used - d5 - d1, d5, d1};
+    return choice;
+}
+
+__host__ __device__ inline Roll50 default_score_lut50(const uint32_t *lut, const uint8_t *dlut, uint32_t key, int32_t n, int32_t pre50,
+                                                      const Strat50 &s) {
+    uint32_t e;
+    const uint32_t choice = discard_lookup50(lut, dlut, key, n, pre50, s, e);
+    return apply_discards50(e, choice);
 }
 
 // ----------------------------------------------------------------------------------------
@@ -877,6 +890,159 @@ __host__ __device__ inline bool should_continue(const Strat &s, int32_t turn_sco
     const bool want_d = cd & (dice_left > s.dice_thr());
     const bool thr = (cs & cd & !s.has(SF_REQUIRE_BOTH)) ? (want_s & want_d) : (want_s | want_d);
     return !stop & (force | entry | thr);
+}
+
+// ----------------------------------------------------------------------------------------
+// The roll step's BACK END (round 8): everything between the two table gathers and the record store, as one pure function.
+// In: the roll's score entry `e` (score table), the discard table's byte `choice` (discard_lookup50), the dice rolled `n`, the
+// owner's strategy, the game's final-round state; in and out: the turn registers and the owner's counter words (RollRegs).
+// Returns whether the turn is over; `overflow` is the guard-band test of the u16 counter fields (the caller raises before it stores).
+// Counter words as in fk_kernels.h:  cA = rolls | farkles << 16   cC = sf_uses | sf_dice << 16   cD = so_uses | so_dice << 16
+//   LEAN:  cB = highest_turn / 50 | hot_dice << 16     cE = score / 50 | flags << 16 (the score is kept in `score` too)
+//   else:  cB = highest_turn / 50 (high half untouched) cE = hot_dice | flags << 16
+// The `_decoded` form is the readable statement (engine.py:241-273 step by step, as the kernels spelled it until round 7); the form
+// beside it is what the game kernels run.  tests/native/roll_back_end_host_check.hip compares the two over their input space.
+// ----------------------------------------------------------------------------------------
+constexpr uint32_t BE_HAS_SCORED = 1u << 16; // flags bit 0 of cE (fk_kernels.h: CE_HAS_SCORED)
+
+struct RollRegs {
+    uint32_t cA, cB, cC, cD, cE;
+    int32_t score;      // the owner's banked total / 50
+    uint32_t dice;      // out: dice of the next roll
+    int32_t turn_score; // / 50
+};
+
+template <bool LEAN>
+__host__ __device__ inline bool roll_back_end50_decoded(uint32_t e, uint32_t choice, uint32_t n, const Strat50 &sp, bool final_round,
+                                                        int32_t stb50, RollRegs &r, bool &overflow) {
+    const Roll50 rr = apply_discards50(e, choice);
+    const bool farkle = rr.score50 == 0;                               // engine.py:135-137, 247-249
+    r.cA += 1u + (farkle ? 0x10000u : 0u);                             // n_rolls (engine.py:98), n_farkles
+    r.cC += (rr.d5 > 0) ? (1u + ((uint32_t)rr.d5 << 16)) : 0u;         // engine.py:139-144
+    r.cD += (rr.d1 > 0) ? (1u + ((uint32_t)rr.d1 << 16)) : 0u;
+    r.dice = (rr.used == (int32_t)n) ? 6u : (n - (uint32_t)rr.used);   // engine.py:146
+    r.turn_score = farkle ? 0 : (r.turn_score + rr.score50);
+    const bool hot = !farkle & sp.has(SF_AUTO_HOT) & (r.dice == 6u);   // _apply_hot_dice, engine.py:149-154, 253
+    if (LEAN) r.cB += hot ? 0x10000u : 0u;
+    else r.cE += hot ? 1u : 0u;
+    const bool keep = should_continue50(sp, r.turn_score, (int32_t)r.dice, (r.cE & BE_HAS_SCORED) != 0u, final_round, stb50, r.score);
+    const bool over = farkle | (!hot & !keep);
+    // bank (engine.py:265-273), branch-free: a farkled turn has turn_score 0 and changes nothing
+    const uint32_t ts = over ? (uint32_t)r.turn_score : 0u;
+    r.cE |= (ts >= 10u) ? BE_HAS_SCORED : 0u;                          // 500 points
+    const uint32_t banked = (r.cE & BE_HAS_SCORED) ? ts : 0u;
+    r.score += (int32_t)banked;
+    if (LEAN) r.cE += banked;
+    r.cB = (banked > (r.cB & 0xffffu)) ? ((r.cB & 0xffff0000u) | banked) : r.cB;
+    // the u16 guard bands (a turn adds <= 1000 rolls and <= 2000 discarded dice; highest_turn must fit 16 bits IN POINTS: 1310 x 50 = 65 500)
+    overflow = (r.turn_score > 1310) | ((r.cA & 0xffffu) > 64000u) | ((r.cC >> 16) > 63000u) | ((r.cD >> 16) > 63000u);
+    return over;
+}
+
+// A predicate as a wave's lane mask (device) or a 0 / ~0 word (host), so that boolean algebra written on it stays on the scalar unit:
+// the compiler otherwise turns a longer i1 expression into 0 / 1 integers in VGPRs (a v_cndmask per term) or into an exec-mask diamond.
+// A lane reads back only its own bit; the bits of inactive lanes are meaningless.
+typedef uint64_t lanes_t;
+__host__ __device__ inline lanes_t lanes(bool p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(p);
+#else
+    return p ? ~0ull : 0ull;
+#endif
+}
+__host__ __device__ inline bool in_lanes(lanes_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+#else
+    return m != 0ull;
+#endif
+}
+
+// A strategy flag as lanes.  MIXED: the flag bits that may differ between the lanes of a wave (the game kernels' template argument);
+// the others are the same for the whole launch and are read from `uniform_bits`, which the caller takes from a kernel argument (never
+// from a vector register): their mask is all or nothing, a scalar select.
+template <uint32_t MIXED>
+__host__ __device__ inline lanes_t flag_lanes(const Strat50 &s, uint32_t uniform_bits, uint32_t f) {
+    return (f & MIXED) ? lanes((s.bits & f) != 0u) : ((uniform_bits & f) != 0u ? ~0ull : 0ull);
+}
+
+// max of both 16-bit halves (v_pk_max_u16 on the device)
+__host__ __device__ inline uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+#else
+    const uint32_t al = a & 0xffffu, bl = b & 0xffffu, ah = a >> 16, bh = b >> 16;
+    return (al > bl ? al : bl) | ((ah > bh ? ah : bh) << 16);
+#endif
+}
+
+// What differs from the decoded form, with the same results:
+//   - the use counters take their increments from the discard byte's high bits (no compare, no select);
+//   - should_continue50's threshold rule as mask algebra, (ws | wd) & (!both | ws & wd): no select between two mask expressions;
+//   - the bank: with entry = !has_scored & turn < 10 (the decision's own term), the turn banks iff over & !entry, and has_scored
+//     afterwards is has_scored | bank: no second test of the 500-point rule, no test of the flag just written;
+//   - highest_turn as a packed 16-bit maximum with the banked turn (its high half is 0: the other half of cB stays).
+template <bool LEAN, uint32_t MIXED = 0xffffu>
+__host__ __device__ inline bool roll_back_end50(uint32_t e, uint32_t choice, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, bool final_round,
+                                                int32_t stb50, RollRegs &r, bool &overflow) {
+    const uint32_t d5 = choice & 3u, d1 = (choice >> 2) & 3u;
+    const int32_t score50 = (int32_t)(e & 63u) - (int32_t)d5 - 2 * (int32_t)d1;
+    const uint32_t used = ((e >> 6) & 7u) - d5 - d1;
+    const bool farkle = score50 == 0;
+    r.cA += 1u + (farkle ? 0x10000u : 0u);
+    r.cC += (d5 << 16) + ((choice >> DCH_ANY5_SHIFT) & 1u);
+    r.cD += (d1 << 16) + ((choice >> DCH_ANY1_SHIFT) & 1u);
+    r.dice = (used == n) ? 6u : (n - used);
+    r.turn_score = farkle ? 0 : (r.turn_score + score50);
+    const lanes_t farkle_l = lanes(score50 == 0);
+    const lanes_t hot_l = ~farkle_l & flag_lanes<MIXED>(sp, uniform_bits, SF_AUTO_HOT) & lanes(r.dice == 6u);
+    const bool hot = in_lanes(hot_l);
+    if (LEAN) r.cB += hot ? 0x10000u : 0u;
+    else r.cE += hot ? 1u : 0u;
+    const lanes_t fr = lanes(final_round), above = lanes(r.score + r.turn_score > stb50);
+    const lanes_t stop = fr & above & ~flag_lanes<MIXED>(sp, uniform_bits, SF_RUN_UP);
+    const lanes_t force = fr & ~above;
+    const lanes_t entry = lanes((r.cE & BE_HAS_SCORED) == 0u) & lanes(r.turn_score < 10); // 500 points (strategies.py:249)
+    const lanes_t cs = flag_lanes<MIXED>(sp, uniform_bits, SF_CONSIDER_SCORE), cd = flag_lanes<MIXED>(sp, uniform_bits, SF_CONSIDER_DICE);
+    const lanes_t ws = cs & lanes(r.turn_score < sp.thr50), wd = cd & lanes((int32_t)r.dice > sp.dice_thr());
+    const lanes_t both = cs & cd & ~flag_lanes<MIXED>(sp, uniform_bits, SF_REQUIRE_BOTH);
+    const lanes_t keep = ~stop & (force | entry | ((ws | wd) & (~both | (ws & wd))));
+    const lanes_t over_l = farkle_l | (~hot_l & ~keep);
+    const bool over = in_lanes(over_l), bank = in_lanes(over_l & ~entry);
+    const uint32_t banked = bank ? (uint32_t)r.turn_score : 0u;
+    r.cE |= bank ? BE_HAS_SCORED : 0u;
+    r.score += (int32_t)banked;
+    if (LEAN) r.cE += banked;
+    r.cB = pk_max_u16(r.cB, banked);
+    overflow = (r.turn_score > 1310) | ((r.cA & 0xffffu) > 64000u) | ((r.cC >> 16) > 63000u) | ((r.cD >> 16) > 63000u);
+    return over;
+}
+
+// ---- two-seat table advance (engine.py:453-472, 523-550) after a roll: the game-level half of the back end, for every lane of the trip ----
+// With two seats the rules collapse: the next seat is always the other one; a turn played in the final round is the last of the game;
+// the first banked total at or above the target starts the final round.  `score` is the owner's banked total / 50.
+struct Table2 {
+    uint32_t seat, rounds, trigger, final_round, safety;
+    int32_t score_to_beat; // / 50
+};
+struct Advance2 {
+    bool ended, sw; // the game has ended / the turn passes to the other seat
+};
+__host__ __device__ inline Advance2 advance2_table50(bool over, int32_t score, int32_t target50, uint32_t max_rounds, Table2 &t) {
+    const bool fr = t.final_round != 0u;
+    const bool trig = over & !fr & (score >= target50);        // engine.py:462-468
+    const bool close = over & !fr & !trig & (t.seat != 0u);    // seat 1 closes a normal round
+    const bool last = close & (t.rounds >= max_rounds);        // `while rounds < max_rounds` ends (engine.py:453, 472)
+    const bool ended = last | (over & fr);                     // the final round's one turn has been played
+    t.rounds += (close & !last) ? 1u : 0u;
+    t.safety = last ? 1u : t.safety;
+    t.score_to_beat = trig ? score : t.score_to_beat;          // engine.py:464
+    t.trigger = trig ? t.seat : t.trigger;
+    t.final_round = (fr | trig) ? 1u : 0u;
+    const bool sw = over & !ended;
+    t.seat ^= sw ? 1u : 0u;
+    return Advance2{ended, sw};
 }
 
 } // namespace fk

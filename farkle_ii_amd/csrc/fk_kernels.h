@@ -52,7 +52,8 @@ enum : uint32_t {
 //   cA = rolls | farkles << 16        cB = highest_turn / 50 | n_turns << 16 (the n_turns half: state store only)
 //   cC = sf_uses | sf_dice << 16      cD = so_uses | so_dice << 16
 //   cE = hot_dice | flags << 16       flags: bit0 has_scored, bit1 has_buf
-constexpr uint32_t CE_HAS_SCORED = 1u << 16, CE_HAS_BUF = 1u << 17;
+constexpr uint32_t CE_HAS_BUF_SHIFT = 17, CE_HAS_SCORED = 1u << 16, CE_HAS_BUF = 1u << CE_HAS_BUF_SHIFT;
+static_assert(CE_HAS_SCORED == BE_HAS_SCORED, "fk_device.h's roll back end sets the flag in cE");
 constexpr uint32_t CE_IDX_SHIFT = 18; // LEAN records in LDS: strategy index in cE[31:18] (S <= 16384)
 // LEAN LDS record, ten dwords: LO0 LO1 | HI0 HI1 | BUF cA | cB cC | cD cE with
 //   cB = highest_turn / 50 | hot_dice << 16        cE = score / 50 | has_scored << 16 | has_buf << 17 | strategy << 18
@@ -833,7 +834,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // two-player lean instances (KC = 2; not state-store): the packed strategies of both seats stay in registers for the game,
     // so a turn start is one increment load instead of LDS read -> index -> strategy load
     constexpr bool PK2 = (KC == 2) && LEAN && !GS;
-    uint2 pk_seat0 = make_uint2(0u, 0u), pk_seat1 = make_uint2(0u, 0u);
+    // Layout of these words, and of `own_bits` while such an instance plays (init_game re-packs the table's entry): .x = thr50;
+    // .y = flags [15:8] as in the table | dice threshold SIGN-EXTENDED in [31:16], low byte 0 — so the threshold is one full-rate
+    // arithmetic shift per roll.  Strat50's two-argument constructor (threshold in the low byte) must not be given such a word:
+    // roll_step passes the decoded threshold explicitly.  Every other instance keeps the table's form (threshold in [7:0]).
+    uint2 pk_seat0 = make_uint2(0u, 0u), pk_delta = make_uint2(0u, 0u); // seat 0's strategy (the first owner's); seat 0's xor seat 1's
 
     // LDS records are contiguous per (seat, lane): record base = (seat * BLOCK + tid) * NFIELDS, field = immediate
     // offset (one address VGPR per record).  Full records: odd stride (17 dwords), ds_read2/ds_write2 dword pairs, the
@@ -882,7 +887,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     };
     // n_turns of seat s of a game that has ended (engine.py:236 counts them turn by turn): every seat began `rounds` turns,
     // minus the seats behind the trigger in its round, plus the final-round turn of every seat but the trigger's.
-    auto seat_turns = [&](uint32_t s) -> uint32_t { return rounds + ((final_round != 0u && s < trigger) ? 1u : 0u); };
+    // (two-seat lean instances carry neither `trigger` nor `safety` through the roll loop, see advance2: the final round's one turn is
+    // played by the seat that did not trigger it, and that seat still owns the turn when the game has ended)
+    auto seat_turns = [&](uint32_t s) -> uint32_t { return rounds + ((final_round != 0u && s < (PK2 ? (seat ^ 1u) : trigger)) ? 1u : 0u); };
 
     // turn owner := seat s (engine.py:236-240): fresh turn registers, read-only data.  n_turns is not stored per turn in
     // the LDS instances (seat_turns above restores it when the game ends).
@@ -905,7 +912,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         }
         if (LEAN) { // read-only per-seat data comes from HBM/L2; the loads overlap the first dice of the turn
             const uint4 inc = a.inc[(size_t)seed_slot * K + s];
-            const uint2 pk = PK2 ? (s ? pk_seat1 : pk_seat0) : a.strat[idx];
+            // (PK2 begins a turn here only for seat 0, at the start of a game — advance2 switches owners — but any seat is served)
+            const uint2 pk = !PK2 ? a.strat[idx] : s == 0u ? pk_seat0 : make_uint2(pk_seat0.x ^ pk_delta.x, pk_seat0.y ^ pk_delta.y);
             own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
             own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
             own_thr = (int32_t)pk.x;
@@ -928,7 +936,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 
     // ---- finished game -> LDS tallies or one result record (run_tournament.py:375-391) ----
     auto finish_game = [&]() {
-        const bool completed = (safety == 0u);
+        const bool completed = PK2 ? (final_round != 0u) : (safety == 0u); // two seats: a game ends in its final round or at the round limit
         uint32_t w = 0;
         int32_t best = seat_score(0);
         for (uint32_t s = 1; s < K; ++s) { // stable sort on score desc: first maximum wins (engine.py:477)
@@ -1038,9 +1046,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 L(F_CD, s) = 0u;
                 L(F_CE, s) = (LEAN && !BLK) ? (idx << CE_IDX_SHIFT) : 0u;
                 if (PK2) {
-                    const uint2 pk = a.strat[BLK ? 2u * a.game_block[id] + s : idx];
+                    uint2 pk = a.strat[BLK ? 2u * a.game_block[id] + s : idx];
+                    pk.y = (pk.y & 0xff00u) | ((uint32_t)(int32_t)(int8_t)(pk.y & 0xffu) << 16);
                     if (s == 0u) pk_seat0 = pk;
-                    else pk_seat1 = pk;
+                    else pk_delta = make_uint2(pk_seat0.x ^ pk.x, pk_seat0.y ^ pk.y);
                 }
             }
         }
@@ -1093,32 +1102,28 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // Some lane of a 64-lane wave ends its turn in nearly every trip, so `advance` above — an exec-masked region of ~47
     // instructions for the third of the lanes whose turn ended — is paid by the whole wave every trip.  With two seats the
     // rules collapse (engine.py:453-472, 523-550): the next seat is always the other one; a turn played in the final round
-    // is the last of the game; the first score at or above the target starts the final round.  That is ~20 predicated
-    // instructions with no region; only the next owner's increment load stays under the exec mask.
+    // is the last of the game; the first score at or above the target starts the final round.  The rules are fk_device.h's
+    // advance2_table50 (plain booleans, which the compiler keeps as lane masks here, and one select per register that changes); only
+    // the change of owner stays under the exec mask: the increment load, and seat, strategy and turn registers switched by xor /
+    // constants (round 8).  Neither the trigger seat nor the safety flag is carried: both follow from the state a two-seat game ends
+    // in (seat_turns, finish_game; tests/native/roll_back_end_host_check.hip asserts the two relations on advance2_table50), so the
+    // registers `trigger` and `safety` are not touched by these instances after init_game.
     auto advance2 = [&](bool over, int32_t score) __attribute__((always_inline)) {
-        const bool fr = final_round != 0u;
-        const bool trig = over & !fr & (score >= a.target50);                 // engine.py:462-468
-        const bool close = over & !fr & !trig & (seat != 0u);                 // seat 1 closes a normal round
-        const bool last = close & (rounds >= max_rounds);                     // `while rounds < max_rounds` ends (engine.py:453, 472)
-        const bool ended = last | (over & fr);                                // the final round's one turn has been played
-        rounds += (close & !last) ? 1u : 0u;
-        safety = last ? 1u : safety;
-        score_to_beat = trig ? score : score_to_beat;                         // engine.py:464
-        trigger = trig ? seat : trigger;
-        final_round = (fr | trig) ? 1u : 0u;
-        const bool sw = over & !ended;
-        st = ended ? (uint32_t)ST_ENDED : st;
-        seat ^= sw ? 1u : 0u;
-        if (sw) { // the new owner's increment: the one memory request of a turn start
-            const uint4 inc = a.inc[(size_t)seed_slot * 2u + seat];
+        Table2 t{seat, rounds, 0u, final_round, 0u, score_to_beat}; // trigger, safety: not carried (above)
+        const Advance2 adv = advance2_table50(over, score, a.target50, max_rounds, t); // fk_device.h
+        rounds = t.rounds, final_round = t.final_round, score_to_beat = t.score_to_beat;
+        st = adv.ended ? (uint32_t)ST_ENDED : st;
+        if (adv.sw) { // the turn passes (t.seat): the other seat, the other strategy = an xor with the game's difference word, fresh turn
+            seat ^= 1u;
+            own_thr ^= (int32_t)pk_delta.x;
+            own_bits ^= pk_delta.y;
+            const uint4 inc = a.inc[(size_t)seed_slot * 2u + seat]; // the new owner's increment: the one memory request of a turn start
             own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
             own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
+            dice = 6u;
+            turn_score = 0;
+            rolls_this_turn = 0u;
         }
-        own_thr = (int32_t)(seat ? pk_seat1.x : pk_seat0.x);
-        own_bits = seat ? pk_seat1.y : pk_seat0.y;
-        dice = sw ? 6u : dice;
-        turn_score = sw ? 0 : turn_score;
-        rolls_this_turn = sw ? 0u : rolls_this_turn;
     };
 
     // ---- one roll of the current turn (engine.py:241-273): record in, roll, score, decide, record out ----
@@ -1155,37 +1160,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             key = roll_counts_sequential<3>(rng, n, nullptr);
         }
         rolls_this_turn += 1u;
-        int32_t dthr = (int32_t)(int8_t)(own_bits & 0xffu);
+        int32_t dthr = PK2 ? ((int32_t)own_bits >> 16) : (int32_t)(int8_t)(own_bits & 0xffu);
         asm volatile("" : "+v"(dthr));
         const Strat50 sp{own_thr, (own_bits & (0xffu | MIXED)) | (a.uflags & (0xff00u & ~MIXED)), dthr};
-        const Roll50 rr = default_score_lut50(a.score_lut, a.discard_lut, key, (int32_t)n, turn_score, sp); // turn_score, score: / 50
-        const bool farkle = rr.score50 == 0;                            // engine.py:135-137, 247-249
-        cA += 1u + (farkle ? 0x10000u : 0u);                            // n_rolls (engine.py:98), n_farkles
-        cC += (rr.d5 > 0) ? (1u + ((uint32_t)rr.d5 << 16)) : 0u;        // engine.py:139-144
-        cD += (rr.d1 > 0) ? (1u + ((uint32_t)rr.d1 << 16)) : 0u;
-        dice = (rr.used == (int32_t)n) ? 6u : (n - (uint32_t)rr.used);  // engine.py:146
-        turn_score = farkle ? 0 : (turn_score + rr.score50);
-        const bool hot = !farkle & sp.has(SF_AUTO_HOT) & (dice == 6u);  // _apply_hot_dice, engine.py:149-154, 253
-        if (LEAN) cB += hot ? 0x10000u : 0u; // hot-dice count: cB[31:16] (lean) or cE[15:0]
-        else cE += hot ? 1u : 0u;
-        const bool keep = should_continue50(sp, turn_score, (int32_t)dice, (cE & CE_HAS_SCORED) != 0u, final_round != 0u,
-                                            score_to_beat, score);
-        const bool over = farkle | (!hot & !keep);
-        // bank (engine.py:265-273), branch-free: a farkled turn has turn_score 0 and changes nothing
-        const uint32_t ts = over ? (uint32_t)turn_score : 0u;
-        cE |= (ts >= 10u) ? CE_HAS_SCORED : 0u;                         // 500 points
-        const uint32_t banked = (cE & CE_HAS_SCORED) ? ts : 0u;
-        score += (int32_t)banked;
-        if (LEAN) cE += banked;
-        cB = (banked > (cB & 0xffffu)) ? ((cB & 0xffff0000u) | banked) : cB;
-        // one rare exit for all error conditions: the roll limit, then the u16 guard bands (a turn adds <= 1000 rolls
-        // and <= 2000 discarded dice; highest_turn must fit 16 bits IN POINTS: 1310 x 50 = 65 500)
-        const bool overflow = (turn_score > 1310) | ((cA & 0xffffu) > 64000u) | ((cC >> 16) > 63000u) | ((cD >> 16) > 63000u);
+        // score, discards, counters, hot dice, decision, bank, guard bands (turn_score, score: / 50): fk_device.h's pure back end
+        uint32_t entry;
+        const uint32_t choice = discard_lookup50(a.score_lut, a.discard_lut, key, (int32_t)n, turn_score, sp, entry);
+        RollRegs rg{cA, cB, cC, cD, cE, score, dice, turn_score};
+        bool overflow;
+        const bool over = roll_back_end50<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
+        cA = rg.cA, cB = rg.cB, cC = rg.cC, cD = rg.cD, cE = rg.cE, score = rg.score, dice = rg.dice, turn_score = rg.turn_score;
+        // one rare exit for all error conditions: the roll limit, then the u16 guard bands
         if (roll_limit | overflow) {
             raise(roll_limit ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
             return;
         }
-        cE = (cE & ~CE_HAS_BUF) | (rng.has_buf ? CE_HAS_BUF : 0u);
+        cE = (cE & ~CE_HAS_BUF) | (rng.has_buf << CE_HAS_BUF_SHIFT); // has_buf is 0 / 1 (fk_device.h): a shift, no compare and select
         if (GS) {
             if (over) { // the turn is over: the record goes back to the state store, the next seat's comes in
                 uint4 *g = reinterpret_cast<uint4 *>(G(s));

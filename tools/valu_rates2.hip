@@ -59,6 +59,9 @@
 #define ASHR(i) "v_ashrrev_i32_e32 %" #i ", 3, %" #i "\n"
 #define NOT(i) "v_not_b32_e32 %" #i ", %" #i "\n"
 #define MAXU(i) "v_max_u32_e32 %" #i ", %" #i ", %13\n"
+#define PKMAX(i) "v_pk_max_u16 %" #i ", %" #i ", %13\n"
+#define BFE_U(i) "v_bfe_u32 %" #i ", %" #i ", 4, 1\n"
+#define LSHL_ADD(i) "v_lshl_add_u32 %" #i ", %13, 16, %" #i "\n"
 #define CND_E64_VCC(i) "v_cndmask_b32_e64 %" #i ", %" #i ", %13, vcc\n"
 
 DEFINE_KERNEL(k_add, R8(ADD))
@@ -105,6 +108,10 @@ DEFINE_KERNEL(k_lshl1, R8(LSHL1))
 DEFINE_KERNEL(k_ashr, R8(ASHR))
 DEFINE_KERNEL(k_not, R8(NOT))
 DEFINE_KERNEL(k_max, R8(MAXU))
+// round 8: the forms the roll step's back end gained (packed 16-bit maximum for highest_turn, the discard byte's bit fields, shifted adds)
+DEFINE_KERNEL(k_pk_max, R8(PKMAX))
+DEFINE_KERNEL(k_bfe_u, R8(BFE_U))
+DEFINE_KERNEL(k_lshl_add, R8(LSHL_ADD))
 // 64-bit forms: 8 instructions per group on the four pairs (two rounds)
 DEFINE_KERNEL(k_mad64_vcc, "v_mad_u64_u32 %8, vcc, %13, %14, %8\nv_mad_u64_u32 %9, vcc, %14, %13, %9\nv_mad_u64_u32 %10, vcc, %13, %14, %10\nv_mad_u64_u32 %11, vcc, %14, %13, %11\n"
                            "v_mad_u64_u32 %8, vcc, %13, %14, %8\nv_mad_u64_u32 %9, vcc, %14, %13, %9\nv_mad_u64_u32 %10, vcc, %13, %14, %10\nv_mad_u64_u32 %11, vcc, %14, %13, %11\n")
@@ -164,6 +171,14 @@ int main(int argc, char **argv) {
     int nb = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&k_add), 256, 0);
     printf("# %d CUs, %d waves per SIMD asked, occupancy API: %d blocks of 256 per CU, %d iterations x 4 groups\n", g_cus, g_waves, nb, g_iters);
+    if (getenv("FK_BACK_END_ONLY")) { // round 8: only the forms the roll step's back end gained, with one control per class
+        run("v_add_u32 (control)", k_add);
+        run("v_max_u32 (control)", k_max);
+        run("v_pk_max_u16", k_pk_max);
+        run("v_bfe_u32", k_bfe_u);
+        run("v_lshl_add_u32", k_lshl_add);
+        return 0;
+    }
     run("v_add_u32 (control)", k_add);
     run("v_cndmask e32 vcc x8", k_cnd_vcc);
     run("v_cndmask e64 vcc x8", k_cnd_e64_vcc);
