@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -107,7 +107,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
 
 
 _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_get_timing", "fk_set_option",
-            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
+            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap"]
@@ -381,6 +381,78 @@ class Engine:
         return {"tally": tally[:n_batches], "seat_stats": None if stats is None else stats[:n_batches],
                 "seat_ratio_sums": None if ratios is None else ratios[:n_batches], "spilled": int(spilled.value),
                 "game_stats": merge_spills(g, spill[:spilled.value], R + 1)}
+
+    def tournament_rare_events(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
+                               shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                               overrides: np.ndarray | None = None, rare_target_score: int = 10_000, thresholds=(),
+                               want_events: bool = True, want_seat_stats: bool = False, spill_capacity: int = 4096,
+                               event_capacity: int = 65_536, retry: bool = True) -> dict:
+        """``tournament_game_stats`` (the same keys, the same values) + ``rare_events`` (``fk_tournament_run_rare_events``): int64
+        ``strategy_second [S][B]`` / ``game_second [B]`` (second-highest seat score / 50 of every game with k >= 2, spills merged)
+        and the games that are rare events under ``rare_target_score`` / ``thresholds`` (at most eight, points), in ascending
+        (shuffle, game) order: ``event_head`` uint32 ``[n][4]``, ``event_seats`` uint16 ``[n][k]`` (``rare_events.event_fields``).
+        ``want_events=False`` is the histograms-only call (``thresholds`` must be empty).  A list that is too small is an
+        ``FK_ERR_ARG`` carrying the size it needs: the range is played again with that room unless ``retry`` is off."""
+        from .game_stats import DEVICE_MARGIN_BINS, DEVICE_ROUNDS_BINS, merge_spills
+        from .rare_events import DEVICE_SECOND_BINS, MAX_THRESHOLDS, SPILL_SECOND, merge_second_spills
+
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        S = len(table)
+        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
+        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
+        n_batches = (n_sh + spb - 1) // spb
+        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.int32)
+        if len(thr) > MAX_THRESHOLDS:
+            raise ValueError(f"at most {MAX_THRESHOLDS} margin thresholds per call, got {len(thr)}")
+        if not want_events and len(thr):
+            raise ValueError("the histograms-only call takes no thresholds")
+        R = max([int(max_rounds)] + [int(v) for v in ov["max_rounds"]])
+        rb, mb, sb = min(R + 1, DEVICE_ROUNDS_BINS), DEVICE_MARGIN_BINS, DEVICE_SECOND_BINS
+        capacity = max(int(spill_capacity), 0)
+        ev_cap = max(int(event_capacity), 0) if want_events else 0
+        attempts = 0
+        while True:
+            attempts += 1
+            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            stats = np.zeros((max(n_batches, 1), S, SEAT_STAT_COLS), dtype=np.int64) if want_seat_stats else None
+            ratios = np.zeros((max(n_batches, 1), S, SEAT_RATIO_COLS), dtype=np.float64) if want_seat_stats else None
+            g = {"strategy_counts": np.zeros((S, 4), np.int64), "strategy_rounds": np.zeros((S, rb), np.int64),
+                 "strategy_runner": np.zeros((S, mb), np.int64), "strategy_spread": np.zeros((S, mb), np.int64),
+                 "game_counts": np.zeros(4, np.int64), "game_rounds": np.zeros(rb, np.int64), "game_runner": np.zeros(mb, np.int64)}
+            s_second, g_second = np.zeros((S, sb), np.int64), np.zeros(sb, np.int64)
+            spill = np.zeros((max(capacity, 1), 3), dtype=np.int32)
+            spilled, n_events = C.c_int64(0), C.c_int64(0)
+            head = np.zeros((max(ev_cap, 1), 4), dtype=np.uint32) if want_events else None
+            seats = np.zeros((max(ev_cap, 1), max(int(k), 1)), dtype=np.uint16) if want_events else None
+            rc = self._lib.fk_tournament_run_rare_events(
+                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
+                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
+                _p(tally), None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
+                _p(g["strategy_counts"]), _p(g["strategy_rounds"]), _p(g["strategy_runner"]), _p(g["strategy_spread"]),
+                _p(g["game_counts"]), _p(g["game_rounds"]), _p(g["game_runner"]), C.c_int64(capacity), C.byref(spilled), _p(spill),
+                C.c_int32(sb), _p(s_second), _p(g_second), C.c_int32(len(thr)), _p(thr) if len(thr) else None,
+                C.c_int64(ev_cap), C.byref(n_events), _p(head), _p(seats))
+            short = spilled.value > capacity or n_events.value > ev_cap
+            if rc == FK_ERR_ARG and short and retry:  # once more with room for all
+                capacity, ev_cap = max(capacity, int(spilled.value)), max(ev_cap, int(n_events.value))
+                continue
+            try:
+                self._check(rc)
+            except FarkleHipError as err:  # (what the lists need travels with the error)
+                err.events_needed, err.spill_needed = int(n_events.value), int(spilled.value)
+                raise
+            break
+        entries = spill[:spilled.value]
+        second = entries[:, 1] == SPILL_SECOND
+        s_second, g_second = merge_second_spills(s_second, g_second, entries[second])
+        n = int(n_events.value)
+        return {"tally": tally[:n_batches], "seat_stats": None if stats is None else stats[:n_batches],
+                "seat_ratio_sums": None if ratios is None else ratios[:n_batches], "spilled": int(spilled.value),
+                "game_stats": merge_spills(g, entries[~second], R + 1), "attempts": attempts,
+                "rare_events": {"strategy_second": s_second, "game_second": g_second, "events": n,
+                                "event_head": head[:n].copy() if want_events else np.zeros((0, 4), np.uint32),
+                                "event_seats": seats[:n].copy() if want_events else np.zeros((0, max(int(k), 1)), np.uint16)}}
 
     def tournament_columns(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, strategy_ids,
                            shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,

@@ -51,6 +51,12 @@ def build_parser() -> argparse.ArgumentParser:
                           "rates) and <k>p_game_stats_sums.parquet (the exact histograms), after the last player count "
                           "game_stats_rare_event_summary.parquet at the results root (analysis.game_stats_margin_thresholds, "
                           "analysis.rare_event_target_score).  Not resumable: an interrupted run asks for --force")
+    run.add_argument("--rare-events", action="store_true",
+                     help="With --game-stats: also write rare_events.parquet at the results root (the game rows of every flagged game of "
+                          "every player count in the reference's schema and order, then the summary rows) and, with "
+                          "analysis.rare_event_write_details, rare_events_details.parquet, from the device's flagged-game list, without "
+                          "rows.  Serves analysis.rare_event_margin_quantile / rare_event_target_rate: a histograms-only pass over "
+                          "every player count resolves the thresholds, then the same shuffle ranges are replayed to collect the games")
     run.add_argument("--performance-bootstrap", action="store_true",
                      help="Write the performance stage's joint deterministic-batch bootstrap from the device: per player count "
                           "analysis/03_metrics/by_k/<k>p/performance_batch_matrix.npy (wins / exposures per batch and strategy), after the "
@@ -143,6 +149,10 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.rng_lag_sums = True
     if args.game_stats:
         cfg.sim.game_stats = True
+    if args.rare_events:
+        if not args.game_stats:
+            raise ValueError("--rare-events rides on the game-stats launches: pass --game-stats with it")
+        cfg.sim.rare_events = True
     if args.performance_bootstrap:
         cfg.sim.performance_bootstrap = True
     if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
@@ -173,7 +183,7 @@ def main(argv: Sequence[str] | None = None) -> None:
     LOGGER.info("Dispatching run command: seed=%s n_players_list=%s results_dir=%s", cfg.sim.seed, cfg.sim.n_players_list,
                 cfg.results_root)
     try:
-        if len(cfg.sim.n_players_list) > 1 or cfg.sim.performance_bootstrap:  # (the bootstrap follows the sweep's last player count)
+        if len(cfg.sim.n_players_list) > 1 or cfg.sim.performance_bootstrap or cfg.sim.rare_events:  # (the bootstrap / the rare-event files follow the sweep's last player count)
             out = runner.run_multi(cfg, force=args.force)
         else:
             out = {cfg.sim.n_players_list[0]: runner.run_single_n(cfg, cfg.sim.n_players_list[0], force=args.force)}

@@ -65,6 +65,7 @@ class SimConfig:
     rng_lag_sums: bool = False  # this engine's option: lag sufficient statistics of the RNG diagnostics' strategy family (rng_lags.py)
     rng_matchup_lags: bool = False  # this engine's option: the RNG diagnostics' matchup family + group selection (rng_matchups.py)
     game_stats: bool = False  # this engine's option: the game-stats stage's per-k tables and rare-event summary without rows (game_stats.py)
+    rare_events: bool = False  # with game_stats: the per-game rows of rare_events.parquet / rare_events_details.parquet and the quantile thresholds (rare_events.py)
     performance_bootstrap: bool = False  # this engine's option: the performance stage's batch matrices + joint batch bootstrap (performance_bootstrap.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
@@ -190,6 +191,36 @@ class AppConfig:
         if isinstance(value, bool) or not isinstance(value, int) or not -(2 ** 31) <= value < 2 ** 31:
             raise ValueError("analysis.rare_event_target_score must be a 32-bit integer")
         return int(value)
+
+    def rare_event_settings(self) -> dict:
+        """What ``--rare-events`` reads beside ``game_stats_margin_thresholds``: ``analysis.rare_event_target_score`` (config.py:325),
+        ``rare_event_write_details`` (default off), ``rare_event_margin_quantile`` / ``rare_event_target_rate`` (default ``None``;
+        each in (0, 1), the reference's messages).  The quantile keys are served here: :meth:`rare_event_target_score` keeps
+        refusing them for ``--game-stats`` alone."""
+        analysis = self.opaque.get("analysis") or {}
+        target = analysis.get("rare_event_target_score", 10_000)
+        if isinstance(target, bool) or not isinstance(target, int) or not -(2 ** 31) <= target < 2 ** 31:
+            raise ValueError("analysis.rare_event_target_score must be a 32-bit integer")
+        out = {"target_score": int(target), "thresholds": self.game_stats_margin_thresholds(),
+               "write_details": bool(analysis.get("rare_event_write_details", False)), "margin_quantile": None, "target_rate": None}
+        for key, name in (("rare_event_margin_quantile", "margin_quantile"), ("rare_event_target_rate", "target_rate")):
+            value = analysis.get(key)
+            if value is None:
+                continue
+            if isinstance(value, bool) or not isinstance(value, (int, float)):
+                raise ValueError(f"analysis.{key} must be a number")
+            if not 0.0 < float(value) < 1.0:
+                raise ValueError(f"{key} must be between 0 and 1")
+            out[name] = float(value)
+        if len(out["thresholds"]) > 8:
+            raise ValueError("--rare-events carries at most 8 margin thresholds per game (analysis.game_stats_margin_thresholds)")
+        return out
+
+    def rare_events_path(self) -> Path:
+        return self.results_root / "rare_events.parquet"
+
+    def rare_events_details_path(self) -> Path:
+        return self.results_root / "rare_events_details.parquet"
 
     def metrics_stage_dir(self) -> Path:
         """The reference's metrics stage directory in its default stage layout (config.py:798-802: ``analysis/03_metrics``)."""

@@ -10,6 +10,7 @@
 #include "fk_row_columns_seats.h" // device side: column images with one thread per (game, seat)
 #include "fk_matchups.h"      // device side: RNG-diagnostics matchup family (key post-pass, grouped lag reduce)
 #include "fk_game_stats.h"    // device side: game-stats stage (game-record pass, per-strategy LDS histogram gather)
+#include "fk_rare_events.h"   // device side: rare-event game list (ordered stream compaction), second-highest-score histograms
 #include "fk_bootstrap.h"     // device side: performance stage's joint batch bootstrap (draws, integer product, ranks, contrasts)
 #include "fk_root_stability.h" // device side: two-root stability stage's bootstrap families (rates of both roots, maxima, top-N membership)
 
@@ -85,6 +86,18 @@ struct GameStatsReq {
     int32_t *spill;       // [spill_capacity][3]
 };
 
+// fk_tournament_run_rare_events (beside the GameStatsReq of the same call)
+struct RareReq {
+    uint32_t second_bins;
+    int64_t *s_second, *g_second; // [S][second_bins], [second_bins]
+    fkre::Thresholds thr;
+    bool events; // false: the histograms-only call
+    int64_t event_capacity;
+    int64_t *event_count; // events the call produced (also when they did not fit)
+    uint32_t *event_head; // [event_capacity][4]
+    uint16_t *event_seats; // [event_capacity][k]
+};
+
 struct fk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -150,6 +163,8 @@ struct fk_ctx {
     DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
     const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
+    const RareReq *rare = nullptr;        // ... and of fk_tournament_run_rare_events (with gstats)
+    DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -1339,6 +1354,7 @@ void fk_destroy(fk_ctx *c) {
                       &c->discard_lut, &c->block_out, &c->stats, &c->ratios, &c->cold, &c->clk, &c->lds_tables, &c->acc, &c->rows_alt, &c->ids, &c->lag_v, &c->lag_out, &c->lag_lags, &c->lag_edge, &c->lag_tmp,
                       &c->m_ids, &c->m_dig, &c->m_seat, &c->m_rnd})
         release(*b);
+    for (DevBuf *b : {&c->r_sec, &c->r_out, &c->r_blk, &c->r_base, &c->r_head, &c->r_seats}) release(*b);
     for (DevBuf &b : c->mr) release(b);
     for (DevBuf &b : c->boot) release(b);
     for (DevBuf &b : c->rootb) release(b);
@@ -1695,6 +1711,46 @@ int fk_tournament_run_game_stats(fk_ctx *c, const fk_strategy *strategies, int32
     return rc;
 }
 
+int fk_tournament_run_rare_events(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                                  int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
+                                  int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
+                                  int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
+                                  int64_t spill_capacity, int64_t *spill_count, int32_t *spill, int32_t second_bins,
+                                  int64_t *strategy_second, int64_t *game_second, int32_t n_thresholds, const int32_t *margin_thresholds,
+                                  int64_t event_capacity, int64_t *event_count, uint32_t *event_head, uint16_t *event_seats) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_second || !game_second || !event_count) return fail(c, FK_ERR_ARG, "strategy_second, game_second and event_count are required");
+    if (second_bins < 1 || second_bins > (int32_t)fkre::MAX_SECOND_BINS) return fail(c, FK_ERR_ARG, "second_bins must be in [1, %u]", fkre::MAX_SECOND_BINS);
+    if (n_thresholds < 0 || n_thresholds > (int32_t)fkre::MAX_THRESHOLDS || (n_thresholds > 0 && !margin_thresholds))
+        return fail(c, FK_ERR_ARG, "n_thresholds must be in [0, %u], with margin_thresholds when > 0", fkre::MAX_THRESHOLDS);
+    if (event_capacity < 0 || (event_capacity > 0 && (!event_head || !event_seats)))
+        return fail(c, FK_ERR_ARG, "event_capacity must be >= 0, with event_head and event_seats when > 0");
+    if (shuffle_end > shuffle_begin && shuffle_end - shuffle_begin > 0xffffffffull)
+        return fail(c, FK_ERR_ARG, "rare events: an event names its shuffle in 32 bits; split the range");
+    if (k > 0 && S / k > 65536) return fail(c, FK_ERR_ARG, "rare events: an event names its game in 16 bits (S / k <= 65536)");
+    *event_count = 0;
+    RareReq rr{};
+    rr.second_bins = (uint32_t)second_bins;
+    rr.s_second = strategy_second;
+    rr.g_second = game_second;
+    rr.thr.n = n_thresholds;
+    for (int32_t i = 0; i < n_thresholds; ++i) rr.thr.v[i] = margin_thresholds[i];
+    rr.events = !(event_capacity == 0 && n_thresholds == 0 && !event_head && !event_seats); // that form: the histograms only
+    rr.event_capacity = event_capacity;
+    rr.event_count = event_count;
+    rr.event_head = event_head;
+    rr.event_seats = event_seats;
+    c->rare = &rr;
+    const int rc = fk_tournament_run_game_stats(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score,
+                                                max_rounds, ov, n_ov, tally, rows, perms, seat_stats, seat_ratio_sums, rare_target_score,
+                                                rounds_bins, margin_bins, strategy_counts, strategy_rounds, strategy_runner, strategy_spread,
+                                                game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill);
+    c->rare = nullptr;
+    return rc;
+}
+
 int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
                            uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
                            const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
@@ -1992,6 +2048,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         if (rc) return rc;
     }
     const GameStatsReq *gst = c->gstats; // fk_tournament_run_game_stats (null otherwise)
+    const RareReq *rare = gst ? c->rare : nullptr; // fk_tournament_run_rare_events
     const bool want_state = rows != nullptr || seat_stats != nullptr || gst != nullptr;
     const bool want_recs = !plan.lds_tally || want_state || lag != nullptr;
     const size_t stats_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_SEAT_STAT_COLS;
@@ -2012,7 +2069,8 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                                                                     (seat_stats ? (size_t)k * 32 : 0)) // + the exposure digests
                                      + (lag ? (size_t)S * 2 : 0)                                         // + the lag value matrix row
                                      + (lag && lag->m_digest ? (size_t)gps * (10 + 2 * (size_t)k) : 0)   // + the matchup records
-                                     + (gst ? (size_t)gps * 16 : 0);                                      // + the game-stat records
+                                     + (gst ? (size_t)gps * 16 : 0)                                       // + the game-stat records
+                                     + (rare ? (size_t)gps * 4 + ((size_t)gps + 255) / 256 * 12 : 0);     // + second scores, workgroup counts / bases
     // (column images are larger than AoS rows: the workspace figure above counts 4 + 28 k bytes per game)
     uint64_t chunk_sh = std::max<uint64_t>(1, (uint64_t)workspace_budget(c) / bytes_per_shuffle);
     chunk_sh = std::min<uint64_t>(chunk_sh, (uint64_t)0x7fffffff / gps);
@@ -2060,6 +2118,23 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         g_spill.count = static_cast<unsigned long long *>(c->g_out.p) + g_cnt;
         g_spill.entries = reinterpret_cast<int32_t *>(static_cast<unsigned long long *>(c->g_out.p) + g_u64);
         g_spill.cap = (uint64_t)gst->spill_capacity;
+    }
+
+    // rare events (fk_tournament_run_rare_events): r_out = u64 [S][sb] second | [sb] game second | event total
+    const uint32_t r_sb = rare ? rare->second_bins : 0u;
+    const uint32_t r_ws = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(r_sb, c->game_stats_window) : r_sb;
+    const size_t r_gs = (size_t)S * r_sb, r_tot = r_gs + r_sb, r_u64 = r_tot + 1;
+    if (rare) {
+        const size_t max_blocks = ((size_t)chunk_sh * gps + fkre::COUNT_BLOCK - 1) / fkre::COUNT_BLOCK;
+        if ((rc = ensure(c, c->r_sec, (size_t)chunk_sh * gps * 4))) return rc;
+        if ((rc = ensure(c, c->r_out, r_u64 * 8))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->r_out.p, 0, r_u64 * 8, c->stream));
+        if (rare->events) {
+            if ((rc = ensure(c, c->r_blk, max_blocks * 4))) return rc;
+            if ((rc = ensure(c, c->r_base, max_blocks * 8))) return rc;
+            if ((rc = ensure(c, c->r_head, (size_t)std::max<int64_t>(rare->event_capacity, 1) * 16))) return rc;
+            if ((rc = ensure(c, c->r_seats, (size_t)std::max<int64_t>(rare->event_capacity, 1) * (size_t)k * 2))) return rc;
+        }
     }
 
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
@@ -2234,6 +2309,30 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                                (uint32_t)S, (uint32_t)k, gps, n_sh, rows_per_seg, g_wr, g_wm, g_rb, g_mb, o + g_sc, o + g_sr, o + g_sru, o + g_ssp,
                                g_spill);
             HIPCHK(c, hipGetLastError());
+            if (rare) {
+                unsigned long long *ro = static_cast<unsigned long long *>(c->r_out.p);
+                if (k >= 2) { // one seat has no second score: it contributes nothing
+                    hipLaunchKernelGGL(fkre::fk_second_score_kernel, dim3(rec_grid), dim3(256), (size_t)r_ws * 4, c->stream,
+                                       static_cast<const uint32_t *>(CSET(c).state.p), scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr,
+                                       n_games, gps, n_sh, (uint32_t)k, r_ws, static_cast<uint32_t *>(c->r_sec.p), ro + r_gs, g_spill);
+                    hipLaunchKernelGGL(fkre::fk_second_gather_kernel, dim3((uint32_t)S, n_seg), dim3(256), (size_t)r_ws * 4, c->stream,
+                                       static_cast<const uint32_t *>(c->r_sec.p), static_cast<const uint16_t *>(CSET(c).draws.p), slots, (uint32_t)S,
+                                       (uint32_t)k, gps, n_sh, rows_per_seg, r_ws, r_sb, ro, g_spill);
+                }
+                if (rare->events) { // ordered compaction of the flagged games: count per workgroup, scan from the running total, scatter
+                    const uint32_t n_blk = (n_games + fkre::COUNT_BLOCK - 1u) / fkre::COUNT_BLOCK;
+                    hipLaunchKernelGGL(fkre::fk_event_count_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream,
+                                       static_cast<const uint4 *>(c->g_rec.p), n_games, rare->thr, static_cast<uint32_t *>(c->r_blk.p));
+                    hipLaunchKernelGGL(fkre::fk_event_scan_kernel, dim3(1), dim3(fkre::SCAN_BLOCK), 0, c->stream,
+                                       static_cast<const uint32_t *>(c->r_blk.p), n_blk, ro + r_tot, static_cast<unsigned long long *>(c->r_base.p));
+                    hipLaunchKernelGGL(fkre::fk_event_scatter_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream,
+                                       static_cast<const uint4 *>(c->g_rec.p), static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)S,
+                                       (uint32_t)k, gps, n_games, (uint32_t)done, rare->thr, static_cast<const unsigned long long *>(c->r_base.p),
+                                       (unsigned long long)rare->event_capacity, static_cast<uint4 *>(c->r_head.p),
+                                       static_cast<uint16_t *>(c->r_seats.p));
+                }
+                HIPCHK(c, hipGetLastError());
+            }
         }
         if (seat_stats) {
             const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
@@ -2408,6 +2507,13 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         for (const auto &pt : parts)
             HIPCHK(c, hipMemcpyAsync(pt.first, o + pt.second.first * 8, pt.second.second * 8, hipMemcpyDeviceToHost, c->stream));
     }
+    int64_t r_events = 0;
+    if (rare) {
+        const uint8_t *o = static_cast<const uint8_t *>(c->r_out.p);
+        HIPCHK(c, hipMemcpyAsync(rare->s_second, o, r_gs * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rare->g_second, o + r_gs * 8, (size_t)r_sb * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&r_events, o + r_tot * 8, 8, hipMemcpyDeviceToHost, c->stream));
+    }
     if (lag) {
         const size_t edge_bytes = (size_t)edge_rows * (size_t)S * 2;
         HIPCHK(c, hipMemcpyAsync(lag->sums, c->lag_out.p, lag_sum_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2422,13 +2528,26 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         if (rc) return rc;
         if (rc_t) return rc_t;
     }
+    if (rare) *rare->event_count = r_events; // (reported beside the spill count when both lists are too small)
     if (gst) { // the exact values outside the histogram windows
         *gst->spill_count = g_spilled;
+        if (rare && r_events > rare->event_capacity && g_spilled > gst->spill_capacity)
+            return fail(c, FK_ERR_ARG, "rare events: the event list needs %lld entries, event_capacity is %lld; the spill list needs %lld, spill_capacity is %lld",
+                        (long long)r_events, (long long)rare->event_capacity, (long long)g_spilled, (long long)gst->spill_capacity);
         if (g_spilled > gst->spill_capacity)
             return fail(c, FK_ERR_ARG, "game statistics: the spill list needs %lld entries, spill_capacity is %lld", (long long)g_spilled,
                         (long long)gst->spill_capacity);
         if (g_spilled)
             HIPCHK(c, hipMemcpy(gst->spill, static_cast<const unsigned long long *>(c->g_out.p) + g_u64, (size_t)g_spilled * 12, hipMemcpyDeviceToHost));
+    }
+    if (rare) { // the flagged games, in (shuffle, game) order
+        if (r_events > rare->event_capacity)
+            return fail(c, FK_ERR_ARG, "rare events: the event list needs %lld entries, event_capacity is %lld", (long long)r_events,
+                        (long long)rare->event_capacity);
+        if (r_events) {
+            HIPCHK(c, hipMemcpy(rare->event_head, c->r_head.p, (size_t)r_events * 16, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(rare->event_seats, c->r_seats.p, (size_t)r_events * (size_t)k * 2, hipMemcpyDeviceToHost));
+        }
     }
     HIPCHK(c, hipEventElapsedTime(&c->timing.total_ms, t0, t1));
     return FK_OK;

@@ -562,7 +562,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                    all_player_dir: Path | None = None, sidecars: "_Sidecars | None" = None,
                    rng_lags: Sequence[int] | None = None, defer_final_checkpoint: bool = False, packed_table: np.ndarray | None = None,
                    defer_tail: list | None = None, rng_matchups: int | None = None, game_stats: bool = False,
-                   performance_bootstrap: bool = False) -> dict:
+                   performance_bootstrap: bool = False, rare_events: "Mapping[str, Any] | None" = None) -> dict:
     """Play every deterministic batch not yet owned by the checkpoint and persist the aggregates.  ``defer_final_checkpoint``: the final
     checkpoint's file write may still be in flight on return — the caller joins ``result["checkpoint_written"]`` before reading the file.  ``rng_lags``: also accumulate the lag
     sufficient statistics of the RNG diagnostics' strategy family over the WHOLE shuffle range (``fk_tournament_run_lags``; launch
@@ -572,7 +572,10 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
     game-stats stage's histograms of the WHOLE range (``fk_tournament_run_game_stats``, on the same launch as the all-player batches),
     summed on rank 0 — ``result["game_stats"]`` (game_stats.GameStatsSummary).  ``performance_bootstrap``: keep the wins / exposures of
     every deterministic batch (the stats launch of the all-player batches) — ``result["performance_matrix"]`` on rank 0
-    (performance_bootstrap.BatchMatrix)."""
+    (performance_bootstrap.BatchMatrix).  ``rare_events`` (needs ``game_stats``; ``target_score``, ``thresholds``, ``want_events``):
+    the game-stats launches become ``fk_tournament_run_rare_events`` — ``result["rare_events"]`` on rank 0: the second-score
+    histograms of the whole range with the game statistics (rare_events.RareEventSummary) and, with ``want_events``, the flagged
+    games of the whole range in (shuffle, game) order (launch groups and ranks are contiguous ranges that concatenate in order)."""
     rank, world = _rank_world()
     _trace(f"{n_players}p run_tournament")
     eng = get_engine()
@@ -684,8 +687,12 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
             raise ValueError("game statistics need every shuffle of the run; this checkpoint already owns batches: use --force")
         if row_dir is not None or rng_lags:
             raise ValueError("--game-stats runs without rows / lag statistics (one post-pass per launch): run them separately")
-        rare_target = cfg.rare_event_target_score()
+        rare_target = int(rare_events["target_score"]) if rare_events is not None else cfg.rare_event_target_score()
         cfg.game_stats_margin_thresholds()  # (validated before anything plays)
+    elif rare_events is not None:
+        raise ValueError("the rare-event list rides on the game-stats launches: rare_events needs game_stats")
+    rare_total = None   # rare_events.RareEventSummary of the range so far (rank 0)
+    rare_parts: list = []  # (head, seats) per call range, heads rebased to the run's first shuffle (rank 0)
     target = oracle_game_profile.default_target_score if oracle_game_profile else 10_000
     max_rounds = oracle_game_profile.default_max_rounds if oracle_game_profile else 200
     ov = oracle_game_profile.tournament_overrides() if oracle_game_profile else None
@@ -762,7 +769,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
 
     def finish(b0, b1, lo, hi, j, local, local_stats, local_ratios, row_records, fragments, res, shard_job, per_batch) -> None:
         """What follows a launch group's engine call: its shards' manifest lines, the reduction over ranks, chunk files, checkpoint."""
-        nonlocal total, games_done, lag_total, gs_total, batches_since_save, last_save
+        nonlocal total, games_done, lag_total, gs_total, rare_total, batches_since_save, last_save
         if shard_job is not None:
             row_records = shard_job.result()
             if callable(row_records):  # the per-shard manifest lines: built here, not on the shard thread (its host threads would idle)
@@ -785,6 +792,19 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                 for piece in parts:
                     if piece is not None:
                         gs_total = piece if gs_total is None else gs_total.merge(piece)
+        if rare_events is not None:  # ranks hold contiguous whole batches in rank order: histograms add, events concatenate
+            from .rare_events import RareEventSummary, concat_events
+
+            part = None
+            if res is not None and hi > lo:
+                r = res["rare_events"]
+                part = (RareEventSummary.from_engine(res, k), concat_events([(r["event_head"], r["event_seats"])], [lo]))
+            parts = gather_objects(part, dst=0) if world > 1 else [part]
+            if rank == 0:
+                for piece in parts:
+                    if piece is not None:
+                        rare_total = piece[0] if rare_total is None else rare_total.merge(piece[0])
+                        rare_parts.append(piece[1])
         if rng_matchups:  # the group's per-game records in rank order = coordinate order (contiguous whole batches per rank)
             rec = res["matchups"] if hi > lo else None
             recs = gather_objects(rec, dst=0) if world > 1 else [rec]
@@ -893,6 +913,12 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
         elif rng_matchups:
             res = eng.tournament_matchups(table, k, cfg.sim.seed, lo, hi, rng_lags, np.asarray(ids, dtype=np.int32), rng_matchups,
                                           shuffles_per_batch=batch_arg, target_score=target, max_rounds=max_rounds, overrides=ov)
+        elif game_stats and rare_events is not None:
+            res = eng.tournament_rare_events(table, k, cfg.sim.seed, lo, hi, shuffles_per_batch=batch_arg, target_score=target,
+                                             max_rounds=max_rounds, overrides=ov, rare_target_score=rare_target,
+                                             thresholds=tuple(rare_events["thresholds"]) if rare_events["want_events"] else (),
+                                             want_events=bool(rare_events["want_events"]),
+                                             want_seat_stats=bool(g["extra"].get("want_seat_stats")))
         elif game_stats:
             res = eng.tournament_game_stats(table, k, cfg.sim.seed, lo, hi, shuffles_per_batch=batch_arg, target_score=target,
                                             max_rounds=max_rounds, overrides=ov, rare_target_score=rare_target,
@@ -1102,6 +1128,14 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                     sidecars.write("shard_manifest", manifest)
         barrier()
         result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total, game_stats=gs_total)
+        if rare_events is not None and rank == 0 and rare_total is not None:
+            from .rare_events import concat_events
+
+            head, seats = concat_events(rare_parts, [0] * len(rare_parts))
+            result["rare_events"] = {"summary": rare_total, "event_head": head, "event_seats": seats.reshape(len(head), k),
+                                     "games_per_shuffle": gps, "n_games": plan.required_shuffles * gps, "n_shuffles": plan.required_shuffles,
+                                     "target_score": target, "max_rounds": max_rounds, "overrides": ov, "table": table,
+                                     "shuffles_per_call": max(1, group_batches * spb)}
         if performance_bootstrap and rank == 0:
             from .performance_bootstrap import BatchMatrix
 
@@ -1222,7 +1256,7 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
                             packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
                             rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats,
-                            performance_bootstrap=cfg.sim.performance_bootstrap)
+                            performance_bootstrap=cfg.sim.performance_bootstrap, rare_events=_rare_event_plan(cfg))
     finally:
         if published is not None:
             published.result()  # the inputs are on disk (or their error is raised) before the summaries and the stamp name them
@@ -1293,7 +1327,7 @@ def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrate
     from . import game_stats as gs
 
     thresholds = cfg.game_stats_margin_thresholds()
-    rare_target = cfg.rare_event_target_score()
+    rare_target = cfg.rare_event_settings()["target_score"] if cfg.sim.rare_events else cfg.rare_event_target_score()
     ids = np.asarray([int(s.strategy_id) for s in strategies], dtype=np.int64)
     summary = result["game_stats"]
     table = gs.game_stats_table(summary, ids, n, thresholds)
@@ -1301,6 +1335,9 @@ def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrate
         _write_parquet_atomic(table, cfg.game_stats_path(n))
     settings = {b"root_seed": str(int(cfg.sim.seed)).encode(), b"rare_target_score": str(rare_target).encode()}
     _write_parquet_atomic(summary.sums_table(ids).replace_schema_metadata(settings), cfg.game_stats_sums_path(n))
+    if cfg.sim.rare_events:  # the root's summary follows the sweep, under the RESOLVED thresholds: _publish_rare_events
+        _RARE_STATE.setdefault(str(cfg.results_root), {})[int(n)] = {**result["rare_events"], "tally": np.asarray(result["tally"])}
+        return
     counts, _ = _filter_player_counts(list(cfg.sim.n_players_list), len(ids))
     paths = {int(v): cfg.game_stats_sums_path(int(v)) for v in counts}
     if not all(p.exists() for p in paths.values()):
@@ -1316,6 +1353,90 @@ def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrate
         cfg.game_stats_rare_summary_path().unlink(missing_ok=True)
     else:
         _write_parquet_atomic(rare, cfg.game_stats_rare_summary_path())
+
+
+_RARE_STATE: dict[str, dict[int, Any]] = {}  # results root -> player count -> run_tournament's result["rare_events"] (rank 0, one sweep)
+
+
+def _rare_event_plan(cfg: AppConfig) -> dict | None:
+    """What ``run_tournament`` asks the engine for under ``--rare-events``: with fixed thresholds the flagged games under them;
+    with a quantile key the histograms only (the thresholds are resolved after the sweep's last player count)."""
+    if not cfg.sim.rare_events:
+        return None
+    if not cfg.sim.game_stats:
+        raise ValueError("--rare-events rides on the game-stats launches: pass --game-stats with it")
+    st = cfg.rare_event_settings()
+    quantile = st["margin_quantile"] is not None or st["target_rate"] is not None
+    return {"target_score": st["target_score"], "thresholds": st["thresholds"], "want_events": not quantile}
+
+
+def _publish_rare_events(cfg: AppConfig, counts: Sequence[int], strategies: list[ThresholdStrategy]) -> dict:
+    """After the sweep's last player count, on rank 0: ``rare_events.parquet`` (game rows of every player count + summary rows),
+    ``game_stats_rare_event_summary.parquet`` (the summary rows alone) and, with ``analysis.rare_event_write_details``,
+    ``rare_events_details.parquet`` — all under the resolved thresholds.  With a quantile key the thresholds are resolved from the
+    histograms of the first pass, every player count's shuffle ranges are REPLAYED with them on this rank's engine (a game is a pure
+    function of its coordinate) and the replay's tally is checked against the first pass's."""
+    from . import rare_events as rev
+    from .game_stats import rare_event_summary_table
+
+    state = _RARE_STATE.pop(str(cfg.results_root), {})
+    missing = [int(v) for v in counts if state.get(int(v)) is None]
+    if missing:
+        raise ValueError(f"--rare-events needs every player count of the run in one sweep; {missing} were not played (already complete?): "
+                         "use --force")
+    st = cfg.rare_event_settings()
+    ids = np.asarray([int(s.strategy_id) for s in strategies], dtype=np.int64)
+    summaries = {int(v): state[int(v)]["summary"] for v in counts}
+    thresholds, target = rev.resolve_rare_event_thresholds(summaries, st["thresholds"], st["target_score"], st["margin_quantile"],
+                                                           st["target_rate"])
+    quantile = st["margin_quantile"] is not None or st["target_rate"] is not None
+    for s in summaries.values():  # the launch's own rare target: the tail of the second-score histograms is its multi-target count
+        if not rev.tail_equals_multi_target(s, st["target_score"]):
+            raise RuntimeError("rare events: the second-score histograms disagree with the multi-target counts of the same launch")
+    events = {}
+    for v in counts:
+        v = int(v)
+        part = state[v]
+        head, seats = part["event_head"], part["event_seats"]
+        if quantile:
+            eng = get_engine()
+            pieces, offsets, tally, replayed = [], [], None, []
+            for lo in range(0, part["n_shuffles"], part["shuffles_per_call"]):
+                hi = min(lo + part["shuffles_per_call"], part["n_shuffles"])
+                res = eng.tournament_rare_events(part["table"], v, cfg.sim.seed, lo, hi, target_score=part["target_score"],
+                                                 max_rounds=part["max_rounds"], overrides=part["overrides"], rare_target_score=target,
+                                                 thresholds=thresholds)
+                pieces.append((res["rare_events"]["event_head"], res["rare_events"]["event_seats"]))
+                offsets.append(lo)
+                tally = res["tally"].sum(axis=0) if tally is None else tally + res["tally"].sum(axis=0)
+                replayed.append(rev.RareEventSummary.from_engine(res, v))
+            replay = replayed[0]
+            for piece in replayed[1:]:
+                replay = replay.merge(piece)
+            first = summaries[v]
+            same = (np.array_equal(first.stats.game_rounds, replay.stats.game_rounds) and np.array_equal(first.game_second, replay.game_second)
+                    and np.array_equal(first.stats.strategy_counts[:, :3], replay.stats.strategy_counts[:, :3])
+                    and np.array_equal(first.stats.game_runner, replay.stats.game_runner))
+            if not same or tally is None or not np.array_equal(tally, np.asarray(part["tally"])):
+                raise RuntimeError(f"rare events: the replay of {v}p did not play the games of the first pass")
+            head, seats = rev.concat_events(pieces, offsets)
+            seats = seats.reshape(len(head), v)
+        events[v] = (head, seats, part["games_per_shuffle"], part["n_games"])
+    under = {v: s.under_target(target) for v, s in summaries.items()}
+    summary = rare_event_summary_table(under, ids, thresholds)
+    final = rev.rare_events_table(events, summaries, ids, thresholds, target)
+    for table, path in ((summary, cfg.game_stats_rare_summary_path()), (final, cfg.rare_events_path())):
+        if table is None:  # no flagged game in the root: the reference writes no file either
+            path.unlink(missing_ok=True)
+        else:
+            _write_parquet_atomic(table, path)
+    if st["write_details"]:
+        details = rev.rare_event_details_table(events, ids, thresholds)
+        if details is None:
+            cfg.rare_events_details_path().unlink(missing_ok=True)
+        else:
+            _write_parquet_atomic(details, cfg.rare_events_details_path())
+    return {"thresholds": tuple(thresholds), "target_score": int(target), "events": {v: len(e[0]) for v, e in events.items()}}
 
 
 def _check_performance_bootstrap(cfg: AppConfig, strategies: list[ThresholdStrategy]) -> None:
@@ -1567,6 +1688,8 @@ def run_multi(cfg: AppConfig, player_counts: Sequence[int] | None = None, *, for
             _TRACE.clear()
     if cfg.sim.performance_bootstrap and valid and _rank_world()[0] == 0:  # the matrices of every count are reduced on rank 0
         _publish_performance_bootstrap(cfg, valid)
+    if cfg.sim.rare_events and valid and _rank_world()[0] == 0:  # the lists of every count, under thresholds resolved across them
+        _publish_rare_events(cfg, valid, strategies)
     return results
 
 

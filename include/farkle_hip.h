@@ -355,6 +355,40 @@ int fk_tournament_run_game_stats(fk_ctx *ctx, const fk_strategy *strategies, int
                                  int64_t *game_rounds, int64_t *game_runner, int64_t spill_capacity, int64_t *spill_count,
                                  int32_t *spill);
 
+/* fk_tournament_run_game_stats (every argument and output up to `spill` as there, the same bits) + what the reference's
+ * rare-event shards need beyond the summary sums (analysis/game_stats.py: _build_rare_event_summary_shard :2715-2984,
+ * _rare_event_details :2987-3153, _resolve_rare_event_thresholds :3293-3328):
+ *   strategy_second [S][second_bins], game_second [second_bins]   int64 histograms of the game's second-highest seat score / 50
+ *                             over ALL attempted games with k >= 2, safety-limit games included (_second_highest :3395-3406), per
+ *                             seat exposure and per game as the runner-up histograms; k = 1 contributes nothing.  A value
+ *                             >= second_bins is a spill entry of kind 3 in the same spill list.  1 <= second_bins <= 4096.
+ *   margin_thresholds [n_thresholds]   0 .. 8 thresholds in points, any sign.  A game is an EVENT when
+ *                             multi        at least two seats have score >= rare_target_score, or
+ *                             margin_le[i] it completed, k >= 2 and its runner-up margin in points is <= margin_thresholds[i].
+ *   event_head  uint32 [event_capacity][4]:  x = shuffle index - shuffle_begin;
+ *                             y = game index | completed << 16 | multi << 17 | threshold mask << 18 (bit i = margin_le[i]);
+ *                             z = runner-up margin / 50, w = score spread / 50 (both 0 unless completed with k >= 2)
+ *   event_seats uint16 [event_capacity][k]:  the seats' strategy table indices in seat order
+ * Events come out in ascending (shuffle, game) order, whatever the grid, the workspace chunking ("chunk_bytes") and the split of a
+ * shuffle range over calls: the lists of a split, concatenated (x rebased), equal the list of the one call.  *event_count = the
+ * events the call produced; more than event_capacity returns FK_ERR_ARG (call again with that capacity; when the spill list is
+ * too small as well, both counts are reported by the same return).  event_capacity = 0 with n_thresholds = 0 and null lists is
+ * the histograms-only call: no game is examined for events and *event_count = 0.  The range may hold at most 2^32 - 1 shuffles and
+ * S / k at most 65536 games per shuffle.  The second score is kept in a second per-game record array (4 bytes per game), so the
+ * 16-byte game records of fk_tournament_run_game_stats are unchanged; the list is an order-preserving stream compaction
+ * (wave ballots, a one-workgroup scan of the workgroup counts carried across chunks, a scatter): farkle_ii_amd/csrc/fk_rare_events.h;
+ * farkle_ii_amd/rare_events.py resolves the quantile thresholds and holds the host statement. */
+int fk_tournament_run_rare_events(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch,
+                                  int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov,
+                                  int64_t *tally, void *rows, int32_t *perms, int64_t *seat_stats, double *seat_ratio_sums,
+                                  int32_t rare_target_score, int32_t rounds_bins, int32_t margin_bins, int64_t *strategy_counts,
+                                  int64_t *strategy_rounds, int64_t *strategy_runner, int64_t *strategy_spread, int64_t *game_counts,
+                                  int64_t *game_rounds, int64_t *game_runner, int64_t spill_capacity, int64_t *spill_count,
+                                  int32_t *spill, int32_t second_bins, int64_t *strategy_second, int64_t *game_second,
+                                  int32_t n_thresholds, const int32_t *margin_thresholds, int64_t event_capacity,
+                                  int64_t *event_count, uint32_t *event_head, uint16_t *event_seats);
+
 /* Explicit game list: game g seats strategies table[seat_strategy[g*k+i]] with streams coords[g](seat i).
  * rows: n_games * (4+28k) bytes (required). */
 int fk_play_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
