@@ -1315,7 +1315,7 @@ int fk_init(int device_ordinal, fk_ctx **out) {
         fk_destroy(c);
         return FK_ERR_HIP;
     }
-    if (ensure(c, c->discard_lut, DISCARD_LUT_KEYS) != FK_OK) {
+    if (ensure(c, c->discard_lut, DISCARD_LUT_KEYS * (1 + sizeof(uint32_t))) != FK_OK) { // the byte table and, behind it, the wide one
         fk_destroy(c);
         return FK_ERR_HIP;
     }

@@ -214,6 +214,9 @@ __host__ __device__ inline uint32_t mulhi32(uint32_t a, uint32_t b) {
 // face-1 field (at most 6 counts in a field: no carry between fields), taken off at the end.  No per-die "is this die rolled" bit,
 // and no per-die choice between the two word alignments.  A drawn word that is not rolled (the high half of the last output when m
 // is odd: the next roll's buffered die) is replaced by 1 in its own draw's region.
+// Round 9: the key leaves MULTIPLIED BY 4: it is the byte offset of the roll's entry in the score table, for a gather with a scalar base
+// and no address arithmetic.  Each die's term is then 4 << 3 f, added to the running key by the same instruction that shifts it; the
+// start value and the face-1 correction scale with it (4 n - 24).
 __device__ inline uint32_t roll_key_fast(Rng &r, uint32_t n, bool &detour) {
     const uint32_t hb = r.has_buf, m = n - hb;
     const uint32_t need = (m + 1u) >> 1; // new 64-bit outputs, 0..3
@@ -241,11 +244,13 @@ __device__ inline uint32_t roll_key_fast(Rng &r, uint32_t n, bool &detour) {
     // both halves of a product where one word select does
     asm("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3), "+v"(s4), "+v"(s5b));
     const uint32_t w[6] = {s0, s1, s2, s3, s4, s5b};
-    uint32_t key = n - 6u, minleft = 0xffffffffu;
+    uint32_t key4 = 4u * n - 24u, minleft = 0xffffffffu;
+    asm("" : "+v"(key4));
 #pragma unroll
     for (uint32_t i = 0; i < 6; ++i) {
         const uint64_t pw = (uint64_t)w[i] * 6u; // face - 1 = high word; rejection iff low word < 4
-        key += 1u << (3u * (uint32_t)(pw >> 32));
+        key4 += 4u << (3u * (uint32_t)(pw >> 32));
+        asm("" : "+v"(key4)); // one v_lshl_add_u32 per die, in a chain: left to itself the compiler shifts every term apart and adds them up in threes
         minleft = min(minleft, (uint32_t)pw);
     }
     r.has_buf = (n + hb) & 1u;
@@ -254,7 +259,7 @@ __device__ inline uint32_t roll_key_fast(Rng &r, uint32_t n, bool &detour) {
 #ifdef FK_FORCE_DETOUR
     detour = detour || ((((uint32_t)(r.lo >> 17)) & (uint32_t)(FK_FORCE_DETOUR - 1)) == 0u); // see roll_counts_fast
 #endif
-    return key;
+    return key4;
 }
 
 // roll_counts_fast: the converged part.  `detour` = some low product word fell below the rejection bound: the caller restores the
@@ -262,7 +267,7 @@ __device__ inline uint32_t roll_key_fast(Rng &r, uint32_t n, bool &detour) {
 // restore from the seat record in LDS instead of keeping a copy of the state in registers).
 template <uint32_t STRIDE = 4>
 __device__ inline uint32_t roll_counts_fast(Rng &r, uint32_t n, bool &detour, uint32_t *faces_out = nullptr) {
-    if (STRIDE == 3u) return roll_key_fast(r, n, detour); // the score-table key: no faces
+    if (STRIDE == 3u) return roll_key_fast(r, n, detour) >> 2; // the score-table key: no faces (roll_key_fast returns it times 4)
     const uint32_t hb = r.has_buf, buf_in = r.buf;
     const uint32_t need = (n - hb + 1u) >> 1; // new 64-bit outputs: ceil((n - has_buf) / 2), 0..3
     uint32_t lo0 = 1, hi0 = 1, lo1 = 1, hi1 = 1, lo2 = 1, hi2 = 1, last_hi = r.buf;
@@ -628,6 +633,20 @@ __host__ __device__ inline uint8_t discard_lut_entry(uint32_t key) {
     return (uint8_t)(ch | ((ch & 3u) ? 1u << DCH_ANY5_SHIFT : 0u) | ((ch & 12u) ? 1u << DCH_ANY1_SHIFT : 0u));
 }
 
+// The WIDE entry (round 9; a second table of 2^16 dwords behind the byte table, the game kernels' one): the same choice with every
+// value the roll step's back end takes from it where one instruction picks it up —
+//   [0] a five was returned, [17:16] d5: `x & DW_INC` is the increment of cC (sf_uses | sf_dice << 16)
+//   [4] a one was returned,  [21:20] d1: `(x >> DW_D1_SHIFT) & DW_INC` is the increment of cD
+//   [15:8]  d5 + 2 d1, the points / 50 the discards take off the roll's score  (a whole byte each: a byte-select operand)
+//   [31:24] d5 + d1,   the dice they give back
+constexpr uint32_t DW_INC = 0x00030001u, DW_D1_SHIFT = 4, DW_POINTS_SHIFT = 8, DW_DICE_SHIFT = 24;
+
+__host__ __device__ inline uint32_t discard_lut_entry32(uint32_t key) {
+    const uint32_t ch = discard_lut_entry(key), d5 = ch & 3u, d1 = (ch >> 2) & 3u;
+    const uint32_t inc5 = (d5 << 16) | (d5 ? 1u : 0u), inc1 = (d1 << 16) | (d1 ? 1u : 0u);
+    return inc5 | (inc1 << DW_D1_SHIFT) | ((d5 + 2u * d1) << DW_POINTS_SHIFT) | ((d5 + d1) << DW_DICE_SHIFT);
+}
+
 __host__ __device__ inline RollResult apply_discards(const RawScore raw, uint32_t choice) {
     const int32_t d5 = (int32_t)(choice & 3u), d1 = (int32_t)((choice >> 2) & 3u);
     RollResult out;
@@ -744,6 +763,27 @@ __host__ __device__ inline uint32_t discard_lookup50(const uint32_t *lut, const 
         choice = dlut[(e >> 16) | (s.bits & SF_DISCARD_KEY_BITS) | vpart | cpart];
     }
     return choice;
+}
+
+// The game kernels' gathers since round 9: `key4` = 4 x the key, the entry's byte offset as roll_key_fast returns it (no address
+// arithmetic in front of the load), and the discard table's WIDE entry (discard_lut_entry32: the same choice, laid out for the back end).
+__host__ __device__ inline uint32_t discard_lookup50w(const uint32_t *lut, const uint32_t *dlutw, uint32_t key4, int32_t n, int32_t pre50,
+                                                      const Strat50 &s, uint32_t &e_out) {
+    const uint32_t e = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(lut) + key4);
+    e_out = e;
+    const int32_t raw50 = (int32_t)(e & 63u), used = (int32_t)((e >> 6) & 7u);
+    const bool eligible = s.has(SF_SMART_FIVE) & ((e & SE_SINGLES) != 0u) & (used != n); // scoring.py:433
+    uint32_t x = 0u;
+    if (eligible) { // the key as in discard_lookup50
+        int32_t v = pre50 + raw50 - s.thr50;
+        v = v < -1 ? -1 : (v > 6 ? 6 : v);
+        int32_t c = s.dice_thr() - n + used;
+        c = c < -1 ? -1 : (c > 4 ? 4 : c);
+        const uint32_t vpart = s.has(SF_CONSIDER_SCORE) ? (uint32_t)(v + 1) << DKEY_VMIN_SHIFT : 0u;
+        const uint32_t cpart = s.has(SF_CONSIDER_DICE) ? (uint32_t)(c + 1) << DKEY_CMIN_SHIFT : 0u;
+        x = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(dlutw) + 4u * ((e >> 16) | (s.bits & SF_DISCARD_KEY_BITS) | vpart | cpart));
+    }
+    return x;
 }
 
 __host__ __device__ inline Roll50 default_score_lut50(const uint32_t *lut, const uint8_t *dlut, uint32_t key, int32_t n, int32_t pre50,
@@ -912,6 +952,35 @@ struct RollRegs {
     int32_t turn_score; // / 50
 };
 
+// ---- the guards of a roll: does the lane leave through the error exit, and with which code ----
+// ROLL_LIMIT (engine.py:36, 242): a turn that has made 1 000 rolls may not make another; tested on the rolls made BEFORE this one.  The
+// guard bands of the 16-bit fields, tested on the registers AFTER this roll: a turn adds at most 1 000 rolls and 2 000 returned dice of
+// either kind to a field before the next test, and highest_turn must fit 16 bits in points (1 310 x 50 = 65 500).  The roll limit comes
+// first where both hold.  `_decoded` decodes every field; the kernels' form compares whole words (a field in the high half of its word
+// is above its limit iff the word is at or above limit + 1 in that half; n_rolls, in the low half, by a 16-bit compare) — round 9 costed
+// three foldings of these five compares (a v_max3_u32 in front of one compare, a shadow word of biased fields tested by one mask, a roll
+// count taken from n_rolls): each saves exactly what its extra instruction costs (profiles/r09_ab_roll_bookkeeping.txt), so the five
+// compares stay.  tests/native/roll_guards_host_check.hip compares the two forms around every limit.
+enum : uint32_t { RG_NONE = 0, RG_ROLL_LIMIT = 1, RG_OVERFLOW = 2 };
+constexpr uint32_t RG_TURN_ROLLS = 1000u, RG_TURN50 = 1310u, RG_N_ROLLS = 64000u, RG_DICE = 63000u;
+
+__host__ __device__ inline uint32_t roll_guards50_decoded(uint32_t rolls_before, const RollRegs &r) {
+    const uint32_t n_rolls = r.cA & 0xffffu, sf_dice = r.cC >> 16, so_dice = r.cD >> 16;
+    if (rolls_before >= RG_TURN_ROLLS) return RG_ROLL_LIMIT;
+    if (r.turn_score > (int32_t)RG_TURN50 || n_rolls > RG_N_ROLLS || sf_dice > RG_DICE || so_dice > RG_DICE) return RG_OVERFLOW;
+    return RG_NONE;
+}
+
+__host__ __device__ inline bool roll_overflow50(const RollRegs &r) {
+    return (r.turn_score >= (int32_t)(RG_TURN50 + 1u)) | ((uint16_t)r.cA >= (uint16_t)(RG_N_ROLLS + 1u)) | (r.cC >= ((RG_DICE + 1u) << 16)) |
+           (r.cD >= ((RG_DICE + 1u) << 16));
+}
+
+__host__ __device__ inline uint32_t roll_guards50(uint32_t rolls_before, const RollRegs &r) {
+    const bool limit = rolls_before >= RG_TURN_ROLLS, overflow = roll_overflow50(r);
+    return limit ? (uint32_t)RG_ROLL_LIMIT : overflow ? (uint32_t)RG_OVERFLOW : (uint32_t)RG_NONE;
+}
+
 template <bool LEAN>
 __host__ __device__ inline bool roll_back_end50_decoded(uint32_t e, uint32_t choice, uint32_t n, const Strat50 &sp, bool final_round,
                                                         int32_t stb50, RollRegs &r, bool &overflow) {
@@ -983,16 +1052,15 @@ __host__ __device__ inline uint32_t pk_max_u16(uint32_t a, uint32_t b) {
 //   - the bank: with entry = !has_scored & turn < 10 (the decision's own term), the turn banks iff over & !entry, and has_scored
 //     afterwards is has_scored | bank: no second test of the 500-point rule, no test of the flag just written;
 //   - highest_turn as a packed 16-bit maximum with the banked turn (its high half is 0: the other half of cB stays).
-template <bool LEAN, uint32_t MIXED = 0xffffu>
-__host__ __device__ inline bool roll_back_end50(uint32_t e, uint32_t choice, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, bool final_round,
-                                                int32_t stb50, RollRegs &r, bool &overflow) {
-    const uint32_t d5 = choice & 3u, d1 = (choice >> 2) & 3u;
-    const int32_t score50 = (int32_t)(e & 63u) - (int32_t)d5 - 2 * (int32_t)d1;
-    const uint32_t used = ((e >> 6) & 7u) - d5 - d1;
+// (the part behind the discard entry's decoding: `score50`, `used` = the roll's score / 50 and dice used after the discards; `inc_c`,
+// `inc_d` = the increments of cC and cD)
+template <bool LEAN, uint32_t MIXED>
+__host__ __device__ inline bool roll_back_end50_core(int32_t score50, uint32_t used, uint32_t inc_c, uint32_t inc_d, uint32_t n, const Strat50 &sp,
+                                                     uint32_t uniform_bits, bool final_round, int32_t stb50, RollRegs &r, bool &overflow) {
     const bool farkle = score50 == 0;
     r.cA += 1u + (farkle ? 0x10000u : 0u);
-    r.cC += (d5 << 16) + ((choice >> DCH_ANY5_SHIFT) & 1u);
-    r.cD += (d1 << 16) + ((choice >> DCH_ANY1_SHIFT) & 1u);
+    r.cC += inc_c;
+    r.cD += inc_d;
     r.dice = (used == n) ? 6u : (n - used);
     r.turn_score = farkle ? 0 : (r.turn_score + score50);
     const lanes_t farkle_l = lanes(score50 == 0);
@@ -1015,8 +1083,28 @@ __host__ __device__ inline bool roll_back_end50(uint32_t e, uint32_t choice, uin
     r.score += (int32_t)banked;
     if (LEAN) r.cE += banked;
     r.cB = pk_max_u16(r.cB, banked);
-    overflow = (r.turn_score > 1310) | ((r.cA & 0xffffu) > 64000u) | ((r.cC >> 16) > 63000u) | ((r.cD >> 16) > 63000u);
+    overflow = roll_overflow50(r);
     return over;
+}
+
+// ... from the byte table's entry (round 8's form; the host checks' one) ...
+template <bool LEAN, uint32_t MIXED = 0xffffu>
+__host__ __device__ inline bool roll_back_end50(uint32_t e, uint32_t choice, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, bool final_round,
+                                                int32_t stb50, RollRegs &r, bool &overflow) {
+    const uint32_t d5 = choice & 3u, d1 = (choice >> 2) & 3u;
+    const int32_t score50 = (int32_t)(e & 63u) - (int32_t)d5 - 2 * (int32_t)d1;
+    const uint32_t used = ((e >> 6) & 7u) - d5 - d1;
+    return roll_back_end50_core<LEAN, MIXED>(score50, used, (d5 << 16) + ((choice >> DCH_ANY5_SHIFT) & 1u), (d1 << 16) + ((choice >> DCH_ANY1_SHIFT) & 1u), n,
+                                             sp, uniform_bits, final_round, stb50, r, overflow);
+}
+
+// ... and from the wide entry (round 9, the game kernels' form): four fields, each one instruction away from its use
+template <bool LEAN, uint32_t MIXED = 0xffffu>
+__host__ __device__ inline bool roll_back_end50w(uint32_t e, uint32_t x, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, bool final_round,
+                                                 int32_t stb50, RollRegs &r, bool &overflow) {
+    const int32_t score50 = (int32_t)(e & 63u) - (int32_t)((x >> DW_POINTS_SHIFT) & 0xffu);
+    const uint32_t used = ((e >> 6) & 7u) - (x >> DW_DICE_SHIFT);
+    return roll_back_end50_core<LEAN, MIXED>(score50, used, x & DW_INC, (x >> DW_D1_SHIFT) & DW_INC, n, sp, uniform_bits, final_round, stb50, r, overflow);
 }
 
 // ---- two-seat table advance (engine.py:453-472, 523-550) after a roll: the game-level half of the back end, for every lane of the trip ----

@@ -132,7 +132,7 @@ struct SeedArgs {
 struct PlayArgs {
     const uint2 *strat;          // [S] packed strategies
     const uint32_t *score_lut;   // [SCORE_LUT_KEYS] score table, 32-bit entries (fk_device.h: score_lut_entry32)
-    const uint8_t *discard_lut;  // [DISCARD_LUT_KEYS] discard table (fk_device.h)
+    const uint8_t *discard_lut;  // [DISCARD_LUT_KEYS] discard table (fk_device.h), followed by its wide form, [DISCARD_LUT_KEYS] dwords
     const uint16_t *perm_T;      // blocked permutations (MODE_PERM), see perm_at()
     uint32_t perm_slots;
     const int32_t *seat_strategy; // [n_games][k] (MODE_LIST)
@@ -839,6 +839,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // arithmetic shift per roll.  Strat50's two-argument constructor (threshold in the low byte) must not be given such a word:
     // roll_step passes the decoded threshold explicitly.  Every other instance keeps the table's form (threshold in [7:0]).
     uint2 pk_seat0 = make_uint2(0u, 0u), pk_delta = make_uint2(0u, 0u); // seat 0's strategy (the first owner's); seat 0's xor seat 1's
+    // ... and so does the LDS address of the turn owner's record (round 9): with two seats it changes only where the owner does, by one
+    // subtraction from a per-lane constant (advance2), instead of a multiply-add on the seat number in front of every roll
+    typedef __attribute__((address_space(3))) uint32_t lds_u32; // (the address as the 32-bit number ds_read / ds_write take)
+    auto lds_addr = [&](uint32_t dword) -> uint32_t { return (uint32_t)(uintptr_t)((lds_u32 *)lds + dword); };
+    uint32_t own_rec = 0;
+    // ... and the address of the owner's PCG increment (records of 16 bytes, seat 0's at an even index: the other seat's is an xor away).
+    // `seat` itself is not carried through these instances' roll loop: it is read back from own_rec where a game ends (finish_game).
+    uint64_t own_inc_at = 0;
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) u32x4 global_u4; // (a global load: the address is a number, not a pointer the compiler can trace)
 
     // LDS records are contiguous per (seat, lane): record base = (seat * BLOCK + tid) * NFIELDS, field = immediate
     // offset (one address VGPR per record).  Full records: odd stride (17 dwords), ds_read2/ds_write2 dword pairs, the
@@ -924,6 +934,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             own_thr = (int32_t)L(F_SPX, s);
             own_bits = L(F_SPY, s);
         }
+        if (PK2) {
+            own_rec = lds_addr(__umul24(s, SEAT_STRIDE) + lane_base);
+            own_inc_at = (uint64_t)(uintptr_t)&a.inc[(size_t)seed_slot * K + s];
+        }
         dice = 6;
         turn_score = 0;
         rolls_this_turn = 0;
@@ -936,6 +950,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 
     // ---- finished game -> LDS tallies or one result record (run_tournament.py:375-391) ----
     auto finish_game = [&]() {
+        if (PK2 && max_rounds != 0u) seat = own_rec != lds_addr(lane_base) ? 1u : 0u; // the owner of the game's last turn (a game without rounds has none)
         const bool completed = PK2 ? (final_round != 0u) : (safety == 0u); // two seats: a game ends in its final round or at the round limit
         uint32_t w = 0;
         int32_t best = seat_score(0);
@@ -1104,20 +1119,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // rules collapse (engine.py:453-472, 523-550): the next seat is always the other one; a turn played in the final round
     // is the last of the game; the first score at or above the target starts the final round.  The rules are fk_device.h's
     // advance2_table50 (plain booleans, which the compiler keeps as lane masks here, and one select per register that changes); only
-    // the change of owner stays under the exec mask: the increment load, and seat, strategy and turn registers switched by xor /
-    // constants (round 8).  Neither the trigger seat nor the safety flag is carried: both follow from the state a two-seat game ends
+    // the change of owner stays under the exec mask: the increment load, and strategy and turn registers switched by xor / constants
+    // (round 8); since round 9 the owner is known by the LDS address of its record (own_rec, toggled there by one subtraction) and the
+    // increment's address by an xor, so no seat number is carried and no record address is formed per roll.  Neither the trigger seat nor the safety flag is carried: both follow from the state a two-seat game ends
     // in (seat_turns, finish_game; tests/native/roll_back_end_host_check.hip asserts the two relations on advance2_table50), so the
     // registers `trigger` and `safety` are not touched by these instances after init_game.
     auto advance2 = [&](bool over, int32_t score) __attribute__((always_inline)) {
-        Table2 t{seat, rounds, 0u, final_round, 0u, score_to_beat}; // trigger, safety: not carried (above)
+        Table2 t{own_rec != lds_addr(lane_base) ? 1u : 0u, rounds, 0u, final_round, 0u, score_to_beat}; // trigger, safety: not carried (above)
         const Advance2 adv = advance2_table50(over, score, a.target50, max_rounds, t); // fk_device.h
         rounds = t.rounds, final_round = t.final_round, score_to_beat = t.score_to_beat;
         st = adv.ended ? (uint32_t)ST_ENDED : st;
         if (adv.sw) { // the turn passes (t.seat): the other seat, the other strategy = an xor with the game's difference word, fresh turn
-            seat ^= 1u;
+            own_rec = (lds_addr(lane_base) + lds_addr(lane_base + SEAT_STRIDE)) - own_rec; // the sum of the two records' addresses less this one
             own_thr ^= (int32_t)pk_delta.x;
             own_bits ^= pk_delta.y;
-            const uint4 inc = a.inc[(size_t)seed_slot * 2u + seat]; // the new owner's increment: the one memory request of a turn start
+            own_inc_at ^= 16u;
+            const u32x4 inc = *(global_u4 *)own_inc_at; // the new owner's increment: the one memory request of a turn start
             own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
             own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
             dice = 6u;
@@ -1128,12 +1145,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 
     // ---- one roll of the current turn (engine.py:241-273): record in, roll, score, decide, record out ----
     auto roll_step = [&]() __attribute__((always_inline)) {
-        const bool roll_limit = rolls_this_turn >= 1000u; // ROLL_LIMIT, engine.py:36,242 (raised below, before any store)
+        const uint32_t rolls_before = rolls_this_turn; // ROLL_LIMIT, engine.py:36,242 (raised below, before any store)
         const uint32_t s = seat;
         uint32_t cA, cB, cC, cD, cE, buf0;
         int32_t score;
         uint64_t lo0, hi0;
-        uint2 *const rec = reinterpret_cast<uint2 *>(&L(F_LO0, s)); // LEAN: five aligned pairs
+        uint2 *const rec = PK2 ? reinterpret_cast<uint2 *>((uint32_t *)(lds_u32 *)(uintptr_t)own_rec) : reinterpret_cast<uint2 *>(&L(F_LO0, s)); // LEAN: five aligned pairs
         if (LEAN) {
             const uint2 p0 = rec[0], p1 = rec[1], p2 = rec[2], p3 = rec[3], p4 = rec[4];
             lo0 = (uint64_t)p0.x | ((uint64_t)p0.y << 32);
@@ -1150,14 +1167,21 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         Rng rng{hi0, lo0, own_inc_hi, own_inc_lo, buf0, (cE & CE_HAS_BUF) ? 1u : 0u};
         const uint32_t n = dice;
         bool detour;
-        uint32_t key = roll_counts_fast<3>(rng, n, detour);
+        uint32_t key = roll_key_fast(rng, n, detour); // 4 x the score table's key
         if (detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
             asm volatile("" ::: "memory"); // really re-read it: values forwarded from the loads above would stay live across the whole roll
-            rng.lo = (uint64_t)L(F_LO0, s) | ((uint64_t)L(F_LO1, s) << 32);
-            rng.hi = (uint64_t)L(F_HI0, s) | ((uint64_t)L(F_HI1, s) << 32);
-            rng.buf = L(F_BUF, s);
+            if (PK2) { // (F_LO0 ... F_BUF are the first five dwords of a lean record)
+                const uint32_t *r0 = reinterpret_cast<const uint32_t *>(rec);
+                rng.lo = (uint64_t)r0[0] | ((uint64_t)r0[1] << 32);
+                rng.hi = (uint64_t)r0[2] | ((uint64_t)r0[3] << 32);
+                rng.buf = r0[4];
+            } else {
+                rng.lo = (uint64_t)L(F_LO0, s) | ((uint64_t)L(F_LO1, s) << 32);
+                rng.hi = (uint64_t)L(F_HI0, s) | ((uint64_t)L(F_HI1, s) << 32);
+                rng.buf = L(F_BUF, s);
+            }
             rng.has_buf = (cE & CE_HAS_BUF) ? 1u : 0u;
-            key = roll_counts_sequential<3>(rng, n, nullptr);
+            key = 4u * roll_counts_sequential<3>(rng, n, nullptr);
         }
         rolls_this_turn += 1u;
         int32_t dthr = PK2 ? ((int32_t)own_bits >> 16) : (int32_t)(int8_t)(own_bits & 0xffu);
@@ -1165,14 +1189,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const Strat50 sp{own_thr, (own_bits & (0xffu | MIXED)) | (a.uflags & (0xff00u & ~MIXED)), dthr};
         // score, discards, counters, hot dice, decision, bank, guard bands (turn_score, score: / 50): fk_device.h's pure back end
         uint32_t entry;
-        const uint32_t choice = discard_lookup50(a.score_lut, a.discard_lut, key, (int32_t)n, turn_score, sp, entry);
+        const uint32_t choice = discard_lookup50w(a.score_lut, reinterpret_cast<const uint32_t *>(a.discard_lut + DISCARD_LUT_KEYS), key, (int32_t)n, turn_score, sp, entry);
         RollRegs rg{cA, cB, cC, cD, cE, score, dice, turn_score};
-        bool overflow;
-        const bool over = roll_back_end50<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
+        bool overflow; // (not read here: roll_guards50 below restates it)
+        const bool over = roll_back_end50w<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
         cA = rg.cA, cB = rg.cB, cC = rg.cC, cD = rg.cD, cE = rg.cE, score = rg.score, dice = rg.dice, turn_score = rg.turn_score;
-        // one rare exit for all error conditions: the roll limit, then the u16 guard bands
-        if (roll_limit | overflow) {
-            raise(roll_limit ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
+        // one rare exit for all error conditions: the roll limit, then the u16 guard bands (fk_device.h: roll_guards50; `overflow` is its second half)
+        const uint32_t guard = roll_guards50(rolls_before, rg);
+        if (guard != RG_NONE) {
+            raise(guard == RG_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
             return;
         }
         cE = (cE & ~CE_HAS_BUF) | (rng.has_buf << CE_HAS_BUF_SHIFT); // has_buf is 0 / 1 (fk_device.h): a shift, no compare and select
@@ -1264,10 +1289,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             handover(waiting);
             continue;
         }
+        bool playing = st == ST_ACTIVE;
         do {
-            if (st == ST_ACTIVE) roll_step();
+            if (playing) roll_step();
+            playing = st == ST_ACTIVE;
             waiting = __ballot(st == ST_ENDED);
-            active = __ballot(st == ST_ACTIVE);
+            active = __ballot(playing);
         } while (active && !handover_due(waiting, active));
     }
 
@@ -1824,9 +1851,12 @@ __global__ void fk_score_lut_kernel(uint32_t *lut) { // the score table of fk_de
     if (key < SCORE_LUT_KEYS) lut[key] = score_lut_entry32(key);
 }
 
-__global__ void fk_discard_lut_kernel(uint8_t *lut) { // the discard table of fk_device.h
+__global__ void fk_discard_lut_kernel(uint8_t *lut) { // the discard table of fk_device.h: 2^16 bytes, then the 2^16 wide entries
     const uint32_t key = blockIdx.x * blockDim.x + threadIdx.x;
-    if (key < DISCARD_LUT_KEYS) lut[key] = discard_lut_entry(key);
+    if (key < DISCARD_LUT_KEYS) {
+        lut[key] = discard_lut_entry(key);
+        reinterpret_cast<uint32_t *>(lut + DISCARD_LUT_KEYS)[key] = discard_lut_entry32(key);
+    }
 }
 
 __global__ void fk_dbg_score_kernel(int64_t n, const uint8_t *faces, const int32_t *len, const int32_t *pre,
