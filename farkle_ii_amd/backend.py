@@ -92,7 +92,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -110,7 +110,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts"]
 _libs: dict = {}
 
 
@@ -453,6 +453,55 @@ class Engine:
                 "rare_events": {"strategy_second": s_second, "game_second": g_second, "events": n,
                                 "event_head": head[:n].copy() if want_events else np.zeros((0, 4), np.uint32),
                                 "event_seats": seats[:n].copy() if want_events else np.zeros((0, max(int(k), 1)), np.uint16)}}
+
+    def tournament_seat_counts(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
+                               shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                               overrides: np.ndarray | None = None, strategy_ids=None, want_mirrored: bool = False,
+                               pair_capacity: int = 65_536, retry: bool = True) -> dict:
+        """``tournament`` (the same tally) + the seat-analysis stage's counts of the range (``fk_tournament_run_seat_counts``):
+        ``seat_counts`` int64 ``[n_batches][S][k][3]`` = wins, completed exposures, safety-limit exposures per batch, table index and
+        seat.  ``want_mirrored`` (k = 2, unique ``strategy_ids``, ``shuffle_begin`` on a batch boundary): ``pair_index`` uint16
+        ``[n][2]`` (table indices, the lower ID first) and ``pair_sums`` int64 ``[n][6]`` (``seat_analysis.PAIR_COLUMNS``) in
+        ascending ID order.  A pair list that is too small is an ``FK_ERR_ARG`` carrying the size it needs: the range is played
+        once more with that room unless ``retry`` is off."""
+        from .seat_analysis import id_ranks
+
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        S = len(table)
+        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
+        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
+        n_batches = (n_sh + spb - 1) // spb
+        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        rank = None
+        if want_mirrored:
+            if strategy_ids is None:
+                raise ValueError("mirrored pairs need strategy_ids")
+            rank = id_ranks(strategy_ids, S)
+        capacity = max(int(pair_capacity), 0) if want_mirrored else 0
+        attempts = 0
+        while True:
+            attempts += 1
+            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            counts = np.zeros((max(n_batches, 1), S, max(int(k), 1), 3), dtype=np.int64)
+            n_pairs = C.c_int64(0)
+            index = np.zeros((max(capacity, 1), 2), dtype=np.uint16) if want_mirrored else None
+            sums = np.zeros((max(capacity, 1), 6), dtype=np.int64) if want_mirrored else None
+            rc = self._lib.fk_tournament_run_seat_counts(
+                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
+                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
+                _p(tally), _p(counts), _p(rank), C.c_int64(capacity), C.byref(n_pairs) if want_mirrored else None, _p(index), _p(sums))
+            if rc == FK_ERR_ARG and want_mirrored and n_pairs.value > capacity and retry and attempts == 1:
+                capacity = int(n_pairs.value)
+                continue
+            try:
+                self._check(rc)
+            except FarkleHipError as err:  # (what the list needs travels with the error)
+                err.pairs_needed = int(n_pairs.value)
+                raise
+            break
+        n = int(n_pairs.value)
+        return {"tally": tally[:n_batches], "seat_counts": counts[:n_batches], "attempts": attempts,
+                "pair_index": index[:n].copy() if want_mirrored else None, "pair_sums": sums[:n].copy() if want_mirrored else None}
 
     def tournament_columns(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, strategy_ids,
                            shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,

@@ -57,6 +57,13 @@ def build_parser() -> argparse.ArgumentParser:
                           "analysis.rare_event_write_details, rare_events_details.parquet, from the device's flagged-game list, without "
                           "rows.  Serves analysis.rare_event_margin_quantile / rare_event_target_rate: a histograms-only pass over "
                           "every player count resolves the thresholds, then the same shuffle ranges are replayed to collect the games")
+    run.add_argument("--seat-analysis", action="store_true",
+                     help="Write the seat-analysis stage's tables from device counts, without rows: per player count "
+                          "analysis/03_metrics/by_k/<k>p/seat_batch_counts.parquet, seat_effects.parquet and seat_population_effects.parquet, "
+                          "after the last player count across_k/seat_effects_standardized_across_k.parquet (k_aggregation) and "
+                          "diagnostics/seat_exposure_mixture.parquet, seat_selfplay_p1.parquet and seat_mirrored_games.parquet (the "
+                          "mirrored-game pairs of k = 2).  Runs without rows and the other analysis options.  Not resumable: an interrupted "
+                          "run asks for --force")
     run.add_argument("--performance-bootstrap", action="store_true",
                      help="Write the performance stage's joint deterministic-batch bootstrap from the device: per player count "
                           "analysis/03_metrics/by_k/<k>p/performance_batch_matrix.npy (wins / exposures per batch and strategy), after the "
@@ -155,6 +162,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.rare_events = True
     if args.performance_bootstrap:
         cfg.sim.performance_bootstrap = True
+    if args.seat_analysis:
+        cfg.sim.seat_analysis = True
     if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
         cfg.sim.rng_lag_sums = cfg.sim.rng_matchup_lags = True
     _maybe_init_distributed()

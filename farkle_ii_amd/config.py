@@ -66,6 +66,7 @@ class SimConfig:
     rng_matchup_lags: bool = False  # this engine's option: the RNG diagnostics' matchup family + group selection (rng_matchups.py)
     game_stats: bool = False  # this engine's option: the game-stats stage's per-k tables and rare-event summary without rows (game_stats.py)
     rare_events: bool = False  # with game_stats: the per-game rows of rare_events.parquet / rare_events_details.parquet and the quantile thresholds (rare_events.py)
+    seat_analysis: bool = False  # this engine's option: the seat-analysis stage's count tables, seat effects and mirrored pairs without rows (seat_analysis.py)
     performance_bootstrap: bool = False  # this engine's option: the performance stage's batch matrices + joint batch bootstrap (performance_bootstrap.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
@@ -237,6 +238,34 @@ class AppConfig:
     def performance_control_contrasts_path(self) -> Path:
         """config.py:1006-1009."""
         return self.metrics_stage_dir() / "across_k" / "performance_control_contrasts.parquet"
+
+    def seat_batch_counts_path(self, n: int) -> Path:
+        """config.py:1098-1101: ``by_k/<k>p/seat_batch_counts.parquet``."""
+        return self.metrics_stage_dir() / "by_k" / f"{n}p" / "seat_batch_counts.parquet"
+
+    def seat_effects_by_k_path(self, n: int) -> Path:
+        """config.py:1103-1106."""
+        return self.metrics_stage_dir() / "by_k" / f"{n}p" / "seat_effects.parquet"
+
+    def seat_population_by_k_path(self, n: int) -> Path:
+        """config.py:1108-1111."""
+        return self.metrics_stage_dir() / "by_k" / f"{n}p" / "seat_population_effects.parquet"
+
+    def seat_standardized_across_k_path(self) -> Path:
+        """config.py:1113-1116."""
+        return self.metrics_stage_dir() / "across_k" / "seat_effects_standardized_across_k.parquet"
+
+    def seat_exposure_mixture_diagnostic_path(self) -> Path:
+        """config.py:1118-1121."""
+        return self.metrics_stage_dir() / "diagnostics" / "seat_exposure_mixture.parquet"
+
+    def seat_selfplay_diagnostic_path(self) -> Path:
+        """config.py:1123-1126."""
+        return self.metrics_stage_dir() / "diagnostics" / "seat_selfplay_p1.parquet"
+
+    def seat_mirrored_diagnostic_path(self) -> Path:
+        """config.py:1128-1131."""
+        return self.metrics_stage_dir() / "diagnostics" / "seat_mirrored_games.parquet"
 
     def root_stability_settings(self) -> dict:
         """What the two-root stability stage reads beside ``screening``: ``robustness.delta_seed_stability`` (config.py:201, default

@@ -13,6 +13,7 @@
 #include "fk_rare_events.h"   // device side: rare-event game list (ordered stream compaction), second-highest-score histograms
 #include "fk_bootstrap.h"     // device side: performance stage's joint batch bootstrap (draws, integer product, ranks, contrasts)
 #include "fk_root_stability.h" // device side: two-root stability stage's bootstrap families (rates of both roots, maxima, top-N membership)
+#include "fk_seat_analysis.h"  // device side: seat-analysis stage (per-seat counts from rec0, mirrored-pair sort-and-segment reduce)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -98,6 +99,16 @@ struct RareReq {
     uint16_t *event_seats; // [event_capacity][k]
 };
 
+// fk_tournament_run_seat_counts: host pointers of the request
+struct SeatReq {
+    int64_t *counts;          // [n_batches][S][k][3]
+    const uint16_t *id_rank;  // null: no mirrored pairs
+    int64_t pair_capacity;
+    int64_t *pair_count;      // pairs the call produced (also when they did not fit)
+    uint16_t *pair_index;     // [pair_capacity][2]
+    int64_t *pair_sums;       // [pair_capacity][6]
+};
+
 struct fk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -165,6 +176,8 @@ struct fk_ctx {
     const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
     const RareReq *rare = nullptr;        // ... and of fk_tournament_run_rare_events (with gstats)
     DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
+    const SeatReq *seatreq = nullptr;    // the request of the running fk_tournament_run_seat_counts call
+    DevBuf sa_counts, sa[16];            // its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -1357,6 +1370,8 @@ void fk_destroy(fk_ctx *c) {
     for (DevBuf *b : {&c->r_sec, &c->r_out, &c->r_blk, &c->r_base, &c->r_head, &c->r_seats}) release(*b);
     for (DevBuf &b : c->mr) release(b);
     for (DevBuf &b : c->boot) release(b);
+    release(c->sa_counts);
+    for (DevBuf &b : c->sa) release(b);
     for (DevBuf &b : c->rootb) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
@@ -1751,6 +1766,39 @@ int fk_tournament_run_rare_events(fk_ctx *c, const fk_strategy *strategies, int3
     return rc;
 }
 
+int fk_tournament_run_seat_counts(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, int64_t *seat_counts,
+                                  const uint16_t *id_rank, int64_t pair_capacity, int64_t *pair_count, uint16_t *pair_index,
+                                  int64_t *pair_sums) {
+    if (!c) return FK_ERR_ARG;
+    if (!seat_counts) return fail(c, FK_ERR_ARG, "seat_counts is required");
+    if (k < 1 || k > (int32_t)fksa::MAX_K) return fail(c, FK_ERR_ARG, "seat counts are made for 1 .. %u seats, got %d", fksa::MAX_K, (int)k);
+    const bool mirrored = id_rank || pair_count || pair_index || pair_sums || pair_capacity != 0;
+    if (mirrored) {
+        if (k != 2) return fail(c, FK_ERR_ARG, "mirrored pairs exist at k = 2 only: the pair arguments must be null / 0 at k = %d", (int)k);
+        if (!id_rank || !pair_count) return fail(c, FK_ERR_ARG, "mirrored pairs need id_rank and pair_count");
+        if (pair_capacity < 0 || (pair_capacity > 0 && (!pair_index || !pair_sums)))
+            return fail(c, FK_ERR_ARG, "pair_capacity must be >= 0, with pair_index and pair_sums when > 0");
+        if (shuffles_per_batch == 0 || shuffle_begin % shuffles_per_batch != 0)
+            return fail(c, FK_ERR_ARG, "mirrored pairs: shuffle_begin must be a multiple of shuffles_per_batch (a call never starts inside a batch)");
+        if (S >= 2 && shuffle_end > shuffle_begin && (shuffle_end - shuffle_begin) > (uint64_t)0x7ffffffe / (uint64_t)(S / 2))
+            return fail(c, FK_ERR_ARG, "mirrored pairs: the range may hold at most 2^31 - 2 games (one sort, 32-bit positions, one end entry); split it at a batch boundary");
+        std::vector<uint8_t> seen((size_t)std::max(S, 0), 0);
+        for (int32_t i = 0; i < S; ++i) {
+            if (id_rank[i] >= (uint32_t)S || seen[id_rank[i]]) return fail(c, FK_ERR_ARG, "id_rank must be a permutation of 0 .. S - 1 (strategy IDs are unique)");
+            seen[id_rank[i]] = 1;
+        }
+        *pair_count = 0;
+    }
+    const SeatReq req{seat_counts, mirrored ? id_rank : nullptr, pair_capacity, pair_count, pair_index, pair_sums};
+    c->seatreq = &req;
+    const int rc = tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov,
+                                   n_ov, tally, nullptr, nullptr, nullptr, nullptr);
+    c->seatreq = nullptr;
+    return rc;
+}
+
 int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
                            uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
                            const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
@@ -1942,6 +1990,38 @@ int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *diges
     HIPCHK(c, hipStreamSynchronize(st));
     return FK_OK;
 }
+// The pair reduce of fk_tournament_run_seat_counts over the call's n mirror records (c->sa[1] keys, c->sa[3] payloads), on the
+// context's stream with no host round trip: sa[13] = pair ranks [capacity][2], sa[14] = pair sums [capacity][6], sa[15] = the pair count.
+static int mirror_reduce(fk_ctx *c, uint32_t n, uint64_t capacity) {
+    int rc = 0;
+    const size_t n1 = (size_t)n + 1;
+    // 5 fr | 6 e_fr | 7 sh | 8 e_sh | 9 ph | 10 e_ph | 11 seg_start | 12 pair_start + seg_diff
+    const size_t sizes[] = {8 * n1, 8 * n1, 8 * n1, 8 * n1, 4 * n1, 4 * n1, 4 * n1, 4 * n1 + 4 * n1};
+    for (int i = 0; i < 8; ++i)
+        if ((rc = ensure(c, c->sa[5 + i], sizes[i]))) return rc;
+    if ((rc = ensure(c, c->sa[13], std::max<size_t>((size_t)capacity, 1) * 4))) return rc;
+    if ((rc = ensure(c, c->sa[14], std::max<size_t>((size_t)capacity, 1) * fksa::PAIR_COLS * 8))) return rc;
+    if ((rc = ensure(c, c->sa[15], 8))) return rc;
+    auto U64 = [&](int i) { return static_cast<unsigned long long *>(c->sa[i].p); };
+    auto U32 = [&](int i) { return static_cast<uint32_t *>(c->sa[i].p); };
+    const hipStream_t st = c->stream;
+    const dim3 bn((unsigned)((n1 + 255u) / 256u)), b256(256);
+    FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(1), U64(2), U32(3), U32(4), (int)n, 0, 64, st);
+    hipLaunchKernelGGL(fksa::fk_mirror_flags_kernel, bn, b256, 0, st, U64(2), U32(4), n, U64(5), U64(7), U32(9));
+    HIPCHK(c, hipGetLastError());
+    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U64(5), U64(6), (int)n1, st);
+    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U64(7), U64(8), (int)n1, st);
+    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U32(9), U32(10), (int)n1, st);
+    uint32_t *pair_start = U32(12);
+    int32_t *seg_diff = reinterpret_cast<int32_t *>(U32(12) + n1);
+    HIPCHK(c, hipMemsetAsync(seg_diff, 0, 4 * n1, st));
+    hipLaunchKernelGGL(fksa::fk_mirror_starts_kernel, bn, b256, 0, st, U64(7), U64(8), U32(9), U32(10), n, U32(11), pair_start);
+    hipLaunchKernelGGL(fksa::fk_mirror_segment_kernel, bn, b256, 0, st, U64(2), U32(4), n, U64(6), U64(8), U32(11), seg_diff);
+    hipLaunchKernelGGL(fksa::fk_mirror_pair_sum_kernel, bn, b256, 0, st, U64(2), U64(6), U64(8), U32(10), n, U32(11), pair_start, seg_diff,
+                       (unsigned long long)capacity, static_cast<uint16_t *>(c->sa[13].p), static_cast<long long *>(c->sa[14].p), U64(15));
+    HIPCHK(c, hipGetLastError());
+    return FK_OK;
+}
 #undef FKM_CUB
 
 static int tournament_call(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
@@ -2049,6 +2129,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     const GameStatsReq *gst = c->gstats; // fk_tournament_run_game_stats (null otherwise)
     const RareReq *rare = gst ? c->rare : nullptr; // fk_tournament_run_rare_events
+    const SeatReq *sq = c->seatreq; // fk_tournament_run_seat_counts
     const bool want_state = rows != nullptr || seat_stats != nullptr || gst != nullptr;
     const bool want_recs = !plan.lds_tally || want_state || lag != nullptr;
     const size_t stats_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_SEAT_STAT_COLS;
@@ -2056,6 +2137,19 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         rc = ensure(c, c->stats, stats_bytes);
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(c->stats.p, 0, stats_bytes, c->stream));
+    }
+    const size_t sq_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * (size_t)k * fksa::COUNT_COLS;
+    const uint32_t sq_n = sq && sq->id_rank ? (uint32_t)(n_sh_total * gps) : 0u; // mirror records of the call (the entry bounds the range)
+    if (sq) {
+        if ((rc = ensure(c, c->sa_counts, sq_bytes))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->sa_counts.p, 0, sq_bytes, c->stream));
+    }
+    if (sq_n) { // 0 id ranks | 1, 2 keys | 3, 4 payloads (two sort buffers each)
+        const size_t n = sq_n;
+        const size_t sizes[5] = {2ul * (size_t)S, 8ul * n, 8ul * n, 4ul * n, 4ul * n};
+        for (int i = 0; i < 5; ++i)
+            if ((rc = ensure(c, c->sa[i], sizes[i]))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->sa[0].p, sq->id_rank, 2ul * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
     const size_t ratio_bytes = sizeof(double) * (size_t)n_batches * (size_t)S * FK_SEAT_RATIO_COLS;
     if (seat_ratios) { // running float64 sums, carried from chunk to chunk on the device (all-zero bits = 0.0)
@@ -2265,7 +2359,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             }
         }
         if (wait_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, c->sets[c->cur].ready, 0));
-        rc = launch_play_stage(c, sa, pa, plan, want_state, want_recs, want_recs);
+        rc = launch_play_stage(c, sa, pa, plan, want_state, want_recs || sq != nullptr, want_recs);
         if (rc) return rc;
         // The last chunk of a call without rows: its error record travels with the tally, behind the post-passes — one host
         // round trip per call instead of two (the post-passes only read; on an error their output is discarded).
@@ -2285,7 +2379,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             hipLaunchKernelGGL(fk_invert_sched_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
                                static_cast<const uint32_t *>(CSET(c).order.p), n_games, static_cast<uint32_t *>(c->inv.p));
         }
-        if (seat_stats || gst) {
+        if (seat_stats || gst || sq) {
             rc = ensure(c, CSET(c).draws, (size_t)perm_blocks * S * slots * 2); // the draws buffer is free again: inverse permutations
             if (rc) return rc;
             const uint32_t cells = perm_blocks * (uint32_t)S * slots;
@@ -2333,6 +2427,22 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                 }
                 HIPCHK(c, hipGetLastError());
             }
+        }
+        if (sq) { // seat counts from rec0 through the inverse permutation; at k = 2 the chunk's mirror records
+            const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
+            const uint32_t nb = (uint32_t)((done + n_sh - 1) / shuffles_per_batch) - first_batch + 1u;
+            const uint32_t s_blocks = ((uint32_t)S + fksa::COUNT_BLOCK - 1u) / fksa::COUNT_BLOCK;
+            const uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(shuffles_per_batch, n_sh) / 8, (4096u + nb * s_blocks - 1u) / (nb * s_blocks)));
+            hipLaunchKernelGGL(fksa::fk_seat_counts_kernel, dim3(s_blocks, nb * ppb), dim3(fksa::COUNT_BLOCK),
+                               (size_t)k * fksa::COUNT_COLS * fksa::COUNT_BLOCK * 4, c->stream, static_cast<const uint32_t *>(c->rec0.p),
+                               static_cast<const uint16_t *>(CSET(c).draws.p), slots, (uint32_t)S, (uint32_t)k, gps, n_sh, (uint32_t)done,
+                               shuffles_per_batch, ppb, first_batch, static_cast<long long *>(c->sa_counts.p));
+            if (sq_n)
+                hipLaunchKernelGGL(fksa::fk_mirror_record_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
+                                   static_cast<const uint32_t *>(c->rec0.p), static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)S, gps,
+                                   n_games, (uint32_t)done, shuffles_per_batch, static_cast<const uint16_t *>(c->sa[0].p), (uint32_t)(done * gps),
+                                   static_cast<unsigned long long *>(c->sa[1].p), static_cast<uint32_t *>(c->sa[3].p));
+            HIPCHK(c, hipGetLastError());
         }
         if (seat_stats) {
             const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
@@ -2462,6 +2572,10 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     } else if (rows) {
         HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     }
+    if (sq_n) {
+        rc = mirror_reduce(c, sq_n, (uint64_t)std::max<int64_t>(sq->pair_capacity, 0));
+        if (rc) return rc;
+    }
     const uint32_t n_rows = (uint32_t)(n_batches * (uint64_t)S);
     hipLaunchKernelGGL(fk_finalize_tally, dim3((n_rows + 255u) / 256u), dim3(256), 0, c->stream,
                        static_cast<unsigned long long *>(c->tally.p), n_rows, (uint32_t)S, shuffles_per_batch, n_sh_total, 1u);
@@ -2497,6 +2611,9 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     if (seat_stats) HIPCHK(c, hipMemcpyAsync(seat_stats, c->stats.p, stats_bytes, hipMemcpyDeviceToHost, c->stream));
     if (seat_ratios) HIPCHK(c, hipMemcpyAsync(seat_ratios, c->ratios.p, ratio_bytes, hipMemcpyDeviceToHost, c->stream));
+    int64_t sq_pairs = 0;
+    if (sq) HIPCHK(c, hipMemcpyAsync(sq->counts, c->sa_counts.p, sq_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sq_n) HIPCHK(c, hipMemcpyAsync(&sq_pairs, c->sa[15].p, 8, hipMemcpyDeviceToHost, c->stream));
     int64_t g_spilled = 0;
     if (gst) {
         const uint8_t *o = static_cast<const uint8_t *>(c->g_out.p);
@@ -2547,6 +2664,19 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         if (r_events) {
             HIPCHK(c, hipMemcpy(rare->event_head, c->r_head.p, (size_t)r_events * 16, hipMemcpyDeviceToHost));
             HIPCHK(c, hipMemcpy(rare->event_seats, c->r_seats.p, (size_t)r_events * (size_t)k * 2, hipMemcpyDeviceToHost));
+        }
+    }
+    if (sq_n) { // the pair rows, in ascending (rank a, rank b); ranks -> table indices
+        *sq->pair_count = sq_pairs;
+        if (sq_pairs > sq->pair_capacity)
+            return fail(c, FK_ERR_ARG, "mirrored pairs: the pair list needs %lld rows, pair_capacity is %lld", (long long)sq_pairs,
+                        (long long)sq->pair_capacity);
+        if (sq_pairs) {
+            HIPCHK(c, hipMemcpy(sq->pair_index, c->sa[13].p, (size_t)sq_pairs * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(sq->pair_sums, c->sa[14].p, (size_t)sq_pairs * fksa::PAIR_COLS * 8, hipMemcpyDeviceToHost));
+            std::vector<uint16_t> index_of((size_t)S);
+            for (int32_t i = 0; i < S; ++i) index_of[sq->id_rank[i]] = (uint16_t)i;
+            for (int64_t i = 0; i < 2 * sq_pairs; ++i) sq->pair_index[i] = index_of[sq->pair_index[i]];
         }
     }
     HIPCHK(c, hipEventElapsedTime(&c->timing.total_ms, t0, t1));

@@ -562,7 +562,8 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                    all_player_dir: Path | None = None, sidecars: "_Sidecars | None" = None,
                    rng_lags: Sequence[int] | None = None, defer_final_checkpoint: bool = False, packed_table: np.ndarray | None = None,
                    defer_tail: list | None = None, rng_matchups: int | None = None, game_stats: bool = False,
-                   performance_bootstrap: bool = False, rare_events: "Mapping[str, Any] | None" = None) -> dict:
+                   performance_bootstrap: bool = False, rare_events: "Mapping[str, Any] | None" = None,
+                   seat_analysis: bool = False) -> dict:
     """Play every deterministic batch not yet owned by the checkpoint and persist the aggregates.  ``defer_final_checkpoint``: the final
     checkpoint's file write may still be in flight on return — the caller joins ``result["checkpoint_written"]`` before reading the file.  ``rng_lags``: also accumulate the lag
     sufficient statistics of the RNG diagnostics' strategy family over the WHOLE shuffle range (``fk_tournament_run_lags``; launch
@@ -575,7 +576,10 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
     (performance_bootstrap.BatchMatrix).  ``rare_events`` (needs ``game_stats``; ``target_score``, ``thresholds``, ``want_events``):
     the game-stats launches become ``fk_tournament_run_rare_events`` — ``result["rare_events"]`` on rank 0: the second-score
     histograms of the whole range with the game statistics (rare_events.RareEventSummary) and, with ``want_events``, the flagged
-    games of the whole range in (shuffle, game) order (launch groups and ranks are contiguous ranges that concatenate in order)."""
+    games of the whole range in (shuffle, game) order (launch groups and ranks are contiguous ranges that concatenate in order).
+    ``seat_analysis``: the launches become ``fk_tournament_run_seat_counts`` — ``result["seat_analysis"]`` on rank 0: the per-batch seat
+    counts of the whole range and, at k = 2, its mirrored pairs (seat_analysis.SeatCounts, MirroredPairs; every rank plays whole
+    batches, so both merge in any order)."""
     rank, world = _rank_world()
     _trace(f"{n_players}p run_tournament")
     eng = get_engine()
@@ -691,6 +695,15 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
         cfg.game_stats_margin_thresholds()  # (validated before anything plays)
     elif rare_events is not None:
         raise ValueError("the rare-event list rides on the game-stats launches: rare_events needs game_stats")
+    seat_total = None   # [seat_analysis.SeatCounts, MirroredPairs | None] of the range so far (rank 0)
+    if seat_analysis:
+        if done_batches:  # the counts are held in memory until the run's end: a partial replay cannot rebuild them
+            raise ValueError("seat analysis needs every shuffle of the run; this checkpoint already owns batches: use --force")
+        if row_dir is not None or rng_lags or game_stats or want_stats:
+            raise ValueError("--seat-analysis runs without rows and the other analysis options (one post-pass per launch): run them separately")
+        from .seat_analysis import id_ranks
+
+        id_ranks(ids, S)  # (duplicate strategy IDs are refused before anything plays)
     rare_total = None   # rare_events.RareEventSummary of the range so far (rank 0)
     rare_parts: list = []  # (head, seats) per call range, heads rebased to the run's first shuffle (rank 0)
     target = oracle_game_profile.default_target_score if oracle_game_profile else 10_000
@@ -769,7 +782,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
 
     def finish(b0, b1, lo, hi, j, local, local_stats, local_ratios, row_records, fragments, res, shard_job, per_batch) -> None:
         """What follows a launch group's engine call: its shards' manifest lines, the reduction over ranks, chunk files, checkpoint."""
-        nonlocal total, games_done, lag_total, gs_total, rare_total, batches_since_save, last_save
+        nonlocal total, games_done, lag_total, gs_total, rare_total, seat_total, batches_since_save, last_save
         if shard_job is not None:
             row_records = shard_job.result()
             if callable(row_records):  # the per-shard manifest lines: built here, not on the shard thread (its host threads would idle)
@@ -792,6 +805,22 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                 for piece in parts:
                     if piece is not None:
                         gs_total = piece if gs_total is None else gs_total.merge(piece)
+        if seat_analysis:  # whole batches per rank: counts and pair sums add in any order
+            from .seat_analysis import MirroredPairs, SeatCounts
+
+            part = None
+            if res is not None and hi > lo:
+                part = (SeatCounts.from_engine(res, k, lo // spb), MirroredPairs.from_engine(res, ids) if k == 2 else None)
+            parts = gather_objects(part, dst=0) if world > 1 else [part]
+            if rank == 0:
+                for piece in parts:
+                    if piece is None:
+                        continue
+                    if seat_total is None:
+                        seat_total = list(piece)
+                    else:
+                        seat_total[0] = seat_total[0].merge(piece[0])
+                        seat_total[1] = seat_total[1].merge(piece[1]) if k == 2 else None
         if rare_events is not None:  # ranks hold contiguous whole batches in rank order: histograms add, events concatenate
             from .rare_events import RareEventSummary, concat_events
 
@@ -913,6 +942,10 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
         elif rng_matchups:
             res = eng.tournament_matchups(table, k, cfg.sim.seed, lo, hi, rng_lags, np.asarray(ids, dtype=np.int32), rng_matchups,
                                           shuffles_per_batch=batch_arg, target_score=target, max_rounds=max_rounds, overrides=ov)
+        elif seat_analysis:
+            res = eng.tournament_seat_counts(table, k, cfg.sim.seed, lo, hi, shuffles_per_batch=spb, target_score=target,
+                                             max_rounds=max_rounds, overrides=ov, strategy_ids=np.asarray(ids, dtype=np.int32),
+                                             want_mirrored=k == 2)
         elif game_stats and rare_events is not None:
             res = eng.tournament_rare_events(table, k, cfg.sim.seed, lo, hi, shuffles_per_batch=batch_arg, target_score=target,
                                              max_rounds=max_rounds, overrides=ov, rare_target_score=rare_target,
@@ -985,7 +1018,7 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
           lo, hi = shard_shuffle_range(b0 * spb, min(b1 * spb, plan.required_shuffles), rank, world, batch_size=spb)
           # Per-batch tallies are only needed for the metric chunk files; without them the group is one tally, which the
           # engine keeps in LDS when the table is small.
-          per_batch = metric_chunk_dir is not None or want_stats
+          per_batch = metric_chunk_dir is not None or want_stats or seat_analysis  # (the seat counts are per batch)
           g: dict[str, Any] = dict(
               index=n_groups + (1 if awaiting_post is not None else 0), b0=b0, b1=b1, lo=lo, hi=hi, j=j, per_batch=per_batch,
               local=np.zeros((b1 - b0 if per_batch else 1, S, 26), dtype=np.int64),
@@ -1128,6 +1161,8 @@ def run_tournament(*, cfg: AppConfig, n_players: int, strategies: list[Threshold
                     sidecars.write("shard_manifest", manifest)
         barrier()
         result.update(tally=total, games=games_done, seconds=time.perf_counter() - t_start, lag_summary=lag_total, game_stats=gs_total)
+        if seat_analysis and rank == 0 and seat_total is not None:
+            result["seat_analysis"] = {"counts": seat_total[0], "pairs": seat_total[1]}
         if rare_events is not None and rank == 0 and rare_total is not None:
             from .rare_events import concat_events
 
@@ -1179,6 +1214,9 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if cfg.sim.game_stats and not cfg.game_stats_sums_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.game_stats_sums_path(n).name}: --game-stats needs every game of "
                              "the run; use --force to replay it with the game statistics")
+        if cfg.sim.seat_analysis and not cfg.seat_batch_counts_path(n).exists():
+            raise ValueError(f"{n}p is already complete without {cfg.seat_batch_counts_path(n).name}: --seat-analysis needs every game of "
+                             "the run; use --force to replay it with the seat counts")
         if cfg.sim.performance_bootstrap and not cfg.performance_batch_matrix_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.performance_batch_matrix_path(n).name}: --performance-bootstrap needs "
                              "the statistics of every deterministic batch; use --force to replay it")
@@ -1204,7 +1242,9 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
             for path in (ckpt_path, n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), simulation_done_path(cfg, n),
                          cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n), cfg.game_stats_path(n),
                          cfg.game_stats_sums_path(n), cfg.performance_batch_matrix_path(n), cfg.performance_bootstrap_path(),
-                         cfg.performance_control_contrasts_path()):
+                         cfg.performance_control_contrasts_path(), cfg.seat_batch_counts_path(n), cfg.seat_effects_by_k_path(n),
+                         cfg.seat_population_by_k_path(n), cfg.seat_standardized_across_k_path(), cfg.seat_exposure_mixture_diagnostic_path(),
+                         cfg.seat_selfplay_diagnostic_path(), *((cfg.seat_mirrored_diagnostic_path(),) if n == 2 else ())):
                 path.unlink(missing_ok=True)
                 path.with_name(path.name + ".sidecar.json").unlink(missing_ok=True)
             for d in (row_dir, metric_chunk_dir, all_player_dir):
@@ -1256,7 +1296,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
                             packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
                             rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats,
-                            performance_bootstrap=cfg.sim.performance_bootstrap, rare_events=_rare_event_plan(cfg))
+                            performance_bootstrap=cfg.sim.performance_bootstrap, rare_events=_rare_event_plan(cfg),
+                            seat_analysis=cfg.sim.seat_analysis)
     finally:
         if published is not None:
             published.result()  # the inputs are on disk (or their error is raised) before the summaries and the stamp name them
@@ -1353,6 +1394,45 @@ def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrate
         cfg.game_stats_rare_summary_path().unlink(missing_ok=True)
     else:
         _write_parquet_atomic(rare, cfg.game_stats_rare_summary_path())
+
+
+def _publish_seat_analysis(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], result: dict) -> None:
+    """``by_k/<n>p/seat_batch_counts.parquet``, ``seat_effects.parquet`` and ``seat_population_effects.parquet``; at two players the
+    mirrored-game diagnostic (it reads that player count alone); and once every player count of the run has its files, the
+    standardized effects, the exposure mixture and the self-play diagnostic across them — and an empty mirrored diagnostic when the
+    run has no two-player count, as the reference writes one."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    from . import seat_analysis as sa
+
+    ids = np.asarray([int(s.strategy_id) for s in strategies], dtype=np.int64)
+    root = int(cfg.sim.seed)
+    counts = result["seat_analysis"]["counts"]
+    settings = cfg.root_stability_settings()
+    counts_list, _ = _filter_player_counts(list(cfg.sim.n_players_list), len(ids))
+    ks = sorted({int(v) for v in counts_list} | {int(n)})
+    weights = sa.declared_weights(ks, settings["k_aggregation_method"], settings["declared_k_weights"])  # (refused before anything is written)
+    for path in (cfg.seat_batch_counts_path(n), cfg.seat_standardized_across_k_path(), cfg.seat_mirrored_diagnostic_path()):
+        path.parent.mkdir(parents=True, exist_ok=True)
+    by_k, population = sa.within_k_frames(counts, ids, root)
+    _write_parquet_atomic(sa.batch_counts_table(counts, ids, root), cfg.seat_batch_counts_path(n))
+    _write_parquet_atomic(by_k, cfg.seat_effects_by_k_path(n))
+    _write_parquet_atomic(population, cfg.seat_population_by_k_path(n))
+    if n == 2:
+        _write_parquet_atomic(sa.mirrored_frame(result["seat_analysis"]["pairs"], root), cfg.seat_mirrored_diagnostic_path())
+    if not all(cfg.seat_effects_by_k_path(v).exists() and cfg.seat_population_by_k_path(v).exists() for v in ks):
+        return
+    frames = {v: pq.read_table(cfg.seat_effects_by_k_path(v)) for v in ks}
+    populations = {v: pq.read_table(cfg.seat_population_by_k_path(v)) for v in ks}
+    if any(t.num_rows and set(t.column("root_seed").to_pylist()) != {root} for t in frames.values()):
+        raise ValueError("the per-player-count seat files of this root were written for another root: replay them with --force")
+    standardized, mixture = sa.standardized_frames(frames, populations, ks, weights)
+    _write_parquet_atomic(standardized, cfg.seat_standardized_across_k_path())
+    _write_parquet_atomic(mixture, cfg.seat_exposure_mixture_diagnostic_path())
+    _write_parquet_atomic(sa.selfplay_frame(frames), cfg.seat_selfplay_diagnostic_path())
+    if 2 not in ks:
+        _write_parquet_atomic(sa.mirrored_frame(None, root), cfg.seat_mirrored_diagnostic_path())
 
 
 _RARE_STATE: dict[str, dict[int, Any]] = {}  # results root -> player count -> run_tournament's result["rare_events"] (rank 0, one sweep)
@@ -1540,6 +1620,8 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
         _publish_rng_matchups(cfg, n, strategies, result)
     if cfg.sim.game_stats and result.get("game_stats") is not None:
         _publish_game_stats(cfg, n, strategies, result)
+    if cfg.sim.seat_analysis and result.get("seat_analysis") is not None:
+        _publish_seat_analysis(cfg, n, strategies, result)
     if cfg.sim.performance_bootstrap and result.get("performance_matrix") is not None:
         result["performance_matrix"].save(cfg.performance_batch_matrix_path(n))  # (the frames follow the LAST player count: run_multi)
     # (A) summary parquet, (B) expanded metrics parquet — column order, types and values as in runner.py:1612-1712, built column by

@@ -389,6 +389,30 @@ int fk_tournament_run_rare_events(fk_ctx *ctx, const fk_strategy *strategies, in
                                   int32_t n_thresholds, const int32_t *margin_thresholds, int64_t event_capacity,
                                   int64_t *event_count, uint32_t *event_head, uint16_t *event_seats);
 
+/* fk_tournament_run (the same arguments, the same tally bits) + the sufficient statistics of the reference's seat-analysis stage
+ * for this range (analysis/seat_analysis.py: _iter_seat_count_tables :170-235, _MirroredPartitionWriter.__call__ :618-714):
+ *   seat_counts  int64 [n_batches][S][k][3], overwritten: per deterministic batch, strategy (table index) and seat its wins,
+ *                completed exposures and safety-limit exposures (exposures = completed + safety; a cell of all zeros is a cell
+ *                the reference does not emit).  1 <= k <= 16.
+ * Mirrored pairs, k = 2 only (every pair argument null / 0 otherwise, FK_ERR_ARG if not):
+ *   id_rank      uint16 [S]: the rank of table index i by strategy ID (a permutation of 0 .. S - 1: IDs are unique)
+ *   pair_index   uint16 [pair_capacity][2]: the pair's table indices, the lower strategy ID first
+ *   pair_sums    int64 [pair_capacity][6]: paired games, P1-win difference sum, completed games, safety-limit games, unpaired
+ *                forward games, unpaired reverse games — each the sum over the call's batches of the per-batch pairing: inside one
+ *                (batch, pair) the i-th completed forward game (seat 1 = the lower ID) is paired with the i-th completed reverse
+ *                game, in (shuffle, game) order, which is what the reference's two FIFO queues do.
+ *   *pair_count  the pairs the call produced, rows in ascending (rank a, rank b); more than pair_capacity returns FK_ERR_ARG
+ *                (call again with that capacity).
+ * With pair outputs shuffle_begin must be a multiple of shuffles_per_batch (a call never starts inside a batch; it may end with a
+ * short one) and the range may hold at most 2^31 - 2 games.  Results do not depend on "chunk_bytes".  The counts are gathered per
+ * strategy from the 4-byte result word of its game (farkle_ii_amd/csrc/fk_seat_analysis.h); the pairs are one stable radix sort of
+ * the range's games by (rank a, rank b, batch) and a segmented scan.  farkle_ii_amd/seat_analysis.py builds the reference's frames. */
+int fk_tournament_run_seat_counts(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch,
+                                  int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov,
+                                  int64_t *tally, int64_t *seat_counts, const uint16_t *id_rank, int64_t pair_capacity,
+                                  int64_t *pair_count, uint16_t *pair_index, int64_t *pair_sums);
+
 /* Explicit game list: game g seats strategies table[seat_strategy[g*k+i]] with streams coords[g](seat i).
  * rows: n_games * (4+28k) bytes (required). */
 int fk_play_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
