@@ -234,6 +234,10 @@ def make_coords(purpose, root_seed, k, shuffle_index=0, pair_id=0, order=0, game
     return out
 
 
+# the game-stat outputs of fk_tournament_run_game_stats / fk_tournament_run_rare_events, in the entries' argument order
+GAME_STAT_ARRAYS = ("strategy_counts", "strategy_rounds", "strategy_runner", "strategy_spread", "game_counts", "game_rounds", "game_runner")
+
+
 class Engine:
     """One context (HIP stream + device workspace) on one GPU."""
 
@@ -294,6 +298,29 @@ class Engine:
         return (self._lib.fk_last_play_instance(self._ctx) or b"").decode()
 
     # -- hot path ------------------------------------------------------------------------
+    @staticmethod
+    def _setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides):
+        """What every ``tournament*`` method starts with: the packed table, S, the shuffles of the range (an empty or reversed range
+        counts none), the batch size, the batches, the override array and a zeroed tally ``[max(n_batches, 1)][S][TALLY_COLS]``."""
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        S = len(table)
+        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
+        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
+        n_batches = (n_sh + spb - 1) // spb
+        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        return table, S, n_sh, spb, n_batches, ov, np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+
+    def _lead(self, table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally) -> tuple:
+        """The thirteen leading arguments of every ``fk_tournament_run*`` entry."""
+        return (self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin), C.c_uint64(shuffle_end),
+                C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)), _p(tally))
+
+    @staticmethod
+    def _game_stat_arrays(S, rb, mb) -> dict:
+        """The seven int64 game-stat outputs (the entries take them in the order of ``GAME_STAT_ARRAYS``)."""
+        shapes = ((S, 4), (S, rb), (S, mb), (S, mb), 4, rb, mb)
+        return {name: np.zeros(shape, np.int64) for name, shape in zip(GAME_STAT_ARRAYS, shapes)}
+
     def tournament(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
                    shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
                    overrides: np.ndarray | None = None, want_rows: bool = False, want_perms: bool = False,
@@ -302,38 +329,25 @@ class Engine:
         integer statistics ``[n_batches][S][SEAT_STAT_COLS]``, columns ``SEAT_STAT_NAMES``, with the four float64 ratio sums
         ``seat_ratio_sums [n_batches][S][SEAT_RATIO_COLS]`` of the same table unless ``want_seat_ratios`` is off: they are one
         sequential sum per (batch, strategy), which a caller that only reads the integer columns need not wait for)."""
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        S = len(table)
-        n_sh = int(shuffle_end) - int(shuffle_begin)
-        spb = n_sh if not shuffles_per_batch else int(shuffles_per_batch)
-        spb = max(spb, 1)
-        n_batches = max((n_sh + spb - 1) // spb, 0)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         gps = S // k if k > 0 else 0
-        tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
         rows = None
         if want_rows:
-            n_rows = max(n_sh, 0) * gps
+            n_rows = n_sh * gps
             if rows_out is not None:  # e.g. a page-locked buffer from pinned_empty(): rows cross PCIe by DMA while the next chunk plays
                 if rows_out.dtype != row_dtype(k) or len(rows_out) < n_rows or not rows_out.flags["C_CONTIGUOUS"]:
                     raise ValueError("rows_out must be a contiguous array of row_dtype(k) with room for every game")
                 rows = rows_out[:n_rows]
             else:
                 rows = np.zeros(n_rows, dtype=row_dtype(k))
-        perms = np.zeros((max(n_sh, 0), S), dtype=np.int32) if want_perms else None
-        ov = overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE)
-        ov = np.ascontiguousarray(ov, dtype=OVERRIDE_DTYPE)
+        perms = np.zeros((n_sh, S), dtype=np.int32) if want_perms else None
         stats = np.zeros((max(n_batches, 1), S, SEAT_STAT_COLS), dtype=np.int64) if want_seat_stats else None
         ratios = np.zeros((max(n_batches, 1), S, SEAT_RATIO_COLS), dtype=np.float64) if want_seat_stats and want_seat_ratios else None
+        lead = self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally)
         if ratios is not None:  # the all-player accumulators: 31 integer sums + the four float64 sums in (shuffle, game, seat) order
-            self._check(self._lib.fk_tournament_run_all_player(
-                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov),
-                C.c_int32(len(ov)), _p(tally), _p(rows), _p(perms), _p(stats), _p(ratios)))
+            self._check(self._lib.fk_tournament_run_all_player(*lead, _p(rows), _p(perms), _p(stats), _p(ratios)))
         else:
-            self._check(self._lib.fk_tournament_run_stats(
-                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov),
-                C.c_int32(len(ov)), _p(tally), _p(rows), _p(perms), _p(stats)))
+            self._check(self._lib.fk_tournament_run_stats(*lead, _p(rows), _p(perms), _p(stats)))
         return {"tally": tally[:n_batches], "rows": rows, "perms": perms,
                 "seat_stats": None if stats is None else stats[:n_batches],
                 "seat_ratio_sums": None if ratios is None else ratios[:n_batches]}
@@ -349,30 +363,21 @@ class Engine:
         the device's spill entries already merged (``game_stats.merge_spills``)."""
         from .game_stats import DEVICE_MARGIN_BINS, DEVICE_ROUNDS_BINS, merge_spills
 
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        S = len(table)
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         R = max([int(max_rounds)] + [int(v) for v in ov["max_rounds"]])
         rb, mb = min(R + 1, DEVICE_ROUNDS_BINS), DEVICE_MARGIN_BINS
         capacity = max(int(spill_capacity), 0)
         while True:
-            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            tally[:] = 0
             stats = np.zeros((max(n_batches, 1), S, SEAT_STAT_COLS), dtype=np.int64) if want_seat_stats else None
             ratios = np.zeros((max(n_batches, 1), S, SEAT_RATIO_COLS), dtype=np.float64) if want_seat_stats else None
-            g = {"strategy_counts": np.zeros((S, 4), np.int64), "strategy_rounds": np.zeros((S, rb), np.int64),
-                 "strategy_runner": np.zeros((S, mb), np.int64), "strategy_spread": np.zeros((S, mb), np.int64),
-                 "game_counts": np.zeros(4, np.int64), "game_rounds": np.zeros(rb, np.int64), "game_runner": np.zeros(mb, np.int64)}
+            g = self._game_stat_arrays(S, rb, mb)
             spill = np.zeros((max(capacity, 1), 3), dtype=np.int32)
             spilled = C.c_int64(0)
             rc = self._lib.fk_tournament_run_game_stats(
-                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-                _p(tally), None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
-                _p(g["strategy_counts"]), _p(g["strategy_rounds"]), _p(g["strategy_runner"]), _p(g["strategy_spread"]),
-                _p(g["game_counts"]), _p(g["game_rounds"]), _p(g["game_runner"]), C.c_int64(capacity), C.byref(spilled), _p(spill))
+                *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
+                None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
+                *(_p(g[name]) for name in GAME_STAT_ARRAYS), C.c_int64(capacity), C.byref(spilled), _p(spill))
             if rc == FK_ERR_ARG and spilled.value > capacity:  # more values outside the windows than room: once more with room for all
                 capacity = int(spilled.value)
                 continue
@@ -396,12 +401,7 @@ class Engine:
         from .game_stats import DEVICE_MARGIN_BINS, DEVICE_ROUNDS_BINS, merge_spills
         from .rare_events import DEVICE_SECOND_BINS, MAX_THRESHOLDS, SPILL_SECOND, merge_second_spills
 
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        S = len(table)
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         thr = np.ascontiguousarray([int(t) for t in thresholds], dtype=np.int32)
         if len(thr) > MAX_THRESHOLDS:
             raise ValueError(f"at most {MAX_THRESHOLDS} margin thresholds per call, got {len(thr)}")
@@ -414,23 +414,19 @@ class Engine:
         attempts = 0
         while True:
             attempts += 1
-            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            tally[:] = 0
             stats = np.zeros((max(n_batches, 1), S, SEAT_STAT_COLS), dtype=np.int64) if want_seat_stats else None
             ratios = np.zeros((max(n_batches, 1), S, SEAT_RATIO_COLS), dtype=np.float64) if want_seat_stats else None
-            g = {"strategy_counts": np.zeros((S, 4), np.int64), "strategy_rounds": np.zeros((S, rb), np.int64),
-                 "strategy_runner": np.zeros((S, mb), np.int64), "strategy_spread": np.zeros((S, mb), np.int64),
-                 "game_counts": np.zeros(4, np.int64), "game_rounds": np.zeros(rb, np.int64), "game_runner": np.zeros(mb, np.int64)}
+            g = self._game_stat_arrays(S, rb, mb)
             s_second, g_second = np.zeros((S, sb), np.int64), np.zeros(sb, np.int64)
             spill = np.zeros((max(capacity, 1), 3), dtype=np.int32)
             spilled, n_events = C.c_int64(0), C.c_int64(0)
             head = np.zeros((max(ev_cap, 1), 4), dtype=np.uint32) if want_events else None
             seats = np.zeros((max(ev_cap, 1), max(int(k), 1)), dtype=np.uint16) if want_events else None
             rc = self._lib.fk_tournament_run_rare_events(
-                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-                _p(tally), None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
-                _p(g["strategy_counts"]), _p(g["strategy_rounds"]), _p(g["strategy_runner"]), _p(g["strategy_spread"]),
-                _p(g["game_counts"]), _p(g["game_rounds"]), _p(g["game_runner"]), C.c_int64(capacity), C.byref(spilled), _p(spill),
+                *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
+                None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
+                *(_p(g[name]) for name in GAME_STAT_ARRAYS), C.c_int64(capacity), C.byref(spilled), _p(spill),
                 C.c_int32(sb), _p(s_second), _p(g_second), C.c_int32(len(thr)), _p(thr) if len(thr) else None,
                 C.c_int64(ev_cap), C.byref(n_events), _p(head), _p(seats))
             short = spilled.value > capacity or n_events.value > ev_cap
@@ -466,12 +462,7 @@ class Engine:
         once more with that room unless ``retry`` is off."""
         from .seat_analysis import id_ranks
 
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        S = len(table)
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         rank = None
         if want_mirrored:
             if strategy_ids is None:
@@ -481,15 +472,14 @@ class Engine:
         attempts = 0
         while True:
             attempts += 1
-            tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
+            tally[:] = 0
             counts = np.zeros((max(n_batches, 1), S, max(int(k), 1), 3), dtype=np.int64)
             n_pairs = C.c_int64(0)
             index = np.zeros((max(capacity, 1), 2), dtype=np.uint16) if want_mirrored else None
             sums = np.zeros((max(capacity, 1), 6), dtype=np.int64) if want_mirrored else None
             rc = self._lib.fk_tournament_run_seat_counts(
-                self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-                C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-                _p(tally), _p(counts), _p(rank), C.c_int64(capacity), C.byref(n_pairs) if want_mirrored else None, _p(index), _p(sums))
+                *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
+                _p(counts), _p(rank), C.c_int64(capacity), C.byref(n_pairs) if want_mirrored else None, _p(index), _p(sums))
             if rc == FK_ERR_ARG and want_mirrored and n_pairs.value > capacity and retry and attempts == 1:
                 capacity = int(n_pairs.value)
                 continue
@@ -512,23 +502,17 @@ class Engine:
         ``async_rows``: return when the last copy to the host is queued; read ``columns`` after ``rows_wait(result["rows_event"])``.
         ``shuffle_seeds_out`` uint32 ``[n_shuffles]`` / ``game_seeds_out`` uint32 ``[n_shuffles * S / k]``: also filled, complete on return
         (``fk_tournament_run_columns_seeds``: the fingerprints a shard's manifest record and its game_seed column carry)."""
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        S = len(table)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         ids = np.ascontiguousarray(strategy_ids, dtype=np.int32)
         if len(ids) != S:
             raise ValueError("strategy_ids must name every strategy of the table")
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
         stride = row_columns_bytes(k, S // k)
-        tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
         if columns_out is not None:
             if columns_out.dtype != np.uint8 or columns_out.size < n_sh * stride or not columns_out.flags["C_CONTIGUOUS"]:
                 raise ValueError("columns_out must be a contiguous uint8 array with room for every shuffle's image")
             columns = columns_out.reshape(-1)[:n_sh * stride].reshape(n_sh, stride)
         else:
             columns = np.zeros((n_sh, stride), dtype=np.uint8)
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
         rows_event = None
         if n_sh:
             if async_rows:
@@ -554,8 +538,7 @@ class Engine:
 
     def _run_columns(self, table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally, ids, columns,
                      shuffle_seeds=None, game_seeds=None) -> None:
-        args = (self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin), C.c_uint64(shuffle_end),
-                C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)), _p(tally), _p(ids), _p(columns))
+        args = (*self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally), _p(ids), _p(columns))
         if shuffle_seeds is None and game_seeds is None:
             self._check(self._lib.fk_tournament_run_columns(*args))
         else:
@@ -567,22 +550,15 @@ class Engine:
         """``tournament`` + the lag sufficient statistics of the strategy family (``fk_tournament_run_lags``):
         ``lag_sums [S][n_lags][LAG_COLS]`` int64 and the first / last ``min(max lag, n_shuffles)`` series rows
         (``lag_head`` / ``lag_tail``, uint16 ``n_rounds | won << 15``, ``[m][S]``) that ``rng_lags.LagSummary`` merges ranges with."""
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         lags = np.ascontiguousarray(list(lags), dtype=np.int32)
-        S = len(table)
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
-        tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
         m = min(int(lags.max()) if len(lags) else 0, n_sh)
         sums = np.zeros((S, len(lags), LAG_COLS), dtype=np.int64)
         head = np.zeros((max(m, 1), S), dtype=np.uint16)
         tail = np.zeros((max(m, 1), S), dtype=np.uint16)
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
         self._check(self._lib.fk_tournament_run_lags(
-            self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-            C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-            _p(tally), _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail)))
+            *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
+            _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail)))
         return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh}
 
     def tournament_matchups(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, lags, strategy_ids,
@@ -591,17 +567,12 @@ class Engine:
         """``tournament_lags`` + the per-game records of the RNG diagnostics' matchup family (``fk_tournament_run_matchups``), in
         coordinate order: ``matchups = {"digest": uint64 [n], "seats": uint16 [n][k] (table indices in ascending-ID order),
         "rounds": uint16 [n]}``."""
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         lags = np.ascontiguousarray(list(lags), dtype=np.int32)
         ids = np.ascontiguousarray(strategy_ids, dtype=np.int32)
-        S = len(table)
         if len(ids) != S or len(np.unique(ids)) != S:
             raise ValueError("strategy_ids must hold one unique ID per strategy of the table")
-        n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
-        spb = max(n_sh if not shuffles_per_batch else int(shuffles_per_batch), 1)
-        n_batches = (n_sh + spb - 1) // spb
         n_games = n_sh * (S // k if k > 0 else 0)
-        tally = np.zeros((max(n_batches, 1), S, TALLY_COLS), dtype=np.int64)
         m = min(int(lags.max()) if len(lags) else 0, n_sh)
         sums = np.zeros((S, len(lags), LAG_COLS), dtype=np.int64)
         head = np.zeros((max(m, 1), S), dtype=np.uint16)
@@ -609,11 +580,9 @@ class Engine:
         digest = np.zeros(max(n_games, 1), dtype=np.uint64)
         seats = np.zeros((max(n_games, 1), max(k, 1)), dtype=np.uint16)
         rounds = np.zeros(max(n_games, 1), dtype=np.uint16)
-        ov = np.ascontiguousarray(overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE), dtype=OVERRIDE_DTYPE)
         self._check(self._lib.fk_tournament_run_matchups(
-            self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin),
-            C.c_uint64(shuffle_end), C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-            _p(tally), _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail), _p(ids), C.c_int32(max_players),
+            *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
+            _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail), _p(ids), C.c_int32(max_players),
             _p(digest), _p(seats), _p(rounds)))
         return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh,
                 "matchups": {"digest": digest[:n_games], "seats": seats[:n_games], "rounds": rounds[:n_games]}}

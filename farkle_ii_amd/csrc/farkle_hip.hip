@@ -109,6 +109,41 @@ struct SeatReq {
     int64_t *pair_sums;       // [pair_capacity][6]
 };
 
+struct LagReq { // fk_tournament_run_lags: host pointers of the request
+    const int32_t *lags;
+    int32_t n_lags, max_lag;
+    int64_t *sums;
+    uint16_t *head, *tail;
+    // fk_tournament_run_matchups (null otherwise): the caller's strategy IDs, max_players, and the per-game records of the range
+    const int32_t *ids = nullptr;
+    int32_t max_players = 0;
+    uint64_t *m_digest = nullptr;
+    uint16_t *m_seats = nullptr, *m_rounds = nullptr;
+};
+
+// One tournament call, as its entry point has checked it: every fk_tournament_run* entry fills one on its stack and the call path
+// (tournament_call, tournament_run_impl) reads it by const reference.  Members left out are null.
+struct TournamentCall {
+    const fk_strategy *strategies;
+    int32_t S, k;
+    uint64_t root_seed, shuffle_begin, shuffle_end;
+    uint32_t shuffles_per_batch;
+    int32_t target_score, max_rounds;
+    const fk_override *ov;
+    int32_t n_ov;
+    int64_t *tally;
+    void *rows;          // AoS rows, or (with columns_ids) per-shuffle column images
+    int32_t *perms;
+    int64_t *seat_stats;
+    double *seat_ratios;
+    const int32_t *columns_ids;          // fk_tournament_run_columns: the strategy ids the images name
+    uint32_t *shuffle_seeds, *game_seeds; // fk_tournament_run_columns_seeds: host destinations
+    const LagReq *lag;
+    const GameStatsReq *gstats;
+    const RareReq *rare; // (with gstats)
+    const SeatReq *seats;
+};
+
 struct fk_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -173,11 +208,8 @@ struct fk_ctx {
     uint64_t matchup_sort_mask = ~0ull;  // option "matchup_sort_key_mask": the bits of the digest the reduce sorts by (tests)
     DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
-    const GameStatsReq *gstats = nullptr; // the request of the running fk_tournament_run_game_stats call
-    const RareReq *rare = nullptr;        // ... and of fk_tournament_run_rare_events (with gstats)
     DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
-    const SeatReq *seatreq = nullptr;    // the request of the running fk_tournament_run_seat_counts call
-    DevBuf sa_counts, sa[16];            // its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
+    DevBuf sa_counts, sa[16];            // fk_tournament_run_seat_counts: its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -199,8 +231,6 @@ struct fk_ctx {
     // rows mode: the device row buffer exists twice and a copy stream moves chunk i's rows to the host while chunk i + 1 plays
     DevBuf rows_alt;
     // fk_tournament_run_columns: the rows buffer receives per-shuffle column images (fk_row_columns_kernel); the strategy ids they name
-    const int32_t *columns_ids = nullptr;
-    uint32_t *want_shuffle_seeds = nullptr, *want_game_seeds = nullptr; // fk_tournament_run_columns_seeds: host destinations of this call
     DevBuf ids;
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_rows[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
@@ -1557,38 +1587,6 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     return FK_OK;
 }
 
-int fk_tournament_run(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                      uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                      int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms) {
-    return fk_tournament_run_stats(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score,
-                                   max_rounds, ov, n_ov, tally, rows, perms, nullptr);
-}
-
-int fk_tournament_run_columns(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
-                              uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
-                              const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *strategy_ids, void *columns) {
-    if (!c) return FK_ERR_ARG;
-    if (!strategy_ids || !columns) return fail(c, FK_ERR_ARG, "strategy_ids and columns are required");
-    c->columns_ids = strategy_ids;
-    const int rc = fk_tournament_run_stats(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score,
-                                           max_rounds, ov, n_ov, tally, columns, nullptr, nullptr);
-    c->columns_ids = nullptr;
-    return rc;
-}
-
-int fk_tournament_run_columns_seeds(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
-                                    uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
-                                    const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *strategy_ids, void *columns,
-                                    uint32_t *shuffle_seeds, uint32_t *game_seeds) {
-    if (!c) return FK_ERR_ARG;
-    c->want_shuffle_seeds = shuffle_seeds;
-    c->want_game_seeds = game_seeds;
-    const int rc = fk_tournament_run_columns(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds,
-                                             ov, n_ov, tally, strategy_ids, columns);
-    c->want_shuffle_seeds = c->want_game_seeds = nullptr;
-    return rc;
-}
-
 int fk_rows_wait(fk_ctx *c, int32_t slot) {
     if (!c || slot < 0 || slot >= FK_ROWS_EVENTS) return FK_ERR_ARG;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1638,22 +1636,13 @@ int fk_debug_sha256(const void *data, size_t n, uint8_t *out32, int32_t portable
     return FK_OK;
 }
 
-struct LagReq { // fk_tournament_run_lags: host pointers of the request
-    const int32_t *lags;
-    int32_t n_lags, max_lag;
-    int64_t *sums;
-    uint16_t *head, *tail;
-    // fk_tournament_run_matchups (null otherwise): the caller's strategy IDs, max_players, and the per-game records of the range
-    const int32_t *ids = nullptr;
-    int32_t max_players = 0;
-    uint64_t *m_digest = nullptr;
-    uint16_t *m_seats = nullptr, *m_rounds = nullptr;
-};
-
-static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                               uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                               int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                               int64_t *seat_stats, const LagReq *lag, double *seat_ratios = nullptr);
+// a lag list (fk_tournament_run_lags, fk_tournament_run_matchups, fk_matchup_reduce): strictly increasing, each in 1 .. 65535
+static int check_lags(fk_ctx *c, const int32_t *lags, int32_t n_lags, const char *source) {
+    for (int32_t i = 0; i < n_lags; ++i)
+        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
+            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers%s", source);
+    return FK_OK;
+}
 
 extern "C++" { // (this part of the file lies inside the C-ABI's extern "C" block)
 template <int K>
@@ -1679,172 +1668,6 @@ static int launch_matchup_keys(fk_ctx *c, uint32_t k, const uint32_t *recs, cons
     return FK_OK;
 }
 
-static int tournament_call(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                           uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                           int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                           int64_t *seat_stats, const LagReq *lag, double *seat_ratios = nullptr);
-
-int fk_tournament_run_stats(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                            int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                            int64_t *seat_stats) {
-    return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
-                           tally, rows, perms, seat_stats, nullptr);
-}
-
-int fk_tournament_run_all_player(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                                 int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                                 int64_t *seat_stats, double *seat_ratio_sums) {
-    if (!c) return FK_ERR_ARG;
-    if (!seat_stats || !seat_ratio_sums) return fail(c, FK_ERR_ARG, "seat_stats and seat_ratio_sums are required");
-    return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
-                           tally, rows, perms, seat_stats, nullptr, seat_ratio_sums);
-}
-
-int fk_tournament_run_game_stats(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                                 int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                                 int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
-                                 int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
-                                 int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
-                                 int64_t spill_capacity, int64_t *spill_count, int32_t *spill) {
-    if (!c) return FK_ERR_ARG;
-    if (!strategy_counts || !strategy_rounds || !strategy_runner || !strategy_spread || !game_counts || !game_rounds || !game_runner || !spill_count)
-        return fail(c, FK_ERR_ARG, "the game-stat outputs and spill_count are required");
-    if (seat_ratio_sums && !seat_stats) return fail(c, FK_ERR_ARG, "seat_ratio_sums needs seat_stats");
-    if (rounds_bins < 1 || rounds_bins > (int32_t)fkg::MAX_ROUNDS_BINS || margin_bins < 1 || margin_bins > (int32_t)fkg::MAX_MARGIN_BINS)
-        return fail(c, FK_ERR_ARG, "rounds_bins must be in [1, %u] and margin_bins in [1, %u]", fkg::MAX_ROUNDS_BINS, fkg::MAX_MARGIN_BINS);
-    if (spill_capacity < 0 || (spill_capacity > 0 && !spill)) return fail(c, FK_ERR_ARG, "spill_capacity must be >= 0, with a spill buffer when > 0");
-    *spill_count = 0;
-    const GameStatsReq req{rare_target_score, (uint32_t)rounds_bins, (uint32_t)margin_bins, strategy_counts, strategy_rounds, strategy_runner,
-                           strategy_spread, game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill};
-    c->gstats = &req;
-    const int rc = tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov,
-                                   n_ov, tally, rows, perms, seat_stats, nullptr, seat_ratio_sums);
-    c->gstats = nullptr;
-    return rc;
-}
-
-int fk_tournament_run_rare_events(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                                  int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
-                                  int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
-                                  int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
-                                  int64_t spill_capacity, int64_t *spill_count, int32_t *spill, int32_t second_bins,
-                                  int64_t *strategy_second, int64_t *game_second, int32_t n_thresholds, const int32_t *margin_thresholds,
-                                  int64_t event_capacity, int64_t *event_count, uint32_t *event_head, uint16_t *event_seats) {
-    if (!c) return FK_ERR_ARG;
-    if (!strategy_second || !game_second || !event_count) return fail(c, FK_ERR_ARG, "strategy_second, game_second and event_count are required");
-    if (second_bins < 1 || second_bins > (int32_t)fkre::MAX_SECOND_BINS) return fail(c, FK_ERR_ARG, "second_bins must be in [1, %u]", fkre::MAX_SECOND_BINS);
-    if (n_thresholds < 0 || n_thresholds > (int32_t)fkre::MAX_THRESHOLDS || (n_thresholds > 0 && !margin_thresholds))
-        return fail(c, FK_ERR_ARG, "n_thresholds must be in [0, %u], with margin_thresholds when > 0", fkre::MAX_THRESHOLDS);
-    if (event_capacity < 0 || (event_capacity > 0 && (!event_head || !event_seats)))
-        return fail(c, FK_ERR_ARG, "event_capacity must be >= 0, with event_head and event_seats when > 0");
-    if (shuffle_end > shuffle_begin && shuffle_end - shuffle_begin > 0xffffffffull)
-        return fail(c, FK_ERR_ARG, "rare events: an event names its shuffle in 32 bits; split the range");
-    if (k > 0 && S / k > 65536) return fail(c, FK_ERR_ARG, "rare events: an event names its game in 16 bits (S / k <= 65536)");
-    *event_count = 0;
-    RareReq rr{};
-    rr.second_bins = (uint32_t)second_bins;
-    rr.s_second = strategy_second;
-    rr.g_second = game_second;
-    rr.thr.n = n_thresholds;
-    for (int32_t i = 0; i < n_thresholds; ++i) rr.thr.v[i] = margin_thresholds[i];
-    rr.events = !(event_capacity == 0 && n_thresholds == 0 && !event_head && !event_seats); // that form: the histograms only
-    rr.event_capacity = event_capacity;
-    rr.event_count = event_count;
-    rr.event_head = event_head;
-    rr.event_seats = event_seats;
-    c->rare = &rr;
-    const int rc = fk_tournament_run_game_stats(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score,
-                                                max_rounds, ov, n_ov, tally, rows, perms, seat_stats, seat_ratio_sums, rare_target_score,
-                                                rounds_bins, margin_bins, strategy_counts, strategy_rounds, strategy_runner, strategy_spread,
-                                                game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill);
-    c->rare = nullptr;
-    return rc;
-}
-
-int fk_tournament_run_seat_counts(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, int64_t *seat_counts,
-                                  const uint16_t *id_rank, int64_t pair_capacity, int64_t *pair_count, uint16_t *pair_index,
-                                  int64_t *pair_sums) {
-    if (!c) return FK_ERR_ARG;
-    if (!seat_counts) return fail(c, FK_ERR_ARG, "seat_counts is required");
-    if (k < 1 || k > (int32_t)fksa::MAX_K) return fail(c, FK_ERR_ARG, "seat counts are made for 1 .. %u seats, got %d", fksa::MAX_K, (int)k);
-    const bool mirrored = id_rank || pair_count || pair_index || pair_sums || pair_capacity != 0;
-    if (mirrored) {
-        if (k != 2) return fail(c, FK_ERR_ARG, "mirrored pairs exist at k = 2 only: the pair arguments must be null / 0 at k = %d", (int)k);
-        if (!id_rank || !pair_count) return fail(c, FK_ERR_ARG, "mirrored pairs need id_rank and pair_count");
-        if (pair_capacity < 0 || (pair_capacity > 0 && (!pair_index || !pair_sums)))
-            return fail(c, FK_ERR_ARG, "pair_capacity must be >= 0, with pair_index and pair_sums when > 0");
-        if (shuffles_per_batch == 0 || shuffle_begin % shuffles_per_batch != 0)
-            return fail(c, FK_ERR_ARG, "mirrored pairs: shuffle_begin must be a multiple of shuffles_per_batch (a call never starts inside a batch)");
-        if (S >= 2 && shuffle_end > shuffle_begin && (shuffle_end - shuffle_begin) > (uint64_t)0x7ffffffe / (uint64_t)(S / 2))
-            return fail(c, FK_ERR_ARG, "mirrored pairs: the range may hold at most 2^31 - 2 games (one sort, 32-bit positions, one end entry); split it at a batch boundary");
-        std::vector<uint8_t> seen((size_t)std::max(S, 0), 0);
-        for (int32_t i = 0; i < S; ++i) {
-            if (id_rank[i] >= (uint32_t)S || seen[id_rank[i]]) return fail(c, FK_ERR_ARG, "id_rank must be a permutation of 0 .. S - 1 (strategy IDs are unique)");
-            seen[id_rank[i]] = 1;
-        }
-        *pair_count = 0;
-    }
-    const SeatReq req{seat_counts, mirrored ? id_rank : nullptr, pair_capacity, pair_count, pair_index, pair_sums};
-    c->seatreq = &req;
-    const int rc = tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov,
-                                   n_ov, tally, nullptr, nullptr, nullptr, nullptr);
-    c->seatreq = nullptr;
-    return rc;
-}
-
-int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
-                           uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
-                           const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
-                           uint16_t *edge_head, uint16_t *edge_tail) {
-    if (!c) return FK_ERR_ARG;
-    if (!lags || !lag_sums || !edge_head || !edge_tail || n_lags < 1 || n_lags > FK_MAX_LAGS)
-        return fail(c, FK_ERR_ARG, "lags, lag_sums, edge_head, edge_tail are required; 1 <= n_lags <= %d", FK_MAX_LAGS);
-    for (int32_t i = 0; i < n_lags; ++i)
-        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
-            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers (rng_diagnostic_lags, config.py:1933-1939)");
-    if (max_rounds > 32767) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: max_rounds must be <= 32767");
-    for (int32_t i = 0; i < n_ov; ++i)
-        if (ov && ov[i].max_rounds > 32767u) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: override max_rounds must be <= 32767");
-    const LagReq req{lags, n_lags, lags[n_lags - 1], lag_sums, edge_head, edge_tail};
-    return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
-                           tally, nullptr, nullptr, nullptr, &req);
-}
-
-int fk_tournament_run_matchups(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
-                               uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
-                               const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
-                               uint16_t *edge_head, uint16_t *edge_tail, const int32_t *strategy_ids, int32_t max_players,
-                               uint64_t *m_digest, uint16_t *m_seats, uint16_t *m_rounds) {
-    if (!c) return FK_ERR_ARG;
-    if (!strategy_ids || !m_digest || !m_seats || !m_rounds) return fail(c, FK_ERR_ARG, "strategy_ids, m_digest, m_seats, m_rounds are required");
-    if (k < 1 || k > (int32_t)fkm::MAX_K) return fail(c, FK_ERR_ARG, "matchup records are made for 1 .. %u seats, got %d", fkm::MAX_K, (int)k);
-    if (max_players < k || max_players > (int32_t)fkm::MAX_PLAYERS)
-        return fail(c, FK_ERR_ARG, "max_players must be in [k, %u] (one BLAKE2b block), got %d", fkm::MAX_PLAYERS, (int)max_players);
-    if (!lags || !lag_sums || !edge_head || !edge_tail || n_lags < 1 || n_lags > FK_MAX_LAGS)
-        return fail(c, FK_ERR_ARG, "lags, lag_sums, edge_head, edge_tail are required; 1 <= n_lags <= %d", FK_MAX_LAGS);
-    for (int32_t i = 0; i < n_lags; ++i)
-        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
-            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers (rng_diagnostic_lags, config.py:1933-1939)");
-    if (max_rounds > 32767) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: max_rounds must be <= 32767");
-    for (int32_t i = 0; i < n_ov; ++i)
-        if (ov && ov[i].max_rounds > 32767u) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: override max_rounds must be <= 32767");
-    LagReq req{lags, n_lags, lags[n_lags - 1], lag_sums, edge_head, edge_tail};
-    req.ids = strategy_ids;
-    req.max_players = max_players;
-    req.m_digest = m_digest;
-    req.m_seats = m_seats;
-    req.m_rounds = m_rounds;
-    return tournament_call(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov,
-                           tally, nullptr, nullptr, nullptr, &req);
-}
-
 // hipcub device-wide primitives: size query, the context's scratch buffer, the call
 #define FKM_CUB(FN, ...)                                                     \
     do {                                                                     \
@@ -1864,9 +1687,7 @@ int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *diges
     if (k < 1 || k > (int32_t)fkm::MAX_K) return fail(c, FK_ERR_ARG, "k must be in [1, %u]", fkm::MAX_K);
     if (n_obs < 0 || n_obs > (int64_t)0x7fffffff) return fail(c, FK_ERR_ARG, "n_obs must be in [0, 2^31)");
     if (n_lags < 1 || n_lags > FK_MAX_LAGS) return fail(c, FK_ERR_ARG, "1 <= n_lags <= %d", FK_MAX_LAGS);
-    for (int32_t i = 0; i < n_lags; ++i)
-        if (lags[i] < 1 || lags[i] > 65535 || (i > 0 && lags[i] <= lags[i - 1]))
-            return fail(c, FK_ERR_ARG, "lags must be strictly increasing positive integers");
+    if (int rc_l = check_lags(c, lags, n_lags, "")) return rc_l;
     HIPCHK(c, hipSetDevice(c->device));
     const uint32_t n = (uint32_t)n_obs, K = (uint32_t)k, minimum = (uint32_t)lags[0] + 2u, H = minimum + 64u;
     for (int i = 0; i < 4; ++i) counts[i] = 0;
@@ -2024,62 +1845,19 @@ static int mirror_reduce(fk_ctx *c, uint32_t n, uint64_t capacity) {
 }
 #undef FKM_CUB
 
-static int tournament_call(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                           uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                           int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                           int64_t *seat_stats, const LagReq *lag, double *seat_ratios) {
-    if (!c) return FK_ERR_ARG;
-    c->ran_hc = false;
-    c->last_tally_bytes = 0;
-    c->oom = false;
-    c->oom_replays = 0;
-    c->chunk_limit = 0;
-    int rc = tournament_run_impl(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds,
-                                 ov, n_ov, tally, rows, perms, seat_stats, lag, seat_ratios);
-    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
-        // out of device memory although the budget was sized from hipMemGetInfo: somebody else's allocation came in between.  Give the
-        // workspace back, plan with half, play the call again from its first shuffle (every output is overwritten).
-        c->oom = false;
-        ++c->oom_replays;
-        release_workspace(c);
-        c->chunk_limit = c->last_budget / 2;
-        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
-        rc = tournament_run_impl(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds,
-                                 ov, n_ov, tally, rows, perms, seat_stats, lag, seat_ratios);
-    }
-    c->chunk_limit = 0;
-    if (rc == FK_ERR_COUNTER_OVERFLOW && c->ran_hc) {
-        // the hot / cold kernel's narrower counter fields (fk_play_hc.h) left their guard bands: the call is replayed on
-        // fk_play_kernel, whose 16-bit fields are the ABI's stated limits
-        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "hot / cold kernel replayed: %s\n", c->err.c_str());
-        const int32_t saved = c->hc;
-        c->hc = 0;
-        for (auto &cs : c->sets) cs.prepared = false;
-        rc = tournament_run_impl(c, strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds,
-                                 ov, n_ov, tally, rows, perms, seat_stats, lag, seat_ratios);
-        c->hc = saved;
-    }
-    if (rc == 0 && c->resident && c->last_tally_bytes) {
-        // the call's tally (still in c->tally) joins the resident accumulator — only now: a call that raised a device error,
-        // the overflow that is replayed above included, must not have added anything (shape changes start a new accumulator)
-        const size_t tally_bytes = c->last_tally_bytes, n_el = tally_bytes / sizeof(int64_t);
-        if (c->acc_n != n_el) {
-            rc = ensure(c, c->acc, tally_bytes);
-            if (rc) return rc;
-            HIPCHK(c, hipMemsetAsync(c->acc.p, 0, tally_bytes, c->stream));
-            c->acc_n = n_el;
-        }
-        hipLaunchKernelGGL(fk_add_i64_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, c->stream,
-                           static_cast<unsigned long long *>(c->acc.p), static_cast<const unsigned long long *>(c->tally.p), n_el);
-        HIPCHK(c, hipGetLastError());
-    }
-    return rc;
-}
-
-static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
-                               uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
-                               int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
-                               int64_t *seat_stats, const LagReq *lag, double *seat_ratios) {
+// The tournament call path: an entry point checks its own arguments and fills a TournamentCall on its stack; tournament_call plays it
+// through the driver below, once or again on one of its three replays.  Nothing that describes the call in progress is in the context.
+static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
+    const fk_strategy *strategies = call.strategies;
+    const int32_t S = call.S, k = call.k, target_score = call.target_score, max_rounds = call.max_rounds, n_ov = call.n_ov;
+    const uint64_t root_seed = call.root_seed, shuffle_begin = call.shuffle_begin, shuffle_end = call.shuffle_end;
+    const uint32_t shuffles_per_batch = call.shuffles_per_batch;
+    const fk_override *ov = call.ov;
+    const LagReq *lag = call.lag;
+    int64_t *tally = call.tally, *seat_stats = call.seat_stats;
+    void *rows = call.rows;
+    int32_t *perms = call.perms;
+    double *seat_ratios = call.seat_ratios;
     if (!strategies || !tally) return fail(c, FK_ERR_ARG, "strategies and tally are required");
     if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
     if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
@@ -2099,19 +1877,17 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     const size_t tally_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_TALLY_COLS;
     if (n_sh_total == 0) return FK_OK;
     const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
-    const bool columns = rows != nullptr && c->columns_ids != nullptr; // fk_tournament_run_columns
+    const bool columns = rows != nullptr && call.columns_ids != nullptr; // fk_tournament_run_columns
     const size_t rows_per_shuffle = columns ? fksw::shard_image_bytes(k, (int)gps) : (size_t)gps * row_bytes;
 
     int rc = upload_strategies(c, strategies, S);
     if (rc) return rc;
     if (columns) {
         if (k > 64) return fail(c, FK_ERR_ARG, "column images hold tables of at most 64 seats, got %d", (int)k);
-        rc = ensure(c, c->ids, sizeof(int32_t) * (size_t)S);
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->ids.p, c->columns_ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
+        if ((rc = ensure(c, c->ids, sizeof(int32_t) * (size_t)S))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->ids.p, call.columns_ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
-    rc = ensure(c, c->tally, tally_bytes);
-    if (rc) return rc;
+    if ((rc = ensure(c, c->tally, tally_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->tally.p, 0, tally_bytes, c->stream));
 
     LaunchPlan plan = plan_play(c, k, S, n_batches == 1, target_score);
@@ -2124,18 +1900,16 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     if (plan.hc) c->ran_hc = true;
     if (plan.hc && !plan.hc_cl) { // cold seat records of every lane the grid can seat
-        rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k * 16);
-        if (rc) return rc;
+        if ((rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k * 16))) return rc;
     }
-    const GameStatsReq *gst = c->gstats; // fk_tournament_run_game_stats (null otherwise)
-    const RareReq *rare = gst ? c->rare : nullptr; // fk_tournament_run_rare_events
-    const SeatReq *sq = c->seatreq; // fk_tournament_run_seat_counts
+    const GameStatsReq *gst = call.gstats; // fk_tournament_run_game_stats (null otherwise)
+    const RareReq *rare = gst ? call.rare : nullptr; // fk_tournament_run_rare_events
+    const SeatReq *sq = call.seats; // fk_tournament_run_seat_counts
     const bool want_state = rows != nullptr || seat_stats != nullptr || gst != nullptr;
     const bool want_recs = !plan.lds_tally || want_state || lag != nullptr;
     const size_t stats_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_SEAT_STAT_COLS;
     if (seat_stats) {
-        rc = ensure(c, c->stats, stats_bytes);
-        if (rc) return rc;
+        if ((rc = ensure(c, c->stats, stats_bytes))) return rc;
         HIPCHK(c, hipMemsetAsync(c->stats.p, 0, stats_bytes, c->stream));
     }
     const size_t sq_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * (size_t)k * fksa::COUNT_COLS;
@@ -2153,8 +1927,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     const size_t ratio_bytes = sizeof(double) * (size_t)n_batches * (size_t)S * FK_SEAT_RATIO_COLS;
     if (seat_ratios) { // running float64 sums, carried from chunk to chunk on the device (all-zero bits = 0.0)
-        rc = ensure(c, c->ratios, ratio_bytes);
-        if (rc) return rc;
+        if ((rc = ensure(c, c->ratios, ratio_bytes))) return rc;
         HIPCHK(c, hipMemsetAsync(c->ratios.p, 0, ratio_bytes, c->stream));
     }
 
@@ -2234,17 +2007,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
     const uint32_t state_dw = (plan.gs || want_state) ? STATE_DW : 4u;
     auto describe = [&](uint64_t first_shuffle, uint32_t count, uint32_t dw) {
-        ChunkDesc d;
-        d.epoch = c->table_epoch;
-        d.root = root_seed;
-        d.sh0 = first_shuffle;
-        d.n_sh = count;
-        d.S = (uint32_t)S;
-        d.k = (uint32_t)k;
-        d.state_dw = dw;
-        d.sched = c->longest_first ? 1u : 0u;
-        d.slots = slots;
-        return d;
+        return ChunkDesc{c->table_epoch, root_seed, first_shuffle, count, (uint32_t)S, (uint32_t)k, dw, c->longest_first ? 1u : 0u, slots};
     };
     // the hint (fk_tournament_hint_next) is for the call that FOLLOWS this one
     const bool hinted = c->hint_valid && c->hint_end > c->hint_begin;
@@ -2260,6 +2023,8 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         const uint64_t sh0 = shuffle_begin + done;
         const uint32_t n_games = n_sh * gps;
         const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
+        const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch); // the batches the chunk touches
+        const uint32_t nb = (uint32_t)((done + n_sh - 1) / shuffles_per_batch) - first_batch + 1u;
 
         // the chunk's preparation: already made on the side stream (by the previous chunk, or by the previous call after a
         // hint), or made now in front of the game kernel
@@ -2276,8 +2041,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             wait_ready = true;
         } else {
             if (c->sets[c->cur].prepared) c->cur ^= 1; // keep a prepared (hinted) chunk for its own call if there is room
-            rc = prep_tournament_chunk(c, c->cur, c->stream, d, CSET(c).sa);
-            if (rc) return rc;
+            if ((rc = prep_tournament_chunk(c, c->cur, c->stream, d, CSET(c).sa))) return rc;
         }
         CSET(c).prepared = false; // consumed
         const SeedArgs sa = CSET(c).sa;
@@ -2307,15 +2071,13 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                 }
             if (!replaced) dov.push_back(DevOverride{game, ov[i].max_rounds});
         }
-        rc = upload_overrides(c, dov);
-        if (rc) return rc;
+        if ((rc = upload_overrides(c, dov))) return rc;
         // the device row buffers alternate over chunks — and, in async mode, over calls: a one-chunk call's row kernel then has not to wait for the previous call's copy
         const int rb = (int)((done / chunk_sh + (c->rows_async ? c->rows_calls : 0u)) & 1u);
         DevBuf &row_buf = rb ? c->rows_alt : c->rows;
         if (rows) {
             if ((size_t)n_sh * rows_per_shuffle > row_buf.cap) HIPCHK(c, hipStreamSynchronize(c->copy_stream)); // growing: no copy may be reading it
-            rc = ensure(c, row_buf, (size_t)n_sh * rows_per_shuffle);
-            if (rc) return rc;
+            if ((rc = ensure(c, row_buf, (size_t)n_sh * rows_per_shuffle))) return rc;
         }
 
         PlayArgs pa{};
@@ -2354,13 +2116,11 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                 have_next = true;
             }
             if (have_next) {
-                rc = prep_tournament_chunk(c, c->cur ^ 1, c->prep_stream, next, c->sets[c->cur ^ 1].sa);
-                if (rc) return rc;
+                if ((rc = prep_tournament_chunk(c, c->cur ^ 1, c->prep_stream, next, c->sets[c->cur ^ 1].sa))) return rc;
             }
         }
         if (wait_ready) HIPCHK(c, hipStreamWaitEvent(c->stream, c->sets[c->cur].ready, 0));
-        rc = launch_play_stage(c, sa, pa, plan, want_state, want_recs || sq != nullptr, want_recs);
-        if (rc) return rc;
+        if ((rc = launch_play_stage(c, sa, pa, plan, want_state, want_recs || sq != nullptr, want_recs))) return rc;
         // The last chunk of a call without rows: its error record travels with the tally, behind the post-passes — one host
         // round trip per call instead of two (the post-passes only read; on an error their output is discarded).
         const bool defer_check = done + chunk_sh >= n_sh_total && !rows && c->err_host;
@@ -2369,13 +2129,11 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             deferred = true;
             deferred_base = (int64_t)done * gps;
         } else {
-            rc = finish_play(c, pa, (int64_t)done * gps, "tournament");
-            if (rc) return rc;
+            if ((rc = finish_play(c, pa, (int64_t)done * gps, "tournament"))) return rc;
         }
         const bool scheduled = c->longest_first != 0;
         if (want_state && scheduled) { // game id -> slot of its state records
-            rc = ensure(c, c->inv, (size_t)n_games * 4);
-            if (rc) return rc;
+            if ((rc = ensure(c, c->inv, (size_t)n_games * 4))) return rc;
             hipLaunchKernelGGL(fk_invert_sched_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
                                static_cast<const uint32_t *>(CSET(c).order.p), n_games, static_cast<uint32_t *>(c->inv.p));
         }
@@ -2429,8 +2187,6 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             }
         }
         if (sq) { // seat counts from rec0 through the inverse permutation; at k = 2 the chunk's mirror records
-            const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
-            const uint32_t nb = (uint32_t)((done + n_sh - 1) / shuffles_per_batch) - first_batch + 1u;
             const uint32_t s_blocks = ((uint32_t)S + fksa::COUNT_BLOCK - 1u) / fksa::COUNT_BLOCK;
             const uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(shuffles_per_batch, n_sh) / 8, (4096u + nb * s_blocks - 1u) / (nb * s_blocks)));
             hipLaunchKernelGGL(fksa::fk_seat_counts_kernel, dim3(s_blocks, nb * ppb), dim3(fksa::COUNT_BLOCK),
@@ -2445,14 +2201,11 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
             HIPCHK(c, hipGetLastError());
         }
         if (seat_stats) {
-            const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
-            const uint32_t nb = (uint32_t)((done + n_sh - 1) / shuffles_per_batch) - first_batch + 1u;
             const uint32_t s_blocks = ((uint32_t)S + 255u) / 256u;
             // enough (strategy block, batch, part) workgroups to fill the chip; a part is at least 8 shuffles
             const uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(shuffles_per_batch, n_sh) / 8, (4096u + nb * s_blocks - 1u) / (nb * s_blocks)));
             // phase 1, game-major: one 32-byte digest per exposure; phase 2 gathers them per strategy
-            rc = ensure(c, c->digest, (size_t)n_games * k * 32);
-            if (rc) return rc;
+            if ((rc = ensure(c, c->digest, (size_t)n_games * k * 32))) return rc;
             const size_t pairs = (size_t)n_games * k;
             hipLaunchKernelGGL(fk_seat_digest_kernel, dim3((unsigned)((pairs + 255u) / 256u)), dim3(256), 0, c->stream,
                                static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
@@ -2516,9 +2269,6 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                 // smaller ones would need
                 const uint32_t slice = (uint32_t)std::min<int64_t>(S, 896);
                 const uint32_t n_slices = ((uint32_t)S + slice - 1u) / slice;
-                const uint32_t first_batch = (uint32_t)(done / shuffles_per_batch);
-                const uint32_t last_batch = (uint32_t)((done + n_sh - 1) / shuffles_per_batch);
-                const uint32_t nb = last_batch - first_batch + 1u;
                 // enough parts to fill the chip, at least ~16 K games each
                 uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(games_per_batch / 16384, (2048u + nb * n_slices - 1u) / (nb * n_slices)));
                 static int reduce_configured = -1;
@@ -2555,8 +2305,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
                                    static_cast<const int32_t *>(c->ids.p), static_cast<uint8_t *>(row_buf.p), rows_per_shuffle);
                 HIPCHK(c, hipGetLastError());
             } else {
-                rc = rows_pass(c, sa, scheduled, n_games, gps, n_sh, true, static_cast<uint8_t *>(row_buf.p));
-                if (rc) return rc;
+                if ((rc = rows_pass(c, sa, scheduled, n_games, gps, n_sh, true, static_cast<uint8_t *>(row_buf.p)))) return rc;
             }
             HIPCHK(c, hipEventRecord(c->ev_rows[rb], c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_rows[rb], 0));
@@ -2573,8 +2322,7 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
         HIPCHK(c, hipStreamSynchronize(c->copy_stream));
     }
     if (sq_n) {
-        rc = mirror_reduce(c, sq_n, (uint64_t)std::max<int64_t>(sq->pair_capacity, 0));
-        if (rc) return rc;
+        if ((rc = mirror_reduce(c, sq_n, (uint64_t)std::max<int64_t>(sq->pair_capacity, 0)))) return rc;
     }
     const uint32_t n_rows = (uint32_t)(n_batches * (uint64_t)S);
     hipLaunchKernelGGL(fk_finalize_tally, dim3((n_rows + 255u) / 256u), dim3(256), 0, c->stream,
@@ -2582,31 +2330,27 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     HIPCHK(c, hipGetLastError());
     c->last_tally_bytes = tally_bytes; // (fk_tournament_run_stats adds it to the resident accumulator once the call has succeeded)
     HIPCHK(c, hipEventRecord(t1, c->stream));
-    const size_t game_seed_bytes = c->want_game_seeds ? (size_t)n_sh_total * gps * 4 : 0, shuffle_seed_bytes = c->want_shuffle_seeds ? (size_t)n_sh_total * 4 : 0;
+    const size_t game_seed_bytes = call.game_seeds ? (size_t)n_sh_total * gps * 4 : 0, shuffle_seed_bytes = call.shuffle_seeds ? (size_t)n_sh_total * 4 : 0;
     reserve_mail(c, tally_bytes + game_seed_bytes + shuffle_seed_bytes + 256);
-    rc = post_d2h(c, tally, c->tally.p, tally_bytes);
-    if (rc) return rc;
+    if ((rc = post_d2h(c, tally, c->tally.p, tally_bytes))) return rc;
     if (game_seed_bytes + shuffle_seed_bytes) {
         // the fingerprints the row shards carry (game_seed column: ns 102, run_tournament.py:340-350) and their manifest names
         // (shuffle_seed: ns 100 = the same coordinate with game_index 0): with the tally, one host round trip for the launch group
         const size_t shuffle_at = (game_seed_bytes + 255u) & ~(size_t)255u;
-        rc = ensure(c, c->dbg[5], shuffle_at + shuffle_seed_bytes);
-        if (rc) return rc;
+        if ((rc = ensure(c, c->dbg[5], shuffle_at + shuffle_seed_bytes))) return rc;
         uint8_t *d_seeds = static_cast<uint8_t *>(c->dbg[5].p);
         if (game_seed_bytes) {
             const size_t n = (size_t)n_sh_total * gps;
             hipLaunchKernelGGL(fk_game_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, seed_prefix(102u /* TOURNAMENT_GAME */, root_seed, (uint64_t)k),
                                shuffle_begin, (uint32_t)n_sh_total, gps, reinterpret_cast<uint32_t *>(d_seeds));
             HIPCHK(c, hipGetLastError());
-            rc = post_d2h(c, c->want_game_seeds, d_seeds, game_seed_bytes);
-            if (rc) return rc;
+            if ((rc = post_d2h(c, call.game_seeds, d_seeds, game_seed_bytes))) return rc;
         }
         if (shuffle_seed_bytes) {
             hipLaunchKernelGGL(fk_game_seed_kernel, dim3((unsigned)((n_sh_total + 255) / 256)), dim3(256), 0, c->stream, seed_prefix(100u /* TOURNAMENT_SHUFFLE */, root_seed, (uint64_t)k),
                                shuffle_begin, (uint32_t)n_sh_total, 1u, reinterpret_cast<uint32_t *>(d_seeds + shuffle_at));
             HIPCHK(c, hipGetLastError());
-            rc = post_d2h(c, c->want_shuffle_seeds, d_seeds + shuffle_at, shuffle_seed_bytes);
-            if (rc) return rc;
+            if ((rc = post_d2h(c, call.shuffle_seeds, d_seeds + shuffle_at, shuffle_seed_bytes))) return rc;
         }
     }
     if (seat_stats) HIPCHK(c, hipMemcpyAsync(seat_stats, c->stats.p, stats_bytes, hipMemcpyDeviceToHost, c->stream));
@@ -2681,6 +2425,251 @@ static int tournament_run_impl(fk_ctx *c, const fk_strategy *strategies, int32_t
     }
     HIPCHK(c, hipEventElapsedTime(&c->timing.total_ms, t0, t1));
     return FK_OK;
+}
+
+static int tournament_call(fk_ctx *c, const TournamentCall &call) {
+    if (!c) return FK_ERR_ARG;
+    c->ran_hc = false;
+    c->last_tally_bytes = 0;
+    c->oom = false;
+    c->oom_replays = 0;
+    c->chunk_limit = 0;
+    int rc = tournament_run_impl(c, call);
+    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
+        // out of device memory although the budget was sized from hipMemGetInfo: somebody else's allocation came in between.  Give the
+        // workspace back, plan with half, play the call again from its first shuffle (every output is overwritten).
+        c->oom = false;
+        ++c->oom_replays;
+        release_workspace(c);
+        c->chunk_limit = c->last_budget / 2;
+        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
+        rc = tournament_run_impl(c, call);
+    }
+    c->chunk_limit = 0;
+    if (rc == FK_ERR_COUNTER_OVERFLOW && c->ran_hc) {
+        // the hot / cold kernel's narrower counter fields (fk_play_hc.h) left their guard bands: the call is replayed on
+        // fk_play_kernel, whose 16-bit fields are the ABI's stated limits
+        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "hot / cold kernel replayed: %s\n", c->err.c_str());
+        const int32_t saved = c->hc;
+        c->hc = 0;
+        for (auto &cs : c->sets) cs.prepared = false;
+        rc = tournament_run_impl(c, call);
+        c->hc = saved;
+    }
+    if (rc == 0 && c->resident && c->last_tally_bytes) {
+        // the call's tally (still in c->tally) joins the resident accumulator — only now: a call that raised a device error,
+        // the overflow that is replayed above included, must not have added anything (shape changes start a new accumulator)
+        const size_t tally_bytes = c->last_tally_bytes, n_el = tally_bytes / sizeof(int64_t);
+        if (c->acc_n != n_el) {
+            rc = ensure(c, c->acc, tally_bytes);
+            if (rc) return rc;
+            HIPCHK(c, hipMemsetAsync(c->acc.p, 0, tally_bytes, c->stream));
+            c->acc_n = n_el;
+        }
+        hipLaunchKernelGGL(fk_add_i64_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, c->stream,
+                           static_cast<unsigned long long *>(c->acc.p), static_cast<const unsigned long long *>(c->tally.p), n_el);
+        HIPCHK(c, hipGetLastError());
+    }
+    return rc;
+}
+
+// ---- the entry points: each checks its own arguments and fills the request
+int fk_tournament_run(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                      uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                      int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms) {
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, rows, perms};
+    return tournament_call(c, call);
+}
+
+int fk_tournament_run_columns(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                              uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
+                              const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *strategy_ids, void *columns) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_ids || !columns) return fail(c, FK_ERR_ARG, "strategy_ids and columns are required");
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, columns};
+    call.columns_ids = strategy_ids;
+    return tournament_call(c, call);
+}
+
+int fk_tournament_run_columns_seeds(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                                    uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
+                                    const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *strategy_ids, void *columns,
+                                    uint32_t *shuffle_seeds, uint32_t *game_seeds) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_ids || !columns) return fail(c, FK_ERR_ARG, "strategy_ids and columns are required");
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, columns};
+    call.columns_ids = strategy_ids;
+    call.shuffle_seeds = shuffle_seeds;
+    call.game_seeds = game_seeds;
+    return tournament_call(c, call);
+}
+
+int fk_tournament_run_stats(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                            int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                            int64_t *seat_stats) {
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, rows, perms, seat_stats};
+    return tournament_call(c, call);
+}
+
+int fk_tournament_run_all_player(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                 int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                                 int64_t *seat_stats, double *seat_ratio_sums) {
+    if (!c) return FK_ERR_ARG;
+    if (!seat_stats || !seat_ratio_sums) return fail(c, FK_ERR_ARG, "seat_stats and seat_ratio_sums are required");
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, rows, perms, seat_stats, seat_ratio_sums};
+    return tournament_call(c, call);
+}
+
+// the game-stat part of a request (fk_tournament_run_game_stats, fk_tournament_run_rare_events): checked, its count cleared
+static int check_game_stats(fk_ctx *c, const TournamentCall &call) {
+    const GameStatsReq &r = *call.gstats;
+    if (!r.s_counts || !r.s_rounds || !r.s_runner || !r.s_spread || !r.g_counts || !r.g_rounds || !r.g_runner || !r.spill_count)
+        return fail(c, FK_ERR_ARG, "the game-stat outputs and spill_count are required");
+    if (call.seat_ratios && !call.seat_stats) return fail(c, FK_ERR_ARG, "seat_ratio_sums needs seat_stats");
+    if (r.rounds_bins < 1 || r.rounds_bins > fkg::MAX_ROUNDS_BINS || r.margin_bins < 1 || r.margin_bins > fkg::MAX_MARGIN_BINS) // (negative: far above)
+        return fail(c, FK_ERR_ARG, "rounds_bins must be in [1, %u] and margin_bins in [1, %u]", fkg::MAX_ROUNDS_BINS, fkg::MAX_MARGIN_BINS);
+    if (r.spill_capacity < 0 || (r.spill_capacity > 0 && !r.spill)) return fail(c, FK_ERR_ARG, "spill_capacity must be >= 0, with a spill buffer when > 0");
+    *r.spill_count = 0;
+    return FK_OK;
+}
+
+int fk_tournament_run_game_stats(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                 uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                 int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                                 int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
+                                 int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
+                                 int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
+                                 int64_t spill_capacity, int64_t *spill_count, int32_t *spill) {
+    if (!c) return FK_ERR_ARG;
+    const GameStatsReq req{rare_target_score, (uint32_t)rounds_bins, (uint32_t)margin_bins, strategy_counts, strategy_rounds, strategy_runner,
+                           strategy_spread, game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill};
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, rows, perms, seat_stats, seat_ratio_sums};
+    call.gstats = &req;
+    const int rc = check_game_stats(c, call);
+    return rc ? rc : tournament_call(c, call);
+}
+
+int fk_tournament_run_rare_events(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, void *rows, int32_t *perms,
+                                  int64_t *seat_stats, double *seat_ratio_sums, int32_t rare_target_score, int32_t rounds_bins,
+                                  int32_t margin_bins, int64_t *strategy_counts, int64_t *strategy_rounds, int64_t *strategy_runner,
+                                  int64_t *strategy_spread, int64_t *game_counts, int64_t *game_rounds, int64_t *game_runner,
+                                  int64_t spill_capacity, int64_t *spill_count, int32_t *spill, int32_t second_bins,
+                                  int64_t *strategy_second, int64_t *game_second, int32_t n_thresholds, const int32_t *margin_thresholds,
+                                  int64_t event_capacity, int64_t *event_count, uint32_t *event_head, uint16_t *event_seats) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_second || !game_second || !event_count) return fail(c, FK_ERR_ARG, "strategy_second, game_second and event_count are required");
+    if (second_bins < 1 || second_bins > (int32_t)fkre::MAX_SECOND_BINS) return fail(c, FK_ERR_ARG, "second_bins must be in [1, %u]", fkre::MAX_SECOND_BINS);
+    if (n_thresholds < 0 || n_thresholds > (int32_t)fkre::MAX_THRESHOLDS || (n_thresholds > 0 && !margin_thresholds))
+        return fail(c, FK_ERR_ARG, "n_thresholds must be in [0, %u], with margin_thresholds when > 0", fkre::MAX_THRESHOLDS);
+    if (event_capacity < 0 || (event_capacity > 0 && (!event_head || !event_seats)))
+        return fail(c, FK_ERR_ARG, "event_capacity must be >= 0, with event_head and event_seats when > 0");
+    if (shuffle_end > shuffle_begin && shuffle_end - shuffle_begin > 0xffffffffull)
+        return fail(c, FK_ERR_ARG, "rare events: an event names its shuffle in 32 bits; split the range");
+    if (k > 0 && S / k > 65536) return fail(c, FK_ERR_ARG, "rare events: an event names its game in 16 bits (S / k <= 65536)");
+    *event_count = 0;
+    RareReq rr{};
+    rr.second_bins = (uint32_t)second_bins;
+    rr.s_second = strategy_second;
+    rr.g_second = game_second;
+    rr.thr.n = n_thresholds;
+    for (int32_t i = 0; i < n_thresholds; ++i) rr.thr.v[i] = margin_thresholds[i];
+    rr.events = !(event_capacity == 0 && n_thresholds == 0 && !event_head && !event_seats); // that form: the histograms only
+    rr.event_capacity = event_capacity;
+    rr.event_count = event_count;
+    rr.event_head = event_head;
+    rr.event_seats = event_seats;
+    const GameStatsReq req{rare_target_score, (uint32_t)rounds_bins, (uint32_t)margin_bins, strategy_counts, strategy_rounds, strategy_runner,
+                           strategy_spread, game_counts, game_rounds, game_runner, spill_capacity, spill_count, spill};
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally, rows, perms, seat_stats, seat_ratio_sums};
+    call.gstats = &req;
+    call.rare = &rr;
+    const int rc = check_game_stats(c, call);
+    return rc ? rc : tournament_call(c, call);
+}
+
+int fk_tournament_run_seat_counts(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                                  uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                                  int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, int64_t *seat_counts,
+                                  const uint16_t *id_rank, int64_t pair_capacity, int64_t *pair_count, uint16_t *pair_index,
+                                  int64_t *pair_sums) {
+    if (!c) return FK_ERR_ARG;
+    if (!seat_counts) return fail(c, FK_ERR_ARG, "seat_counts is required");
+    if (k < 1 || k > (int32_t)fksa::MAX_K) return fail(c, FK_ERR_ARG, "seat counts are made for 1 .. %u seats, got %d", fksa::MAX_K, (int)k);
+    const bool mirrored = id_rank || pair_count || pair_index || pair_sums || pair_capacity != 0;
+    if (mirrored) {
+        if (k != 2) return fail(c, FK_ERR_ARG, "mirrored pairs exist at k = 2 only: the pair arguments must be null / 0 at k = %d", (int)k);
+        if (!id_rank || !pair_count) return fail(c, FK_ERR_ARG, "mirrored pairs need id_rank and pair_count");
+        if (pair_capacity < 0 || (pair_capacity > 0 && (!pair_index || !pair_sums)))
+            return fail(c, FK_ERR_ARG, "pair_capacity must be >= 0, with pair_index and pair_sums when > 0");
+        if (shuffles_per_batch == 0 || shuffle_begin % shuffles_per_batch != 0)
+            return fail(c, FK_ERR_ARG, "mirrored pairs: shuffle_begin must be a multiple of shuffles_per_batch (a call never starts inside a batch)");
+        if (S >= 2 && shuffle_end > shuffle_begin && (shuffle_end - shuffle_begin) > (uint64_t)0x7ffffffe / (uint64_t)(S / 2))
+            return fail(c, FK_ERR_ARG, "mirrored pairs: the range may hold at most 2^31 - 2 games (one sort, 32-bit positions, one end entry); split it at a batch boundary");
+        std::vector<uint8_t> seen((size_t)std::max(S, 0), 0);
+        for (int32_t i = 0; i < S; ++i) {
+            if (id_rank[i] >= (uint32_t)S || seen[id_rank[i]]) return fail(c, FK_ERR_ARG, "id_rank must be a permutation of 0 .. S - 1 (strategy IDs are unique)");
+            seen[id_rank[i]] = 1;
+        }
+        *pair_count = 0;
+    }
+    const SeatReq req{seat_counts, mirrored ? id_rank : nullptr, pair_capacity, pair_count, pair_index, pair_sums};
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally};
+    call.seats = &req;
+    return tournament_call(c, call);
+}
+
+// the lag part of a request (fk_tournament_run_lags, fk_tournament_run_matchups): checked, then gathered
+static int lag_request(fk_ctx *c, const TournamentCall &call, const int32_t *lags, int32_t n_lags, int64_t *lag_sums, uint16_t *edge_head,
+                       uint16_t *edge_tail, LagReq &req) {
+    if (!lags || !lag_sums || !edge_head || !edge_tail || n_lags < 1 || n_lags > FK_MAX_LAGS)
+        return fail(c, FK_ERR_ARG, "lags, lag_sums, edge_head, edge_tail are required; 1 <= n_lags <= %d", FK_MAX_LAGS);
+    const int rc = check_lags(c, lags, n_lags, " (rng_diagnostic_lags, config.py:1933-1939)");
+    if (rc) return rc;
+    if (call.max_rounds > 32767) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: max_rounds must be <= 32767");
+    for (int32_t i = 0; i < call.n_ov; ++i)
+        if (call.ov && call.ov[i].max_rounds > 32767u) return fail(c, FK_ERR_ARG, "lag statistics carry n_rounds in 15 bits: override max_rounds must be <= 32767");
+    req = LagReq{lags, n_lags, lags[n_lags - 1], lag_sums, edge_head, edge_tail};
+    return FK_OK;
+}
+
+int fk_tournament_run_lags(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                           uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
+                           const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
+                           uint16_t *edge_head, uint16_t *edge_tail) {
+    if (!c) return FK_ERR_ARG;
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally};
+    LagReq req{};
+    const int rc = lag_request(c, call, lags, n_lags, lag_sums, edge_head, edge_tail, req);
+    if (rc) return rc;
+    call.lag = &req;
+    return tournament_call(c, call);
+}
+
+int fk_tournament_run_matchups(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                               uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds,
+                               const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags, int64_t *lag_sums,
+                               uint16_t *edge_head, uint16_t *edge_tail, const int32_t *strategy_ids, int32_t max_players,
+                               uint64_t *m_digest, uint16_t *m_seats, uint16_t *m_rounds) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategy_ids || !m_digest || !m_seats || !m_rounds) return fail(c, FK_ERR_ARG, "strategy_ids, m_digest, m_seats, m_rounds are required");
+    if (k < 1 || k > (int32_t)fkm::MAX_K) return fail(c, FK_ERR_ARG, "matchup records are made for 1 .. %u seats, got %d", fkm::MAX_K, (int)k);
+    if (max_players < k || max_players > (int32_t)fkm::MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "max_players must be in [k, %u] (one BLAKE2b block), got %d", fkm::MAX_PLAYERS, (int)max_players);
+    TournamentCall call{strategies, S, k, root_seed, shuffle_begin, shuffle_end, shuffles_per_batch, target_score, max_rounds, ov, n_ov, tally};
+    LagReq req{};
+    const int rc = lag_request(c, call, lags, n_lags, lag_sums, edge_head, edge_tail, req);
+    if (rc) return rc;
+    req.ids = strategy_ids;
+    req.max_players = max_players;
+    req.m_digest = m_digest;
+    req.m_seats = m_seats;
+    req.m_rounds = m_rounds;
+    call.lag = &req;
+    return tournament_call(c, call);
 }
 
 int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
