@@ -1860,6 +1860,10 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     double *seat_ratios = call.seat_ratios;
     if (!strategies || !tally) return fail(c, FK_ERR_ARG, "strategies and tally are required");
     if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
+    if (k > FK_MAX_PLAYERS) // the result word's seven winner-seat bits, the row's int8 winner_seat (REC_SAFETY is the next bit up)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    if (rows != nullptr && call.columns_ids != nullptr && k > 64)
+        return fail(c, FK_ERR_ARG, "column images hold tables of at most 64 seats, got %d", (int)k);
     if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
     if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
     if (shuffle_end < shuffle_begin || shuffles_per_batch == 0) return fail(c, FK_ERR_ARG, "bad shuffle range / batch size");
@@ -1883,7 +1887,6 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     int rc = upload_strategies(c, strategies, S);
     if (rc) return rc;
     if (columns) {
-        if (k > 64) return fail(c, FK_ERR_ARG, "column images hold tables of at most 64 seats, got %d", (int)k);
         if ((rc = ensure(c, c->ids, sizeof(int32_t) * (size_t)S))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->ids.p, call.columns_ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
@@ -2677,6 +2680,8 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     if (!c) return FK_ERR_ARG;
     if (!coords || !table || !seat_strategy || !rows) return fail(c, FK_ERR_ARG, "coords, table, seat_strategy, rows are required");
     if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7fffffff / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
+    if (k > FK_MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
     if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
     for (int64_t i = 0; i < n_games * k; ++i)
         if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);

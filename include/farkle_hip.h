@@ -89,6 +89,10 @@ typedef struct {
     uint64_t root_seed, k, shuffle_index, pair_id, order, game_index, seat_index, replicate_index;
 } fk_coord;
 
+/* The most seats a game may have, for every entry that plays games with a caller-chosen seat count (fk_tournament_run* and
+ * fk_play_games): a row names its winner in an int8 (fk_row_hdr.winner_seat) and a rank in a uint8, and the device's result word
+ * carries the winner's seat in seven bits.  More seats return FK_ERR_ARG before any device work. */
+#define FK_MAX_PLAYERS 128
 #define FK_SEAT_STAT_COLS 31 /* all-seat integer statistics per strategy, see fk_tournament_run_stats */
 #define FK_LAG_COLS 11 /* lag sufficient statistics per (strategy, lag), see fk_tournament_run_lags */
 #define FK_MAX_LAGS 16
@@ -172,7 +176,7 @@ int fk_get_option(fk_ctx *ctx, const char *name, int64_t *value);
  *   tally       int64 [n_batches][S][26], n_batches = ceil(n_shuffles / shuffles_per_batch); overwritten.
  *   rows        nullable; n_shuffles * (S/k) rows of 4+28k bytes, game-major in (shuffle, game) order.
  *   perms       nullable; int32 [n_shuffles][S] (the permutation of each shuffle; tests/diagnostics).
- * Requires S % k == 0 (run_tournament.py:274), S <= 65535, max_rounds <= 65535.  Targets above 3 200 000 points play with
+ * Requires 1 <= k <= FK_MAX_PLAYERS, S % k == 0 (run_tournament.py:274), S <= 65535, max_rounds <= 65535.  Targets above 3 200 000 points play with
  * full LDS records (lean ones carry the banked total / 50 in 16 bits): FK_ERR_ARG if k of those do not fit LDS, and for the
  * batched head-to-head entry points. */
 int fk_tournament_run(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
@@ -191,7 +195,7 @@ int fk_tournament_run(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int
  *                                    n_smart_one_dice, hot_dice, n_turns                                   (the schema's column order)
  *     uint8 status[gps]              1 = safety limit: the row's nullable fields are null and every hit flag is set (engine.py:485-489)
  *     uint8 winner_seat[gps]         0-based; uint8 rank_order[gps][k]: seats in rank order (the seat_ranks list)
- *   columns     n_shuffles images, shuffle-major; k <= 64.     strategy_ids   int32 [S]: the strategy_id of table row i. */
+ *   columns     n_shuffles images, shuffle-major; k <= 64 (narrower than FK_MAX_PLAYERS).     strategy_ids   int32 [S]: the strategy_id of table row i. */
 int fk_tournament_run_columns(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                               uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch,
                               int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov,
@@ -245,7 +249,7 @@ int fk_write_row_shards(const fk_shard_job *job, int64_t *byte_length, uint8_t *
  * lockstep form — digests of data[0 .. n/2) and data[n/2 .. n) into out32[0 .. 32) and out32[32 .. 64)): parity probe. */
 int fk_debug_sha256(const void *data, size_t n, uint8_t *out32, int32_t portable);
 
-/* fk_tournament_run plus the integer sufficient statistics of ALL seats (not winners only), per batch and strategy:
+/* fk_tournament_run (k <= FK_MAX_PLAYERS) plus the integer sufficient statistics of ALL seats (not winners only), per batch and strategy:
  *   seat_stats  nullable; int64 [n_batches][S][FK_SEAT_STAT_COLS]; overwritten.  Columns:
  *     0 exposures, 1 completed exposures, 2 safety-limit exposures (= max-round aborts), 3 wins,
  *     4/5 sum / sum of squares of the final score, 6/7 of n_turns, 8 exposures with n_turns != n_rounds,
@@ -261,7 +265,7 @@ int fk_tournament_run_stats(fk_ctx *ctx, const fk_strategy *strategies, int32_t 
                             int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov,
                             int64_t *tally, void *rows, int32_t *perms, int64_t *seat_stats);
 
-/* fk_tournament_run_stats plus the four float64 accumulators of the same table (all_player_metrics.py:308-321), per batch and strategy:
+/* fk_tournament_run_stats (k <= FK_MAX_PLAYERS) plus the four float64 accumulators of the same table (all_player_metrics.py:308-321), per batch and strategy:
  *   seat_ratio_sums  double [n_batches][S][FK_SEAT_RATIO_COLS]; overwritten.  Columns: sum of score / n_turns over the strategy's
  *     exposures (0 where n_turns is 0), sum of its squares, sum of score / n_rounds, sum of its squares.
  * The reference adds them with np.add.at in source-row order (:174-177), i.e. one sequential float64 sum per strategy over its
@@ -296,7 +300,7 @@ int fk_tournament_hint_next(fk_ctx *ctx, uint64_t shuffle_begin, uint64_t shuffl
  *               batches per rank) combine on the host: sums add, plus the pairs that straddle the cut, which need exactly the
  *               tail of the earlier and the head of the later range (farkle_ii_amd/rng_lags.py: LagSummary.merge).
  * The matchup family of the same module is fk_tournament_run_matchups + fk_matchup_reduce below.
- * Requires max_rounds (and every override) <= 32767. */
+ * Requires max_rounds (and every override) <= 32767 and k <= FK_MAX_PLAYERS. */
 int fk_tournament_run_lags(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                            uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
                            int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags,
@@ -309,7 +313,8 @@ int fk_tournament_run_lags(fk_ctx *ctx, const fk_strategy *strategies, int32_t S
  *              person=b"farkle-m"), read little-endian
  *   m_seats    uint16 [n_games][k]: the seats' TABLE indices, ordered by ascending strategy_ids[index]
  *   m_rounds   uint16 [n_games]: n_rounds (15 bits; safety-limit games included)
- *   strategy_ids  int32 [S], unique: the IDs the digest and the order use; 1 <= k <= 16, k <= max_players <= 31. */
+ *   strategy_ids  int32 [S], unique: the IDs the digest and the order use; 1 <= k <= 16 (narrower than FK_MAX_PLAYERS),
+ *              k <= max_players <= 31. */
 int fk_tournament_run_matchups(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
                                uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
                                int32_t max_rounds, const fk_override *ov, int32_t n_ov, int64_t *tally, const int32_t *lags, int32_t n_lags,
@@ -343,7 +348,7 @@ int fk_matchup_reduce(fk_ctx *ctx, int32_t k, int64_t n_obs, const uint64_t *dig
  * Nothing is clamped: a value beyond its histogram (n_rounds >= rounds_bins, margin / 50 >= margin_bins) is an entry of
  *   spill   int32 [spill_capacity][3]: strategy table index (-1: the game level), kind (0 n_rounds, 1 runner-up, 2 spread), value
  * *spill_count = the entries the call produced; more than spill_capacity returns FK_ERR_ARG (call again with that capacity).
- * 1 <= rounds_bins <= 4096, 1 <= margin_bins <= 2048.  Option "game_stats_window" (tests): > 0 narrows both device windows to that
+ * 1 <= rounds_bins <= 4096, 1 <= margin_bins <= 2048, k <= FK_MAX_PLAYERS.  Option "game_stats_window" (tests): > 0 narrows both device windows to that
  * many bins, so that values spill; results are the same.  Per workgroup the device gathers one strategy's exposures over a segment
  * of shuffles into LDS histograms (farkle_ii_amd/csrc/fk_game_stats.h); farkle_ii_amd/game_stats.py builds the reference's tables. */
 int fk_tournament_run_game_stats(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
@@ -372,7 +377,7 @@ int fk_tournament_run_game_stats(fk_ctx *ctx, const fk_strategy *strategies, int
  * Events come out in ascending (shuffle, game) order, whatever the grid, the workspace chunking ("chunk_bytes") and the split of a
  * shuffle range over calls: the lists of a split, concatenated (x rebased), equal the list of the one call.  *event_count = the
  * events the call produced; more than event_capacity returns FK_ERR_ARG (call again with that capacity; when the spill list is
- * too small as well, both counts are reported by the same return).  event_capacity = 0 with n_thresholds = 0 and null lists is
+ * too small as well, both counts are reported by the same return).  k <= FK_MAX_PLAYERS.  event_capacity = 0 with n_thresholds = 0 and null lists is
  * the histograms-only call: no game is examined for events and *event_count = 0.  The range may hold at most 2^32 - 1 shuffles and
  * S / k at most 65536 games per shuffle.  The second score is kept in a second per-game record array (4 bytes per game), so the
  * 16-byte game records of fk_tournament_run_game_stats are unchanged; the list is an order-preserving stream compaction
@@ -393,7 +398,7 @@ int fk_tournament_run_rare_events(fk_ctx *ctx, const fk_strategy *strategies, in
  * for this range (analysis/seat_analysis.py: _iter_seat_count_tables :170-235, _MirroredPartitionWriter.__call__ :618-714):
  *   seat_counts  int64 [n_batches][S][k][3], overwritten: per deterministic batch, strategy (table index) and seat its wins,
  *                completed exposures and safety-limit exposures (exposures = completed + safety; a cell of all zeros is a cell
- *                the reference does not emit).  1 <= k <= 16.
+ *                the reference does not emit).  1 <= k <= 16 (narrower than FK_MAX_PLAYERS).
  * Mirrored pairs, k = 2 only (every pair argument null / 0 otherwise, FK_ERR_ARG if not):
  *   id_rank      uint16 [S]: the rank of table index i by strategy ID (a permutation of 0 .. S - 1: IDs are unique)
  *   pair_index   uint16 [pair_capacity][2]: the pair's table indices, the lower strategy ID first
@@ -414,7 +419,7 @@ int fk_tournament_run_seat_counts(fk_ctx *ctx, const fk_strategy *strategies, in
                                   int64_t *pair_count, uint16_t *pair_index, int64_t *pair_sums);
 
 /* Explicit game list: game g seats strategies table[seat_strategy[g*k+i]] with streams coords[g](seat i).
- * rows: n_games * (4+28k) bytes (required). */
+ * rows: n_games * (4+28k) bytes (required).  1 <= k <= FK_MAX_PLAYERS. */
 int fk_play_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
                   const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds, void *rows);
 

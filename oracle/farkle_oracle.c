@@ -500,7 +500,9 @@ static int play_players(player_t *pl, script_t *sc, const int32_t *seat_strategy
     return FKO_OK;
 }
 
-#define FKO_MAX_K 64
+/* sizes the two stack arrays of player_t below and nothing else; 128 is the ceiling of the row format itself: a row names its
+ * winner in an int8 (winner_seat, -1 = none), so seat 127 is the last one a row can report */
+#define FKO_MAX_K 128
 
 int fko_play_game(const fko_coord *gc, const fko_strategy *table, const int32_t *seat_strategy, int32_t k,
                   int32_t target_score, int32_t max_rounds, void *row) { /* _play_game simulation.py:576-655 */
