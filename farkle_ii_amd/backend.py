@@ -36,6 +36,11 @@ H2H_BLOCK_DTYPE = np.dtype(
     [("seats", STRATEGY_DTYPE, (2,)), ("pair_id", "<u8"), ("order", "<u4"), ("pad", "<u4"), ("target", "<u8"),
      ("max_attempts", "<u8"), ("state", "<u8", (5,))]
 )
+# fk_roll_event, include/farkle_hip.h: one roll of a traced game (fk_trace_games; decoders in farkle_ii_amd/trace.py)
+EVENT_DTYPE = np.dtype(
+    [("dice", "<u4"), ("turn_score", "<i4"), ("points", "<u2"), ("round", "<u2"), ("seat", "u1"), ("used_left", "u1"),
+     ("discards", "u1"), ("flags", "u1")]
+)
 TALLY_COLS = 26
 LAG_COLS = 11  # FK_LAG_COLS: pairs | win: sx sy sxx syy sxy | n_rounds: sx sy sxx syy sxy
 SEAT_STAT_COLS = 31
@@ -92,7 +97,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
@@ -110,7 +115,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games"]
 _libs: dict = {}
 
 
@@ -664,6 +669,27 @@ class Engine:
         self._check(self._lib.fk_play_games(self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss),
                                             C.c_int32(k), C.c_int32(target_score), C.c_int32(max_rounds), _p(rows)))
         return rows
+
+    def trace_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
+                    max_rounds: int = 200) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """``fk_trace_games``: the rows ``play_games`` returns for the same arguments, ``event_begin`` (int64 ``[n_games + 1]``) and
+        the roll events of every game (``EVENT_DTYPE``; game g owns ``events[event_begin[g]:event_begin[g + 1]]``, in play order).
+        A counting call sizes the event list, an exact-size call fills it."""
+        coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        ss = np.ascontiguousarray(seat_strategy, dtype=np.int32).reshape(-1)
+        n = len(coords)
+        if ss.size != n * k:
+            raise ValueError("seat_strategy must hold n_games * k entries")
+        rows = np.zeros(n, dtype=row_dtype(k))
+        begin = np.zeros(n + 1, dtype=np.int64)
+        lead = (self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss), C.c_int32(k), C.c_int32(target_score),
+                C.c_int32(max_rounds), _p(rows), _p(begin))
+        self._check(self._lib.fk_trace_games(*lead, None, C.c_int64(0)))
+        events = np.zeros(int(begin[-1]), dtype=EVENT_DTYPE)
+        if len(events):
+            self._check(self._lib.fk_trace_games(*lead, _p(events), C.c_int64(len(events))))
+        return rows, begin, events
 
     def h2h(self, seats: np.ndarray, root_seed: int, pair_id: int, order: int, target: int, max_attempts: int,
             chunk_games: int, target_score: int = 10_000, max_rounds: int = 200, overrides: np.ndarray | None = None,

@@ -1,10 +1,12 @@
-"""``farkle`` command line for the simulation path: ``run``, ``time`` and ``root-stability``.
+"""``farkle`` command line for the simulation path: ``run``, ``time``, ``watch`` and ``root-stability``.
 
-Mirrors ``src/farkle/cli/main.py`` (:53-140 parser, :325-464 dispatch) for the two commands on this path; the
+Mirrors ``src/farkle/cli/main.py`` (:53-140 parser, :325-470 dispatch) for the commands on this path; the
 analysis/orchestration commands of the reference are out of scope and are rejected with a clear message.
 
     python -m farkle_ii_amd --config configs/fast.yaml --set sim.n_players_list=[2] --set sim.seed_list=[42] run --metrics
     python -m farkle_ii_amd time --players 2 --n-games 1000 --seed 42
+    python -m farkle_ii_amd watch --seed 42
+    python -m farkle_ii_amd --config cfg.yaml watch --players 4 --shuffle 17 --game 3      (replay a tournament game of the config's grid)
     python -m farkle_ii_amd --config cfg.yaml root-stability --root-results data/results_seed_11 --root-results data/results_seed_23
     torchrun --nproc-per-node 8 -m farkle_ii_amd --config cfg.yaml run      (one process per GPU, RCCL tally reduce)
 """
@@ -18,7 +20,7 @@ from pathlib import Path
 from typing import Sequence
 
 LOGGER = logging.getLogger("farkle_ii_amd.cli")
-_OUT_OF_SCOPE = ("watch", "analyze", "two-seed-pipeline")
+_OUT_OF_SCOPE = ("analyze", "two-seed-pipeline")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -85,6 +87,14 @@ def build_parser() -> argparse.ArgumentParser:
     t.add_argument("--n-games", dest="n_games", type=int, default=1000, help="Number of games to run (default: 1000)")
     t.add_argument("--jobs", type=int, default=1, help="Parallel jobs (accepted for compatibility)")
     t.add_argument("--seed", type=int, default=42, help="Seed (default: 42)")
+    w = sub.add_parser("watch", help="Play one game and log every roll, scoring call and decision")
+    w.add_argument("--seed", type=int, default=None, help="Seed of the two random strategies and of the game (cli/main.py:103-105)")
+    w.add_argument("--config", dest="watch_config", type=Path, default=None, metavar="C",
+                   help="Replay a tournament game instead: the root seed and the strategy grid come from this configuration "
+                        "(the global --config and --set apply as well)")
+    w.add_argument("--players", type=int, default=None, metavar="K", help="Replay: players per game")
+    w.add_argument("--shuffle", type=int, default=None, metavar="S", help="Replay: shuffle index of the game's row")
+    w.add_argument("--game", type=int, default=None, metavar="G", help="Replay: game index inside the shuffle")
     rs = sub.add_parser("root-stability", help="The two-root stability stage's bootstrap families from two roots' batch matrices")
     rs.add_argument("--root-results", action="append", default=[], type=Path, metavar="DIR",
                     help="Results root of one `farkle run --performance-bootstrap` (its analysis/03_metrics/by_k/<k>p/"
@@ -125,11 +135,31 @@ def main(argv: Sequence[str] | None = None) -> None:
         out = measure_sim_times(n_games=args.n_games, players=args.players, seed=args.seed, jobs=args.jobs)
         print(f"{args.n_games} games, {args.players} players: {out['games_per_sec']:.1f} games/s; winners {out['winners']}")
         return
+    replay = args.command == "watch" and (args.watch_config is not None or any(v is not None for v in (args.players, args.shuffle, args.game)))
+    if args.command == "watch" and not replay:
+        from .watch_game import watch_game
+
+        watch_game(seed=args.seed)  # (no seed: the reference's ValueError)
+        return
     from . import runner
     from .config import AppConfig, apply_dot_overrides, load_app_config
 
-    cfg = load_app_config(args.config, seed_list_len=None) if args.config is not None else AppConfig()
+    config_path = args.watch_config if replay and args.watch_config is not None else args.config
+    cfg = load_app_config(config_path, seed_list_len=None) if config_path is not None else AppConfig()
     cfg = apply_dot_overrides(cfg, list(args.overrides or []))
+    if replay:
+        from .watch_game import watch_tournament_game
+
+        if args.seed is not None:
+            raise SystemExit("farkle watch: --seed plays the reference's two-random-strategy game; a replay takes its root from the configuration")
+        if None in (args.players, args.shuffle, args.game):
+            raise SystemExit("farkle watch: a replay needs --players, --shuffle and --game")
+        if cfg.sim.seed_list is not None and len(cfg.sim.seed_list) != 1:
+            raise ValueError(f"sim.seed_list must contain exactly 1 seeds, got {cfg.sim.seed_list!r}")
+        cfg.sim.populate_seed_list(1)
+        strategies, _ = runner._resolve_strategies(cfg, None)
+        watch_tournament_game(strategies, cfg.sim.seed, args.players, args.shuffle, args.game)
+        return
     if args.command == "root-stability":
         written = runner.run_root_stability(cfg, args.root_results, out=args.out)
         print({name: str(path) for name, path in written.items()})

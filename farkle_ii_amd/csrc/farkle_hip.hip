@@ -14,6 +14,7 @@
 #include "fk_bootstrap.h"     // device side: performance stage's joint batch bootstrap (draws, integer product, ranks, contrasts)
 #include "fk_root_stability.h" // device side: two-root stability stage's bootstrap families (rates of both roots, maxima, top-N membership)
 #include "fk_seat_analysis.h"  // device side: seat-analysis stage (per-seat counts from rec0, mirrored-pair sort-and-segment reduce)
+#include "fk_trace.h"          // device side: roll-level game trace (its own table-free game loop, events at scanned offsets)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -210,6 +211,7 @@ struct fk_ctx {
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
     DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
     DevBuf sa_counts, sa[16];            // fk_tournament_run_seat_counts: its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
+    DevBuf tr[8];                        // fk_trace_games: strategies in points, seat workspace, event counts / begins, rows, error word, events, hipcub scratch
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -1403,6 +1405,7 @@ void fk_destroy(fk_ctx *c) {
     release(c->sa_counts);
     for (DevBuf &b : c->sa) release(b);
     for (DevBuf &b : c->rootb) release(b);
+    for (DevBuf &b : c->tr) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
@@ -2742,6 +2745,118 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     HIPCHK(c, hipMemcpyAsync(rows, c->rows.p, (size_t)n_games * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->timing.total_ms = c->timing.seed_ms + c->timing.play_ms;
+    return FK_OK;
+}
+
+// Roll-level trace of an explicit game list (fk_trace.h).  Counting pass (events per game + rows) -> exclusive scan -> the host
+// reads the total and checks the capacity -> writing pass.  Nothing of the call stays in the context but device buffers.
+int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S, const int32_t *seat_strategy,
+                   int32_t k, int32_t target_score, int32_t max_rounds, void *rows, int64_t *event_begin, fk_roll_event *events,
+                   int64_t event_capacity) {
+    if (!c) return FK_ERR_ARG;
+    if (!coords || !table || !seat_strategy || !rows || !event_begin)
+        return fail(c, FK_ERR_ARG, "coords, table, seat_strategy, rows, event_begin are required");
+    if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7ffffffe / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
+    if (k > FK_MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    if (events && event_capacity < 0) return fail(c, FK_ERR_ARG, "event_capacity must not be negative");
+    for (int64_t i = 0; i < n_games * k; ++i)
+        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
+    for (int64_t i = 0; i < n_games; ++i) {
+        if (coords[i].k != (uint64_t)k) // simulation.py:438
+            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
+        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
+    }
+    int rc = validate_strategies(c, table, S);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timing = fk_timing{};
+    c->play_instance.clear();
+    c->pending.clear();
+    event_begin[0] = 0;
+    if (n_games == 0) return FK_OK;
+    // The strategies as the table-free functions take them: thresholds in points.  A score threshold is only ever compared with
+    // turn totals in [50, 3 000 000] (1000 rolls of at most 3000 points), so clamping it to [0, 2^30] changes no comparison and
+    // keeps `turn + roll - threshold` inside int32.
+    std::vector<int2> packed((size_t)S);
+    for (int32_t i = 0; i < S; ++i)
+        packed[(size_t)i] = make_int2(std::min(std::max(table[i].score_threshold, 0), 1 << 30), (int)pack_strategy(table[i]).y);
+    const uint32_t n = (uint32_t)n_games, n_pad = (n + fktr::TR_BLOCK - 1u) / fktr::TR_BLOCK * fktr::TR_BLOCK;
+    const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
+    const size_t sz[6] = {sizeof(int2) * (size_t)S, (size_t)k * fktr::TR_FIELDS * n_pad * 4, 8 * ((size_t)n + 1), 8 * ((size_t)n + 1), (size_t)n * row_bytes, 8};
+    for (int i = 0; i < 6; ++i)
+        if ((rc = ensure(c, c->tr[i], sz[i]))) return rc;
+    if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
+    if ((rc = ensure(c, c->seatlist, sizeof(int32_t) * (size_t)n * k))) return rc;
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy, sizeof(int32_t) * (size_t)n * k, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->tr[0].p, packed.data(), sz[0], hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->tr[2].p, 0, sz[2], st));    // (the scan's last input, behind the games' counts)
+    HIPCHK(c, hipMemsetAsync(c->tr[5].p, 0xff, sz[5], st)); // TR_NO_ERROR
+    fktr::TraceArgs a{};
+    a.coords = static_cast<const fk_coord *>(c->coords.p);
+    a.strat = static_cast<const int2 *>(c->tr[0].p);
+    a.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+    a.n_games = n;
+    a.n_pad = n_pad;
+    a.k = (uint32_t)k;
+    a.target_score = target_score;
+    a.max_rounds = (uint32_t)max_rounds;
+    a.ws = static_cast<uint32_t *>(c->tr[1].p);
+    a.rows = static_cast<uint8_t *>(c->tr[4].p);
+    a.counts = static_cast<long long *>(c->tr[2].p);
+    a.begin = static_cast<const long long *>(c->tr[3].p);
+    a.err = static_cast<unsigned long long *>(c->tr[5].p);
+    const dim3 grid(n_pad / fktr::TR_BLOCK), block(fktr::TR_BLOCK);
+    {
+        Timer t(c, &c->timing.play_ms, SLOT_PLAY);
+        hipLaunchKernelGGL(fktr::fk_trace_kernel<false>, grid, block, 0, st, a);
+        HIPCHK(c, hipGetLastError());
+        t.stop();
+    }
+    {
+        size_t tb = 0;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, a.counts, static_cast<long long *>(c->tr[3].p), (int)(n + 1u), st));
+        if ((rc = ensure(c, c->tr[7], std::max<size_t>(tb, 1)))) return rc;
+        tb = c->tr[7].cap;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->tr[7].p, tb, a.counts, static_cast<long long *>(c->tr[3].p), (int)(n + 1u), st));
+    }
+    unsigned long long err = fktr::TR_NO_ERROR;
+    HIPCHK(c, hipMemcpyAsync(&err, c->tr[5].p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(event_begin, c->tr[3].p, sz[3], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rows, c->tr[4].p, sz[4], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, collect_timers(c));
+    c->timing.play_launches = 1;
+    c->timing.play_block = (int32_t)fktr::TR_BLOCK;
+    c->timing.play_grid = (int32_t)grid.x;
+    c->timing.games = n_games;
+    c->timing.total_ms = c->timing.play_ms;
+    if (err != fktr::TR_NO_ERROR) {
+        const int32_t h[2] = {(err & 0xffu) == fktr::TR_ERR_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW, (int32_t)(err >> 8)};
+        return report_device_error(c, h, 0, "trace");
+    }
+    const int64_t total = event_begin[n];
+    if (!events) return FK_OK;
+    if (event_capacity < total)
+        return fail(c, FK_ERR_ARG, "event_capacity %lld is too small: the games roll %lld times (call again with that capacity)",
+                    (long long)event_capacity, (long long)total);
+    if (total == 0) return FK_OK;
+    if ((rc = ensure(c, c->tr[6], sizeof(fk_roll_event) * (size_t)total))) return rc;
+    a.events = static_cast<uint4 *>(c->tr[6].p);
+    {
+        Timer t(c, &c->timing.play_ms, SLOT_PLAY);
+        hipLaunchKernelGGL(fktr::fk_trace_kernel<true>, grid, block, 0, st, a);
+        HIPCHK(c, hipGetLastError());
+        t.stop();
+    }
+    HIPCHK(c, hipMemcpyAsync(events, c->tr[6].p, sizeof(fk_roll_event) * (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, collect_timers(c));
+    c->timing.play_launches = 2;
+    c->timing.total_ms = c->timing.play_ms;
     return FK_OK;
 }
 

@@ -423,6 +423,43 @@ int fk_tournament_run_seat_counts(fk_ctx *ctx, const fk_strategy *strategies, in
 int fk_play_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
                   const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds, void *rows);
 
+/* One roll of a traced game (fk_trace_games), 16 bytes.  What FarklePlayer.take_turn (src/farkle/game/engine.py:208-273) sees and does
+ * at one trip of its loop: _roll (:85-101), _score_roll (:103-147), _apply_hot_dice (:149-154), _should_continue (:156-205). */
+typedef struct {
+    uint32_t dice;       /* bits 3i..3i+2, i < n_dice: face (1..6) of die i in DRAW order; bits 18..20: n_dice; rest 0 */
+    int32_t  turn_score; /* the turn's points after this roll (0 after a farkle) */
+    uint16_t points;     /* default_score's score for this roll, after discards; 0 = farkle */
+    uint16_t round;      /* 1-based round the roll belongs to (the final round's turns carry the trigger's round) */
+    uint8_t  seat;       /* 0-based */
+    uint8_t  used_left;  /* low nibble: default_score's `used` (0 on a farkle); high nibble: dice the turn goes on with
+                            (_score_roll's next_dice: 0 farkle, 6 hot dice, else reroll) */
+    uint8_t  discards;   /* low nibble d5, high nibble d1 (default_score(return_discards=True)) */
+    uint8_t  flags;      /* 1: strategy.decide was consulted (not on a farkle, not on an auto-hot-dice roll, not when
+                            _should_continue banks on `final_round and running_total > score_to_beat and not run_up_score`);
+                            2: the turn rolls again; 4: final_round; 8: this roll was continued by auto_hot_dice */
+} fk_roll_event;
+#define FK_EV_DECIDE 1
+#define FK_EV_ROLL_AGAIN 2
+#define FK_EV_FINAL_ROUND 4
+#define FK_EV_AUTO_HOT 8
+
+/* Roll-level trace of an explicit game list: the arguments and checks of fk_play_games, the same rows, plus per game the ordered
+ * list of its roll events — FarkleGame.play / _run_final_round (src/farkle/game/engine.py:436-550) around FarklePlayer.take_turn
+ * (:208-273), which is what `farkle watch` logs (src/farkle/simulation/watch_game.py:141-221).
+ *   rows         n_games * (4+28k) bytes, required: byte for byte the rows fk_play_games returns for the same arguments
+ *   event_begin  int64 [n_games + 1], required: game g owns events [event_begin[g], event_begin[g + 1]), in play order; games in
+ *                input order; a game without a roll (max_rounds = 0) owns an empty range
+ *   events       NULL = a counting call (rows and event_begin only); else event_capacity records.  A capacity below
+ *                event_begin[n_games] returns FK_ERR_ARG with event_begin filled, nothing stored in `events` and the needed count
+ *                in the error text (the convention of the spill and pair lists).
+ * The trace is played by its own kernel (farkle_ii_amd/csrc/fk_trace.h) from the table-free device functions — sequential dice,
+ * SWAR scorer, should_continue in points — and shares neither the score / discard tables nor the fast dice path with the game
+ * kernels: equal rows are a cross-check of those kernels through an independent path, not a recording of their lanes.  A turn of
+ * more than 1000 rolls returns FK_ERR_ROLL_LIMIT, a row counter beyond 65535 FK_ERR_COUNTER_OVERFLOW. */
+int fk_trace_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
+                   const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds,
+                   void *rows, int64_t *event_begin, fk_roll_event *events, int64_t event_capacity);
+
 /* H2H block: attempts [state[0], min(max_attempts, state[0]+chunk_games)) of (root, pair, order) in
  * attempt order until `target` completed games; state = {attempted, completed, safety, wins_seat1,
  * wins_seat2} in/out (h2h_schedule.py:1165-1235). */
