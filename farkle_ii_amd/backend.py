@@ -71,7 +71,9 @@ class _Timing(C.Structure):
     _fields_ = [("perm_ms", C.c_float), ("seed_ms", C.c_float), ("play_ms", C.c_float), ("total_ms", C.c_float),
                 ("play_launches", C.c_int32), ("play_block", C.c_int32), ("play_grid", C.c_int32),
                 ("play_lds_bytes", C.c_int32), ("games", C.c_int64), ("prefetched_chunks", C.c_int32), ("play_clock_mhz", C.c_int32),
-                ("play_block_end_p50_ms", C.c_float), ("play_block_end_max_ms", C.c_float), ("play_mixed_flags", C.c_int32)]
+                ("play_block_end_p50_ms", C.c_float), ("play_block_end_max_ms", C.c_float), ("play_mixed_flags", C.c_int32),
+                ("ho_handovers", C.c_int64), ("ho_lanes_served", C.c_int64), ("ho_trips", C.c_int64),
+                ("ho_waiting_lane_trips", C.c_int64), ("ho_rolling_lane_trips", C.c_int64), ("ho_waves", C.c_int64)]
 
 
 class FarkleHipError(RuntimeError):
@@ -87,6 +89,8 @@ def hip_sources() -> list[Path]:
 
 
 VARIANTS = {"detour": ["-DFK_FORCE_DETOUR=4"]}  # test builds: libfarkle_hip_<variant>.so beside the product library
+# measuring builds, compiled on demand (build_library(variant=...)) and never by build(): "count" fills fk_timing's ho_* hand-over counts
+TOOL_VARIANTS = {"count": ["-DFK_COUNT_HANDOVER"]}
 
 
 def library_path(variant: str | None = None) -> Path:
@@ -100,7 +104,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *(VARIANTS[variant] if variant else []), "-o", str(out),
+    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *({**VARIANTS, **TOOL_VARIANTS}[variant] if variant else []), "-o", str(out),
            *[str(s) for s in hip_sources()]]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode != 0:

@@ -175,6 +175,7 @@ struct fk_ctx {
     int32_t max_waves = 6;     // resident waves per SIMD the launch plan may count on
     int32_t lean = -1;         // -1 auto, 0 full 17-dword seat records, 1 lean 11-dword records
     int32_t gs = -1;           // -1 / 0: LDS records whenever k of them fit a wave's share of LDS, 1: state-store instances always
+    int32_t flat_handover = 1;      // 0: two-seat launches take the general hand-over (A/B, tests of the general copy of the loop nest)
     int32_t uniform_flags_opt = -1; // -1 auto (scalar-flag instance when the table allows it), 0 never
     uint32_t table_flags = 0;            // set by upload_strategies: flag bits shared by the whole table ...
     uint32_t table_mixed_flags = 0xff00u; // ... and the flag bits that differ between its strategies
@@ -944,6 +945,12 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
     const int auto_thr = sa.k >= 11 ? 16 : sa.k >= 9 ? 12 : 8;
     pa.batch_threshold = (uint32_t)std::max(1, std::min(64, c->batch_threshold > 0 ? c->batch_threshold : auto_thr));
     pa.use_lds_tally = plan.lds_tally ? 1u : 0u;
+    pa.no_flat = c->flat_handover ? 0u : 1u;
+#ifdef FK_COUNT_HANDOVER // measuring build: the hand-over counts of fk_play_kernel, six zeroed words of the chunk's misc block
+    pa.hcount = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(cs.misc.p) + 128);
+#else
+    pa.hcount = nullptr;
+#endif
     pa.clk = nullptr;
     c->clk_grid = 0;
     if (c->clock_stamps) {
@@ -1014,6 +1021,12 @@ int finish_timers(fk_ctx *c) {
 // waits for the game kernel, reads its error record and the kernel timers
 int finish_play(fk_ctx *c, const PlayArgs &pa, int64_t game_base, const char *what) {
     const int rc_dev = check_device_error(c, pa.err, game_base, what); // synchronises the main stream
+    if (pa.hcount) { // (measuring build only)
+        unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+        HIPCHK(c, hipMemcpy(h, pa.hcount, sizeof(h), hipMemcpyDeviceToHost));
+        c->timing.ho_handovers += (int64_t)h[0], c->timing.ho_lanes_served += (int64_t)h[1], c->timing.ho_trips += (int64_t)h[2];
+        c->timing.ho_waiting_lane_trips += (int64_t)h[3], c->timing.ho_rolling_lane_trips += (int64_t)h[4], c->timing.ho_waves += (int64_t)h[5];
+    }
     const int rc = finish_timers(c);
     return rc_dev ? rc_dev : rc;
 }
@@ -1579,6 +1592,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "columns_by_seat") c->columns_by_seat = (int32_t)value;
     else if (n == "pipeline") c->pipeline = (int32_t)value;
     else if (n == "uniform_flags") c->uniform_flags_opt = (int32_t)value;
+    else if (n == "flat_handover") c->flat_handover = value != 0 ? 1 : 0;
     else if (n == "matchup_sort_key_mask") c->matchup_sort_mask = (uint64_t)value;
     else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
     else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
@@ -2129,7 +2143,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         if ((rc = launch_play_stage(c, sa, pa, plan, want_state, want_recs || sq != nullptr, want_recs))) return rc;
         // The last chunk of a call without rows: its error record travels with the tally, behind the post-passes — one host
         // round trip per call instead of two (the post-passes only read; on an error their output is discarded).
-        const bool defer_check = done + chunk_sh >= n_sh_total && !rows && c->err_host;
+        const bool defer_check = done + chunk_sh >= n_sh_total && !rows && c->err_host && !pa.hcount; // (measuring builds read their counts in finish_play)
         if (defer_check) {
             HIPCHK(c, hipMemcpyAsync(c->err_host, pa.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
             deferred = true;

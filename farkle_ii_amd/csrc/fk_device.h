@@ -1133,4 +1133,60 @@ __host__ __device__ inline Advance2 advance2_table50(bool over, int32_t score, i
     return Advance2{ended, sw};
 }
 
+// ---- the end of a two-seat game on lean records (run_tournament.py:375-391, engine.py:477): who won, and the winner's ten metrics ----
+// The counter words of a lean seat record (fk_kernels.h): cA = rolls | farkles << 16, cB = highest_turn / 50 | hot_dice << 16,
+// cC = sf_uses | sf_dice << 16, cD = so_uses | so_dice << 16, cE = score / 50 | flags << 16 | strategy index << LEAN_IDX_SHIFT.
+// A two-seat game has completed iff it ended in its final round (the other way to end is the round limit; a game with max_rounds 0
+// plays no round and has no final one).  The winner is the first maximum of the scores: seat 0 wins a tie.  The metrics are in the
+// order of the tally's sum columns: winning score, rounds, farkles, rolls, highest turn, smart-five uses / dice, smart-one uses / dice,
+// hot dice (points multiplied out).  A game that has not completed has no winner: its metrics are those of seat 0 and are not used.
+// `_decoded` decodes every field of both seats and then picks; the kernels' form picks the winner's five words and decodes those.
+// tests/native/finish2_host_check.hip compares the two.
+constexpr uint32_t LEAN_IDX_SHIFT = 18;
+struct LeanCounters {
+    uint32_t cA, cB, cC, cD, cE;
+};
+struct Finish2 {
+    bool completed;
+    uint32_t winner, widx; // winner seat; the strategy index its record carries
+    uint32_t m[10];
+};
+
+__host__ __device__ inline Finish2 finish2_50_decoded(const LeanCounters &s0, const LeanCounters &s1, uint32_t rounds, uint32_t final_round,
+                                                      uint32_t max_rounds) {
+    const LeanCounters *seats[2] = {&s0, &s1};
+    uint32_t score[2], idx[2], farkles[2], rolls[2], highest[2], sf_uses[2], sf_dice[2], so_uses[2], so_dice[2], hot[2];
+    for (int s = 0; s < 2; ++s) {
+        const LeanCounters &r = *seats[s];
+        score[s] = r.cE & 0xffffu, idx[s] = r.cE >> LEAN_IDX_SHIFT;
+        rolls[s] = r.cA & 0xffffu, farkles[s] = r.cA >> 16;
+        highest[s] = r.cB & 0xffffu, hot[s] = r.cB >> 16;
+        sf_uses[s] = r.cC & 0xffffu, sf_dice[s] = r.cC >> 16;
+        so_uses[s] = r.cD & 0xffffu, so_dice[s] = r.cD >> 16;
+    }
+    Finish2 f;
+    f.completed = max_rounds != 0u && final_round != 0u;
+    f.winner = score[1] > score[0] ? 1u : 0u;
+    const uint32_t w = f.winner;
+    f.widx = idx[w];
+    f.m[0] = score[w] * 50u, f.m[1] = rounds, f.m[2] = farkles[w], f.m[3] = rolls[w], f.m[4] = highest[w] * 50u;
+    f.m[5] = sf_uses[w], f.m[6] = sf_dice[w], f.m[7] = so_uses[w], f.m[8] = so_dice[w], f.m[9] = hot[w];
+    return f;
+}
+
+__host__ __device__ inline Finish2 finish2_50(const LeanCounters &s0, const LeanCounters &s1, uint32_t rounds, uint32_t final_round,
+                                              uint32_t max_rounds) {
+    (void)max_rounds; // final_round is set by a turn, and a game with max_rounds 0 plays none
+    const bool second = (s1.cE & 0xffffu) > (s0.cE & 0xffffu);
+    const uint32_t a = second ? s1.cA : s0.cA, b = second ? s1.cB : s0.cB, c = second ? s1.cC : s0.cC, d = second ? s1.cD : s0.cD,
+                   e = second ? s1.cE : s0.cE;
+    Finish2 f;
+    f.completed = final_round != 0u;
+    f.winner = second ? 1u : 0u;
+    f.widx = e >> LEAN_IDX_SHIFT;
+    f.m[0] = (e & 0xffffu) * 50u, f.m[1] = rounds, f.m[2] = a >> 16, f.m[3] = a & 0xffffu, f.m[4] = (b & 0xffffu) * 50u;
+    f.m[5] = c & 0xffffu, f.m[6] = c >> 16, f.m[7] = d & 0xffffu, f.m[8] = d >> 16, f.m[9] = b >> 16;
+    return f;
+}
+
 } // namespace fk

@@ -33,6 +33,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 using namespace fk;
 
 namespace {
@@ -160,6 +162,9 @@ struct PlayArgs {
     uint32_t uflags;             // the flag bits (8..15) every strategy of the table shares, see MIXED below
     uint4 *cold;                 // fk_play_hc_kernel: [resident lanes][k] cold seat records (fk_play_hc.h)
     const uint8_t *lds_tables;   // fk_play_hc_kernel, LT instances: the LDS image of the score / discard tables (LT_BYTES, fk_device.h)
+    uint32_t no_flat;            // option "flat_handover" 0: the two-seat instance takes the general copy of its loop nest (fk_play_kernel)
+    unsigned long long *hcount;  // nullable; FK_COUNT_HANDOVER builds of fk_play_kernel only: [6] hand-overs, lanes served, roll trips, waiting-lane
+                                 // trips, rolling-lane trips, waves — summed over the launch's waves (fk_timing.ho_*)
     unsigned long long *clk;     // nullable (option "clock_stamps"): [grid][4] = s_memtime, s_memrealtime at the block's first and last
                                  // instruction (zeroed before the launch) — the shader clock the launch really ran at (MI355X_MICROARCH.md, DVFS give-back item 6)
 };
@@ -1237,10 +1242,179 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         else if (!GS && over) advance(score);
     };
 
+    // ---- the two-seat lean instance of tournament and game-list launches (round 10): a flat hand-over ----
+    // finish_game / init_game above serve every instance: they dispatch at run time on the launch's mode, record size, index source,
+    // schedule, overrides and outputs, seat by seat, so a game's loads form a chain (seat 0's state, its index, its strategy, then seat
+    // 1's) and the kernel arguments are re-read inside the path.  The two-seat instance takes none of the other combinations.  Here
+    // every launch-uniform choice is one bit of `ho_bits` and every base pointer a scalar, read once in front of the outer loop and pinned in
+    // SGPRs (the empty asm: the compiler may not re-load them from the argument segment inside the path); a game's independent loads —
+    // the schedule entry, both state records, both strategy indices (one dword: two adjacent u16 at an even index) and seat 0's increment
+    // — are issued together, the two strategy loads behind them: two waits.  Record addresses are 32-bit byte offsets from the scalar
+    // bases (global_load with an SGPR base); a chunk whose buffers could reach 4 GiB, or a launch whose index source is neither the
+    // index plane nor the full state record, keeps the general path (HO_FLAT clear).
+    // The end of a game is fk_device.h's finish2_50 (pure; tests/native/finish2_host_check.hip).
+    // The batched-H2H instance (BLK) keeps the general path: its index comes from the block map behind the schedule entry, a third
+    // round trip, and with the flat path it measured +0.3 % at config 5 (profiles/r10_ab_handover.txt).
+    // Option "flat_handover" 0 (PlayArgs::no_flat) sends a launch through the general copy: the A/B of the log, and the test of that copy.
+    constexpr bool FLAT2 = PK2 && !BLK;
+    static_assert(CE_IDX_SHIFT == LEAN_IDX_SHIFT, "finish2_50 reads the strategy index of a lean record");
+    enum : uint32_t { HO_LDS_TALLY = 1, HO_REC0 = 2, HO_RECS = 4, HO_GS_OUT = 8, HO_OV = 16, HO_SCHED = 32, HO_PERM = 64, HO_IDX_STATE = 128,
+                      HO_FLAT = 256 };
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    typedef __attribute__((address_space(1))) u32x4 global_u4_rw;
+    typedef const __attribute__((address_space(1))) u32x2 global_u2;
+    typedef __attribute__((address_space(1))) uint32_t global_u32;
+    uint32_t ho_bits = 0, st_rec = 0, ho_max_rounds = a.max_rounds, ho_thr = a.batch_threshold;
+    int32_t ho_beat50 = a.beat50;
+    uint64_t st_base = 0, inc_base = 0, idx_base = 0, sched_base = 0, strat_base = 0, rec0_base = 0;
+    if constexpr (FLAT2) {
+        const bool idx_state = a.state_dw == STATE_DW;
+        const bool flat = !a.no_flat && (idx_state || a.seat_idx != nullptr) && (uint64_t)a.n_games * (2u * STATE_DW * 4u) <= 0xffffffffull;
+        ho_bits = (a.use_lds_tally ? HO_LDS_TALLY : 0u) | (a.rec0 ? HO_REC0 : 0u) | (a.recs ? HO_RECS : 0u) | (a.gs_out ? HO_GS_OUT : 0u) |
+             (a.n_ov ? HO_OV : 0u) | (a.sched ? HO_SCHED : 0u) | (a.mode == MODE_PERM ? HO_PERM : 0u) | (idx_state ? HO_IDX_STATE : 0u) |
+             (flat ? HO_FLAT : 0u);
+        st_rec = a.state_dw * 4u; // bytes of one seat's state record
+        st_base = (uint64_t)(uintptr_t)a.state, inc_base = (uint64_t)(uintptr_t)a.inc, sched_base = (uint64_t)(uintptr_t)a.sched;
+        idx_base = idx_state ? st_base + R_IDX * 4u : (uint64_t)(uintptr_t)a.seat_idx;
+        strat_base = (uint64_t)(uintptr_t)a.strat, rec0_base = (uint64_t)(uintptr_t)a.rec0;
+        asm volatile("" : "+s"(ho_bits), "+s"(st_rec), "+s"(ho_max_rounds), "+s"(ho_thr), "+s"(ho_beat50), "+s"(st_base), "+s"(inc_base), "+s"(idx_base),
+                     "+s"(sched_base), "+s"(strat_base), "+s"(rec0_base));
+    }
+    auto ld1 = [](uint64_t base, uint32_t off) __attribute__((always_inline)) -> uint32_t { return *(const global_u32 *)(base + (uint64_t)off); };
+    auto ld2 = [](uint64_t base, uint32_t off) __attribute__((always_inline)) -> u32x2 { return *(global_u2 *)(base + (uint64_t)off); };
+    auto ld4 = [](uint64_t base, uint32_t off) __attribute__((always_inline)) -> u32x4 { return *(global_u4 *)(base + (uint64_t)off); };
+
+    // the game behind `ticket` into this lane: two records of five ds_write_b64, the strategies and the first turn's registers
+    auto init_game2 = [&](uint32_t ticket) __attribute__((always_inline)) {
+        // (an opaque copy of the flag word: tested here by s_bitcmp, where the compiler would otherwise keep the outcome of every test
+        // as a lane mask in an SGPR pair across the roll loop — twenty SGPRs, spilled to VGPR lanes)
+        uint32_t ho = ho_bits;
+        asm volatile("" : "+s"(ho));
+        uint32_t id = ticket, slot = ticket; // state records sit at the ticket position when there is a schedule (init_game)
+        uint32_t id_ld = 0;
+        if (ho & HO_SCHED) {
+            id_ld = ld1(sched_base, ticket * 4u);
+        } else if (ho & HO_PERM) { // no schedule: the seed kernel's walk order, shuffle-minor
+            const uint32_t sh = id / a.gps, g = id - sh * a.gps;
+            slot = g * a.n_sh + sh;
+        }
+        const uint32_t soff = slot * (2u * st_rec);
+        const u32x4 s0 = ld4(st_base, soff), s1 = ld4(st_base, soff + st_rec);
+        const u32x4 inc = ld4(inc_base, slot * 32u);
+        // index plane: seats 0 and 1 are the halves of one dword (read twice: one address form for both sources); full state records:
+        // one dword each
+        const uint32_t ioff = (ho & HO_IDX_STATE) ? soff : slot * 4u;
+        const uint32_t w0 = ld1(idx_base, ioff), w1 = ld1(idx_base, ioff + ((ho & HO_IDX_STATE) ? st_rec : 0u));
+        if (ho & HO_SCHED) id = id_ld;
+        const uint32_t idx0 = (ho & HO_IDX_STATE) ? w0 : (w0 & 0xffffu), idx1 = (ho & HO_IDX_STATE) ? w1 : (w1 >> 16);
+        u32x2 pk0 = ld2(strat_base, idx0 * 8u), pk1 = ld2(strat_base, idx1 * 8u);
+        game_id = id;
+        seed_slot = slot;
+        max_rounds = ho_max_rounds;
+        if (ho & HO_OV) { // sorted by game id: binary search
+            uint32_t lo = 0, hi = a.n_ov;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (a.ov[mid].game < id) lo = mid + 1u;
+                else hi = mid;
+            }
+            if (lo < a.n_ov && a.ov[lo].game == id) max_rounds = a.ov[lo].max_rounds;
+        }
+        uint2 *r0 = reinterpret_cast<uint2 *>(lds + lane_base), *r1 = reinterpret_cast<uint2 *>(lds + SEAT_STRIDE + lane_base);
+        r0[0] = make_uint2(s0.x, s0.y), r0[1] = make_uint2(s0.z, s0.w);
+        r0[2] = make_uint2(0u, 0u), r0[3] = make_uint2(0u, 0u), r0[4] = make_uint2(0u, idx0 << CE_IDX_SHIFT);
+        r1[0] = make_uint2(s1.x, s1.y), r1[1] = make_uint2(s1.z, s1.w);
+        r1[2] = make_uint2(0u, 0u), r1[3] = make_uint2(0u, 0u), r1[4] = make_uint2(0u, idx1 << CE_IDX_SHIFT);
+        pk0.y = (pk0.y & 0xff00u) | ((uint32_t)(int32_t)(int8_t)(pk0.y & 0xffu) << 16); // the playing form of the strategy word (above)
+        pk1.y = (pk1.y & 0xff00u) | ((uint32_t)(int32_t)(int8_t)(pk1.y & 0xffu) << 16);
+        pk_seat0 = make_uint2(pk0.x, pk0.y);
+        pk_delta = make_uint2(pk0.x ^ pk1.x, pk0.y ^ pk1.y);
+        seat = 0;
+        final_round = 0;
+        score_to_beat = ho_beat50; // engine.py:451 (units of 50)
+        // seat 0 owns the first turn (begin_turn(0))
+        own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
+        own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
+        own_thr = (int32_t)pk0.x;
+        own_bits = pk0.y;
+        own_rec = lds_addr(lane_base);
+        own_inc_at = inc_base + (uint64_t)(slot * 32u);
+        dice = 6;
+        turn_score = 0;
+        rolls_this_turn = 0;
+        const bool none = max_rounds == 0u; // `while rounds < max_rounds` never entered (engine.py:453)
+        rounds = none ? 0u : 1u;
+        st = none ? (uint32_t)ST_ENDED : (uint32_t)ST_ACTIVE;
+    };
+
+    // the lane's ended game -> LDS tallies, final state records, result record (what finish_game does, for two lean records)
+    auto finish_game2 = [&]() __attribute__((always_inline)) {
+        uint32_t ho = ho_bits; // (opaque copy, see init_game2)
+        asm volatile("" : "+s"(ho));
+        const uint2 *r0 = reinterpret_cast<const uint2 *>(lds + lane_base), *r1 = reinterpret_cast<const uint2 *>(lds + SEAT_STRIDE + lane_base);
+        const uint2 p2 = r0[2], p3 = r0[3], p4 = r0[4], q2 = r1[2], q3 = r1[3], q4 = r1[4]; // buf cA | cB cC | cD cE
+        const LeanCounters c0{p2.y, p3.x, p3.y, p4.x, p4.y}, c1{q2.y, q3.x, q3.y, q4.x, q4.y};
+        const Finish2 f = finish2_50(c0, c1, rounds, final_round, max_rounds);
+        const uint32_t idx0 = c0.cE >> CE_IDX_SHIFT, idx1 = c1.cE >> CE_IDX_SHIFT, widx = f.widx;
+        if (ho & HO_GS_OUT) { // final records of both seats -> state store, in its format (R_*): score and n_turns spelled out
+            // n_turns (seat_turns): every seat began `rounds` turns, plus the final round's one turn, which the seat that did not trigger
+            // it played and still owns; a game without rounds has no owner
+            const uint32_t last = (max_rounds != 0u && own_rec != lds_addr(lane_base)) ? 1u : 0u;
+            const uint32_t t0 = rounds + ((final_round != 0u && last == 0u) ? 1u : 0u), t1 = rounds; // seat s < (last ^ 1): only seat 0, when seat 1 triggered
+            const uint2 p0 = r0[0], p1 = r0[1], q0 = r1[0], q1 = r1[1];
+            const uint32_t soff = seed_slot * (2u * st_rec);
+            global_u4_rw *g0 = (global_u4_rw *)(st_base + (uint64_t)soff), *g1 = (global_u4_rw *)(st_base + (uint64_t)(soff + st_rec));
+            g0[0] = u32x4{p0.x, p0.y, p1.x, p1.y};
+            g0[1] = u32x4{p2.x, c0.cE & 0xffffu, c0.cA, (c0.cB & 0xffffu) | (t0 << 16)};
+            g0[2] = u32x4{c0.cC, c0.cD, (c0.cB >> 16) | (c0.cE & (CE_HAS_SCORED | CE_HAS_BUF)), idx0};
+            g1[0] = u32x4{q0.x, q0.y, q1.x, q1.y};
+            g1[1] = u32x4{q2.x, c1.cE & 0xffffu, c1.cA, (c1.cB & 0xffffu) | (t1 << 16)};
+            g1[2] = u32x4{c1.cC, c1.cD, (c1.cB >> 16) | (c1.cE & (CE_HAS_SCORED | CE_HAS_BUF)), idx1};
+        }
+        if (ho & HO_LDS_TALLY) {
+            // exposures: tournament mode counts only safety-limit exposures (completed is derived in fk_finalize_tally)
+            if (!f.completed || !(ho & HO_PERM)) {
+                const uint32_t col = f.completed ? 1u : 2u;
+                atomicAdd(&tl[idx0 * LT_COLS + col], 1ull);
+                atomicAdd(&tl[idx1 * LT_COLS + col], 1ull);
+            }
+            if (f.completed) { // the twenty sums unconditionally: adding a zero is exact, and a skip costs a branch per metric
+                unsigned long long *t = tl + widx * LT_COLS;
+                atomicAdd(&t[0], 1ull);
+#pragma unroll
+                for (int j = 0; j < 10; ++j) {
+                    atomicAdd(&t[3 + j], (unsigned long long)f.m[j]);
+                    atomicAdd(&t[13 + j], (unsigned long long)f.m[j] * f.m[j]);
+                }
+            }
+        }
+        if (ho & HO_REC0) {
+            const uint32_t d0 = f.completed ? (widx | (f.winner << 24)) : REC_SAFETY; // (no index with a safety-limit game outside block launches)
+            *(global_u32 *)(rec0_base + (uint64_t)(game_id * 4u)) = d0;
+            if (ho & HO_RECS) {
+                uint32_t m[10];
+#pragma unroll
+                for (int j = 0; j < 10; ++j) m[j] = f.completed ? f.m[j] : 0u;
+                uint4 *r = reinterpret_cast<uint4 *>(a.recs + (size_t)game_id * REC_DW);
+                r[0] = make_uint4(d0, m[0], rounds | (m[2] << 16), m[3] | (m[4] << 16)); // points: highest_turn <= 65 500 by its guard band
+                r[1] = make_uint4(m[5] | (m[6] << 16), m[7] | (m[8] << 16), m[9], 0u);
+            }
+        }
+    };
+
+#ifdef FK_COUNT_HANDOVER // measuring build (backend.TOOL_VARIANTS "count"): per-wave counts in scalars, added to a.hcount once at the wave's end
+    uint32_t cnt_handovers = 0, cnt_served = 0, cnt_trips = 0, cnt_waiting = 0, cnt_rolling = 0;
+#endif
+
     // ---- wave-level hand-over: finish ended games, deal new tickets ----
-    auto handover = [&](uint64_t waiting) {
+    // (`flat`: std::true_type in the loop of a launch that takes the flat path — the choice is made once, around the whole loop nest, see below)
+    auto handover = [&](uint64_t waiting, auto flat) {
+        constexpr bool FLAT = decltype(flat)::value;
         const bool mine = (st == ST_FRESH || st == ST_ENDED);
-        if (st == ST_ENDED) finish_game();
+        if (st == ST_ENDED) {
+            if constexpr (FLAT) finish_game2();
+            else finish_game();
+        }
         const uint32_t n = (uint32_t)__popcll(waiting);
         const uint32_t avail = pool_end - pool_next;
         uint32_t new_base = 0, new_avail = 0;
@@ -1263,8 +1437,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             uint32_t ticket = 0xffffffffu;
             if (rank < avail) ticket = pool_next + rank;
             else if (rank - avail < new_avail) ticket = new_base + (rank - avail);
-            if (ticket != 0xffffffffu) init_game(a.sched ? a.sched[ticket] : ticket, ticket);
-            else st = ST_DONE;
+            if (ticket != 0xffffffffu) {
+                if constexpr (FLAT) init_game2(ticket);
+                else init_game(a.sched ? a.sched[ticket] : ticket, ticket);
+            } else {
+                st = ST_DONE;
+            }
         }
         if (n <= avail) {
             pool_next += n;
@@ -1278,24 +1456,46 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // Two nested loops.  The inner one is the hot roll loop: a bottom-tested loop with a single back edge whose exit
     // test is wave-uniform (ballots and the v_readlane'd ticket pool), so its loop-carried registers stay put (no PHI
     // copies, no full s_waitcnt at a merge point).  The rare hand-over sits on the outer back edge.
+    // A hand-over is due when enough lanes wait to share its cost, when nobody plays, or when the wave's tickets have run out.  Round 10
+    // measured the rule without the last term (ended lanes of an exhausted wave wait for the threshold or for `!active`; hand-overs per
+    // wave 236 -> 198 at config 2): -0.7 % at config 2, inside five within-build ranges, and +1.3 % at config 5, +0.3 % at config 3 —
+    // `exhausted` is also set while the wave still holds the tickets of a partial last chunk, and those then wait for the threshold.
+    // Not kept (profiles/r10_ab_handover.txt).
     auto handover_due = [&](uint64_t waiting, uint64_t active) -> bool {
-        return waiting && (!active || (uint32_t)__popcll(waiting) >= a.batch_threshold || exhausted);
+        return waiting && (!active || (uint32_t)__popcll(waiting) >= ho_thr || exhausted);
     };
-    while (true) {
-        uint64_t waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
-        uint64_t active = __ballot(st == ST_ACTIVE);
-        if (!(waiting | active)) break; // no lane is active and none waits: the wave has drained
-        if (handover_due(waiting, active)) {
-            handover(waiting);
-            continue;
+    auto play = [&](auto flat) {
+        while (true) {
+            uint64_t waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
+            uint64_t active = __ballot(st == ST_ACTIVE);
+            if (!(waiting | active)) break; // no lane is active and none waits: the wave has drained
+            if (handover_due(waiting, active)) {
+#ifdef FK_COUNT_HANDOVER
+                cnt_handovers += 1u, cnt_served += (uint32_t)__popcll(waiting);
+#endif
+                handover(waiting, flat);
+                continue;
+            }
+            bool playing = st == ST_ACTIVE;
+            do {
+#ifdef FK_COUNT_HANDOVER
+                cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(waiting), cnt_rolling += (uint32_t)__popcll(active);
+#endif
+                if (playing) roll_step();
+                playing = st == ST_ACTIVE;
+                waiting = __ballot(st == ST_ENDED);
+                active = __ballot(playing);
+            } while (active && !handover_due(waiting, active));
         }
-        bool playing = st == ST_ACTIVE;
-        do {
-            if (playing) roll_step();
-            playing = st == ST_ACTIVE;
-            waiting = __ballot(st == ST_ENDED);
-            active = __ballot(playing);
-        } while (active && !handover_due(waiting, active));
+    };
+    // The two-seat lean instance holds the loop nest twice, and a launch runs one of them: with the flat hand-over, or — a chunk too large
+    // for 32-bit record offsets, an index source the flat path does not read — with the general one.  One loop with the choice inside
+    // the hand-over keeps the general path's launch-uniform tests alive across the roll loop, as lane masks in SGPR pairs that spill.
+    if constexpr (FLAT2) {
+        if (ho_bits & HO_FLAT) play(std::true_type{});
+        else play(std::false_type{});
+    } else {
+        play(std::false_type{});
     }
 
     if (a.use_lds_tally) {
@@ -1309,6 +1509,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             atomicAdd(&a.tally[(size_t)idx * FK_TALLY_COLS + col], v);
         }
     }
+#ifdef FK_COUNT_HANDOVER
+    if (a.hcount && lane_id() == 0u) {
+        const uint32_t c[6] = {cnt_handovers, cnt_served, cnt_trips, cnt_waiting, cnt_rolling, 1u};
+        for (int i = 0; i < 6; ++i) atomicAdd(&a.hcount[i], (unsigned long long)c[i]);
+    }
+#endif
     clock_stamp(a.clk, 1u);
 }
 

@@ -127,6 +127,9 @@ typedef struct {
                                   stretch in which the chip drains behind the longest games */
     int32_t play_mixed_flags;  /* the strategy-flag form of the last game kernel instance: 0 (every flag shared by the whole table: scalar),
                                   0xc000 (only require_both / favor_score differ) or 0xff00 (any flag may differ) */
+    /* Hand-over counts of the call's fk_play_kernel launches, summed over their waves.  Only a measuring build of the library
+     * (-DFK_COUNT_HANDOVER, never the product) fills them; 0 otherwise.  A trip is one pass of a wave through the roll loop. */
+    int64_t ho_handovers, ho_lanes_served, ho_trips, ho_waiting_lane_trips, ho_rolling_lane_trips, ho_waves;
 } fk_timing;
 
 typedef struct fk_ctx fk_ctx;
@@ -152,7 +155,8 @@ int fk_host_free(fk_ctx *ctx, void *p);
  * -1 auto, 0 full, 1 lean), "state_store" (-1 auto: seat records live in the HBM state store, with only the turn owner's staged in LDS, when
  * k of them do not fit LDS (k > 64); 0 the same; 1 always), "blocks_per_cu", "max_waves" (resident waves per SIMD the launch plan counts
  * on, default 6), "longest_first" (1 = deal
- * never-banking pairings first), "uniform_flags" (-1 auto: tables whose strategies share all flag bits run the scalar-flag
+ * never-banking pairings first), "flat_handover" (1, default: two-seat tournament and game-list launches end and start games on the flat
+ * path of fk_play_kernel; 0: on the general one, as a chunk too large for 32-bit record offsets does), "uniform_flags" (-1 auto: tables whose strategies share all flag bits run the scalar-flag
  * kernel instance, 0 never), "perm_split" (-1 auto), "columns_by_seat" (-1 auto: the column images of fk_tournament_run_columns by one thread per (game, seat) up to sixteen seats, per game beyond; 0 / 1 force), "perm_draw_wave" (-1 auto: a shuffle's Fisher-Yates draws by a whole wave in chunks of up to 32 768 shuffles, by one thread beyond; 0 / 1 force), "pipeline" (1, default: the next chunk / hinted call is prepared around the
  * current game kernel — permutations in front of it, schedule and seat seeding on a low-priority stream in its drain tail;
  * 0: every chunk is prepared on the main stream in front of its own game kernel), "hot_cold" (tournament launches of 4..12 seats on
