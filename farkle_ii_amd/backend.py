@@ -101,7 +101,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", SRC_DIR / "fk_census.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *({**VARIANTS, **TOOL_VARIANTS}[variant] if variant else []), "-o", str(out),
@@ -119,7 +119,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census"]
 _libs: dict = {}
 
 
@@ -146,6 +146,22 @@ def load_library(variant: str | None = None) -> C.CDLL:
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+CENSUS_TABLES = ("roll_cells", "strategy_dice", "strategy_turns", "turn_hist")
+CENSUS_ROLL_SHAPE = (6, 61, 7)  # dice rolled - 1, raw score / 50, raw dice used
+
+
+class _Census(C.Structure):  # fk_census
+    _fields_ = [("turn_bins", C.c_int32), ("roll_cells", C.c_void_p), ("strategy_dice", C.c_void_p), ("strategy_turns", C.c_void_p),
+                ("turn_hist", C.c_void_p)]
+
+
+def _census_tables(S: int, turn_bins: int) -> tuple[dict, _Census]:
+    """Zeroed int64 tables of a census call and the ``fk_census`` that points at them."""
+    shapes = (CENSUS_ROLL_SHAPE, (S, 6, 3), (S, 3), (S, max(int(turn_bins), 0)))
+    tables = {name: np.zeros(shape, dtype=np.int64) for name, shape in zip(CENSUS_TABLES, shapes)}
+    return tables, _Census(int(turn_bins), *(tables[name].ctypes.data for name in CENSUS_TABLES))
 
 
 def row_columns_bytes(k: int, games_per_shuffle: int) -> int:
@@ -694,6 +710,35 @@ class Engine:
         if len(events):
             self._check(self._lib.fk_trace_games(*lead, _p(events), C.c_int64(len(events))))
         return rows, begin, events
+
+    def census_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
+                     max_rounds: int = 200, turn_bins: int = 256) -> dict:
+        """``fk_census_games``: the roll census of an explicit game list — int64 ``roll_cells [6][61][7]``, ``strategy_dice [S][6][3]``,
+        ``strategy_turns [S][3]``, ``turn_hist [S][turn_bins]`` (``include/farkle_hip.h``: ``fk_census``), equal to
+        ``roll_census.RollCensus.from_events`` of what ``trace_games`` returns for the same arguments."""
+        coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
+        ss = np.ascontiguousarray(seat_strategy, dtype=np.int32).reshape(-1)
+        n = len(coords)
+        if ss.size != n * k:
+            raise ValueError("seat_strategy must hold n_games * k entries")
+        tables, census = _census_tables(len(table), turn_bins)
+        self._check(self._lib.fk_census_games(self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss), C.c_int32(k),
+                                              C.c_int32(target_score), C.c_int32(max_rounds), C.byref(census)))
+        return tables
+
+    def tournament_census(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
+                          shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                          overrides: np.ndarray | None = None, turn_bins: int = 256) -> dict:
+        """``fk_tournament_run_census``: the roll census (the tables of ``census_games``) of the games ``tournament`` plays for the same
+        range — the same permutations, seat streams and overrides."""
+        table, S, n_sh, spb, n_batches, ov, _ = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
+        tables, census = _census_tables(S, turn_bins)
+        self._check(self._lib.fk_tournament_run_census(self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed),
+                                                       C.c_uint64(shuffle_begin), C.c_uint64(max(shuffle_end, shuffle_begin)), C.c_uint32(spb),
+                                                       C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
+                                                       C.byref(census)))
+        return tables
 
     def h2h(self, seats: np.ndarray, root_seed: int, pair_id: int, order: int, target: int, max_attempts: int,
             chunk_games: int, target_score: int = 10_000, max_rounds: int = 200, overrides: np.ndarray | None = None,

@@ -72,6 +72,14 @@ def build_parser() -> argparse.ArgumentParser:
                           "last player count across_k/performance_bootstrap.parquet and across_k/performance_control_contrasts.parquet "
                           "(screening.bootstrap_replicates, delta_across_k, candidate_contribution_size, controls).  May be combined "
                           "with --all-player-batches (the same statistics launch).  Not resumable: an interrupted run asks for --force")
+    run.add_argument("--roll-census", nargs="?", const=0, type=int, default=None, metavar="SHUFFLES",
+                     help="After the run, census the rolls of the first SHUFFLES shuffles of every player count's range (default: one "
+                          "deterministic batch) on the device and hold them against the exact dice law: diagnostics/"
+                          "roll_outcome_distribution_exact.parquet and roll_summary_exact.parquet (the reference's exact ordered-roll "
+                          "enumeration), roll_outcome_distribution_observed.parquet, roll_fit.parquet (Pearson X^2 per dice count) and per "
+                          "player count <k>p_strategy_turns.parquet (farkle rates, points per turn, turn-score quantiles per strategy).  "
+                          "Needs no other flag and changes no other artifact of the run.  With several ranks, rank 0 censuses alone "
+                          "on its own GPU after the run; the other ranks take no part")
     run.add_argument("--sidecars", action="store_true",
                      help="Write <artifact>.sidecar.json (producer contract + SHA-256 / size of the artifact) beside every output")
     run.add_argument("--code-identity", metavar="COMMIT[:DIRTY_SHA256[:POLICY]]",
@@ -229,6 +237,8 @@ def main(argv: Sequence[str] | None = None) -> None:
     finally:
         if active is not None:
             active.result()
+    if args.roll_census is not None:
+        runner.run_roll_census(cfg, args.roll_census or None)
     if rank == 0:
         print({f"{k}p_games": v for k, v in out.items()})
 

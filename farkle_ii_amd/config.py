@@ -295,6 +295,25 @@ class AppConfig:
     def game_stats_rare_summary_path(self) -> Path:
         return self.results_root / "game_stats_rare_event_summary.parquet"
 
+    def roll_diagnostics_dir(self) -> Path:
+        """``diagnostics/`` of the game-stats stage (config.py:949-957), beside this engine's game-stats frames at the results root."""
+        return self.results_root / "diagnostics"
+
+    def exact_roll_distribution_path(self) -> Path:
+        return self.roll_diagnostics_dir() / "roll_outcome_distribution_exact.parquet"
+
+    def exact_roll_summary_path(self) -> Path:
+        return self.roll_diagnostics_dir() / "roll_summary_exact.parquet"
+
+    def observed_roll_distribution_path(self) -> Path:
+        return self.roll_diagnostics_dir() / "roll_outcome_distribution_observed.parquet"
+
+    def roll_fit_path(self) -> Path:
+        return self.roll_diagnostics_dir() / "roll_fit.parquet"
+
+    def strategy_turns_path(self, n: int) -> Path:
+        return self.n_dir(n) / f"{n}p_strategy_turns.parquet"
+
     def rng_max_matchup_groups(self) -> int | None:
         """``analysis.rng_max_matchup_groups`` (config.py:333, validated like :1928-1932): ``None`` or a positive integer."""
         cap = (self.opaque.get("analysis") or {}).get("rng_max_matchup_groups", 100_000)

@@ -15,6 +15,7 @@
 #include "fk_root_stability.h" // device side: two-root stability stage's bootstrap families (rates of both roots, maxima, top-N membership)
 #include "fk_seat_analysis.h"  // device side: seat-analysis stage (per-seat counts from rec0, mirrored-pair sort-and-segment reduce)
 #include "fk_trace.h"          // device side: roll-level game trace (its own table-free game loop, events at scanned offsets)
+#include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -213,6 +214,8 @@ struct fk_ctx {
     DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
     DevBuf sa_counts, sa[16];            // fk_tournament_run_seat_counts: its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
     DevBuf tr[8];                        // fk_trace_games: strategies in points, seat workspace, event counts / begins, rows, error word, events, hipcub scratch
+    DevBuf cn[3];                        // fk_census_games / fk_tournament_run_census: strategies in points, seat workspace, the four tables + error word
+    int64_t census_chunk_games = 0;      // option "census_chunk_games": > 0 caps the games of one census chunk (tests drive the chunk loop)
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -309,7 +312,7 @@ static std::vector<DevBuf *> workspace_buffers(fk_ctx *c) {
                           &cs.game_block, &cs.game_row})
             out.push_back(b);
     // (only buffers that every call sizes and ensures per chunk: c->slow — the patience table upload_strategies fills once per TABLE — is not one)
-    for (DevBuf *b : {&c->recs, &c->rec0, &c->rows, &c->rows_alt, &c->digest, &c->inv, &c->lag_v, &c->lag_tmp}) out.push_back(b);
+    for (DevBuf *b : {&c->recs, &c->rec0, &c->rows, &c->rows_alt, &c->digest, &c->inv, &c->lag_v, &c->lag_tmp, &c->cn[1]}) out.push_back(b);
     return out;
 }
 
@@ -1048,6 +1051,70 @@ int run_chunk(fk_ctx *c, const SeedArgs &sa_in, PlayArgs pa, const LaunchPlan &p
     return finish_play(c, pa, game_base, what);
 }
 
+// The permutation kernels of shuffles [d.sh0, d.sh0 + d.n_sh) into cs.perm (blocked layout, perm_at()) on `st`; the caller has
+// ensured cs.perm.  Shared by the tournament chunks and the roll census (fk_tournament_run_census).
+int launch_perm_kernels(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &d) {
+    const int32_t S = (int32_t)d.S;
+    const uint32_t n_sh = d.n_sh, slots = d.slots;
+    const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
+    const SeedPool perm_prefix = seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k);
+    int rc;
+    const size_t perm_lds = (size_t)slots * S * 2;
+    static int perm_configured = -1; // per device (a second context may sit on another GPU of this process)
+    if (perm_configured != c->device) {
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_apply_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
+        HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_parallel_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_LIMIT - 1024))); // + its static words
+        perm_configured = c->device;
+    }
+    // large tables: the draws at full occupancy first (fk_perm_draw_kernel); then either the chain-free
+    // permutation (fk_perm_parallel_kernel, one workgroup per shuffle, 14 B of LDS per strategy) or, for tables
+    // beyond its LDS reach, the bare swap chains over LDS arrays (fk_perm_apply_kernel)
+    const bool split = c->perm_split >= 1 || (c->perm_split < 0 && S >= 1024 && n_sh >= 256);
+    const size_t pp_lds = (size_t)S * 14;
+    const bool parallel = split && c->perm_split != 1 && pp_lds <= LDS_LIMIT - 1024;
+    // the draws: a wave per shuffle while the launch is small (fk_perm_wave.h: ~20 us instead of the thread-per-shuffle kernel's
+    // 1 ms latency), a thread per shuffle when there are enough shuffles to fill the chip with them
+    const bool wave_draw = c->perm_draw_wave == 1 || (c->perm_draw_wave < 0 && n_sh <= WAVE_DRAW_MAX_SH);
+    if (parallel) {
+        const uint32_t groups = ((uint32_t)S - 1u + 7u) / 8u, row_u4 = groups + 1u; // a row also holds the S results
+        rc = ensure(c, cs.draws, (size_t)n_sh * row_u4 * 16);
+        if (rc) return rc;
+        if (wave_draw)
+            hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
+                               perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
+        else
+            hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
+                               perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
+        hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), pp_lds, st,
+                           static_cast<uint4 *>(cs.draws.p), row_u4, n_sh, (uint32_t)S);
+        hipLaunchKernelGGL(fk_perm_block_kernel, dim3(((uint32_t)S + 255u) / 256u, perm_blocks), dim3(256), 0, st,
+                           static_cast<const uint16_t *>(cs.draws.p), row_u4 * 8u, n_sh, (uint32_t)S, slots,
+                           static_cast<uint16_t *>(cs.perm.p));
+    } else if (split) {
+        const uint32_t n_sh_pad = (n_sh + 63u) & ~63u, groups = ((uint32_t)S - 1u + 7u) / 8u;
+        rc = ensure(c, cs.draws, (size_t)groups * n_sh_pad * 16);
+        if (rc) return rc;
+        if (wave_draw)
+            hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
+                               perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
+        else
+            hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
+                               perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
+        hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
+                           static_cast<const uint4 *>(cs.draws.p), n_sh_pad, n_sh, (uint32_t)S, slots,
+                           static_cast<uint16_t *>(cs.perm.p));
+    } else {
+        hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
+                           perm_prefix, d.sh0, n_sh, (uint32_t)S, slots, static_cast<uint16_t *>(cs.perm.p));
+    }
+    HIPCHK(c, hipGetLastError());
+    return FK_OK;
+}
+
 // Tournament chunk into chunk set `si`: permutations of shuffles [d.sh0, d.sh0 + d.n_sh) on the main stream, then schedule +
 // seat seeding on `st`.  `sa` comes back with every pointer the game kernel and the post-passes need.
 //   st == main stream: the chunk is about to be played.
@@ -1064,65 +1131,10 @@ int prep_tournament_chunk(fk_ctx *c, int si, hipStream_t st_seed, const ChunkDes
     const int32_t S = (int32_t)d.S;
     const uint32_t n_sh = d.n_sh, slots = d.slots, gps = d.S / d.k;
     const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
-    const SeedPool perm_prefix = seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k);
     int rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2);
     if (rc) return rc;
     (void)hipEventRecord(cs.ev[0], st);
-    {
-        const size_t perm_lds = (size_t)slots * S * 2;
-        static int perm_configured = -1; // per device (a second context may sit on another GPU of this process)
-        if (perm_configured != c->device) {
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_apply_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT));
-            HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_parallel_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_LIMIT - 1024))); // + its static words
-            perm_configured = c->device;
-        }
-        // large tables: the draws at full occupancy first (fk_perm_draw_kernel); then either the chain-free
-        // permutation (fk_perm_parallel_kernel, one workgroup per shuffle, 14 B of LDS per strategy) or, for tables
-        // beyond its LDS reach, the bare swap chains over LDS arrays (fk_perm_apply_kernel)
-        const bool split = c->perm_split >= 1 || (c->perm_split < 0 && S >= 1024 && n_sh >= 256);
-        const size_t pp_lds = (size_t)S * 14;
-        const bool parallel = split && c->perm_split != 1 && pp_lds <= LDS_LIMIT - 1024;
-        // the draws: a wave per shuffle while the launch is small (fk_perm_wave.h: ~20 us instead of the thread-per-shuffle kernel's
-        // 1 ms latency), a thread per shuffle when there are enough shuffles to fill the chip with them
-        const bool wave_draw = c->perm_draw_wave == 1 || (c->perm_draw_wave < 0 && n_sh <= WAVE_DRAW_MAX_SH);
-        if (parallel) {
-            const uint32_t groups = ((uint32_t)S - 1u + 7u) / 8u, row_u4 = groups + 1u; // a row also holds the S results
-            rc = ensure(c, cs.draws, (size_t)n_sh * row_u4 * 16);
-            if (rc) return rc;
-            if (wave_draw)
-                hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
-                                   perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
-            else
-                hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
-                                   perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
-            hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), pp_lds, st,
-                               static_cast<uint4 *>(cs.draws.p), row_u4, n_sh, (uint32_t)S);
-            hipLaunchKernelGGL(fk_perm_block_kernel, dim3(((uint32_t)S + 255u) / 256u, perm_blocks), dim3(256), 0, st,
-                               static_cast<const uint16_t *>(cs.draws.p), row_u4 * 8u, n_sh, (uint32_t)S, slots,
-                               static_cast<uint16_t *>(cs.perm.p));
-        } else if (split) {
-            const uint32_t n_sh_pad = (n_sh + 63u) & ~63u, groups = ((uint32_t)S - 1u + 7u) / 8u;
-            rc = ensure(c, cs.draws, (size_t)groups * n_sh_pad * 16);
-            if (rc) return rc;
-            if (wave_draw)
-                hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
-                                   perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
-            else
-                hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
-                                   perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
-            hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
-                               static_cast<const uint4 *>(cs.draws.p), n_sh_pad, n_sh, (uint32_t)S, slots,
-                               static_cast<uint16_t *>(cs.perm.p));
-        } else {
-            hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
-                               perm_prefix, d.sh0, n_sh, (uint32_t)S, slots, static_cast<uint16_t *>(cs.perm.p));
-        }
-        HIPCHK(c, hipGetLastError());
-    }
+    if ((rc = launch_perm_kernels(c, cs, st, d))) return rc;
     (void)hipEventRecord(cs.ev[1], st);
     sa = SeedArgs{};
     sa.prefix = seed_prefix(103u /* TOURNAMENT_PLAYER */, d.root, (uint64_t)d.k);
@@ -1557,6 +1569,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "rows_chunk_games") *value = c->rows_chunk_games;
     else if (n == "rows_async") *value = c->rows_async;
     else if (n == "rows_event") *value = c->last_rows_event;
+    else if (n == "census_chunk_games") *value = c->census_chunk_games;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1596,6 +1609,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "matchup_sort_key_mask") c->matchup_sort_mask = (uint64_t)value;
     else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
     else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
+    else if (n == "census_chunk_games") c->census_chunk_games = std::max<int64_t>(value, 0);
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
             return fail(c, FK_ERR_ARG, "block must be 0, 64, 128, 256, 512, 768 (lean records only) or 1024");
@@ -2872,6 +2886,213 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
     c->timing.play_launches = 2;
     c->timing.total_ms = c->timing.play_ms;
     return FK_OK;
+}
+
+// ---- roll census (fk_census.h).  One call = the tables zeroed on the device, the games played in chunks that fit the workspace
+// budget (the per-seat workspace is [k][CN_FIELDS][chunk games]), one error word for the whole call, the tables copied out after the
+// last chunk.  Nothing of the call stays in the context but device buffers; a failed call stores nothing in the caller's tables.
+struct CensusCall {
+    size_t n_u64[4]; // elements of roll_cells, strategy_dice, strategy_turns, turn_hist
+    size_t off[5];   // their offsets in cn[2] (u64 units, the layout of fkcn::CensusArgs::tables); [4] = the error word
+};
+
+static int census_check_out(fk_ctx *c, const fk_census *out) {
+    if (!out || !out->roll_cells || !out->strategy_dice || !out->strategy_turns || !out->turn_hist)
+        return fail(c, FK_ERR_ARG, "the census and its four tables are required");
+    if (out->turn_bins < 2 || out->turn_bins > 4096) return fail(c, FK_ERR_ARG, "turn_bins must be in [2, 4096], got %d", (int)out->turn_bins);
+    return FK_OK;
+}
+
+// strategies in points, zeroed tables, error word; fills the table pointers of `a`
+static int census_begin(fk_ctx *c, const fk_strategy *table, int32_t S, int32_t k, int32_t target_score, int32_t max_rounds, const fk_census *out,
+                        CensusCall &cc, fkcn::CensusArgs &a) {
+    int rc;
+    c->timing = fk_timing{};
+    c->play_instance.clear();
+    c->pending.clear();
+    // thresholds in points, clamped as fk_trace_games clamps them
+    std::vector<int2> packed((size_t)S);
+    for (int32_t i = 0; i < S; ++i)
+        packed[(size_t)i] = make_int2(std::min(std::max(table[i].score_threshold, 0), 1 << 30), (int)pack_strategy(table[i]).y);
+    cc.n_u64[0] = fkcn::CN_CELLS;
+    cc.n_u64[1] = (size_t)S * fkcn::CN_N * fkcn::CN_DICE_COLS;
+    cc.n_u64[2] = (size_t)S * fkcn::CN_TURN_COLS;
+    cc.n_u64[3] = (size_t)S * (size_t)out->turn_bins;
+    cc.off[0] = 0;
+    cc.off[1] = fkcn::dice_offset((uint32_t)S);
+    cc.off[2] = fkcn::turns_offset((uint32_t)S);
+    cc.off[3] = fkcn::hist_offset((uint32_t)S);
+    cc.off[4] = fkcn::err_offset((uint32_t)S, (uint32_t)out->turn_bins);
+    if ((rc = ensure(c, c->cn[0], sizeof(int2) * (size_t)S))) return rc;
+    if ((rc = ensure(c, c->cn[2], 8 * (cc.off[4] + 1)))) return rc;
+    const hipStream_t st = c->stream;
+    HIPCHK(c, hipMemcpyAsync(c->cn[0].p, packed.data(), sizeof(int2) * (size_t)S, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->cn[2].p, 0, 8 * cc.off[4], st));
+    HIPCHK(c, hipMemsetAsync(static_cast<unsigned long long *>(c->cn[2].p) + cc.off[4], 0xff, 8, st)); // TR_NO_ERROR
+    HIPCHK(c, hipStreamSynchronize(st)); // `packed` goes out of scope
+    a = fkcn::CensusArgs{};
+    a.strat = static_cast<const int2 *>(c->cn[0].p);
+    a.k = (uint32_t)k;
+    a.S = (uint32_t)S;
+    a.target_score = target_score;
+    a.max_rounds = (uint32_t)max_rounds;
+    a.turn_bins = (uint32_t)out->turn_bins;
+    a.tables = static_cast<unsigned long long *>(c->cn[2].p);
+    return FK_OK;
+}
+
+// games one chunk may hold: the workspace budget over the per-game seat workspace, whole workgroups; option "census_chunk_games" caps it
+static uint64_t census_chunk_games(fk_ctx *c, int32_t k) {
+    const uint64_t per_game = (uint64_t)k * fkcn::CN_FIELDS * 4;
+    uint64_t n = (uint64_t)workspace_budget(c) / per_game / fkcn::CN_BLOCK * fkcn::CN_BLOCK;
+    n = std::min<uint64_t>(std::max<uint64_t>(n, fkcn::CN_BLOCK), (uint64_t)1 << 30);
+    if (c->census_chunk_games > 0) n = std::min<uint64_t>(n, (uint64_t)c->census_chunk_games);
+    return n;
+}
+
+// one chunk: a.n_games games from a.game_base; waits for it and reads the error word
+static int census_chunk(fk_ctx *c, fkcn::CensusArgs &a, bool list, const char *what) {
+    int rc;
+    a.n_pad = (a.n_games + fkcn::CN_BLOCK - 1u) / fkcn::CN_BLOCK * fkcn::CN_BLOCK;
+    if ((rc = ensure(c, c->cn[1], (size_t)a.k * fkcn::CN_FIELDS * a.n_pad * 4))) return rc;
+    a.ws = static_cast<uint32_t *>(c->cn[1].p);
+    const dim3 grid(a.n_pad / fkcn::CN_BLOCK), block(fkcn::CN_BLOCK);
+    {
+        Timer t(c, &c->timing.play_ms, SLOT_PLAY);
+        if (list) hipLaunchKernelGGL(fkcn::fk_census_kernel<true>, grid, block, 0, c->stream, a);
+        else hipLaunchKernelGGL(fkcn::fk_census_kernel<false>, grid, block, 0, c->stream, a);
+        HIPCHK(c, hipGetLastError());
+        t.stop();
+    }
+    unsigned long long err = fktr::TR_NO_ERROR;
+    HIPCHK(c, hipMemcpyAsync(&err, a.tables + fkcn::err_offset(a.S, a.turn_bins), 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.play_launches += 1;
+    c->timing.play_block = (int32_t)fkcn::CN_BLOCK;
+    c->timing.play_grid = (int32_t)grid.x;
+    c->timing.play_lds_bytes = (int32_t)(fkcn::CN_CELLS * 4);
+    c->timing.games += a.n_games;
+    c->timing.total_ms = c->timing.play_ms;
+    if (err != fktr::TR_NO_ERROR) {
+        const int32_t h[2] = {(err & 0xffu) == fktr::TR_ERR_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW, 0};
+        return report_device_error(c, h, (int64_t)(err >> 8), what);
+    }
+    return FK_OK;
+}
+
+static int census_end(fk_ctx *c, const CensusCall &cc, const fk_census *out) {
+    const unsigned long long *t = static_cast<const unsigned long long *>(c->cn[2].p);
+    uint64_t *dst[4] = {out->roll_cells, out->strategy_dice, out->strategy_turns, out->turn_hist};
+    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemcpyAsync(dst[i], t + cc.off[i], 8 * cc.n_u64[i], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+int fk_census_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S, const int32_t *seat_strategy,
+                    int32_t k, int32_t target_score, int32_t max_rounds, fk_census *out) {
+    if (!c) return FK_ERR_ARG;
+    if (!coords || !table || !seat_strategy) return fail(c, FK_ERR_ARG, "coords, table, seat_strategy are required");
+    if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7ffffffe / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
+    if (k > FK_MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    int rc = census_check_out(c, out);
+    if (rc) return rc;
+    for (int64_t i = 0; i < n_games * k; ++i)
+        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
+    for (int64_t i = 0; i < n_games; ++i) {
+        if (coords[i].k != (uint64_t)k) // simulation.py:438
+            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
+        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
+    }
+    if ((rc = validate_strategies(c, table, S))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    CensusCall cc{};
+    fkcn::CensusArgs a{};
+    if ((rc = census_begin(c, table, S, k, target_score, max_rounds, out, cc, a))) return rc;
+    const uint64_t chunk = census_chunk_games(c, k);
+    for (uint64_t done = 0; done < (uint64_t)n_games; done += chunk) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, (uint64_t)n_games - done);
+        if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
+        if ((rc = ensure(c, c->seatlist, sizeof(int32_t) * (size_t)n * k))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->coords.p, coords + done, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy + done * (uint64_t)k, sizeof(int32_t) * (size_t)n * k, hipMemcpyHostToDevice, c->stream));
+        a.coords = static_cast<const fk_coord *>(c->coords.p);
+        a.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+        a.n_games = n;
+        a.game_base = done;
+        if ((rc = census_chunk(c, a, true, "census"))) return rc;
+    }
+    return census_end(c, cc, out);
+}
+
+int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed, uint64_t shuffle_begin,
+                             uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score, int32_t max_rounds, const fk_override *ov,
+                             int32_t n_ov, fk_census *out) {
+    if (!c) return FK_ERR_ARG;
+    if (!strategies) return fail(c, FK_ERR_ARG, "strategies are required");
+    if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
+    if (k > FK_MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
+    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    if (shuffle_end < shuffle_begin || shuffles_per_batch == 0) return fail(c, FK_ERR_ARG, "bad shuffle range / batch size");
+    if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
+    int rc = census_check_out(c, out);
+    if (rc) return rc;
+    if ((rc = validate_strategies(c, strategies, S))) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    CensusCall cc{};
+    fkcn::CensusArgs a{};
+    if ((rc = census_begin(c, strategies, S, k, target_score, max_rounds, out, cc, a))) return rc;
+    const uint64_t n_sh_total = shuffle_end - shuffle_begin;
+    const uint32_t gps = (uint32_t)(S / k);
+    const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2))); // as tournament_run_impl
+    uint64_t chunk_sh = std::max<uint64_t>(1, census_chunk_games(c, k) / gps);
+    chunk_sh = std::min<uint64_t>(chunk_sh, (uint64_t)0x7fffffff / gps);
+    // the chunk set no prepared (hinted) tournament chunk sits in; whatever it held is void afterwards
+    const int si = c->sets[c->cur].prepared ? c->cur ^ 1 : c->cur;
+    ChunkSet &cs = c->sets[si];
+    for (uint64_t done = 0; done < n_sh_total; done += chunk_sh) {
+        const uint32_t n_sh = (uint32_t)std::min<uint64_t>(chunk_sh, n_sh_total - done);
+        const uint64_t sh0 = shuffle_begin + done;
+        // overrides that fall into this chunk -> chunk-local game ids (as tournament_run_impl: the last entry for a game wins)
+        std::vector<DevOverride> dov;
+        for (int32_t i = 0; i < n_ov; ++i) {
+            if (ov[i].root_seed != root_seed || ov[i].k_or_order != (uint32_t)k) continue;
+            if (ov[i].a < sh0 || ov[i].a >= sh0 + n_sh || ov[i].b >= gps) continue;
+            if (ov[i].max_rounds > 65535u) return fail(c, FK_ERR_ARG, "override max_rounds must be <= 65535");
+            const uint32_t game = (uint32_t)((ov[i].a - sh0) * gps + ov[i].b);
+            bool replaced = false;
+            for (auto &dv : dov)
+                if (dv.game == game) {
+                    dv.max_rounds = ov[i].max_rounds;
+                    replaced = true;
+                }
+            if (!replaced) dov.push_back(DevOverride{game, ov[i].max_rounds});
+        }
+        if ((rc = upload_overrides(c, dov))) return rc;
+        cs.prepared = false;
+        HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
+        const ChunkDesc d{c->table_epoch, root_seed, sh0, n_sh, (uint32_t)S, (uint32_t)k, 0u, 0u, slots};
+        const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
+        if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2))) return rc;
+        if ((rc = launch_perm_kernels(c, cs, c->stream, d))) return rc;
+        a.coords = nullptr;
+        a.seat_strategy = nullptr;
+        a.perm_T = static_cast<const uint16_t *>(cs.perm.p);
+        a.perm_slots = slots;
+        a.gps = gps;
+        a.root_seed = root_seed;
+        a.shuffle0 = sh0;
+        a.ov = static_cast<const DevOverride *>(c->ov.p);
+        a.n_ov = (uint32_t)dov.size();
+        a.n_games = n_sh * gps;
+        a.game_base = done * gps;
+        if ((rc = census_chunk(c, a, false, "census"))) return rc;
+    }
+    return census_end(c, cc, out);
 }
 
 // Many H2H blocks advanced together.  Each pass plays, for every block that still needs games, exactly

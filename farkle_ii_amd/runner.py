@@ -1360,6 +1360,49 @@ def _publish_rng_matchups(cfg: AppConfig, n: int, strategies: list[ThresholdStra
     os.replace(tmp, cfg.rng_group_selection_path())
 
 
+def run_roll_census(cfg: AppConfig, shuffles: int | None = None, strategies: list[ThresholdStrategy] | None = None, *,
+                    oracle_game_profile: GameProfile | None = None, turn_bins: int | None = None) -> dict:
+    """``farkle run --roll-census [SHUFFLES]``: per player count of the run, the roll census (``Engine.tournament_census``) of the first
+    ``shuffles`` shuffles of its range — default: one deterministic batch — with the run's table, seat streams, target, round limit
+    and overrides.  Rank 0 censuses alone (the other ranks return at once) and writes ``diagnostics/roll_outcome_distribution_exact
+    .parquet`` and ``roll_summary_exact.parquet`` (the reference's exact enumeration), ``roll_outcome_distribution_observed.parquet``
+    (all player counts merged as ``n_players`` 0, then each), ``roll_fit.parquet`` and ``<n>p_strategy_turns.parquet``.  Reads and
+    changes no other artifact of the run.  Returns the census per player count (rank 0; empty elsewhere)."""
+    import pyarrow as pa
+
+    from . import roll_census as rc
+
+    rank, _ = _rank_world()
+    if rank != 0:
+        return {}
+    if shuffles is not None and int(shuffles) < 1:
+        raise ValueError(f"--roll-census takes a positive number of shuffles, got {shuffles}")
+    strategies, grid_size = _resolve_strategies(cfg, strategies)
+    table = rt.pack_strategies(strategies)
+    ids = [int(s.strategy_id) for s in strategies]
+    target = oracle_game_profile.default_target_score if oracle_game_profile else 10_000
+    max_rounds = oracle_game_profile.default_max_rounds if oracle_game_profile else 200
+    ov = oracle_game_profile.tournament_overrides() if oracle_game_profile else None
+    bins = rc.DEFAULT_TURN_BINS if turn_bins is None else int(turn_bins)
+    eng = get_engine()
+    censuses: dict[int, rc.RollCensus] = {}
+    for n in cfg.sim.n_players_list:
+        n = int(n)
+        plan = _plan_workload_from_config(cfg, grid_size, n)
+        n_sh = min(int(shuffles) if shuffles is not None else int(plan.shuffles_per_batch), int(plan.required_shuffles))
+        censuses[n] = rc.RollCensus.from_engine(eng.tournament_census(table, n, cfg.sim.seed, 0, n_sh, shuffles_per_batch=plan.shuffles_per_batch,
+                                                                      target_score=target, max_rounds=max_rounds, overrides=ov, turn_bins=bins))
+        LOGGER.info("Roll census %dp: %d shuffles, %d rolls", n, n_sh, int(censuses[n].roll_cells.sum()))
+    exact_distribution, exact_summary = rc.enumerate_ordered_roll_outcomes()
+    frames = [(exact_distribution, cfg.exact_roll_distribution_path()), (exact_summary, cfg.exact_roll_summary_path()),
+              (rc.observed_table(censuses), cfg.observed_roll_distribution_path()), (rc.fit_table(censuses), cfg.roll_fit_path())]
+    frames += [(rc.strategy_turn_table(census, ids), cfg.strategy_turns_path(n)) for n, census in censuses.items()]
+    for frame, path in frames:
+        path.parent.mkdir(parents=True, exist_ok=True)
+        _write_parquet_atomic(pa.Table.from_pandas(frame, preserve_index=False), path)
+    return censuses
+
+
 def _publish_game_stats(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy], result: dict) -> None:
     """``<n>p_game_stats.parquet`` (the reference's per-k table) and ``<n>p_game_stats_sums.parquet`` (its exact histograms), and once
     every player count of the run has its sums file, the root's ``game_stats_rare_event_summary.parquet`` across them."""

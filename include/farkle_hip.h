@@ -464,6 +464,38 @@ int fk_trace_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const f
                    const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds,
                    void *rows, int64_t *event_begin, fk_roll_event *events, int64_t event_capacity);
 
+/* Roll census: exact integer tables over every roll and turn of the games of a call (farkle_ii_amd/csrc/fk_census.h).  "Raw" is the
+ * roll's maximum immediate score and its scoring dice BEFORE Smart-5 / Smart-1 discards — the reference's
+ * score_roll_cached(outcome)[:2] (src/farkle/analysis/roll_enumeration.py), whose exact law over the 6^n ordered outcomes has 127
+ * cells.  The caller owns the four tables; a call SETS them (it does not add to them) and a failed call stores nothing in them.
+ *   roll_cells      [6][61][7]      [dice rolled - 1][raw score / 50][raw dice used]: rolls
+ *   strategy_dice   [S][6][3]       for the strategy whose turn it is, by dice rolled - 1: rolls, farkles (raw score 0), rolls in which
+ *                                   every die scored (raw used == dice rolled)
+ *   strategy_turns  [S][3]          turns, turns that ended on a farkle, sum of the turns' final turn_score in points (0 after a farkle)
+ *   turn_hist       [S][turn_bins]  turns by final turn_score / 50, clamped to turn_bins - 1; 2 <= turn_bins <= 4096 */
+typedef struct {
+    int32_t turn_bins;
+    uint64_t *roll_cells;       /* [6][61][7] */
+    uint64_t *strategy_dice;    /* [S][6][3]  */
+    uint64_t *strategy_turns;   /* [S][3]     */
+    uint64_t *turn_hist;        /* [S][turn_bins] */
+} fk_census;
+
+/* The census of an explicit game list: the arguments and checks of fk_trace_games.  The tables are a pure function of the event
+ * stream fk_trace_games returns for the same arguments (a turn ends at the event without FK_EV_ROLL_AGAIN; a roll's raw cell follows
+ * from its faces), played by a kernel of its own that stores no event and no row.  The list is played in chunks that fit the
+ * context's workspace budget; option "census_chunk_games" > 0 caps a chunk (tests).  A turn of more than 1000 rolls returns
+ * FK_ERR_ROLL_LIMIT, a row counter beyond 65535 FK_ERR_COUNTER_OVERFLOW, naming the smallest offending game as fk_trace_games does. */
+int fk_census_games(fk_ctx *ctx, const fk_coord *coords, int64_t n_games, const fk_strategy *table, int32_t S,
+                    const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds, fk_census *out);
+
+/* The census of the games fk_tournament_run plays for the same range: the same permutations (made on the device by the same
+ * kernels), seat streams (namespace 103) and max_rounds overrides.  shuffles_per_batch is checked and otherwise unused: the tables
+ * cover the whole range.  Errors name the game's index in the range (shuffle - shuffle_begin) * (S / k) + game. */
+int fk_tournament_run_census(fk_ctx *ctx, const fk_strategy *strategies, int32_t S, int32_t k, uint64_t root_seed,
+                             uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch, int32_t target_score,
+                             int32_t max_rounds, const fk_override *ov, int32_t n_ov, fk_census *out);
+
 /* H2H block: attempts [state[0], min(max_attempts, state[0]+chunk_games)) of (root, pair, order) in
  * attempt order until `target` completed games; state = {attempted, completed, safety, wins_seat1,
  * wins_seat2} in/out (h2h_schedule.py:1165-1235). */
