@@ -16,12 +16,14 @@
 #include "fk_seat_analysis.h"  // device side: seat-analysis stage (per-seat counts from rec0, mirrored-pair sort-and-segment reduce)
 #include "fk_trace.h"          // device side: roll-level game trace (its own table-free game loop, events at scanned offsets)
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
+#include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -29,6 +31,7 @@
 #include <mutex>
 #include <sys/mman.h>
 #include <unordered_map>
+#include <utility>
 #include <thread>
 #include <cstdarg>
 #include <cstdio>
@@ -195,11 +198,6 @@ struct fk_ctx {
     int32_t use_lds_tally = -1;
     int32_t block = 0;
     int32_t hc = -1;           // hot / cold game kernel (fk_play_hc.h): -1 auto, 0 never, 1 whenever the table allows it
-    int32_t hc_waves = 5;      // resident waves per SIMD the plan counts on for it
-    int32_t hc_block = 256;    // its block size: 256, 768 or 1024
-    int32_t hc_tables = 1;     // 1: score / discard tables in LDS (LT instances)
-    int32_t hc_inc_regs = 1;   // 1: the seats' PCG increments in registers (k >= 5, 256-thread blocks, LDS tables)
-    int32_t hc_cl = -1;        // cold records in LDS beside the hot part (k = 3 .. 5): -1 auto (k = 4), 0 never, 1 always
     DevBuf lds_tables;         // their LDS image (fk_play_hc.h)
     DevBuf cold;
     int32_t clock_stamps = 0;  // option "clock_stamps": every game-kernel block stamps s_memtime / s_memrealtime at both ends
@@ -413,176 +411,18 @@ SeedPool seed_prefix(uint32_t purpose, uint64_t root_seed, uint64_t k) {
     return p;
 }
 
-struct LaunchPlan {
-    int block = 0, grid = 0, cus = 1;
-    mutable int launched_grid = 0; // the grid after the occupancy clamp of the launch
-    mutable const char *instance = nullptr; // the kernel instance the launch ran, as the compiler spells its template (fk_last_play_instance)
-    size_t lds = 0;
-    bool lds_tally = false;
-    bool lean = false; // 10-dword seat records (increment + strategy re-read from HBM/L2 each turn, 16-bit score / 50)
-    bool gs = false;   // state-store instance: one LDS record per lane, the others in HBM
-    bool blk = false;  // batched-H2H instance (strategy index from the lane's block index)
-    bool hc = false;   // hot / cold instance (fk_play_hc.h): 20 bytes of LDS per seat, cold records in an L2-resident plane
-    bool hc_lt = false; // ... with the score / discard tables in LDS
-    int hc_ki = 0;      // ... with every seat's PCG increment in registers (2: the four-wave instances of k = 5 .. 7)
-    bool hc_cl = false; // ... with the cold records in LDS (32 bytes per seat and lane, no plane)
-    int wpe = 4;       // waves per SIMD the chosen instance is compiled for
-    uint32_t mixed_flags = 0xff00u; // flag bits that differ between strategies of the table (selects the kernel instance)
-};
-
-constexpr size_t LDS_LIMIT = 160 * 1024;
-
-size_t play_lds_bytes(int32_t k, int block, bool lean, bool gs, bool lds_tally, int32_t S, bool blocks_mode = false) {
-    const size_t per_lane = (size_t)(lean ? LEAN_DW : NF) * 4 * (size_t)(gs ? 1 : k) + (blocks_mode ? 4 : 0);
-    return per_lane * (size_t)block + (lds_tally ? (size_t)S * LT_COLS * 8 : 0);
-}
-
-// Pick block size / record layout for the most resident lanes per CU (ties: full records, larger blocks).
-// Instances are compiled for 4 waves/SIMD (<= 128 VGPRs); the 768-thread LEAN instances for 6 (80 VGPRs): their 12 waves
-// split evenly over the 4 SIMDs, so two blocks (24 waves) co-reside.  State-store (GS) instances are chosen for k >= 3:
-// their LDS use does not grow with k.
-// Lean records carry the banked total / 50 in 16 bits: tables whose target is above 50 * LEAN_MAX_TARGET50 points play with
-// full records; block == 0 in the result = no instance fits (such a target with batched H2H, or with more seats than
-// LDS holds full records for).
-LaunchPlan plan_play(const fk_ctx *c, int32_t k, int64_t S, bool single_batch, int32_t target_score, bool blocks_mode = false) {
-    LaunchPlan best;
-    const bool lean_ok = ceil_div50(target_score) <= LEAN_MAX_TARGET50;
-    if (blocks_mode) {
-        if (!lean_ok) return best;
-        // batched H2H: the one instance built for it (768 threads, lean LDS records of both seats + block index)
-        best.block = 768;
-        best.lean = true;
-        best.blk = true;
-        best.wpe = 6;
-        best.lds = play_lds_bytes(2, 768, true, false, false, 0, true);
-        const int per_cu = c->blocks_per_cu > 0 ? std::min(2, c->blocks_per_cu) : 2;
-        best.grid = c->prop.multiProcessorCount * per_cu;
-        best.cus = c->prop.multiProcessorCount;
-        return best;
-    }
-    const bool want_tally = single_batch && !blocks_mode && (c->use_lds_tally != 0) && S <= 4096;
-    int best_lanes = -1;
-    // state-store instances only on request: measured 2x slower than LDS records at k = 4 / 8 (the per-turn record
-    // exchange is bound by L2 / Infinity-Cache request throughput); they remain the path for tables too wide for LDS
-    const bool gs_wanted = c->gs == 1;
-    for (int gs = 0; gs <= 1; ++gs) {
-        if (gs != (gs_wanted ? 1 : 0) && best_lanes >= 0) continue; // the other layout only if the wanted one does not fit
-        for (int lean = 0; lean <= 1; ++lean) {
-            if (gs && !lean) continue;
-            if (lean && !lean_ok) continue;
-            if (!gs && c->lean >= 0 && lean != c->lean) continue;
-            if (!gs && lean && !blocks_mode && S > (1 << (32 - CE_IDX_SHIFT))) continue; // strategy index must fit cE[31:18]
-            for (int block : {1024, 768, 512, 256, 128, 64}) {
-                if (gs && block != 768) continue; // (one record per lane: 768-thread blocks seat six waves per SIMD whatever k is)
-                if (c->block != 0 && block != c->block && !gs) continue;
-                if (block == 768 && !lean) continue;
-                const int wpe = (block == 768) ? 6 : 4;
-                bool tally = want_tally && play_lds_bytes(k, block, lean != 0, gs != 0, true, (int32_t)S) <= LDS_LIMIT / (gs ? 2 : 1);
-                size_t lds = play_lds_bytes(k, block, lean != 0, gs != 0, tally, (int32_t)S, blocks_mode);
-                if (lds > LDS_LIMIT) continue;
-                int per_cu = (int)(LDS_LIMIT / std::max<size_t>(lds, 1));
-                // waves per SIMD: the occupancy an instance is compiled for (WPE) is a floor, not a ceiling — every instance
-                // allocates at most 80 VGPRs, so six waves fit (launch_play_u trims the grid to the occupancy HIP reports).
-                // Measured at k = 2 / 5160 strategies: 4 waves 25.8 ms, 6 waves (80 VGPRs) 22.4 ms, 7 waves (72 VGPRs) 23.5 ms.
-                (void)wpe;
-                per_cu = std::min(per_cu, std::max(1, c->max_waves * 4 * 64 / block));
-                if (c->blocks_per_cu > 0) per_cu = std::min(per_cu, c->blocks_per_cu);
-                per_cu = std::max(per_cu, 1);
-                int lanes = (per_cu * block) * 4 + (tally ? 2 : 0) + (lean ? 0 : 1); // tie-breaks: tally, then full records
-                if (gs == (gs_wanted ? 1 : 0)) lanes += 1 << 24;                     // the wanted layout wins when it fits
-                if (lanes > best_lanes) {
-                    best_lanes = lanes;
-                    best.block = block;
-                    best.lds = lds;
-                    best.lds_tally = tally;
-                    best.lean = lean != 0;
-                    best.gs = gs != 0;
-                    best.wpe = wpe;
-                    best.grid = c->prop.multiProcessorCount * per_cu;
-                    best.cus = c->prop.multiProcessorCount;
-                }
-            }
-        }
-    }
-    return best; // feasible whenever lean records are: a GS instance needs 40 bytes of LDS per lane whatever k is
-}
-
-// The hot / cold instance (fk_play_hc.h) for a tournament launch, when the table allows it and it seats more waves than
-// the LDS-record plan: 20 bytes of LDS per seat and lane, 256-thread blocks (one wave per SIMD each).
-bool plan_play_hc(const fk_ctx *c, int32_t k, int32_t target_score, const LaunchPlan &base, LaunchPlan &out) {
-    if (c->hc == 0 || c->gs == 1 || base.lds_tally) return false;
-    if (k < 3 || k > (int32_t)HC_MAX_K || ceil_div50(target_score) > HC_MAX_TARGET50) return false;
-    const int max_waves = std::max(1, std::min(c->hc_waves, c->max_waves));
-    if (k <= 5 && (c->hc_cl > 0 || (c->hc_cl < 0 && k == 4))) {
-        // cold records in LDS: 32 k bytes per lane; six / five / four waves per SIMD at k = 3 / 4 / 5.  Auto at k = 4 only (+5 %
-        // over ten-dword records; k = 3 and k = 5 measured +-0 against ten-dword records / the register instance).  k = 4 runs four
-        // 320-thread blocks: five 256-thread blocks of 32 768 bytes do NOT fit the 160 KB once each is rounded up to the LDS
-        // allocation granule (measured: the fifth block never became resident, tools/exp_occupancy.py).
-        const int block_cl = (k == 4 && c->hc_cl != 2) ? 320 : 256; // (2: the 5 x 256 launch, for the record)
-        const int waves = k == 3 ? 6 : k == 4 ? 5 : 4;
-        const size_t lds_cl = (size_t)block_cl * 32 * (size_t)k;
-        int per_cu = (int)std::min<size_t>(LDS_LIMIT / lds_cl, (size_t)(waves * 256 / block_cl));
-        if (c->blocks_per_cu > 0) per_cu = std::min(per_cu, c->blocks_per_cu);
-        per_cu = std::max(per_cu, 1);
-        out = base;
-        out.hc = true;
-        out.hc_lt = false;
-        out.hc_ki = 0;
-        out.hc_cl = true;
-        out.lean = true;
-        out.gs = false;
-        out.blk = false;
-        out.block = block_cl;
-        out.lds = lds_cl;
-        out.wpe = per_cu * block_cl / 256;
-        out.grid = c->prop.multiProcessorCount * per_cu;
-        out.cus = c->prop.multiProcessorCount;
-        return true;
-    }
-    const bool lt = c->hc_tables != 0;
-    // register instances (increments of every seat in registers, tables in LDS).  k = 5 .. 7 run FOUR waves per SIMD — 128
-    // registers hold the increments when the packed strategies are loaded per turn instead — in whatever block size lets
-    // the hot planes and the table images fit: 4 x 256 threads at k = 5, 2 x 512 at k = 6, 1 x 1 024 at k = 7; k = 8 (hot
-    // planes alone 160 KB at four waves) stays at 3 x 256, and so does everything when the option caps the waves.
-    const bool ki = c->hc_inc_regs != 0 && lt && c->hc_block != 1024 && c->hc_block != 768;
-    const bool four = ki && k >= 5 && k <= 7 && max_waves >= 4;
-    // nine to twelve seats (round 5): ONE 768-thread block per CU = three waves per SIMD, 168 registers per lane; the hot planes (16 k bytes
-    // per lane since the buffered half word moved to the cold slot: 147 456 bytes at twelve seats) fit beside the table image
-    const bool wide = ki && k >= 9 && max_waves >= 3;
-    // the shipped library holds the plan's own instances only: k = 5 .. 7 at four waves, k = 8 at three, k = 9 .. 12 as above.  A cap below
-    // that (option max_waves) sends the call to the LDS-record kernel instead of to an instance that was not compiled.
-    if (k >= 5 && k <= 7 && !four) return false;
-    if (k == 8 && !(ki && max_waves >= 3)) return false;
-    if (k >= 9 && !wide) return false;
-    const int block = wide ? 768 : four ? (k == 5 ? 256 : k == 6 ? 512 : 1024) : ki ? 256 : (c->hc_block == 1024 || c->hc_block == 768) ? c->hc_block : 256;
-    // hot part: the generator state, 16 bytes per seat and lane (the buffered half word rides in the cold-plane slot)
-    const size_t hot_bytes = 16;
-    const size_t lds = (size_t)block * hot_bytes * (size_t)k + (lt ? LT_BYTES : 0);
-    if (lds > LDS_LIMIT) return false;
-    int per_cu = (int)std::min<size_t>(LDS_LIMIT / lds, (size_t)std::max(1, 256 * max_waves / block));
-    if (wide) per_cu = 1;
-    else if (four) per_cu = std::min(per_cu, 1024 / block);
-    else if (ki) per_cu = std::min(per_cu, k <= 4 ? 4 : 3); // 128 / 168 registers per lane
-    if (c->blocks_per_cu > 0) per_cu = std::min(per_cu, c->blocks_per_cu);
-    per_cu = std::max(per_cu, 1);
-    const int base_lanes = base.block * std::max(1, base.grid / std::max(1, base.cus));
-    // auto: k >= 5.  Measured on the 5 160-strategy grid against the LDS-record kernel in the same process (round 3,
-    // tools/exp_hc2.py, tools/exp_hc3.py): k = 8 +27 %, k = 7 +25 %, k = 6 +23 %, k = 5 +10 % games/s; k = 4 +-0 (five waves,
-    // spilling) or -2 % (four), k = 3 -7 %.
-    if (c->hc < 0 && (k < 5 || per_cu * block <= base_lanes)) return false;
-    out = base;
-    out.hc = true;
-    out.hc_lt = lt;
-    out.hc_ki = ki ? (wide ? 3 : four ? 2 : 1) : 0;
-    out.lean = true;
-    out.gs = false;
-    out.blk = false;
-    out.block = block;
-    out.lds = lds;
-    out.wpe = (per_cu * block + 255) / 256;
-    out.grid = c->prop.multiProcessorCount * per_cu;
-    out.cus = c->prop.multiProcessorCount;
-    return true;
+// the options and the device figure the launch plan (fk_plan.h) depends on
+PlanKnobs plan_knobs(const fk_ctx *c) {
+    PlanKnobs kn;
+    kn.cus = c->prop.multiProcessorCount;
+    kn.max_waves = c->max_waves;
+    kn.blocks_per_cu = c->blocks_per_cu;
+    kn.block = c->block;
+    kn.lean = c->lean;
+    kn.gs = c->gs;
+    kn.hc = c->hc;
+    kn.use_lds_tally = c->use_lds_tally;
+    return kn;
 }
 
 // LDS image of the score / discard tables (fk_play_hc.h), from the same __host__ __device__ functions that build the
@@ -593,12 +433,21 @@ std::vector<uint8_t> build_lds_tables() {
     return img;
 }
 
-template <int BLOCK, bool LEAN, int WPE, uint32_t MIXED, bool GS, bool BLK = false, int KC = 0>
-hipError_t launch_play_u(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
+constexpr size_t LDS_LIMIT = 160 * 1024; // the dynamic LDS a game-kernel launch may ask for
+static_assert(LDS_LIMIT == PLAN_LDS_LIMIT, "the launch plan (fk_plan.h) seats blocks in the LDS a launch may ask for");
+
+constexpr uint32_t MIXED_ALL = 0xff00u, MIXED_NONE = 0u, MIXED_RB_FAV = SF_REQUIRE_BOTH | SF_FAVOR_SCORE;
+constexpr uint32_t MIXED_FORMS[3] = {MIXED_NONE, MIXED_RB_FAV, MIXED_ALL};
+// the narrowest form whose MIXED set covers the flags that actually vary in this table
+inline int mixed_form(uint32_t varying) { return varying == MIXED_NONE ? 0 : (varying & ~MIXED_RB_FAV) == 0u ? 1 : 2; }
+
+// One game-kernel instance on the stream: a persistent grid of at most p.grid blocks.
+template <auto KERNEL>
+hipError_t launch_instance(const LaunchPlan &p, const PlayArgs &a, hipStream_t s, const std::string &name) {
     static int configured_dev = -1; // the dynamic-LDS ceiling of an instance is raised once per device, not per launch
     static size_t occ_lds = ~(size_t)0;
     static int occ_blocks = 0;
-    const void *fn = reinterpret_cast<const void *>(&fk_play_kernel<BLOCK, LEAN, WPE, MIXED, GS, BLK, KC>);
+    const void *fn = reinterpret_cast<const void *>(KERNEL);
     int dev = 0;
     (void)hipGetDevice(&dev);
     if (configured_dev != dev) { // a context on another device of this process: the attribute and the occupancy are per device
@@ -610,132 +459,49 @@ hipError_t launch_play_u(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) 
     const size_t lds = std::max<size_t>(p.lds, 16);
     if (occ_lds != lds) { // resident blocks per CU as the runtime counts them (registers, LDS, wave slots)
         int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, lds);
+        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, p.block, lds);
         if (e != hipSuccess) return e;
         occ_blocks = std::max(nb, 1);
         occ_lds = lds;
     }
-    // a persistent grid: blocks beyond the resident ones would only queue behind them
+    // blocks beyond the resident ones would only queue behind them
     const int grid = std::min(p.grid, occ_blocks * p.cus);
     p.launched_grid = grid;
-    static const std::string instance = [] {
-        char b[96];
-        snprintf(b, sizeof(b), "fk_play_kernel<%d, %s, %d, %uu, %s, %s, %d>", BLOCK, LEAN ? "true" : "false", WPE, MIXED,
-                 GS ? "true" : "false", BLK ? "true" : "false", KC);
-        return std::string(b);
-    }();
-    p.instance = instance.c_str();
-    hipLaunchKernelGGL((fk_play_kernel<BLOCK, LEAN, WPE, MIXED, GS, BLK, KC>), dim3((unsigned)grid), dim3(BLOCK), lds, s, a);
+    p.instance = name.c_str();
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3((unsigned)p.block), lds, s, a);
     return hipGetLastError();
 }
 
-constexpr uint32_t MIXED_ALL = 0xff00u, MIXED_NONE = 0u, MIXED_RB_FAV = SF_REQUIRE_BOTH | SF_FAVOR_SCORE;
-
-template <int BLOCK, bool LEAN, int WPE = 4, bool GS = false, bool BLK = false, int KC = 0>
-hipError_t launch_play_t(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
-    // the narrowest instance whose MIXED set covers the flags that actually vary in this table
-    if (p.mixed_flags == MIXED_NONE) return launch_play_u<BLOCK, LEAN, WPE, MIXED_NONE, GS, BLK, KC>(p, a, s);
-    if ((p.mixed_flags & ~MIXED_RB_FAV) == 0u) return launch_play_u<BLOCK, LEAN, WPE, MIXED_RB_FAV, GS, BLK, KC>(p, a, s);
-    return launch_play_u<BLOCK, LEAN, WPE, MIXED_ALL, GS, BLK, KC>(p, a, s);
+// an instance as the compiler spells its template (fk_last_play_instance; tests/kernel_instances.py parses it)
+std::string instance_name(const PlayRow &r, uint32_t mixed) {
+    auto tf = [](bool v) { return v ? "true" : "false"; };
+    char b[96];
+    if (r.hc) snprintf(b, sizeof(b), "fk_play_hc_kernel<%d, %uu, %s, %d, %d, %s, %s, %d>", r.block, mixed, tf(r.lt), r.ki, r.wpe, tf(r.pkr), tf(r.cl), r.ns);
+    else snprintf(b, sizeof(b), "fk_play_kernel<%d, %s, %d, %uu, %s, %s, %d>", r.block, tf(r.lean), r.wpe, mixed, tf(r.gs), tf(r.blk), r.kc);
+    return b;
 }
 
-template <int BLOCK, uint32_t MIXED, bool LT, int KI = 0, int WPE = 0, bool PKR = true, bool CL = false, int NS = 8>
-hipError_t launch_play_hc_u(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
-    static int configured_dev = -1; // dynamic-LDS ceiling and occupancy are per device
-    static size_t occ_lds = ~(size_t)0;
-    static int occ_blocks = 0;
-    const void *fn = reinterpret_cast<const void *>(&fk_play_hc_kernel<BLOCK, MIXED, LT, KI, WPE, PKR, CL, NS>);
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (configured_dev != dev) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_LIMIT);
-        if (e != hipSuccess) return e;
-        configured_dev = dev;
-        occ_lds = ~(size_t)0;
-    }
-    if (occ_lds != p.lds) {
-        int nb = 0;
-        hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, BLOCK, p.lds);
-        if (e != hipSuccess) return e;
-        occ_blocks = std::max(nb, 1);
-        occ_lds = p.lds;
-    }
-    const int grid = std::min(p.grid, occ_blocks * p.cus);
-    p.launched_grid = grid;
-    static const std::string instance = [] {
-        char b[96];
-        snprintf(b, sizeof(b), "fk_play_hc_kernel<%d, %uu, %s, %d, %d, %s, %s, %d>", BLOCK, MIXED, LT ? "true" : "false", KI, WPE,
-                 PKR ? "true" : "false", CL ? "true" : "false", NS);
-        return std::string(b);
-    }();
-    p.instance = instance.c_str();
-    hipLaunchKernelGGL((fk_play_hc_kernel<BLOCK, MIXED, LT, KI, WPE, PKR, CL, NS>), dim3((unsigned)grid), dim3(BLOCK), p.lds, s, a);
-    return hipGetLastError();
+// row ROW of the instance table (fk_plan.h) in flag form FORM
+template <int ROW, int FORM>
+hipError_t launch_row(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
+    constexpr PlayRow R = PLAY_ROWS[ROW];
+    constexpr uint32_t MIXED = MIXED_FORMS[FORM];
+    static const std::string name = instance_name(R, MIXED);
+    if constexpr (R.hc) return launch_instance<&fk_play_hc_kernel<R.block, MIXED, R.lt, R.ki, R.wpe, R.pkr, R.cl, R.ns>>(p, a, s, name);
+    else return launch_instance<&fk_play_kernel<R.block, R.lean, R.wpe, MIXED, R.gs, R.blk, R.kc>>(p, a, s, name);
 }
 
-template <int BLOCK, bool LT, int KI = 0, int WPE = 0, bool PKR = true, bool CL = false, int NS = 8>
-hipError_t launch_play_hc_t(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
-    if (p.mixed_flags == MIXED_NONE) return launch_play_hc_u<BLOCK, MIXED_NONE, LT, KI, WPE, PKR, CL, NS>(p, a, s);
-    if ((p.mixed_flags & ~MIXED_RB_FAV) == 0u) return launch_play_hc_u<BLOCK, MIXED_RB_FAV, LT, KI, WPE, PKR, CL, NS>(p, a, s);
-    return launch_play_hc_u<BLOCK, MIXED_ALL, LT, KI, WPE, PKR, CL, NS>(p, a, s);
+using LaunchFn = hipError_t (*)(const LaunchPlan &, const PlayArgs &, hipStream_t);
+template <size_t... I>
+constexpr std::array<LaunchFn, sizeof...(I)> launch_table(std::index_sequence<I...>) {
+    return {{&launch_row<(int)(I / 3), (int)(I % 3)>...}};
 }
 
-// The instances the launch plan can reach (plan_play_hc): k = 4 cold records in LDS (four 320-thread blocks, five waves per
-// SIMD), k = 5 .. 7 four waves per SIMD with the increments in registers, k = 8 three.  Every other variant that was built and
-// measured (profiles/HISTORY.md, section 4.9 of the round-4 document: global tables, increments / strategies loaded or held, three-wave forms, other block sizes, cold
-// records in LDS at k = 3 / 5, cold records in registers, increments in the plane) lost or tied; their code left the tree in round 6
-// (the A/B logs stay under profiles/, the sources in the repository's history).
-hipError_t launch_play_hc(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
-    if (p.hc_cl) { // cold records in LDS
-        // (77 VGPRs: a SIMD must be able to take six waves, or the 2 + 1 + 1 + 1 waves of four 320-thread blocks do not all find a
-        // slot — a 96-register build seated three blocks.  Strategies in registers as well: 26.7 against 26.5 ms, not kept)
-        if (p.block == 320 && a.k <= 4u) return launch_play_hc_t<320, false, 0, 6, false, true, 4>(p, a, s);
-        return hipErrorInvalidValue;
-    }
-    if (p.hc_ki == 3) { // nine to twelve seats: one block per CU, increments in registers, strategies loaded per turn
-        if (p.block != 768) return hipErrorInvalidValue;
-        if (a.k <= 10u) return launch_play_hc_t<768, true, 10, 3, false, false, 10>(p, a, s);
-        return launch_play_hc_t<768, true, 12, 3, false, false, 12>(p, a, s);
-    }
-    if (p.hc_ki == 2) { // four waves per SIMD: increments in registers, strategies loaded per turn
-        // (register arrays and select trees sized for the launch's own seat count: five seats take four selects per increment dword
-        // instead of six seats' five, and three index words instead of four — the reference's default configuration plays k = 5)
-        if (a.k == 5u && p.block == 256) return launch_play_hc_t<256, true, 5, 4, false, false, 6>(p, a, s);
-        if (a.k == 6u && p.block == 512) return launch_play_hc_t<512, true, 6, 4, false, false, 6>(p, a, s);
-        if (a.k == 7u && p.block == 1024) return launch_play_hc_t<1024, true, 7, 4, false>(p, a, s);
-        return hipErrorInvalidValue;
-    }
-    if (p.hc_ki && p.block == 256 && p.hc_lt) { // three waves: increments in registers, 256-thread blocks with LDS tables
-        if (a.k == 8u) return launch_play_hc_t<256, true, 8>(p, a, s);
-    }
-    return hipErrorInvalidValue;
-}
-
+// plan -> row -> instance: a plan can only name a compiled instance
 hipError_t launch_play(const LaunchPlan &p, const PlayArgs &a, hipStream_t s) {
-    if (p.lds > LDS_LIMIT) return hipErrorInvalidValue;
-    if (p.hc) return launch_play_hc(p, a, s);
-    if (p.blk) return launch_play_t<768, true, 6, false, true, 2>(p, a, s); // batched H2H: k = 2, lean LDS records
-    if (p.gs) { // state-store instances: the path of tables too wide for LDS records (k > 64); 2 x 768 threads per CU
-        if (p.block == 768) return launch_play_t<768, true, 6, true>(p, a, s);
-        return hipErrorInvalidValue;
-    }
-    if (p.lean) {
-        switch (p.block) {
-        case 1024: return launch_play_t<1024, true>(p, a, s);
-        case 768: return a.k == 2u ? launch_play_t<768, true, 6, false, false, 2>(p, a, s) : launch_play_t<768, true, 6>(p, a, s);
-        case 512: return launch_play_t<512, true>(p, a, s);
-        case 256: return launch_play_t<256, true>(p, a, s);
-        case 128: return launch_play_t<128, true>(p, a, s);
-        default: return launch_play_t<64, true>(p, a, s);
-        }
-    }
-    switch (p.block) {
-    case 1024: return launch_play_t<1024, false>(p, a, s);
-    case 512: return launch_play_t<512, false>(p, a, s);
-    case 256: return launch_play_t<256, false>(p, a, s);
-    case 128: return launch_play_t<128, false>(p, a, s);
-    default: return launch_play_t<64, false>(p, a, s);
-    }
+    static constexpr auto LAUNCH = launch_table(std::make_index_sequence<3 * N_PLAY_ROWS>{});
+    if (p.row < 0 || p.lds > LDS_LIMIT) return hipErrorInvalidValue; // (a plan without an instance: the callers refuse it first)
+    return LAUNCH[(size_t)p.row * 3 + (size_t)mixed_form(p.mixed_flags)](p, a, s);
 }
 
 // Event pairs: kernels of one chunk are enqueued back to back (no host wait between them); their timers are read
@@ -940,7 +706,7 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
     pa.inc = sa.inc;
     pa.rec0 = want_rec0 ? static_cast<uint32_t *>(c->rec0.p) : nullptr;
     pa.recs = want_recs ? static_cast<uint32_t *>(c->recs.p) : nullptr;
-    pa.gs_out = (want_state && !plan.gs) ? 1u : 0u;
+    pa.gs_out = (want_state && !plan.shape().gs) ? 1u : 0u;
     pa.ticket = static_cast<uint32_t *>(cs.misc.p);
     pa.err = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(cs.misc.p) + 16);
     // hand-over threshold: the measured optimum is 8 up to eight seats (rounds 1 - 3) and grows with the game length beyond (round 5,
@@ -973,8 +739,7 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
         HIPCHK(c, e);
         c->play_instance = lp.instance ? lp.instance : "";
         c->timing.play_grid = lp.launched_grid;
-        c->timing.play_mixed_flags = lp.mixed_flags == MIXED_NONE ? (int32_t)MIXED_NONE
-                                     : (lp.mixed_flags & ~MIXED_RB_FAV) == 0u ? (int32_t)MIXED_RB_FAV : (int32_t)MIXED_ALL;
+        c->timing.play_mixed_flags = (int32_t)MIXED_FORMS[mixed_form(lp.mixed_flags)];
         if (pa.clk) c->clk_grid = lp.launched_grid;
     }
     c->timing.play_launches += 1;
@@ -1044,7 +809,7 @@ int run_chunk(fk_ctx *c, const SeedArgs &sa_in, PlayArgs pa, const LaunchPlan &p
     HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
     (void)hipEventRecord(cs.ev[0], c->stream); // no permutations here: an empty interval
     (void)hipEventRecord(cs.ev[1], c->stream);
-    int rc = seed_stage(c, c->cur, c->stream, sa, plan.gs || want_state, true);
+    int rc = seed_stage(c, c->cur, c->stream, sa, plan.shape().gs || want_state, true);
     if (rc) return rc;
     rc = launch_play_stage(c, sa, pa, plan, want_state, want_rec0, want_recs);
     if (rc) return rc;
@@ -1924,16 +1689,12 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     if ((rc = ensure(c, c->tally, tally_bytes))) return rc;
     HIPCHK(c, hipMemsetAsync(c->tally.p, 0, tally_bytes, c->stream));
 
-    LaunchPlan plan = plan_play(c, k, S, n_batches == 1, target_score);
+    LaunchPlan plan = plan_play(plan_knobs(c), PLAN_TOURNAMENT, k, S, n_batches == 1, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: no kernel instance (lean records hold totals up to %d points; %d full records do not fit LDS)",
                     target_score, 50 * LEAN_MAX_TARGET50, (int)k);
-    {
-        LaunchPlan hc_plan;
-        if (plan_play_hc(c, k, target_score, plan, hc_plan)) plan = hc_plan;
-    }
-    if (plan.hc) c->ran_hc = true;
-    if (plan.hc && !plan.hc_cl) { // cold seat records of every lane the grid can seat
+    if (plan.shape().hc) c->ran_hc = true;
+    if (plan.shape().hc && !plan.shape().cl) { // cold seat records of every lane the grid can seat
         if ((rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k * 16))) return rc;
     }
     const GameStatsReq *gst = call.gstats; // fk_tournament_run_game_stats (null otherwise)
@@ -1966,7 +1727,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     }
 
     // chunk planning: whole shuffles per chunk inside the workspace budget
-    const size_t bytes_per_shuffle = (size_t)S * 2 + (size_t)gps * (game_workspace_bytes(k, plan.gs || want_state, want_recs, rows != nullptr) +
+    const size_t bytes_per_shuffle = (size_t)S * 2 + (size_t)gps * (game_workspace_bytes(k, plan.shape().gs || want_state, want_recs, rows != nullptr) +
                                                                     (seat_stats ? (size_t)k * 32 : 0)) // + the exposure digests
                                      + (lag ? (size_t)S * 2 : 0)                                         // + the lag value matrix row
                                      + (lag && lag->m_digest ? (size_t)gps * (10 + 2 * (size_t)k) : 0)   // + the matchup records
@@ -2039,14 +1800,14 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     }
 
     const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
-    const uint32_t state_dw = (plan.gs || want_state) ? STATE_DW : 4u;
+    const uint32_t state_dw = (plan.shape().gs || want_state) ? STATE_DW : 4u;
     auto describe = [&](uint64_t first_shuffle, uint32_t count, uint32_t dw) {
         return ChunkDesc{c->table_epoch, root_seed, first_shuffle, count, (uint32_t)S, (uint32_t)k, dw, c->longest_first ? 1u : 0u, slots};
     };
     // the hint (fk_tournament_hint_next) is for the call that FOLLOWS this one
     const bool hinted = c->hint_valid && c->hint_end > c->hint_begin;
     const uint64_t hint_begin = c->hint_begin, hint_end = c->hint_end;
-    const uint32_t hint_dw = (plan.gs || c->hint_state) ? STATE_DW : 4u;
+    const uint32_t hint_dw = (plan.shape().gs || c->hint_state) ? STATE_DW : 4u;
     c->hint_valid = false;
 
     std::vector<uint16_t> perm_host;
@@ -2740,7 +2501,7 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n_games, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy, sizeof(int32_t) * (size_t)n_games * k, hipMemcpyHostToDevice, c->stream));
 
-    LaunchPlan plan = plan_play(c, k, S, false, target_score);
+    LaunchPlan plan = plan_play(plan_knobs(c), PLAN_LIST, k, S, false, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: no kernel instance (lean records hold totals up to %d points; %d full records do not fit LDS)",
                     target_score, 50 * LEAN_MAX_TARGET50, (int)k);
@@ -3155,11 +2916,11 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
     int rc = upload_strategies(c, table.data(), n_blocks * 2);
     if (rc) return rc;
     const SeedPool seat_prefix = seed_prefix(203u /* H2H_PLAYER */, root_seed, 2u);
-    const LaunchPlan plan = plan_play(c, 2, n_blocks * 2, false, target_score, true);
+    const LaunchPlan plan = plan_play(plan_knobs(c), PLAN_H2H, 2, n_blocks * 2, false, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
                     50 * LEAN_MAX_TARGET50);
-    const uint64_t max_launch = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)workspace_budget(c) / (game_workspace_bytes(2, plan.gs, false, false) + 8), 1u << 30));
+    const uint64_t max_launch = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)workspace_budget(c) / (game_workspace_bytes(2, plan.shape().gs, false, false) + 8), 1u << 30));
     rc = ensure(c, c->block_out, (size_t)n_blocks * 4 * 8);
     if (rc) return rc;
 

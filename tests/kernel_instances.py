@@ -5,7 +5,7 @@ Every result of the engine comes from one instance of ``fk_play_kernel`` (csrc/f
 table size and the ``set_option`` values under which the launch plan picks it, plus the flag form its tables must have.  The library reports
 what it launched (``Engine.last_play_instance``) in the spelling used here: the demangled template name without its namespace.
 
-The flag form of an instance (its ``MIXED`` argument) is chosen from the strategy table (csrc/farkle_hip.hip, ``launch_play_t``):
+The flag form of an instance (its ``MIXED`` argument) is chosen from the strategy table (csrc/farkle_hip.hip, ``mixed_form``):
 ``0u`` every flag shared by the whole table, ``49152u`` only require_both / favor_score differ, ``65280u`` any other flag differs.  In the two
 narrow forms the shared flags come from the launch argument ``PlayArgs.uflags``, so ``flag_tables`` builds tables that share zeros as well
 as ones.

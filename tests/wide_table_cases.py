@@ -133,14 +133,14 @@ def constants() -> dict:
 
 
 def record_lds_bytes(k: int, block: int, lean: bool, gs: bool, tally: bool, S: int) -> int:
-    """``play_lds_bytes`` of csrc/farkle_hip.hip."""
+    """``row_lds_bytes`` of csrc/fk_plan.h for an LDS-record row, plus the LDS tally."""
     c = constants()
     return (c["LEAN_BYTES"] if lean else c["FULL_BYTES"]) * (1 if gs else k) * block + (S * c["LT_COLS"] * 8 if tally else 0)
 
 
 def plan(k: int, S: int, single_batch: bool = False, target_score: int = 10_000, lean: int = -1, state_store: int = -1,
          use_lds_tally: int = -1, max_waves: int = 6) -> dict | None:
-    """``plan_play`` of csrc/farkle_hip.hip for a tournament launch under the options a test sets (block / blocks_per_cu at their
+    """``plan_play`` of csrc/fk_plan.h (its LDS-record part) for a tournament launch under the options a test sets (block / blocks_per_cu at their
     defaults): the most resident lanes per CU; ties go to an LDS tally, then to full records, then to the larger block.  ``None``:
     no instance."""
     c = constants()
