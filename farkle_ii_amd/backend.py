@@ -101,7 +101,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_plan.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", SRC_DIR / "fk_census.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_plan.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", SRC_DIR / "fk_census.h", SRC_DIR / "fk_round_robin.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *({**VARIANTS, **TOOL_VARIANTS}[variant] if variant else []), "-o", str(out),
@@ -119,7 +119,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin"]
 _libs: dict = {}
 
 
@@ -777,6 +777,30 @@ class Engine:
         self._check(self._lib.fk_h2h_run_blocks(self._ctx, _p(blocks), C.c_int64(n), C.c_uint64(root_seed), C.c_uint64(chunk),
                                                 C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov))))
         return blocks["state"].copy()
+
+    def h2h_round_robin(self, table: np.ndarray, root_seed: int, target: int, max_attempts: int, pair_begin: int = 0,
+                        pair_end: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                        summary: np.ndarray | None = None) -> tuple[np.ndarray, np.ndarray]:
+        """Head-to-head round robin (``fk_h2h_round_robin``): pairs ``[pair_begin, pair_end)`` of ``table`` — sorted by strategy id, pairs
+        numbered as ``itertools.combinations(range(n), 2)`` — both seat orders, every block fresh and played to its terminal status.
+        Returns ``(states, summary)``: uint32 ``[pairs, 2, 5]`` = attempted, completed, safety, wins_seat1, wins_seat2 per (pair, order),
+        and int64 ``[n, 8]`` (``round_robin.SUMMARY_COLS``).  A ``summary`` handed in is added to in place (pair ranges and roots
+        accumulate) and returned."""
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE).reshape(-1)
+        n = len(table)
+        end = n * (n - 1) // 2 if pair_end is None else int(pair_end)
+        begin = int(pair_begin)
+        if summary is None:
+            summary = np.zeros((n, 8), dtype=np.int64)
+        elif not (isinstance(summary, np.ndarray) and summary.dtype == np.int64 and summary.shape == (n, 8) and summary.flags.c_contiguous):
+            raise ValueError(f"summary must be a C-contiguous int64 array of shape {(n, 8)}")
+        if min(begin, end, int(target), int(max_attempts), int(root_seed)) < 0:
+            raise ValueError("pair range, target, max_attempts and root_seed must not be negative")
+        states = np.zeros((max(end - begin, 0), 2, 5), dtype=np.uint32)
+        self._check(self._lib.fk_h2h_round_robin(self._ctx, _p(table), C.c_int32(n), C.c_uint64(root_seed), C.c_uint64(begin), C.c_uint64(end),
+                                                 C.c_uint64(target), C.c_uint64(max_attempts), C.c_int32(target_score), C.c_int32(max_rounds),
+                                                 _p(states), _p(summary)))
+        return states, summary
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
     def comm_unique_id(self) -> bytes:

@@ -1,4 +1,4 @@
-"""``farkle`` command line for the simulation path: ``run``, ``time``, ``watch`` and ``root-stability``.
+"""``farkle`` command line for the simulation path: ``run``, ``time``, ``watch``, ``root-stability`` and ``round-robin``.
 
 Mirrors ``src/farkle/cli/main.py`` (:53-140 parser, :325-470 dispatch) for the commands on this path; the
 analysis/orchestration commands of the reference are out of scope and are rejected with a clear message.
@@ -8,6 +8,7 @@ analysis/orchestration commands of the reference are out of scope and are reject
     python -m farkle_ii_amd watch --seed 42
     python -m farkle_ii_amd --config cfg.yaml watch --players 4 --shuffle 17 --game 3      (replay a tournament game of the config's grid)
     python -m farkle_ii_amd --config cfg.yaml root-stability --root-results data/results_seed_11 --root-results data/results_seed_23
+    python -m farkle_ii_amd --config cfg.yaml round-robin --block-games 2191 --strategy-ids family.txt      (every pair, both orders)
     torchrun --nproc-per-node 8 -m farkle_ii_amd --config cfg.yaml run      (one process per GPU, RCCL tally reduce)
 """
 from __future__ import annotations
@@ -112,6 +113,17 @@ def build_parser() -> argparse.ArgumentParser:
                          "DIR/root_stability/ (default: roots_<a>_<b> beside the first results root).  Settings: "
                          "screening.bootstrap_replicates, candidate_contribution_size, practical_delta_by_k, delta_across_k, "
                          "robustness.delta_seed_stability, robustness.joint_discrepancy_alpha, k_aggregation")
+    rr = sub.add_parser("round-robin", help="Head-to-head round robin: every pair of the strategy table, both seat orders, per root")
+    rr.add_argument("--block-games", type=int, required=True, metavar="N",
+                    help="Completed games every (pair, root, order) block must reach; a block plays at most "
+                         "ceil(head2head.max_attempt_multiplier x N) attempts (default multiplier 2.0)")
+    rr.add_argument("--strategy-ids", type=Path, metavar="FILE", help="Restrict the configuration's grid to these strategy ids (one per line)")
+    rr.add_argument("--pairs", metavar="BEGIN:END", help="Play this range of pair ids only (default: every pair of the table)")
+    rr.add_argument("--blocks", action="store_true", help="Also write round_robin_blocks.parquet: two rows per pair and root")
+    rr.add_argument("--out", type=Path, metavar="DIR",
+                    help="Write round_robin_pairs.parquet, round_robin_strategies.parquet and round_robin.json under DIR "
+                         "(default: <results_root>/h2h_round_robin).  Roots: sim.seed_list")
+    rr.add_argument("--force", action="store_true", help="Replace the tables of an existing output directory")
     for name in _OUT_OF_SCOPE:
         sub.add_parser(name, help="(reference command outside the simulation path)")
     return parser
@@ -170,6 +182,16 @@ def main(argv: Sequence[str] | None = None) -> None:
         return
     if args.command == "root-stability":
         written = runner.run_root_stability(cfg, args.root_results, out=args.out)
+        print({name: str(path) for name, path in written.items()})
+        return
+    if args.command == "round-robin":
+        from .round_robin import run_round_robin
+
+        try:
+            written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
+                                      out=args.out, force=args.force)
+        except (ValueError, FileExistsError) as exc:
+            raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})
         return
     if cfg.sim.seed_list is not None and len(cfg.sim.seed_list) != 1:

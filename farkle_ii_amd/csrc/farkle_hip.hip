@@ -16,6 +16,7 @@
 #include "fk_seat_analysis.h"  // device side: seat-analysis stage (per-seat counts from rec0, mirrored-pair sort-and-segment reduce)
 #include "fk_trace.h"          // device side: roll-level game trace (its own table-free game loop, events at scanned offsets)
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
+#include "fk_round_robin.h"    // device side: head-to-head round robin (window tables by unranking, generation planner, apply, summary)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 
 #include <dlfcn.h>
@@ -214,6 +215,8 @@ struct fk_ctx {
     DevBuf tr[8];                        // fk_trace_games: strategies in points, seat workspace, event counts / begins, rows, error word, events, hipcub scratch
     DevBuf cn[3];                        // fk_census_games / fk_tournament_run_census: strategies in points, seat workspace, the four tables + error word
     int64_t census_chunk_games = 0;      // option "census_chunk_games": > 0 caps the games of one census chunk (tests drive the chunk loop)
+    DevBuf rr[12];                       // fk_h2h_round_robin: table (packed, patience), window states, needs, offsets, flags, playing index, playing rows, error record, pass bounds, hipcub scratch, summary
+    int64_t rr_window_blocks = (int64_t)1 << 22; // option "rr_window_blocks": blocks of one round-robin window (even, 2 .. 2^22; scheduling only)
     DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
     DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -364,6 +367,12 @@ int validate_strategies(fk_ctx *c, const fk_strategy *s, int64_t S) {
     return FK_OK;
 }
 
+// patience class of a strategy (upload_strategies explains it)
+uint8_t patience_of(const fk_strategy &s) {
+    if (!(s.consider_dice && (s.require_both || !s.consider_score))) return 0;
+    return s.dice_threshold < 1 ? 3 : s.dice_threshold == 1 ? 2 : s.dice_threshold == 2 ? 1 : 0;
+}
+
 // The packed table (+ the per-strategy patience of the longest-first schedule) goes to the device once per TABLE: a call
 // whose table equals the resident one uploads nothing.
 int upload_strategies(fk_ctx *c, const fk_strategy *s, int64_t S) {
@@ -393,9 +402,7 @@ int upload_strategies(fk_ctx *c, const fk_strategy *s, int64_t S) {
     // score not considered).  With the same "either condition keeps rolling" rule and dice_threshold 1 / 2 it rolls
     // down to one / two dice before it may bank (2 / 1).
     std::vector<uint8_t> patience((size_t)S, 0);
-    for (int64_t i = 0; i < S; ++i)
-        if (s[i].consider_dice && (s[i].require_both || !s[i].consider_score))
-            patience[(size_t)i] = s[i].dice_threshold < 1 ? 3 : s[i].dice_threshold == 1 ? 2 : s[i].dice_threshold == 2 ? 1 : 0;
+    for (int64_t i = 0; i < S; ++i) patience[(size_t)i] = patience_of(s[i]);
     rc = ensure(c, c->slow, patience.size());
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->slow.p, patience.data(), patience.size(), hipMemcpyHostToDevice, c->stream));
@@ -1196,6 +1203,7 @@ void fk_destroy(fk_ctx *c) {
     for (DevBuf &b : c->sa) release(b);
     for (DevBuf &b : c->rootb) release(b);
     for (DevBuf &b : c->tr) release(b);
+    for (DevBuf &b : c->rr) release(b);
     for (auto &cs : c->sets) {
         for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
@@ -1335,6 +1343,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "rows_async") *value = c->rows_async;
     else if (n == "rows_event") *value = c->last_rows_event;
     else if (n == "census_chunk_games") *value = c->census_chunk_games;
+    else if (n == "rr_window_blocks") *value = c->rr_window_blocks;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1375,6 +1384,11 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
     else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
     else if (n == "census_chunk_games") c->census_chunk_games = std::max<int64_t>(value, 0);
+    else if (n == "rr_window_blocks") {
+        if (value < 2 || value > ((int64_t)1 << 22) || (value & 1))
+            return fail(c, FK_ERR_ARG, "rr_window_blocks must be even and in [2, 2^22] (a pair's two blocks share a window)");
+        c->rr_window_blocks = value;
+    }
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
             return fail(c, FK_ERR_ARG, "block must be 0, 64, 128, 256, 512, 768 (lean records only) or 1024");
@@ -3112,6 +3126,257 @@ int fk_h2h_run(fk_ctx *c, const fk_strategy seats[2], uint64_t root_seed, uint64
     memcpy(blk.state, state, sizeof(blk.state));
     const int rc = fk_h2h_run_blocks(c, &blk, 1, root_seed, chunk_games, target_score, max_rounds, ov, n_ov);
     if (rc == FK_OK) memcpy(state, blk.state, sizeof(blk.state));
+    return rc;
+}
+
+// ---- head-to-head round robin: every pair of a table in one call (device side: fk_round_robin.h) ----
+// The window / generation / pass structure is h2h_run_blocks_impl's with the host's per-block work moved to the device: the host
+// reads the generation's total, the number of playing blocks and the call's error record, then two words per pass.
+static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end,
+                                uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds, const LaunchPlan &plan,
+                                uint32_t *block_state, int64_t *summary) {
+    using namespace fkrr;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->timing = fk_timing{};
+    c->play_instance.clear();
+    c->pending.clear();
+    c->letters.clear(); // (a failed call may have left some)
+    c->mail_used = 0;
+    // the n-row table, packed, and its patience classes: uploaded once per call
+    std::vector<uint2> packed((size_t)n);
+    std::vector<uint8_t> patience((size_t)n);
+    uint32_t f_and = 0xff00u, f_or = 0u;
+    for (int32_t i = 0; i < n; ++i) {
+        packed[(size_t)i] = pack_strategy(table[i]);
+        patience[(size_t)i] = patience_of(table[i]);
+        f_and &= packed[(size_t)i].y;
+        f_or |= packed[(size_t)i].y & 0xff00u;
+    }
+    // the resident table of the other entries is replaced by window rows: whatever was prepared for it is void
+    c->strat_host.clear();
+    c->table_epoch += 1;
+    for (auto &cs : c->sets) cs.prepared = false;
+    c->hint_valid = false;
+    if (c->prep_stream) HIPCHK(c, hipStreamSynchronize(c->prep_stream));
+    c->table_mixed_flags = f_or & ~f_and; // every window's rows are rows of this table
+    c->table_flags = f_and;
+
+    const uint64_t n_pairs_call = pair_end - pair_begin;
+    const uint64_t window_pairs = std::min<uint64_t>((uint64_t)c->rr_window_blocks / 2u, n_pairs_call);
+    const uint32_t max_rows = (uint32_t)(window_pairs * 2u);
+    const uint64_t max_launch = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)workspace_budget(c) / (game_workspace_bytes(2, plan.shape().gs, false, false) + 8), 1u << 30));
+    const size_t sizes[9] = {sizeof(uint2) * (size_t)n, (size_t)n, (size_t)max_rows * RR_STATE * 4, ((size_t)max_rows + 1) * 8, ((size_t)max_rows + 1) * 8,
+                             ((size_t)max_rows + 1) * 4, ((size_t)max_rows + 1) * 4, (size_t)max_rows * 4, sizeof(RrError)};
+    int rc = FK_OK;
+    for (int b = 0; b < 9; ++b)
+        if ((rc = ensure(c, c->rr[b], sizes[b]))) return rc;
+    if (summary && (rc = ensure(c, c->rr[11], (size_t)n * RR_COLS * 8))) return rc;
+    if ((rc = ensure(c, c->strat, sizeof(uint2) * 2 * (size_t)max_rows))) return rc;
+    if ((rc = ensure(c, c->slow, 2 * (size_t)max_rows))) return rc;
+    if ((rc = ensure(c, c->block_out, (size_t)max_rows * 4 * 8))) return rc;
+    uint32_t *d_state = static_cast<uint32_t *>(c->rr[2].p);
+    unsigned long long *d_need = static_cast<unsigned long long *>(c->rr[3].p), *d_off = static_cast<unsigned long long *>(c->rr[4].p);
+    uint32_t *d_flag = static_cast<uint32_t *>(c->rr[5].p), *d_aidx = static_cast<uint32_t *>(c->rr[6].p), *d_act = static_cast<uint32_t *>(c->rr[7].p);
+    RrError *d_err = static_cast<RrError *>(c->rr[8].p);
+    {
+        size_t t64 = 0, t32 = 0;
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t64, d_need, d_off, (int)(max_rows + 1u), c->stream));
+        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t32, d_flag, d_aidx, (int)(max_rows + 1u), c->stream));
+        if ((rc = ensure(c, c->rr[10], std::max<size_t>(std::max(t64, t32), 1)))) return rc;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->rr[0].p, packed.data(), sizes[0], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->rr[1].p, patience.data(), sizes[1], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(RrError), c->stream));
+    if (summary) HIPCHK(c, hipMemsetAsync(c->rr[11].p, 0, (size_t)n * RR_COLS * 8, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors are pageable)
+
+    const SeedPool seat_prefix = seed_prefix(203u /* H2H_PLAYER */, root_seed, 2u);
+    const bool pipelined = c->pipeline != 0;
+    std::vector<uint32_t> bounds;
+    for (uint64_t pair0 = pair_begin; pair0 < pair_end; pair0 += window_pairs) {
+        const uint32_t n_pairs = (uint32_t)std::min<uint64_t>(window_pairs, pair_end - pair0), n_rows = 2u * n_pairs;
+        const dim3 rows_grid((n_rows + 1u + 255u) / 256u), b256(256);
+        hipLaunchKernelGGL(fk_rr_window_kernel, rows_grid, b256, 0, c->stream, static_cast<const uint2 *>(c->rr[0].p),
+                           static_cast<const uint8_t *>(c->rr[1].p), (uint32_t)n, pair0, n_rows, static_cast<uint2 *>(c->strat.p),
+                           static_cast<uint8_t *>(c->slow.p));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n_rows * RR_STATE * 4, c->stream)); // every block starts fresh
+        while (true) { // generations
+            hipLaunchKernelGGL(fk_rr_need_kernel, rows_grid, b256, 0, c->stream, d_state, n_rows, (uint32_t)target, (uint32_t)max_attempts, d_need, d_flag);
+            HIPCHK(c, hipGetLastError());
+            size_t tb = c->rr[10].cap;
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->rr[10].p, tb, d_need, d_off, (int)(n_rows + 1u), c->stream));
+            tb = c->rr[10].cap;
+            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->rr[10].p, tb, d_flag, d_aidx, (int)(n_rows + 1u), c->stream));
+            hipLaunchKernelGGL(fk_rr_compact_kernel, rows_grid, b256, 0, c->stream, d_flag, d_aidx, n_rows, d_act);
+            HIPCHK(c, hipGetLastError());
+            unsigned long long total = 0;
+            uint32_t n_act = 0;
+            RrError err{0u, 0u};
+            HIPCHK(c, hipMemcpyAsync(&total, d_off + n_rows, 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&n_act, d_aidx + n_rows, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(&err, d_err, sizeof(err), hipMemcpyDeviceToHost, c->stream)); // of the generation before
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            if (err.raised)
+                return fail(c, FK_ERR_HIP, "h2h block conservation failed (pair %llu, order %u)", (unsigned long long)(pair0 + (err.row >> 1)), err.row & 1u);
+            if (total == 0) break;
+            const uint64_t n_passes64 = (total + max_launch - 1) / max_launch;
+            if (n_passes64 > ((uint64_t)1 << 20))
+                return fail(c, FK_ERR_ARG, "a generation of %llu games needs more than 2^20 launches of %llu games: raise chunk_bytes or lower rr_window_blocks",
+                            total, (unsigned long long)max_launch);
+            const uint32_t n_passes = (uint32_t)n_passes64;
+            if ((rc = ensure(c, c->rr[9], (size_t)n_passes * 8))) return rc;
+            hipLaunchKernelGGL(fk_rr_pass_bounds_kernel, dim3((n_passes + 255u) / 256u), b256, 0, c->stream, d_off, d_need, d_act, n_act, total,
+                               (unsigned long long)max_launch, n_passes, static_cast<uint32_t *>(c->rr[9].p));
+            HIPCHK(c, hipGetLastError());
+            bounds.resize((size_t)n_passes * 2);
+            HIPCHK(c, hipMemcpyAsync(bounds.data(), c->rr[9].p, (size_t)n_passes * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemsetAsync(c->block_out.p, 0, (size_t)n_rows * 4 * 8, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            auto pass_games = [&](size_t i) { return (uint32_t)(std::min<uint64_t>(total, (uint64_t)(i + 1) * max_launch) - (uint64_t)i * max_launch); };
+
+            // preparation of pass `i` into chunk set `si` on stream `st`: its DevBlocks are written on the device
+            auto prepare = [&](size_t i, int si, hipStream_t st, SeedArgs &sa) -> int {
+                ChunkSet &cs = c->sets[si];
+                const uint32_t first = bounds[2 * i], nb = bounds[2 * i + 1] - first, games = pass_games(i);
+                if (bounds[2 * i + 1] <= first || bounds[2 * i + 1] > n_act) return fail(c, FK_ERR_HIP, "round-robin pass %zu has no blocks", i);
+                cs.prepared = false;
+                int rc2 = ensure(c, cs.blocks, (size_t)nb * sizeof(DevBlock));
+                if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)games * 4);
+                if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)games * 4);
+                if (rc2) return rc2;
+                hipLaunchKernelGGL(fk_rr_pass_blocks_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, st, d_off, d_act, d_state, first, nb,
+                                   (unsigned long long)((uint64_t)i * max_launch), pair0, static_cast<DevBlock *>(cs.blocks.p));
+                HIPCHK(c, hipGetLastError());
+                sa = SeedArgs{};
+                sa.prefix = seat_prefix;
+                sa.gps = 0;
+                sa.k = 2;
+                sa.n_games = games;
+                sa.blocks = static_cast<const DevBlock *>(cs.blocks.p);
+                sa.n_blocks = nb;
+                sa.game_block = static_cast<const uint32_t *>(cs.game_block.p);
+                sa.game_row = static_cast<const uint32_t *>(cs.game_row.p);
+                rc2 = seed_stage(c, si, st, sa, false, true);
+                if (rc2) return rc2;
+                HIPCHK(c, hipEventRecord(cs.ready, st));
+                cs.side = (st == c->prep_stream);
+                return FK_OK;
+            };
+
+            std::vector<SeedArgs> sas(n_passes);
+            std::vector<int> set_of(n_passes);
+            set_of[0] = c->cur;
+            HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0)); // an unused side-stream preparation may still own the set
+            (void)hipEventRecord(CSET(c).ev[0], c->stream);             // no permutations here: an empty interval
+            (void)hipEventRecord(CSET(c).ev[1], c->stream);
+            if ((rc = prepare(0, c->cur, c->stream, sas[0]))) return rc;
+            for (size_t i = 0; i < n_passes; ++i) {
+                c->cur = set_of[i];
+                HIPCHK(c, hipEventRecord(c->main_idle, c->stream)); // everything that used the other chunk set is in front of this point
+                if (i + 1 < n_passes) {
+                    set_of[i + 1] = c->cur ^ 1;
+                    if (pipelined) {
+                        HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->main_idle, 0));
+                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->prep_stream);
+                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->prep_stream);
+                        if ((rc = prepare(i + 1, c->cur ^ 1, c->prep_stream, sas[i + 1]))) return rc;
+                    }
+                }
+                PlayArgs pa{};
+                pa.strat = static_cast<const uint2 *>(c->strat.p);
+                pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
+                pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
+                pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
+                pa.game_block = sas[i].game_row; // the kernel wants table rows: seat s of a game plays strategy 2 * row + s
+                pa.ov = nullptr;
+                pa.n_ov = 0;
+                pa.mode = MODE_BLOCKS;
+                pa.n_games = sas[i].n_games;
+                pa.gps = 1;
+                pa.n_sh = 1;
+                pa.k = 2;
+                pa.S = n_rows * 2u;
+                pa.target50 = ceil_div50(target_score);
+                pa.beat50 = floor_div50(target_score);
+                pa.max_rounds = (uint32_t)max_rounds;
+                HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0));
+                if ((rc = launch_play_stage(c, sas[i], pa, plan, false, true, false))) return rc;
+                hipLaunchKernelGGL(fk_h2h_reduce_kernel, dim3((pa.n_games + 256u * H2H_RUN - 1u) / (256u * H2H_RUN)), dim3(256), 0, c->stream,
+                                   static_cast<const uint32_t *>(c->rec0.p), pa.n_games, n_rows, static_cast<unsigned long long *>(c->block_out.p));
+                HIPCHK(c, hipGetLastError());
+                if (!pipelined) {
+                    if ((rc = finish_play(c, pa, 0, "h2h attempt (pass-local index)"))) return rc;
+                    if (i + 1 < n_passes) {
+                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->stream);
+                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->stream);
+                        if ((rc = prepare(i + 1, c->cur ^ 1, c->stream, sas[i + 1]))) return rc;
+                    }
+                } else {
+                    // the pass's error record and timers are read before the next launch reuses the kernel timer events
+                    HIPCHK(c, hipMemcpyAsync(c->err_host, pa.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+                    HIPCHK(c, hipStreamSynchronize(c->stream));
+                    rc = report_device_error(c, c->err_host, 0, "h2h attempt (pass-local index)");
+                    const int rc_t = finish_timers(c);
+                    if (rc) return rc;
+                    if (rc_t) return rc_t;
+                }
+            }
+            hipLaunchKernelGGL(fk_rr_apply_kernel, rows_grid, b256, 0, c->stream, d_state, d_need, static_cast<const unsigned long long *>(c->block_out.p),
+                               n_rows, d_err);
+            HIPCHK(c, hipGetLastError());
+        }
+        if (summary) {
+            hipLaunchKernelGGL(fk_rr_summary_kernel, dim3((n_pairs + 255u) / 256u), b256, 0, c->stream, d_state, (uint32_t)n, pair0, n_pairs,
+                               (uint32_t)target, static_cast<unsigned long long *>(c->rr[11].p));
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(block_state + (size_t)(pair0 - pair_begin) * 2 * RR_STATE, d_state, (size_t)n_rows * RR_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // the next window reuses the device buffers
+    }
+    if (summary) { // added to the caller's buffer only when the whole call has succeeded
+        std::vector<int64_t> add((size_t)n * RR_COLS);
+        HIPCHK(c, hipMemcpy(add.data(), c->rr[11].p, add.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < add.size(); ++i) summary[i] += add[i];
+    }
+    c->timing.total_ms = c->timing.seed_ms + c->timing.play_ms;
+    return FK_OK;
+}
+
+int fk_h2h_round_robin(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                       uint64_t max_attempts, int32_t target_score, int32_t max_rounds, uint32_t *block_state, int64_t *summary) {
+    if (!c) return FK_ERR_ARG;
+    if (!table) return fail(c, FK_ERR_ARG, "the strategy table is required");
+    if (n < 2) return fail(c, FK_ERR_ARG, "a round robin needs at least two strategies, got %d", (int)n);
+    const uint64_t all_pairs = (uint64_t)n * (uint64_t)(n - 1) / 2u;
+    if (pair_begin > pair_end || pair_end > all_pairs)
+        return fail(c, FK_ERR_ARG, "pair range [%llu, %llu) is not inside the %llu pairs of %d strategies", (unsigned long long)pair_begin,
+                    (unsigned long long)pair_end, (unsigned long long)all_pairs, (int)n);
+    if (target == 0 || target > max_attempts || max_attempts > 0x7fffffffull)
+        return fail(c, FK_ERR_ARG, "target must be in [1, max_attempts] and max_attempts at most 2^31 - 1");
+    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    const LaunchPlan plan = plan_play(plan_knobs(c), PLAN_H2H, 2, 4, false, target_score);
+    if (plan.block == 0)
+        return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
+                    50 * LEAN_MAX_TARGET50);
+    int rc = validate_strategies(c, table, n);
+    if (rc) return rc;
+    if (pair_begin == pair_end) return FK_OK; // an empty range touches nothing
+    if (!block_state) return fail(c, FK_ERR_ARG, "block_state is required");
+    c->oom = false;
+    c->oom_replays = 0;
+    c->chunk_limit = 0;
+    rc = h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
+    // no in/out state: the replay after an out-of-memory failure is the call again with half the budget
+    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
+        c->oom = false;
+        ++c->oom_replays;
+        release_workspace(c);
+        c->chunk_limit = c->last_budget / 2;
+        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
+        rc = h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
+    }
+    c->chunk_limit = 0;
     return rc;
 }
 

@@ -520,6 +520,35 @@ typedef struct {
 int fk_h2h_run_blocks(fk_ctx *ctx, fk_h2h_block *blocks, int64_t n_blocks, uint64_t root_seed, uint64_t chunk_games,
                       int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov);
 
+/* Head-to-head round robin: pairs [pair_begin, pair_end) of an n-row table, both seat orders, every (pair, order) block fresh and
+ * played to its terminal status by the prefix rule (h2h_schedule.py:1172-1235): attempts 0, 1, ... in order until `target` games
+ * have completed or `max_attempts` attempts are used.
+ *   pair_id      the position of (i, j), i < j, in itertools.combinations(range(n), 2), as _schedule_frame numbers the pairs of
+ *                sorted(candidates) (h2h_schedule.py:564): the caller passes the table sorted by strategy id
+ *   seats        order 0 seats table[i] in seat 1 and table[j] in seat 2, order 1 swaps them (:567-568); seat streams from
+ *                namespace 203 with (root_seed, k = 2, pair_id, order, attempt_index, seat), as fk_h2h_run_blocks
+ *   block_state  written: [pair_end - pair_begin][2 orders][FK_RR_STATE_COLS] = attempted, completed, safety, wins_seat1,
+ *                wins_seat2 — word for word what fk_h2h_run_blocks returns for a fresh block with these seats, pair_id, order,
+ *                target and max_attempts at chunk_games = max_attempts
+ *   summary      nullable, ADDED to (pair ranges and roots accumulate in the caller's buffer; nothing is added when the call
+ *                fails): [n][FK_RR_SUMMARY_COLS] over the pairs of the range that contain strategy s, both orders —
+ *                0 pairs | 1 pairs_resolved (both blocks reached target) | 2 games_completed | 3 games_safety | 4 wins (of s) |
+ *                5 seat1_games_completed (s in seat 1) | 6 seat1_wins | 7 pairs_ahead (resolved pairs in which s won more games
+ *                over both orders than its opponent)
+ * Nothing per block crosses the bus on the way in: the table is uploaded once and the device unranks pair ids, plans its own
+ * generations and passes (fk_round_robin.h) in windows of option "rr_window_blocks" blocks (even, 2 .. 2^22, default 2^22 — a
+ * scheduling choice only, results are identical for every setting).  FK_ERR_ARG before any device work: n < 2; pair_begin >
+ * pair_end or pair_end > n (n - 1) / 2; target == 0, target > max_attempts or max_attempts > 2^31 - 1; max_rounds outside
+ * [0, 65535]; a target_score the batched H2H instance cannot play; an invalid strategy.  An empty range returns FK_OK and
+ * touches nothing.  fk_timing and fk_last_play_instance are filled as for fk_h2h_run_blocks; an out-of-memory failure replays
+ * the whole call with half the workspace budget.  max_rounds overrides (fk_override) are not part of this entry: they are a
+ * test-oracle device keyed to one planned schedule (use fk_h2h_run_blocks for those). */
+#define FK_RR_STATE_COLS 5
+#define FK_RR_SUMMARY_COLS 8
+int fk_h2h_round_robin(fk_ctx *ctx, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin,
+                       uint64_t pair_end, uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds,
+                       uint32_t *block_state, int64_t *summary);
+
 /* ---- multi-GPU: one process per GPU, one context per process, ONE exchange ----
  * The (seed x shuffle x game) space partitions with no data dependency; the only collective of the path is the integer
  * SUM of the per-strategy tally to one rank — the analogue of OutcomeCounter.absorb + _reduce_metric_chunk_payloads
