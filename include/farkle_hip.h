@@ -38,7 +38,15 @@ enum {
     FK_OK = 0,
     FK_ERR_ROLL_LIMIT = -1,       /* a turn exceeded 1000 rolls (engine.py:36,242) */
     FK_ERR_ARG = -2,              /* invalid argument */
-    FK_ERR_COUNTER_OVERFLOW = -3, /* a per-seat u16 counter left its guarded range */
+    FK_ERR_COUNTER_OVERFLOW = -3, /* a per-seat u16 counter left its guarded range: the game kernels stop a game whose seat holds more
+                                   * than 64 000 rolls or more than 63 000 returned dice of either kind (n_smart_five_dice,
+                                   * n_smart_one_dice), or whose turn is worth more than 65 500 points; fk_trace_games and the census
+                                   * entries refuse a game with a row counter beyond 65 535.  The message names one offending game (its
+                                   * index in the call, or in the launch for head-to-head attempts; trace and census: the smallest).
+                                   * After this error the contents of the call's output buffers are
+                                   * unspecified; buffers a call ADDS to (the resident tally accumulator, the summary of
+                                   * fk_h2h_round_robin) are untouched, and the context serves the next call as if the failed one had
+                                   * not been made (a hint given for it is spent). */
     FK_ERR_HIP = -4,              /* HIP runtime failure */
     FK_ERR_NO_DEVICE = -5,
     FK_ERR_COMM = -6,             /* RCCL not loadable / communicator failure */
