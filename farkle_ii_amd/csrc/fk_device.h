@@ -1174,19 +1174,36 @@ __host__ __device__ inline Finish2 finish2_50_decoded(const LeanCounters &s0, co
     return f;
 }
 
+// The kernels' form in two steps (round 11), so that a kernel reads the loser's score word and nothing else of its record: who won, from
+// the two cE words; then the metrics, from the winner's five words.  finish2_50 is the two put together.
+__host__ __device__ inline bool finish2_second(uint32_t cE0, uint32_t cE1) { return (cE1 & 0xffffu) > (cE0 & 0xffffu); }
+
+__host__ __device__ inline Finish2 finish2_50_winner(const LeanCounters &w, bool second, uint32_t rounds, uint32_t final_round) {
+    Finish2 f;
+    f.completed = final_round != 0u; // final_round is set by a turn, and a game with max_rounds 0 plays none
+    f.winner = second ? 1u : 0u;
+    f.widx = w.cE >> LEAN_IDX_SHIFT;
+    f.m[0] = (w.cE & 0xffffu) * 50u, f.m[1] = rounds, f.m[2] = w.cA >> 16, f.m[3] = w.cA & 0xffffu, f.m[4] = (w.cB & 0xffffu) * 50u;
+    f.m[5] = w.cC & 0xffffu, f.m[6] = w.cC >> 16, f.m[7] = w.cD & 0xffffu, f.m[8] = w.cD >> 16, f.m[9] = w.cB >> 16;
+    return f;
+}
+
 __host__ __device__ inline Finish2 finish2_50(const LeanCounters &s0, const LeanCounters &s1, uint32_t rounds, uint32_t final_round,
                                               uint32_t max_rounds) {
-    (void)max_rounds; // final_round is set by a turn, and a game with max_rounds 0 plays none
-    const bool second = (s1.cE & 0xffffu) > (s0.cE & 0xffffu);
-    const uint32_t a = second ? s1.cA : s0.cA, b = second ? s1.cB : s0.cB, c = second ? s1.cC : s0.cC, d = second ? s1.cD : s0.cD,
-                   e = second ? s1.cE : s0.cE;
-    Finish2 f;
-    f.completed = final_round != 0u;
-    f.winner = second ? 1u : 0u;
-    f.widx = e >> LEAN_IDX_SHIFT;
-    f.m[0] = (e & 0xffffu) * 50u, f.m[1] = rounds, f.m[2] = a >> 16, f.m[3] = a & 0xffffu, f.m[4] = (b & 0xffffu) * 50u;
-    f.m[5] = c & 0xffffu, f.m[6] = c >> 16, f.m[7] = d & 0xffffu, f.m[8] = d >> 16, f.m[9] = b >> 16;
-    return f;
+    (void)max_rounds;
+    const bool second = finish2_second(s0.cE, s1.cE);
+    return finish2_50_winner(second ? s1 : s0, second, rounds, final_round);
+}
+
+// The tally's sums of squares.  Eight of the ten metrics are 16-bit fields of the record (m[2], m[3], m[5..9]) or the round count (m[1] <=
+// max_rounds <= 65 535, checked where a call enters the library): value <= 65 535, square <= 65 535^2 = 4 294 836 225 < 2^32, so one 24-bit
+// multiply gives the whole square and the addend's high half is zero.  The two point-valued metrics (m[0], m[4]: a 16-bit field times 50,
+// up to 3 276 750 < 2^24) keep the 64-bit product.  tests/native/finish2_short_host_check.hip asserts both bounds at the field maxima.
+constexpr uint32_t FINISH2_POINT_METRICS = (1u << 0) | (1u << 4);
+__host__ __device__ inline uint64_t finish2_square(uint32_t j, uint32_t v) {
+    if ((FINISH2_POINT_METRICS >> j) & 1u) return (uint64_t)v * v;
+    const uint32_t x = v & 0xffffu; // (the bound restated for the compiler: it then takes the 24-bit multiply by itself)
+    return (uint64_t)(uint32_t)(x * x);
 }
 
 } // namespace fk

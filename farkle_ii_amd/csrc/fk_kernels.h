@@ -1351,17 +1351,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     auto finish_game2 = [&]() __attribute__((always_inline)) {
         uint32_t ho = ho_bits; // (opaque copy, see init_game2)
         asm volatile("" : "+s"(ho));
-        const uint2 *r0 = reinterpret_cast<const uint2 *>(lds + lane_base), *r1 = reinterpret_cast<const uint2 *>(lds + SEAT_STRIDE + lane_base);
-        const uint2 p2 = r0[2], p3 = r0[3], p4 = r0[4], q2 = r1[2], q3 = r1[3], q4 = r1[4]; // buf cA | cB cC | cD cE
-        const LeanCounters c0{p2.y, p3.x, p3.y, p4.x, p4.y}, c1{q2.y, q3.x, q3.y, q4.x, q4.y};
-        const Finish2 f = finish2_50(c0, c1, rounds, final_round, max_rounds);
-        const uint32_t idx0 = c0.cE >> CE_IDX_SHIFT, idx1 = c1.cE >> CE_IDX_SHIFT, widx = f.widx;
+        // both score words, then the winner's record alone: one select on its address instead of five on its words (round 11)
+        const uint32_t *w0 = lds + lane_base, *w1 = lds + SEAT_STRIDE + lane_base;
+        const uint32_t cE0 = w0[9], cE1 = w1[9];
+        const bool second = finish2_second(cE0, cE1);
+        const uint32_t *ww = second ? w1 : w0;
+        const LeanCounters cw{ww[5], ww[6], ww[7], ww[8], second ? cE1 : cE0};
+        const Finish2 f = finish2_50_winner(cw, second, rounds, final_round);
+        const uint32_t idx0 = cE0 >> CE_IDX_SHIFT, idx1 = cE1 >> CE_IDX_SHIFT, widx = f.widx;
         if (ho & HO_GS_OUT) { // final records of both seats -> state store, in its format (R_*): score and n_turns spelled out
             // n_turns (seat_turns): every seat began `rounds` turns, plus the final round's one turn, which the seat that did not trigger
             // it played and still owns; a game without rounds has no owner
             const uint32_t last = (max_rounds != 0u && own_rec != lds_addr(lane_base)) ? 1u : 0u;
             const uint32_t t0 = rounds + ((final_round != 0u && last == 0u) ? 1u : 0u), t1 = rounds; // seat s < (last ^ 1): only seat 0, when seat 1 triggered
-            const uint2 p0 = r0[0], p1 = r0[1], q0 = r1[0], q1 = r1[1];
+            const uint2 *r0 = reinterpret_cast<const uint2 *>(w0), *r1 = reinterpret_cast<const uint2 *>(w1);
+            const uint2 p0 = r0[0], p1 = r0[1], p2 = r0[2], p3 = r0[3], p4 = r0[4], q0 = r1[0], q1 = r1[1], q2 = r1[2], q3 = r1[3], q4 = r1[4];
+            const LeanCounters c0{p2.y, p3.x, p3.y, p4.x, p4.y}, c1{q2.y, q3.x, q3.y, q4.x, q4.y}; // buf cA | cB cC | cD cE
             const uint32_t soff = seed_slot * (2u * st_rec);
             global_u4_rw *g0 = (global_u4_rw *)(st_base + (uint64_t)soff), *g1 = (global_u4_rw *)(st_base + (uint64_t)(soff + st_rec));
             g0[0] = u32x4{p0.x, p0.y, p1.x, p1.y};
@@ -1384,7 +1389,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 #pragma unroll
                 for (int j = 0; j < 10; ++j) {
                     atomicAdd(&t[3 + j], (unsigned long long)f.m[j]);
-                    atomicAdd(&t[13 + j], (unsigned long long)f.m[j] * f.m[j]);
+                    atomicAdd(&t[13 + j], (unsigned long long)finish2_square((uint32_t)j, f.m[j])); // (fk_device.h: one 24-bit multiply for eight of them)
                 }
             }
         }
@@ -1432,14 +1437,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 if (new_avail < TICKET_CHUNK) exhausted = 1;
             }
         }
-        if (mine) {
+        if constexpr (FLAT) {
+            // one region, entered by the served lanes alone (round 11): the ticket is formed by selects for every lane (none for a lane
+            // that does not wait) and a waiting lane without one is done — `if (mine) { if (ticket) ... else st = DONE; }` is two joins,
+            // and each had its own block of copies of the carried registers
+            const uint32_t rank = mbcnt(waiting);
+            uint32_t ticket = rank < avail ? pool_next + rank : (rank - avail < new_avail) ? new_base + (rank - avail) : 0xffffffffu;
+            ticket = mine ? ticket : 0xffffffffu;
+            st = (mine && ticket == 0xffffffffu) ? (uint32_t)ST_DONE : st;
+            if (ticket != 0xffffffffu) init_game2(ticket);
+        } else if (mine) {
             const uint32_t rank = mbcnt(waiting);
             uint32_t ticket = 0xffffffffu;
             if (rank < avail) ticket = pool_next + rank;
             else if (rank - avail < new_avail) ticket = new_base + (rank - avail);
             if (ticket != 0xffffffffu) {
-                if constexpr (FLAT) init_game2(ticket);
-                else init_game(a.sched ? a.sched[ticket] : ticket, ticket);
+                init_game(a.sched ? a.sched[ticket] : ticket, ticket);
             } else {
                 st = ST_DONE;
             }
@@ -1455,26 +1468,42 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 
     // Two nested loops.  The inner one is the hot roll loop: a bottom-tested loop with a single back edge whose exit
     // test is wave-uniform (ballots and the v_readlane'd ticket pool), so its loop-carried registers stay put (no PHI
-    // copies, no full s_waitcnt at a merge point).  The rare hand-over sits on the outer back edge.
+    // copies, no full s_waitcnt at a merge point).  The rare hand-over sits in front of it: in the general copy on the outer back edge
+    // (`continue`), in the flat copy (round 11) in the outer loop's body, falling through into the roll loop's entry — there the carried
+    // registers have ONE name in the outer loop, the hand-over and the roll loop (see `play`).
     // A hand-over is due when enough lanes wait to share its cost, when nobody plays, or when the wave's tickets have run out.  Round 10
-    // measured the rule without the last term (ended lanes of an exhausted wave wait for the threshold or for `!active`; hand-overs per
-    // wave 236 -> 198 at config 2): -0.7 % at config 2, inside five within-build ranges, and +1.3 % at config 5, +0.3 % at config 3 —
-    // `exhausted` is also set while the wave still holds the tickets of a partial last chunk, and those then wait for the threshold.
-    // Not kept (profiles/r10_ab_handover.txt).
-    auto handover_due = [&](uint64_t waiting, uint64_t active) -> bool {
+    // measured the rule without the last term in every game kernel (ended lanes of an exhausted wave wait for the threshold or for
+    // `!active`; hand-overs per wave 236 -> 198 at config 2): -0.7 % at config 2, inside five within-build ranges, and +1.3 % at config 5,
+    // +0.3 % at config 3 — `exhausted` is also set while the wave still holds the tickets of a partial last chunk, and those then wait for
+    // the threshold.  Not kept in that form (profiles/r10_ab_handover.txt); the general copy, the block instance and fk_play_hc.h keep the full rule.
+    // Round 11, flat path only: the last term holds only while the wave still HAS tickets (a partial last chunk: dealt at once, as before).
+    // A wave without any has nothing to deal, so its ended lanes wait for the threshold or for `!active` like any others and their
+    // games are finished together — round 10's loss came from the tickets that waited, its gain from these hand-overs that deal nothing.
+    auto handover_due_general = [&](uint64_t waiting, uint64_t active) -> bool {
         return waiting && (!active || (uint32_t)__popcll(waiting) >= ho_thr || exhausted);
+    };
+    auto handover_due = [&](uint64_t waiting, uint64_t active, auto flat) -> bool {
+        if constexpr (!decltype(flat)::value) return handover_due_general(waiting, active);
+        else return waiting && (!active || (uint32_t)__popcll(waiting) >= ho_thr || (exhausted && pool_next != pool_end));
     };
     auto play = [&](auto flat) {
         while (true) {
             uint64_t waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
             uint64_t active = __ballot(st == ST_ACTIVE);
             if (!(waiting | active)) break; // no lane is active and none waits: the wave has drained
-            if (handover_due(waiting, active)) {
+            if (handover_due(waiting, active, flat)) {
 #ifdef FK_COUNT_HANDOVER
                 cnt_handovers += 1u, cnt_served += (uint32_t)__popcll(waiting);
 #endif
                 handover(waiting, flat);
-                continue;
+                // The flat path falls through into the roll loop (round 11) instead of going round the outer loop: with `continue` the
+                // carried registers are PHIs of two outer back edges and of the roll loop's entry, and the compiler keeps two names for each
+                // — eighteen copies in front of the served region, eighteen behind it, thirteen on the edge into the roll loop, for every
+                // lane.  A trip in which nobody plays (every dealt game had max_rounds 0, or no ticket was left) costs one ballot.
+                if constexpr (!decltype(flat)::value) continue;
+#ifdef FK_COUNT_HANDOVER // (the first trip's counts are of the lanes as the hand-over left them, as after the general copy's `continue`)
+                waiting = __ballot(st == ST_FRESH || st == ST_ENDED), active = __ballot(st == ST_ACTIVE);
+#endif
             }
             bool playing = st == ST_ACTIVE;
             do {
@@ -1485,7 +1514,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 playing = st == ST_ACTIVE;
                 waiting = __ballot(st == ST_ENDED);
                 active = __ballot(playing);
-            } while (active && !handover_due(waiting, active));
+            } while (active && !handover_due(waiting, active, flat));
         }
     };
     // The two-seat lean instance holds the loop nest twice, and a launch runs one of them: with the flat hand-over, or — a chunk too large
