@@ -37,6 +37,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -614,16 +615,160 @@ int check_device_error(fk_ctx *c, const int32_t *d_err, int64_t game_base, const
     return report_device_error(c, h, game_base, what);
 }
 
-// chunk-local overrides, sorted by game id, on the device
-int upload_overrides(fk_ctx *c, std::vector<DevOverride> &dov) {
+// ---- what every playing entry states once ----
+// A call begins: nothing of the call before it counts any more.  (fk_trace_games and fk_census_games / fk_tournament_run_census used
+// to leave out the last two lines.  That was an omission without effect: they neither post nor deliver a letter, and every entry
+// that does starts here.)
+void begin_call(fk_ctx *c) {
+    c->timing = fk_timing{};
+    c->play_instance.clear();
+    c->pending.clear();
+    c->letters.clear(); // (a failed call may have left some)
+    c->mail_used = 0;
+}
+
+int check_players(fk_ctx *c, int32_t k) { // the result word's seven winner-seat bits, the row's int8 winner_seat (REC_SAFETY is the next bit up)
+    if (k > FK_MAX_PLAYERS)
+        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    return FK_OK;
+}
+
+int check_max_rounds(fk_ctx *c, int32_t max_rounds) {
+    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    return FK_OK;
+}
+
+int check_override_list(fk_ctx *c, const fk_override *ov, int32_t n_ov) {
+    if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
+    return FK_OK;
+}
+
+// The argument checks of the game-list entries, in two halves (each entry has checks of its own between them): the list's shape ...
+int check_list_shape(fk_ctx *c, int64_t n_games, int32_t S, int32_t k, int32_t max_rounds, int64_t max_seats) {
+    if (k < 1 || S < 1 || n_games < 0 || n_games > max_seats / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
+    if (int rc = check_players(c, k)) return rc;
+    return check_max_rounds(c, max_rounds);
+}
+
+// ... and its games
+int check_list_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const int32_t *seat_strategy, int32_t S, int32_t k) {
+    for (int64_t i = 0; i < n_games * k; ++i)
+        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
+    for (int64_t i = 0; i < n_games; ++i) {
+        if (coords[i].k != (uint64_t)k) // simulation.py:438
+            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
+        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
+    }
+    return FK_OK;
+}
+
+// The argument checks of the tournament-range entries, in two halves for the same reason: the table's seating ...
+int check_seating(fk_ctx *c, int32_t S, int32_t k) {
+    if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
+    return check_players(c, k);
+}
+
+// ... and the range
+int check_range(fk_ctx *c, int32_t S, int32_t max_rounds, uint64_t shuffle_begin, uint64_t shuffle_end, uint32_t shuffles_per_batch,
+                const fk_override *ov, int32_t n_ov) {
+    if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
+    if (int rc = check_max_rounds(c, max_rounds)) return rc;
+    if (shuffle_end < shuffle_begin || shuffles_per_batch == 0) return fail(c, FK_ERR_ARG, "bad shuffle range / batch size");
+    return check_override_list(c, ov, n_ov);
+}
+
+// shuffles per permutation block: what fits LDS beside the table's 2-byte rows
+uint32_t perm_slots(int32_t S) { return (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2))); }
+
+// the fields every game-kernel launch fills from the context and the call
+PlayArgs table_args(const fk_ctx *c, int32_t target_score, int32_t max_rounds) {
+    PlayArgs pa{};
+    pa.strat = static_cast<const uint2 *>(c->strat.p);
+    pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
+    pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
+    pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
+    pa.target50 = ceil_div50(target_score);
+    pa.beat50 = floor_div50(target_score);
+    pa.max_rounds = (uint32_t)max_rounds;
+    return pa;
+}
+
+// The strategies as the table-free game loops (fk_trace.h, fk_census.h) take them: thresholds in points.  A score threshold is only ever compared with
+// turn totals in [50, 3 000 000] (1000 rolls of at most 3000 points), so clamping it to [0, 2^30] changes no comparison and
+// keeps `turn + roll - threshold` inside int32.
+std::vector<int2> strategies_in_points(const fk_strategy *table, int32_t S) {
+    std::vector<int2> packed((size_t)S);
+    for (int32_t i = 0; i < S; ++i)
+        packed[(size_t)i] = make_int2(std::min(std::max(table[i].score_threshold, 0), 1 << 30), (int)pack_strategy(table[i]).y);
+    return packed;
+}
+
+// the error word of the trace and census kernels (fk_trace.h: TR_*), once it is on the host
+int report_plain_error(fk_ctx *c, unsigned long long err, const char *what) {
+    if (err == fktr::TR_NO_ERROR) return FK_OK;
+    const int32_t h[2] = {(err & 0xffu) == fktr::TR_ERR_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW, 0};
+    return report_device_error(c, h, (int64_t)(err >> 8), what);
+}
+
+// The caller's overrides that concern a chunk -> chunk-local game ids, sorted by game id, on the device; `n_dev` of them.
+// `locate(o, games)` says whether `o` is about this chunk at all and appends the games it names.  The last entry for a game wins.
+template <class Locate>
+int map_overrides(fk_ctx *c, const fk_override *ov, int32_t n_ov, uint32_t &n_dev, Locate locate) {
+    std::vector<DevOverride> dov;
+    std::vector<uint32_t> games;
+    for (int32_t i = 0; i < n_ov; ++i) {
+        games.clear();
+        if (!locate(ov[i], games)) continue;
+        if (ov[i].max_rounds > 65535u) return fail(c, FK_ERR_ARG, "override max_rounds must be <= 65535");
+        for (const uint32_t game : games) {
+            bool replaced = false;
+            for (auto &dv : dov)
+                if (dv.game == game) {
+                    dv.max_rounds = ov[i].max_rounds;
+                    replaced = true;
+                }
+            if (!replaced) dov.push_back(DevOverride{game, ov[i].max_rounds});
+        }
+    }
+    n_dev = (uint32_t)dov.size();
     if (dov.empty()) return FK_OK;
     std::sort(dov.begin(), dov.end(), [](const DevOverride &x, const DevOverride &y) { return x.game < y.game; });
-    // duplicates: the last entry of the caller's list wins (as the linear scan it replaces did)
     int rc = ensure(c, c->ov, dov.size() * sizeof(DevOverride));
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ov.p, dov.data(), dov.size() * sizeof(DevOverride), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
+}
+
+// ... for shuffles [sh0, sh0 + n_sh) of a tournament: game = (shuffle - sh0) * gps + game of the shuffle
+int map_tournament_overrides(fk_ctx *c, const fk_override *ov, int32_t n_ov, uint64_t root_seed, int32_t k, uint64_t sh0, uint32_t n_sh,
+                             uint32_t gps, uint32_t &n_dev) {
+    return map_overrides(c, ov, n_ov, n_dev, [&](const fk_override &o, std::vector<uint32_t> &games) {
+        if (o.root_seed != root_seed || o.k_or_order != (uint32_t)k) return false;
+        if (o.a < sh0 || o.a >= sh0 + n_sh || o.b >= gps) return false;
+        games.push_back((uint32_t)((o.a - sh0) * gps + o.b));
+        return true;
+    });
+}
+
+// Plays a call; after an out-of-device-memory failure (the budget was sized from hipMemGetInfo: somebody else's allocation came in
+// between) gives the workspace back, plans with half and plays it again from its start.  `run` restores whatever a failed run changed.
+template <class Run>
+int replay_on_oom(fk_ctx *c, Run run) {
+    c->oom = false;
+    c->oom_replays = 0;
+    c->chunk_limit = 0;
+    int rc = run();
+    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
+        c->oom = false;
+        ++c->oom_replays;
+        release_workspace(c);
+        c->chunk_limit = c->last_budget / 2;
+        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
+        rc = run();
+    }
+    c->chunk_limit = 0;
+    return rc;
 }
 
 
@@ -821,6 +966,106 @@ int run_chunk(fk_ctx *c, const SeedArgs &sa_in, PlayArgs pa, const LaunchPlan &p
     rc = launch_play_stage(c, sa, pa, plan, want_state, want_rec0, want_recs);
     if (rc) return rc;
     return finish_play(c, pa, game_base, what);
+}
+
+// Pass `i` of a generation: how many blocks and games it holds; with `dst`, also writes its DevBlocks there on `st`.
+using PassBlocks = std::function<int(size_t i, DevBlock *dst, hipStream_t st, uint32_t &n_blocks, uint32_t &n_games)>;
+// Pass `i`'s pass-local max_rounds overrides, uploaded to c->ov; `n_dev` of them.
+using PassOverrides = std::function<int(size_t i, uint32_t &n_dev)>;
+
+// The passes (launches) of one generation of batched H2H blocks (fk_h2h_run_blocks, fk_h2h_round_robin): the games of every pass
+// are played and their results added to c->block_out by block row, S / 2 rows of two strategies each.  The passes of a generation
+// do not depend on each other's results, so with `pipelined` pass i + 1 is prepared (block table, game -> block map, pools,
+// schedule classes, seat seeding) into the other chunk set on the low-priority stream while pass i plays, as tournament chunks are
+// (15.5 ms of seeding per 6 x 10^8-attempt launch of BASELINE config 5 used to sit between the game kernels).  Without it — the
+// caller's choice, or its per-pass override lists, which live in one device buffer — each pass is finished before the next is
+// prepared on the main stream.  `overrides` may be empty: no pass has any.
+int play_block_passes(fk_ctx *c, size_t n_passes, const LaunchPlan &plan, uint64_t root_seed, uint32_t S, int32_t target_score,
+                      int32_t max_rounds, bool pipelined, const PassBlocks &blocks, const PassOverrides &overrides) {
+    const SeedPool seat_prefix = seed_prefix(203u /* H2H_PLAYER */, root_seed, 2u);
+    // preparation of pass `i` into chunk set `si` on stream `st`
+    auto prepare = [&](size_t i, int si, hipStream_t st, SeedArgs &sa) -> int {
+        ChunkSet &cs = c->sets[si];
+        uint32_t nb = 0, games = 0;
+        int rc2 = blocks(i, nullptr, st, nb, games);
+        if (rc2) return rc2;
+        cs.prepared = false;
+        rc2 = ensure(c, cs.blocks, (size_t)nb * sizeof(DevBlock));
+        if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)games * 4);
+        if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)games * 4);
+        if (!rc2) rc2 = blocks(i, static_cast<DevBlock *>(cs.blocks.p), st, nb, games);
+        if (rc2) return rc2;
+        sa = SeedArgs{};
+        sa.prefix = seat_prefix;
+        sa.gps = 0;
+        sa.k = 2;
+        sa.n_games = games;
+        sa.blocks = static_cast<const DevBlock *>(cs.blocks.p);
+        sa.n_blocks = nb;
+        sa.game_block = static_cast<const uint32_t *>(cs.game_block.p);
+        sa.game_row = static_cast<const uint32_t *>(cs.game_row.p);
+        rc2 = seed_stage(c, si, st, sa, false, true);
+        if (rc2) return rc2;
+        HIPCHK(c, hipEventRecord(cs.ready, st));
+        cs.side = (st == c->prep_stream);
+        return FK_OK;
+    };
+
+    int rc;
+    std::vector<SeedArgs> sas(n_passes);
+    std::vector<int> set_of(n_passes);
+    set_of[0] = c->cur;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0)); // an unused side-stream preparation may still own the set
+    (void)hipEventRecord(CSET(c).ev[0], c->stream);             // no permutations here: an empty interval
+    (void)hipEventRecord(CSET(c).ev[1], c->stream);
+    if ((rc = prepare(0, c->cur, c->stream, sas[0]))) return rc;
+    for (size_t i = 0; i < n_passes; ++i) {
+        c->cur = set_of[i];
+        uint32_t n_ov = 0;
+        if (overrides && (rc = overrides(i, n_ov))) return rc;
+        HIPCHK(c, hipEventRecord(c->main_idle, c->stream)); // everything that used the other chunk set is in front of this point
+        if (i + 1 < n_passes) {
+            set_of[i + 1] = c->cur ^ 1;
+            if (pipelined) {
+                HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->main_idle, 0));
+                (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->prep_stream);
+                (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->prep_stream);
+                if ((rc = prepare(i + 1, c->cur ^ 1, c->prep_stream, sas[i + 1]))) return rc;
+            }
+        }
+        PlayArgs pa = table_args(c, target_score, max_rounds);
+        pa.game_block = sas[i].game_row; // the kernel wants table rows: seat s of a game plays strategy 2 * row + s
+        pa.ov = overrides ? static_cast<const DevOverride *>(c->ov.p) : nullptr;
+        pa.n_ov = n_ov;
+        pa.mode = MODE_BLOCKS;
+        pa.n_games = sas[i].n_games;
+        pa.gps = 1;
+        pa.n_sh = 1;
+        pa.k = 2;
+        pa.S = S;
+        HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0));
+        if ((rc = launch_play_stage(c, sas[i], pa, plan, false, true, false))) return rc;
+        hipLaunchKernelGGL(fk_h2h_reduce_kernel, dim3((pa.n_games + 256u * H2H_RUN - 1u) / (256u * H2H_RUN)), dim3(256), 0, c->stream,
+                           static_cast<const uint32_t *>(c->rec0.p), pa.n_games, S / 2u, static_cast<unsigned long long *>(c->block_out.p));
+        HIPCHK(c, hipGetLastError());
+        if (!pipelined) { // (the next pass may re-use the one override buffer)
+            if ((rc = finish_play(c, pa, 0, "h2h attempt (pass-local index)"))) return rc;
+            if (i + 1 < n_passes) {
+                (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->stream);
+                (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->stream);
+                if ((rc = prepare(i + 1, c->cur ^ 1, c->stream, sas[i + 1]))) return rc;
+            }
+        } else {
+            // the pass's error record and timers are read before the next launch reuses the kernel timer events
+            HIPCHK(c, hipMemcpyAsync(c->err_host, pa.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            rc = report_device_error(c, c->err_host, 0, "h2h attempt (pass-local index)");
+            const int rc_t = finish_timers(c);
+            if (rc) return rc;
+            if (rc_t) return rc_t;
+        }
+    }
+    return FK_OK;
 }
 
 // The permutation kernels of shuffles [d.sh0, d.sh0 + d.n_sh) into cs.perm (blocked layout, perm_at()) on `st`; the caller has
@@ -1669,21 +1914,13 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     int32_t *perms = call.perms;
     double *seat_ratios = call.seat_ratios;
     if (!strategies || !tally) return fail(c, FK_ERR_ARG, "strategies and tally are required");
-    if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
-    if (k > FK_MAX_PLAYERS) // the result word's seven winner-seat bits, the row's int8 winner_seat (REC_SAFETY is the next bit up)
-        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
+    int rc = check_seating(c, S, k);
+    if (rc) return rc;
     if (rows != nullptr && call.columns_ids != nullptr && k > 64)
         return fail(c, FK_ERR_ARG, "column images hold tables of at most 64 seats, got %d", (int)k);
-    if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    if (shuffle_end < shuffle_begin || shuffles_per_batch == 0) return fail(c, FK_ERR_ARG, "bad shuffle range / batch size");
-    if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
+    if ((rc = check_range(c, S, max_rounds, shuffle_begin, shuffle_end, shuffles_per_batch, ov, n_ov))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
-    c->letters.clear(); // (a failed call may have left some)
-    c->mail_used = 0;
+    begin_call(c);
 
     const uint64_t n_sh_total = shuffle_end - shuffle_begin;
     const uint32_t gps = (uint32_t)(S / k);
@@ -1694,8 +1931,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     const bool columns = rows != nullptr && call.columns_ids != nullptr; // fk_tournament_run_columns
     const size_t rows_per_shuffle = columns ? fksw::shard_image_bytes(k, (int)gps) : (size_t)gps * row_bytes;
 
-    int rc = upload_strategies(c, strategies, S);
-    if (rc) return rc;
+    if ((rc = upload_strategies(c, strategies, S))) return rc;
     if (columns) {
         if ((rc = ensure(c, c->ids, sizeof(int32_t) * (size_t)S))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->ids.p, call.columns_ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
@@ -1813,7 +2049,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         }
     }
 
-    const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2)));
+    const uint32_t slots = perm_slots(S);
     const uint32_t state_dw = (plan.shape().gs || want_state) ? STATE_DW : 4u;
     auto describe = [&](uint64_t first_shuffle, uint32_t count, uint32_t dw) {
         return ChunkDesc{c->table_epoch, root_seed, first_shuffle, count, (uint32_t)S, (uint32_t)k, dw, c->longest_first ? 1u : 0u, slots};
@@ -1866,21 +2102,8 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         }
 
         // overrides that fall into this chunk -> chunk-local game ids
-        std::vector<DevOverride> dov;
-        for (int32_t i = 0; i < n_ov; ++i) {
-            if (ov[i].root_seed != root_seed || ov[i].k_or_order != (uint32_t)k) continue;
-            if (ov[i].a < sh0 || ov[i].a >= sh0 + n_sh || ov[i].b >= gps) continue;
-            if (ov[i].max_rounds > 65535u) return fail(c, FK_ERR_ARG, "override max_rounds must be <= 65535");
-            const uint32_t game = (uint32_t)((ov[i].a - sh0) * gps + ov[i].b);
-            bool replaced = false;
-            for (auto &dv : dov)
-                if (dv.game == game) {
-                    dv.max_rounds = ov[i].max_rounds;
-                    replaced = true;
-                }
-            if (!replaced) dov.push_back(DevOverride{game, ov[i].max_rounds});
-        }
-        if ((rc = upload_overrides(c, dov))) return rc;
+        uint32_t n_dov = 0;
+        if ((rc = map_tournament_overrides(c, ov, n_ov, root_seed, k, sh0, n_sh, gps, n_dov))) return rc;
         // the device row buffers alternate over chunks — and, in async mode, over calls: a one-chunk call's row kernel then has not to wait for the previous call's copy
         const int rb = (int)((done / chunk_sh + (c->rows_async ? c->rows_calls : 0u)) & 1u);
         DevBuf &row_buf = rb ? c->rows_alt : c->rows;
@@ -1889,27 +2112,20 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             if ((rc = ensure(c, row_buf, (size_t)n_sh * rows_per_shuffle))) return rc;
         }
 
-        PlayArgs pa{};
-        pa.strat = static_cast<const uint2 *>(c->strat.p);
-        pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
-        pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
+        PlayArgs pa = table_args(c, target_score, max_rounds);
         pa.perm_T = static_cast<const uint16_t *>(CSET(c).perm.p);
         pa.perm_slots = slots;
         pa.seat_strategy = nullptr;
         pa.tally = static_cast<unsigned long long *>(c->tally.p);
         pa.ov = static_cast<const DevOverride *>(c->ov.p);
-        pa.n_ov = (uint32_t)dov.size();
+        pa.n_ov = n_dov;
         pa.mode = MODE_PERM;
         pa.n_games = n_games;
         pa.gps = gps;
         pa.n_sh = n_sh;
         pa.k = (uint32_t)k;
         pa.S = (uint32_t)S;
-        pa.target50 = ceil_div50(target_score);
-        pa.beat50 = floor_div50(target_score);
-        pa.max_rounds = (uint32_t)max_rounds;
         pa.cold = static_cast<uint4 *>(c->cold.p);
-        pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
 
         // The next chunk (or the hinted next call) is prepared into the other chunk set around this game kernel: its permutations
         // in front of it on the main stream, its schedule + seat seeding on the low-priority stream while it runs.
@@ -2240,21 +2456,7 @@ static int tournament_call(fk_ctx *c, const TournamentCall &call) {
     if (!c) return FK_ERR_ARG;
     c->ran_hc = false;
     c->last_tally_bytes = 0;
-    c->oom = false;
-    c->oom_replays = 0;
-    c->chunk_limit = 0;
-    int rc = tournament_run_impl(c, call);
-    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
-        // out of device memory although the budget was sized from hipMemGetInfo: somebody else's allocation came in between.  Give the
-        // workspace back, plan with half, play the call again from its first shuffle (every output is overwritten).
-        c->oom = false;
-        ++c->oom_replays;
-        release_workspace(c);
-        c->chunk_limit = c->last_budget / 2;
-        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
-        rc = tournament_run_impl(c, call);
-    }
-    c->chunk_limit = 0;
+    int rc = replay_on_oom(c, [&] { return tournament_run_impl(c, call); }); // from its first shuffle: every output is overwritten
     if (rc == FK_ERR_COUNTER_OVERFLOW && c->ran_hc) {
         // the hot / cold kernel's narrower counter fields (fk_play_hc.h) left their guard bands: the call is replayed on
         // fk_play_kernel, whose 16-bit fields are the ABI's stated limits
@@ -2485,26 +2687,13 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
                   const int32_t *seat_strategy, int32_t k, int32_t target_score, int32_t max_rounds, void *rows) {
     if (!c) return FK_ERR_ARG;
     if (!coords || !table || !seat_strategy || !rows) return fail(c, FK_ERR_ARG, "coords, table, seat_strategy, rows are required");
-    if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7fffffff / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
-    if (k > FK_MAX_PLAYERS)
-        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    for (int64_t i = 0; i < n_games * k; ++i)
-        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
-    for (int64_t i = 0; i < n_games; ++i) {
-        if (coords[i].k != (uint64_t)k) // simulation.py:438
-            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
-        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
-    c->letters.clear(); // (a failed call may have left some)
-    c->mail_used = 0;
-    if (n_games == 0) return FK_OK;
-    int rc = upload_strategies(c, table, S);
+    int rc = check_list_shape(c, n_games, S, k, max_rounds, 0x7fffffff);
+    if (!rc) rc = check_list_games(c, coords, n_games, seat_strategy, S, k);
     if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    if (n_games == 0) return FK_OK;
+    if ((rc = upload_strategies(c, table, S))) return rc;
     const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
     rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n_games);
     if (rc) return rc;
@@ -2526,11 +2715,7 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     sa.k = (uint32_t)k;
     sa.n_games = (uint32_t)n_games;
 
-    PlayArgs pa{};
-    pa.strat = static_cast<const uint2 *>(c->strat.p);
-    pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
-    pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
-    pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
+    PlayArgs pa = table_args(c, target_score, max_rounds);
     pa.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
     pa.mode = MODE_LIST;
     pa.n_games = (uint32_t)n_games;
@@ -2538,9 +2723,6 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     pa.n_sh = 1;
     pa.k = (uint32_t)k;
     pa.S = (uint32_t)S;
-    pa.target50 = ceil_div50(target_score);
-    pa.beat50 = floor_div50(target_score);
-    pa.max_rounds = (uint32_t)max_rounds;
     rc = run_chunk(c, sa, pa, plan, true, true, true, 0, "list");
     if (rc) return rc;
     rc = rows_pass(c, sa, false, (uint32_t)n_games, 1, 1, false, static_cast<uint8_t *>(c->rows.p));
@@ -2559,32 +2741,16 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
     if (!c) return FK_ERR_ARG;
     if (!coords || !table || !seat_strategy || !rows || !event_begin)
         return fail(c, FK_ERR_ARG, "coords, table, seat_strategy, rows, event_begin are required");
-    if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7ffffffe / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
-    if (k > FK_MAX_PLAYERS)
-        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    if (events && event_capacity < 0) return fail(c, FK_ERR_ARG, "event_capacity must not be negative");
-    for (int64_t i = 0; i < n_games * k; ++i)
-        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
-    for (int64_t i = 0; i < n_games; ++i) {
-        if (coords[i].k != (uint64_t)k) // simulation.py:438
-            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
-        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
-    }
-    int rc = validate_strategies(c, table, S);
+    int rc = check_list_shape(c, n_games, S, k, max_rounds, 0x7ffffffe);
     if (rc) return rc;
+    if (events && event_capacity < 0) return fail(c, FK_ERR_ARG, "event_capacity must not be negative");
+    if ((rc = check_list_games(c, coords, n_games, seat_strategy, S, k))) return rc;
+    if ((rc = validate_strategies(c, table, S))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
+    begin_call(c);
     event_begin[0] = 0;
     if (n_games == 0) return FK_OK;
-    // The strategies as the table-free functions take them: thresholds in points.  A score threshold is only ever compared with
-    // turn totals in [50, 3 000 000] (1000 rolls of at most 3000 points), so clamping it to [0, 2^30] changes no comparison and
-    // keeps `turn + roll - threshold` inside int32.
-    std::vector<int2> packed((size_t)S);
-    for (int32_t i = 0; i < S; ++i)
-        packed[(size_t)i] = make_int2(std::min(std::max(table[i].score_threshold, 0), 1 << 30), (int)pack_strategy(table[i]).y);
+    const std::vector<int2> packed = strategies_in_points(table, S);
     const uint32_t n = (uint32_t)n_games, n_pad = (n + fktr::TR_BLOCK - 1u) / fktr::TR_BLOCK * fktr::TR_BLOCK;
     const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
     const size_t sz[6] = {sizeof(int2) * (size_t)S, (size_t)k * fktr::TR_FIELDS * n_pad * 4, 8 * ((size_t)n + 1), 8 * ((size_t)n + 1), (size_t)n * row_bytes, 8};
@@ -2637,10 +2803,7 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
     c->timing.play_grid = (int32_t)grid.x;
     c->timing.games = n_games;
     c->timing.total_ms = c->timing.play_ms;
-    if (err != fktr::TR_NO_ERROR) {
-        const int32_t h[2] = {(err & 0xffu) == fktr::TR_ERR_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW, (int32_t)(err >> 8)};
-        return report_device_error(c, h, 0, "trace");
-    }
+    if ((rc = report_plain_error(c, err, "trace"))) return rc;
     const int64_t total = event_begin[n];
     if (!events) return FK_OK;
     if (event_capacity < total)
@@ -2682,13 +2845,8 @@ static int census_check_out(fk_ctx *c, const fk_census *out) {
 static int census_begin(fk_ctx *c, const fk_strategy *table, int32_t S, int32_t k, int32_t target_score, int32_t max_rounds, const fk_census *out,
                         CensusCall &cc, fkcn::CensusArgs &a) {
     int rc;
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
-    // thresholds in points, clamped as fk_trace_games clamps them
-    std::vector<int2> packed((size_t)S);
-    for (int32_t i = 0; i < S; ++i)
-        packed[(size_t)i] = make_int2(std::min(std::max(table[i].score_threshold, 0), 1 << 30), (int)pack_strategy(table[i]).y);
+    begin_call(c);
+    const std::vector<int2> packed = strategies_in_points(table, S);
     cc.n_u64[0] = fkcn::CN_CELLS;
     cc.n_u64[1] = (size_t)S * fkcn::CN_N * fkcn::CN_DICE_COLS;
     cc.n_u64[2] = (size_t)S * fkcn::CN_TURN_COLS;
@@ -2749,11 +2907,7 @@ static int census_chunk(fk_ctx *c, fkcn::CensusArgs &a, bool list, const char *w
     c->timing.play_lds_bytes = (int32_t)(fkcn::CN_CELLS * 4);
     c->timing.games += a.n_games;
     c->timing.total_ms = c->timing.play_ms;
-    if (err != fktr::TR_NO_ERROR) {
-        const int32_t h[2] = {(err & 0xffu) == fktr::TR_ERR_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW, 0};
-        return report_device_error(c, h, (int64_t)(err >> 8), what);
-    }
-    return FK_OK;
+    return report_plain_error(c, err, what);
 }
 
 static int census_end(fk_ctx *c, const CensusCall &cc, const fk_census *out) {
@@ -2768,19 +2922,10 @@ int fk_census_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk
                     int32_t k, int32_t target_score, int32_t max_rounds, fk_census *out) {
     if (!c) return FK_ERR_ARG;
     if (!coords || !table || !seat_strategy) return fail(c, FK_ERR_ARG, "coords, table, seat_strategy are required");
-    if (k < 1 || S < 1 || n_games < 0 || n_games > 0x7ffffffe / std::max(k, 1)) return fail(c, FK_ERR_ARG, "bad k / S / n_games");
-    if (k > FK_MAX_PLAYERS)
-        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    int rc = census_check_out(c, out);
+    int rc = check_list_shape(c, n_games, S, k, max_rounds, 0x7ffffffe);
+    if (!rc) rc = census_check_out(c, out);
+    if (!rc) rc = check_list_games(c, coords, n_games, seat_strategy, S, k);
     if (rc) return rc;
-    for (int64_t i = 0; i < n_games * k; ++i)
-        if (seat_strategy[i] < 0 || seat_strategy[i] >= S) return fail(c, FK_ERR_ARG, "seat_strategy[%lld] out of range", (long long)i);
-    for (int64_t i = 0; i < n_games; ++i) {
-        if (coords[i].k != (uint64_t)k) // simulation.py:438
-            return fail(c, FK_ERR_ARG, "Player RNG coordinate k does not match the number of seated strategies");
-        if (coords[i].seat_index != 0) return fail(c, FK_ERR_ARG, "game coordinates carry seat_index 0 (seats are implied)");
-    }
     if ((rc = validate_strategies(c, table, S))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     CensusCall cc{};
@@ -2807,14 +2952,9 @@ int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S
                              int32_t n_ov, fk_census *out) {
     if (!c) return FK_ERR_ARG;
     if (!strategies) return fail(c, FK_ERR_ARG, "strategies are required");
-    if (k < 1 || S < k || S % k != 0) return fail(c, FK_ERR_ARG, "n_players must divide %d", S); // run_tournament.py:274
-    if (k > FK_MAX_PLAYERS)
-        return fail(c, FK_ERR_ARG, "games have at most %d seats (a row names its winner's seat in an int8), got %d", FK_MAX_PLAYERS, (int)k);
-    if (S > 65535) return fail(c, FK_ERR_ARG, "S=%d exceeds 65535 strategies", S);
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    if (shuffle_end < shuffle_begin || shuffles_per_batch == 0) return fail(c, FK_ERR_ARG, "bad shuffle range / batch size");
-    if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
-    int rc = census_check_out(c, out);
+    int rc = check_seating(c, S, k);
+    if (!rc) rc = check_range(c, S, max_rounds, shuffle_begin, shuffle_end, shuffles_per_batch, ov, n_ov);
+    if (!rc) rc = census_check_out(c, out);
     if (rc) return rc;
     if ((rc = validate_strategies(c, strategies, S))) return rc;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2823,7 +2963,7 @@ int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S
     if ((rc = census_begin(c, strategies, S, k, target_score, max_rounds, out, cc, a))) return rc;
     const uint64_t n_sh_total = shuffle_end - shuffle_begin;
     const uint32_t gps = (uint32_t)(S / k);
-    const uint32_t slots = (uint32_t)std::max<size_t>(1, std::min<size_t>(PERM_BLOCK, LDS_LIMIT / ((size_t)S * 2))); // as tournament_run_impl
+    const uint32_t slots = perm_slots(S);
     uint64_t chunk_sh = std::max<uint64_t>(1, census_chunk_games(c, k) / gps);
     chunk_sh = std::min<uint64_t>(chunk_sh, (uint64_t)0x7fffffff / gps);
     // the chunk set no prepared (hinted) tournament chunk sits in; whatever it held is void afterwards
@@ -2832,22 +2972,8 @@ int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S
     for (uint64_t done = 0; done < n_sh_total; done += chunk_sh) {
         const uint32_t n_sh = (uint32_t)std::min<uint64_t>(chunk_sh, n_sh_total - done);
         const uint64_t sh0 = shuffle_begin + done;
-        // overrides that fall into this chunk -> chunk-local game ids (as tournament_run_impl: the last entry for a game wins)
-        std::vector<DevOverride> dov;
-        for (int32_t i = 0; i < n_ov; ++i) {
-            if (ov[i].root_seed != root_seed || ov[i].k_or_order != (uint32_t)k) continue;
-            if (ov[i].a < sh0 || ov[i].a >= sh0 + n_sh || ov[i].b >= gps) continue;
-            if (ov[i].max_rounds > 65535u) return fail(c, FK_ERR_ARG, "override max_rounds must be <= 65535");
-            const uint32_t game = (uint32_t)((ov[i].a - sh0) * gps + ov[i].b);
-            bool replaced = false;
-            for (auto &dv : dov)
-                if (dv.game == game) {
-                    dv.max_rounds = ov[i].max_rounds;
-                    replaced = true;
-                }
-            if (!replaced) dov.push_back(DevOverride{game, ov[i].max_rounds});
-        }
-        if ((rc = upload_overrides(c, dov))) return rc;
+        // overrides that fall into this chunk -> chunk-local game ids
+        if ((rc = map_tournament_overrides(c, ov, n_ov, root_seed, k, sh0, n_sh, gps, a.n_ov))) return rc;
         cs.prepared = false;
         HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
         const ChunkDesc d{c->table_epoch, root_seed, sh0, n_sh, (uint32_t)S, (uint32_t)k, 0u, 0u, slots};
@@ -2862,7 +2988,6 @@ int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S
         a.root_seed = root_seed;
         a.shuffle0 = sh0;
         a.ov = static_cast<const DevOverride *>(c->ov.p);
-        a.n_ov = (uint32_t)dov.size();
         a.n_games = n_sh * gps;
         a.game_base = done * gps;
         if ((rc = census_chunk(c, a, false, "census"))) return rc;
@@ -2881,37 +3006,23 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
 int fk_h2h_run_blocks(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks, uint64_t root_seed, uint64_t chunk_games,
                       int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov) {
     if (!c) return FK_ERR_ARG;
-    c->oom = false;
-    c->oom_replays = 0;
-    c->chunk_limit = 0;
     // the blocks are advanced in place: a replay after an out-of-memory failure starts from the states the caller handed in
     std::vector<fk_h2h_block> saved;
     if (blocks && n_blocks > 0 && n_blocks <= (1 << 22)) saved.assign(blocks, blocks + n_blocks);
-    int rc = h2h_run_blocks_impl(c, blocks, n_blocks, root_seed, chunk_games, target_score, max_rounds, ov, n_ov);
-    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
-        c->oom = false;
-        ++c->oom_replays;
-        release_workspace(c);
-        c->chunk_limit = c->last_budget / 2;
-        std::copy(saved.begin(), saved.end(), blocks);
-        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
-        rc = h2h_run_blocks_impl(c, blocks, n_blocks, root_seed, chunk_games, target_score, max_rounds, ov, n_ov);
-    }
-    c->chunk_limit = 0;
-    return rc;
+    return replay_on_oom(c, [&] {
+        if (c->oom_replays) std::copy(saved.begin(), saved.end(), blocks);
+        return h2h_run_blocks_impl(c, blocks, n_blocks, root_seed, chunk_games, target_score, max_rounds, ov, n_ov);
+    });
 }
 
 static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks, uint64_t root_seed, uint64_t chunk_games,
                                int32_t target_score, int32_t max_rounds, const fk_override *ov, int32_t n_ov) {
     if (!blocks || n_blocks < 0 || n_blocks > (1 << 22)) return fail(c, FK_ERR_ARG, "blocks are required (at most 2^22 per call)");
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
-    if (n_ov < 0 || (n_ov > 0 && !ov)) return fail(c, FK_ERR_ARG, "bad override list");
+    int rc = check_max_rounds(c, max_rounds);
+    if (!rc) rc = check_override_list(c, ov, n_ov);
+    if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
-    c->letters.clear(); // (a failed call may have left some)
-    c->mail_used = 0;
+    begin_call(c);
     if (n_blocks == 0) return FK_OK;
     std::vector<fk_strategy> table((size_t)n_blocks * 2);
     std::vector<uint64_t> stop((size_t)n_blocks);
@@ -2927,9 +3038,7 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
         table[(size_t)b * 2] = blk.seats[0];
         table[(size_t)b * 2 + 1] = blk.seats[1];
     }
-    int rc = upload_strategies(c, table.data(), n_blocks * 2);
-    if (rc) return rc;
-    const SeedPool seat_prefix = seed_prefix(203u /* H2H_PLAYER */, root_seed, 2u);
+    if ((rc = upload_strategies(c, table.data(), n_blocks * 2))) return rc;
     const LaunchPlan plan = plan_play(plan_knobs(c), PLAN_H2H, 2, n_blocks * 2, false, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
@@ -2939,12 +3048,9 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
     if (rc) return rc;
 
     // A GENERATION plays, for every block that still needs games, exactly min(stop - attempted, target - completed) attempts —
-    // all of them planned up front from the blocks' current states and cut into passes (launches) of at most max_launch games.
-    // The passes of a generation do not depend on each other's results, so pass i + 1 is prepared (block table, game -> block
-    // map, pools, schedule classes, seat seeding) into the other chunk set on the low-priority stream while pass i plays, as
-    // tournament chunks are (15.5 ms of seeding per 6 x 10^8-attempt launch of BASELINE config 5 used to sit between the game
-    // kernels); the strategy table (two rows per block of the CALL) and the per-block counts are per call, the error records
-    // are read once per generation.  Blocks with safety-limit games need further (geometrically smaller) generations.
+    // all of them planned up front from the blocks' current states and cut into passes (launches) of at most max_launch games,
+    // which play_block_passes plays.  The strategy table (two rows per block of the CALL) and the per-block counts are per call.
+    // Blocks with safety-limit games need further (geometrically smaller) generations.
     struct Pass {
         std::vector<DevBlock> blocks;
         uint32_t n_games = 0;
@@ -2975,120 +3081,30 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
         if (passes.empty()) break;
         HIPCHK(c, hipMemsetAsync(c->block_out.p, 0, (size_t)n_blocks * 4 * 8, c->stream));
 
-        // preparation of pass `i` into chunk set `si` on stream `st`
-        auto prepare = [&](size_t i, int si, hipStream_t st, SeedArgs &sa) -> int {
+        const PassBlocks pass_blocks = [&](size_t i, DevBlock *dst, hipStream_t st, uint32_t &nb, uint32_t &games) -> int {
             const Pass &p = passes[i];
-            ChunkSet &cs = c->sets[si];
-            const uint32_t nb = (uint32_t)p.blocks.size();
-            cs.prepared = false;
-            int rc2 = ensure(c, cs.blocks, (size_t)nb * sizeof(DevBlock));
-            if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)p.n_games * 4);
-            if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)p.n_games * 4);
-            if (rc2) return rc2;
-            HIPCHK(c, hipMemcpyAsync(cs.blocks.p, p.blocks.data(), (size_t)nb * sizeof(DevBlock), hipMemcpyHostToDevice, st));
-            sa = SeedArgs{};
-            sa.prefix = seat_prefix;
-            sa.gps = 0;
-            sa.k = 2;
-            sa.n_games = p.n_games;
-            sa.blocks = static_cast<const DevBlock *>(cs.blocks.p);
-            sa.n_blocks = nb;
-            sa.game_block = static_cast<const uint32_t *>(cs.game_block.p);
-            sa.game_row = static_cast<const uint32_t *>(cs.game_row.p);
-            rc2 = seed_stage(c, si, st, sa, false, true);
-            if (rc2) return rc2;
-            HIPCHK(c, hipEventRecord(cs.ready, st));
-            cs.side = (st == c->prep_stream);
+            nb = (uint32_t)p.blocks.size();
+            games = p.n_games;
+            if (dst) HIPCHK(c, hipMemcpyAsync(dst, p.blocks.data(), (size_t)nb * sizeof(DevBlock), hipMemcpyHostToDevice, st));
             return FK_OK;
         };
-
-        std::vector<SeedArgs> sas(passes.size());
-        std::vector<int> set_of(passes.size());
-        set_of[0] = c->cur;
-        HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0)); // an unused side-stream preparation may still own the set
-        (void)hipEventRecord(CSET(c).ev[0], c->stream);             // no permutations here: an empty interval
-        (void)hipEventRecord(CSET(c).ev[1], c->stream);
-        rc = prepare(0, c->cur, c->stream, sas[0]);
-        if (rc) return rc;
-        for (size_t i = 0; i < passes.size(); ++i) {
+        // overrides -> pass-local game ids (not pipelined: one device list)
+        const PassOverrides pass_overrides = [&](size_t i, uint32_t &n_dev) -> int {
             const Pass &p = passes[i];
-            c->cur = set_of[i];
-            // overrides -> pass-local game ids (not pipelined: one device list)
-            std::vector<DevOverride> dov;
-            for (int32_t o = 0; o < n_ov; ++o) {
-                if (ov[o].root_seed != root_seed) continue;
-                if (ov[o].max_rounds > 65535u) return fail(c, FK_ERR_ARG, "override max_rounds must be <= 65535");
+            return map_overrides(c, ov, n_ov, n_dev, [&](const fk_override &o, std::vector<uint32_t> &games) {
+                if (o.root_seed != root_seed) return false;
                 for (size_t q = 0; q < p.blocks.size(); ++q) {
                     const DevBlock &db = p.blocks[q];
                     const uint32_t n_q = (q + 1 < p.blocks.size() ? p.blocks[q + 1].start : p.n_games) - db.start;
-                    if (ov[o].a != db.pair || ov[o].k_or_order != db.order) continue;
-                    if (ov[o].b < db.attempt0 || ov[o].b >= db.attempt0 + n_q) continue;
-                    const uint32_t game = db.start + (uint32_t)(ov[o].b - db.attempt0);
-                    bool replaced = false;
-                    for (auto &d : dov)
-                        if (d.game == game) {
-                            d.max_rounds = ov[o].max_rounds;
-                            replaced = true;
-                        }
-                    if (!replaced) dov.push_back(DevOverride{game, ov[o].max_rounds});
+                    if (o.a != db.pair || o.k_or_order != db.order) continue;
+                    if (o.b < db.attempt0 || o.b >= db.attempt0 + n_q) continue;
+                    games.push_back(db.start + (uint32_t)(o.b - db.attempt0));
                 }
-            }
-            rc = upload_overrides(c, dov);
-            if (rc) return rc;
-            HIPCHK(c, hipEventRecord(c->main_idle, c->stream)); // everything that used the other chunk set is in front of this point
-            if (i + 1 < passes.size()) {
-                set_of[i + 1] = c->cur ^ 1;
-                if (pipelined) {
-                    HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->main_idle, 0));
-                    (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->prep_stream);
-                    (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->prep_stream);
-                    rc = prepare(i + 1, c->cur ^ 1, c->prep_stream, sas[i + 1]);
-                    if (rc) return rc;
-                }
-            }
-            PlayArgs pa{};
-            pa.strat = static_cast<const uint2 *>(c->strat.p);
-            pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
-            pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
-            pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
-            pa.game_block = sas[i].game_row; // the kernel wants table rows: seat s of a game plays strategy 2 * row + s
-            pa.ov = static_cast<const DevOverride *>(c->ov.p);
-            pa.n_ov = (uint32_t)dov.size();
-            pa.mode = MODE_BLOCKS;
-            pa.n_games = p.n_games;
-            pa.gps = 1;
-            pa.n_sh = 1;
-            pa.k = 2;
-            pa.S = (uint32_t)n_blocks * 2u;
-            pa.target50 = ceil_div50(target_score);
-            pa.beat50 = floor_div50(target_score);
-            pa.max_rounds = (uint32_t)max_rounds;
-            HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0));
-            rc = launch_play_stage(c, sas[i], pa, plan, false, true, false);
-            if (rc) return rc;
-            hipLaunchKernelGGL(fk_h2h_reduce_kernel, dim3((p.n_games + 256u * H2H_RUN - 1u) / (256u * H2H_RUN)), dim3(256), 0, c->stream,
-                               static_cast<const uint32_t *>(c->rec0.p), p.n_games, (uint32_t)n_blocks, static_cast<unsigned long long *>(c->block_out.p));
-            HIPCHK(c, hipGetLastError());
-            if (!pipelined || n_ov) { // the next pass re-uses the one override buffer: finish this pass first
-                rc = finish_play(c, pa, 0, "h2h attempt (pass-local index)");
-                if (rc) return rc;
-                if (i + 1 < passes.size()) {
-                    (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->stream);
-                    (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->stream);
-                    rc = prepare(i + 1, c->cur ^ 1, c->stream, sas[i + 1]);
-                    if (rc) return rc;
-                }
-            } else {
-                // the pass's error record and timers are read at the end of the generation; its kernel timer events must not
-                // be reused by the next launch
-                HIPCHK(c, hipMemcpyAsync(c->err_host, pa.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-                HIPCHK(c, hipStreamSynchronize(c->stream));
-                rc = report_device_error(c, c->err_host, 0, "h2h attempt (pass-local index)");
-                const int rc_t = finish_timers(c);
-                if (rc) return rc;
-                if (rc_t) return rc_t;
-            }
-        }
+                return true;
+            });
+        };
+        rc = play_block_passes(c, passes.size(), plan, root_seed, (uint32_t)n_blocks * 2u, target_score, max_rounds, pipelined, pass_blocks, pass_overrides);
+        if (rc) return rc;
         HIPCHK(c, hipMemcpyAsync(out.data(), c->block_out.p, (size_t)n_blocks * 4 * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int64_t b = 0; b < n_blocks; ++b) {
@@ -3130,18 +3146,14 @@ int fk_h2h_run(fk_ctx *c, const fk_strategy seats[2], uint64_t root_seed, uint64
 }
 
 // ---- head-to-head round robin: every pair of a table in one call (device side: fk_round_robin.h) ----
-// The window / generation / pass structure is h2h_run_blocks_impl's with the host's per-block work moved to the device: the host
-// reads the generation's total, the number of playing blocks and the call's error record, then two words per pass.
+// The window / generation structure is h2h_run_blocks_impl's with the host's per-block work moved to the device: the host reads the
+// generation's total, the number of playing blocks and the call's error record, then two words per pass; play_block_passes plays them.
 static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end,
                                 uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds, const LaunchPlan &plan,
                                 uint32_t *block_state, int64_t *summary) {
     using namespace fkrr;
     HIPCHK(c, hipSetDevice(c->device));
-    c->timing = fk_timing{};
-    c->play_instance.clear();
-    c->pending.clear();
-    c->letters.clear(); // (a failed call may have left some)
-    c->mail_used = 0;
+    begin_call(c);
     // the n-row table, packed, and its patience classes: uploaded once per call
     std::vector<uint2> packed((size_t)n);
     std::vector<uint8_t> patience((size_t)n);
@@ -3190,7 +3202,6 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     if (summary) HIPCHK(c, hipMemsetAsync(c->rr[11].p, 0, (size_t)n * RR_COLS * 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors are pageable)
 
-    const SeedPool seat_prefix = seed_prefix(203u /* H2H_PLAYER */, root_seed, 2u);
     const bool pipelined = c->pipeline != 0;
     std::vector<uint32_t> bounds;
     for (uint64_t pair0 = pair_begin; pair0 < pair_end; pair0 += window_pairs) {
@@ -3235,93 +3246,19 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
             HIPCHK(c, hipStreamSynchronize(c->stream));
             auto pass_games = [&](size_t i) { return (uint32_t)(std::min<uint64_t>(total, (uint64_t)(i + 1) * max_launch) - (uint64_t)i * max_launch); };
 
-            // preparation of pass `i` into chunk set `si` on stream `st`: its DevBlocks are written on the device
-            auto prepare = [&](size_t i, int si, hipStream_t st, SeedArgs &sa) -> int {
-                ChunkSet &cs = c->sets[si];
-                const uint32_t first = bounds[2 * i], nb = bounds[2 * i + 1] - first, games = pass_games(i);
+            // a pass's DevBlocks are written on the device
+            const PassBlocks pass_blocks = [&](size_t i, DevBlock *dst, hipStream_t st, uint32_t &nb, uint32_t &games) -> int {
+                const uint32_t first = bounds[2 * i];
                 if (bounds[2 * i + 1] <= first || bounds[2 * i + 1] > n_act) return fail(c, FK_ERR_HIP, "round-robin pass %zu has no blocks", i);
-                cs.prepared = false;
-                int rc2 = ensure(c, cs.blocks, (size_t)nb * sizeof(DevBlock));
-                if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)games * 4);
-                if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)games * 4);
-                if (rc2) return rc2;
+                nb = bounds[2 * i + 1] - first;
+                games = pass_games(i);
+                if (!dst) return FK_OK;
                 hipLaunchKernelGGL(fk_rr_pass_blocks_kernel, dim3((nb + 255u) / 256u), dim3(256), 0, st, d_off, d_act, d_state, first, nb,
-                                   (unsigned long long)((uint64_t)i * max_launch), pair0, static_cast<DevBlock *>(cs.blocks.p));
+                                   (unsigned long long)((uint64_t)i * max_launch), pair0, dst);
                 HIPCHK(c, hipGetLastError());
-                sa = SeedArgs{};
-                sa.prefix = seat_prefix;
-                sa.gps = 0;
-                sa.k = 2;
-                sa.n_games = games;
-                sa.blocks = static_cast<const DevBlock *>(cs.blocks.p);
-                sa.n_blocks = nb;
-                sa.game_block = static_cast<const uint32_t *>(cs.game_block.p);
-                sa.game_row = static_cast<const uint32_t *>(cs.game_row.p);
-                rc2 = seed_stage(c, si, st, sa, false, true);
-                if (rc2) return rc2;
-                HIPCHK(c, hipEventRecord(cs.ready, st));
-                cs.side = (st == c->prep_stream);
                 return FK_OK;
             };
-
-            std::vector<SeedArgs> sas(n_passes);
-            std::vector<int> set_of(n_passes);
-            set_of[0] = c->cur;
-            HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0)); // an unused side-stream preparation may still own the set
-            (void)hipEventRecord(CSET(c).ev[0], c->stream);             // no permutations here: an empty interval
-            (void)hipEventRecord(CSET(c).ev[1], c->stream);
-            if ((rc = prepare(0, c->cur, c->stream, sas[0]))) return rc;
-            for (size_t i = 0; i < n_passes; ++i) {
-                c->cur = set_of[i];
-                HIPCHK(c, hipEventRecord(c->main_idle, c->stream)); // everything that used the other chunk set is in front of this point
-                if (i + 1 < n_passes) {
-                    set_of[i + 1] = c->cur ^ 1;
-                    if (pipelined) {
-                        HIPCHK(c, hipStreamWaitEvent(c->prep_stream, c->main_idle, 0));
-                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->prep_stream);
-                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->prep_stream);
-                        if ((rc = prepare(i + 1, c->cur ^ 1, c->prep_stream, sas[i + 1]))) return rc;
-                    }
-                }
-                PlayArgs pa{};
-                pa.strat = static_cast<const uint2 *>(c->strat.p);
-                pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
-                pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
-                pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
-                pa.game_block = sas[i].game_row; // the kernel wants table rows: seat s of a game plays strategy 2 * row + s
-                pa.ov = nullptr;
-                pa.n_ov = 0;
-                pa.mode = MODE_BLOCKS;
-                pa.n_games = sas[i].n_games;
-                pa.gps = 1;
-                pa.n_sh = 1;
-                pa.k = 2;
-                pa.S = n_rows * 2u;
-                pa.target50 = ceil_div50(target_score);
-                pa.beat50 = floor_div50(target_score);
-                pa.max_rounds = (uint32_t)max_rounds;
-                HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0));
-                if ((rc = launch_play_stage(c, sas[i], pa, plan, false, true, false))) return rc;
-                hipLaunchKernelGGL(fk_h2h_reduce_kernel, dim3((pa.n_games + 256u * H2H_RUN - 1u) / (256u * H2H_RUN)), dim3(256), 0, c->stream,
-                                   static_cast<const uint32_t *>(c->rec0.p), pa.n_games, n_rows, static_cast<unsigned long long *>(c->block_out.p));
-                HIPCHK(c, hipGetLastError());
-                if (!pipelined) {
-                    if ((rc = finish_play(c, pa, 0, "h2h attempt (pass-local index)"))) return rc;
-                    if (i + 1 < n_passes) {
-                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[0], c->stream);
-                        (void)hipEventRecord(c->sets[c->cur ^ 1].ev[1], c->stream);
-                        if ((rc = prepare(i + 1, c->cur ^ 1, c->stream, sas[i + 1]))) return rc;
-                    }
-                } else {
-                    // the pass's error record and timers are read before the next launch reuses the kernel timer events
-                    HIPCHK(c, hipMemcpyAsync(c->err_host, pa.err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-                    HIPCHK(c, hipStreamSynchronize(c->stream));
-                    rc = report_device_error(c, c->err_host, 0, "h2h attempt (pass-local index)");
-                    const int rc_t = finish_timers(c);
-                    if (rc) return rc;
-                    if (rc_t) return rc_t;
-                }
-            }
+            if ((rc = play_block_passes(c, n_passes, plan, root_seed, n_rows * 2u, target_score, max_rounds, pipelined, pass_blocks, nullptr))) return rc;
             hipLaunchKernelGGL(fk_rr_apply_kernel, rows_grid, b256, 0, c->stream, d_state, d_need, static_cast<const unsigned long long *>(c->block_out.p),
                                n_rows, d_err);
             HIPCHK(c, hipGetLastError());
@@ -3354,30 +3291,19 @@ int fk_h2h_round_robin(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t 
                     (unsigned long long)pair_end, (unsigned long long)all_pairs, (int)n);
     if (target == 0 || target > max_attempts || max_attempts > 0x7fffffffull)
         return fail(c, FK_ERR_ARG, "target must be in [1, max_attempts] and max_attempts at most 2^31 - 1");
-    if (max_rounds < 0 || max_rounds > 65535) return fail(c, FK_ERR_ARG, "max_rounds must be in [0, 65535]");
+    int rc = check_max_rounds(c, max_rounds);
+    if (rc) return rc;
     const LaunchPlan plan = plan_play(plan_knobs(c), PLAN_H2H, 2, 4, false, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
                     50 * LEAN_MAX_TARGET50);
-    int rc = validate_strategies(c, table, n);
-    if (rc) return rc;
+    if ((rc = validate_strategies(c, table, n))) return rc;
     if (pair_begin == pair_end) return FK_OK; // an empty range touches nothing
     if (!block_state) return fail(c, FK_ERR_ARG, "block_state is required");
-    c->oom = false;
-    c->oom_replays = 0;
-    c->chunk_limit = 0;
-    rc = h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
     // no in/out state: the replay after an out-of-memory failure is the call again with half the budget
-    while (rc == FK_ERR_HIP && c->oom && c->oom_replays < 8 && c->last_budget > ((int64_t)32 << 20)) {
-        c->oom = false;
-        ++c->oom_replays;
-        release_workspace(c);
-        c->chunk_limit = c->last_budget / 2;
-        if (getenv("FK_DEBUG_REPLAY")) fprintf(stderr, "out of device memory: replay %d with a %lld-byte workspace\n", c->oom_replays, (long long)c->chunk_limit);
-        rc = h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
-    }
-    c->chunk_limit = 0;
-    return rc;
+    return replay_on_oom(c, [&] {
+        return h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
+    });
 }
 
 // The NEXT fk_tournament_run / _stats call on this context will play shuffles [shuffle_begin, shuffle_end) of the same table,

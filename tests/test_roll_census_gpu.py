@@ -2,6 +2,8 @@
 
 * ``census_games`` against ``RollCensus.from_events(fk_trace_games(...))`` on the same list — the census is a pure function of the
   trace's event stream, and the trace's events are pinned byte for byte against the CPU oracle by tests/test_trace_gpu.py;
+* ``census_games`` and ``tournament_census`` against the census of the CPU oracle's own events (tests/trace_oracle.py) — directly,
+  so that the census kernel's restatement of the game loop does not rest on the trace kernel's alone;
 * chunked against unchunked, a second call against the first (the tables are set, not added to);
 * ``tournament_census`` against ``census_games`` on the replay coordinates of the same games (``trace.tournament_seats``), and its
   per-strategy rolls, farkles and turns against the sums the hot game kernels report for the same shuffles
@@ -149,6 +151,49 @@ def test_repeated_calls_set_the_tables(eng, list257, want257):
     assert_same(second, want257[256])
     small = device_census(eng, coords[:3], table, ss[:3], 2)  # a smaller call after a larger one: nothing of the larger one is left
     assert_same(small, from_trace(eng, coords[:3], table, ss[:3], 2))
+
+
+def oracle_census(coords, table, ss, k, max_rounds=200, turn_bins=256):
+    """The census of the CPU oracle's events for the list (each game's row pinned against the oracle's row)."""
+    import trace_oracle
+    from farkle_ii_amd.roll_census import RollCensus
+
+    _, begin, events = trace_oracle.pinned(coords, table, ss, k, 10_000, max_rounds)
+    return RollCensus.from_events(events, begin, np.asarray(ss).reshape(len(coords), k), len(table), turn_bins)
+
+
+def test_lists_equal_the_census_of_the_oracles_events(eng, list257):
+    """One full wave plus one lane of the two-seat list, with the clamp bin on the path, and a three-seat list of three games."""
+    from farkle_ii_amd.backend import make_coords
+
+    coords, table, ss = list257
+    got = device_census(eng, coords[:65], table, ss[:65], 2, turn_bins=8)
+    assert_same(got, oracle_census(coords[:65], table, ss[:65], 2, turn_bins=8), "two seats")
+    assert got.turn_hist[:, 7].sum() > 0  # the clamp bin is reached
+    coords3 = make_coords(103, 11, 3, shuffle_index=np.array([5, 6, 7]), game_index=np.array([0, 1, 2]), n=3)
+    ss3 = np.array([[0, 65, 70], [79, 3, 66], [71, 72, 1]], dtype=np.int32)
+    assert_same(device_census(eng, coords3, table, ss3, 3, turn_bins=8), oracle_census(coords3, table, ss3, 3, turn_bins=8), "three seats")
+
+
+def test_tournament_census_equals_the_census_of_the_oracles_events(eng):
+    """k = 2, S = 8, shuffles 1 ... 4, max_rounds = 3 for one game in the middle: the permutations, the rebuilt coordinates and the
+    override search of the tournament instance against the oracle's events for the same games."""
+    from census_engine_stub import tournament_game_list
+    from farkle_ii_amd.backend import OVERRIDE_DTYPE
+    from farkle_ii_amd.roll_census import RollCensus
+
+    table = census_cases.mixed_table()[[0, 21, 42, 63, 65, 70, 75, 79]]
+    k, S, begin, end = 2, 8, 1, 5
+    gps = S // k
+    ov = np.zeros(1, dtype=OVERRIDE_DTYPE)
+    ov[0] = (42, 3, 1, k, 3)  # shuffle 3, game 1: three rounds
+    coords, ss = tournament_game_list(S, k, 42, begin, end)
+    hit = (3 - begin) * gps + 1
+    rest = np.setdiff1d(np.arange(len(coords)), [hit])
+    want = oracle_census(coords[rest], table, ss[rest], k).merge(oracle_census(coords[hit:hit + 1], table, ss[hit:hit + 1], k, max_rounds=3))
+    got = RollCensus.from_engine(eng.tournament_census(table, k, 42, begin, end, overrides=ov))
+    assert_same(got, want)
+    assert not got.equals(oracle_census(coords, table, ss, k))  # the override shortened a game
 
 
 def replay_list(root, k, shuffle_begin, shuffle_end, S):
