@@ -618,7 +618,9 @@ class Engine:
         tied with the last one kept — with their counts and per-lag sums ``[M][n_lags][6]`` (layout of ``rng_matchups.host_reduce``)."""
         lags_a = np.ascontiguousarray(list(lags), dtype=np.int32)
         digest = np.ascontiguousarray(records["digest"], dtype=np.uint64)
-        seats = np.ascontiguousarray(np.asarray(records["seats"], dtype=np.uint16).reshape(-1, k))
+        k = int(k)
+        seats = np.asarray(records["seats"], dtype=np.uint16)
+        seats = np.ascontiguousarray(seats.reshape(-1, k) if k >= 1 else seats)  # (a k below 1 is the library's to refuse)
         rounds = np.ascontiguousarray(records["rounds"], dtype=np.uint16)
         n = len(digest)
         minimum = int(lags_a.min()) + 2 if len(lags_a) else 2
@@ -628,7 +630,7 @@ class Engine:
             counts = np.zeros(4, dtype=np.int64)
             hist = np.zeros(minimum + 64, dtype=np.uint64)
             out_d = np.zeros(max(capacity, 1), dtype=np.uint64)
-            out_s = np.zeros((max(capacity, 1), k), dtype=np.uint16)
+            out_s = np.zeros((max(capacity, 1), max(k, 0)), dtype=np.uint16)
             out_c = np.zeros(max(capacity, 1), dtype=np.int64)
             out_x = np.zeros((max(capacity, 1), len(lags_a), 6), dtype=np.int64)
             rc = self._lib.fk_matchup_reduce(self._ctx, C.c_int32(k), C.c_int64(n), _p(digest), _p(seats), _p(rounds), _p(lags_a),

@@ -82,6 +82,28 @@ def test_ranges_merge_to_the_whole_at_every_cut():
         assert np.array_equal(m.sums, whole.sums) and np.array_equal(m.tail, whole.tail) and np.array_equal(m.head, whole.head), (c1, c2)
 
 
+BEYOND_LAGS = (1, 69, 70, 71, 65535)  # over 70 shuffles: one pair at lag 69, none from the series length on
+BEYOND_SHUFFLES = 70
+
+
+def test_stub_engine_lags_at_and_beyond_the_series_length():
+    """Premise of the GPU test of the same name: the host statement takes a lag at or beyond the series length and finds no pair."""
+    from bench import grid64
+
+    res = StubEngine().tournament_lags(grid64(), 2, 42, 0, BEYOND_SHUFFLES, BEYOND_LAGS)
+    sums = res["lag_sums"]
+    assert sums.shape == (64, len(BEYOND_LAGS), 11)
+    assert np.all(sums[:, 0, 0] == BEYOND_SHUFFLES - 1) and np.all(sums[:, 1, 0] == 1) and not sums[:, 2:].any()
+    assert np.all(sums[:, 1, 6] > 0) and np.all(sums[:, 1, 7] > 0)  # the one pair is (first, last) n_rounds
+    assert np.array_equal(sums[:, 1, 6], res["lag_head"][0] & 0x7FFF) and np.array_equal(sums[:, 1, 7], res["lag_tail"][-1] & 0x7FFF)
+    assert len(res["lag_head"]) == BEYOND_SHUFFLES and np.array_equal(res["lag_head"], res["lag_tail"])  # the whole range
+    # two ranges merge to the whole although every lag but the first is longer than either
+    whole = LagSummary.from_engine(res, BEYOND_LAGS)
+    values = res["lag_head"]
+    merged = LagSummary.from_series(values[:30], BEYOND_LAGS).merge(LagSummary.from_series(values[30:], BEYOND_LAGS))
+    assert np.array_equal(merged.sums, whole.sums) and np.array_equal(merged.head, whole.head) and np.array_equal(merged.tail, whole.tail)
+
+
 def test_stub_engine_split_calls_merge_to_one_call():
     doc = gu.load("rng_lag_vectors.json")
     case, lags = doc["cases"][1], doc["lags"]

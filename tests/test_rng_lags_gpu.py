@@ -71,6 +71,46 @@ def test_hip_equals_the_oracle_statement_on_larger_tables_and_across_chunks(eng)
         assert np.array_equal(merged.sums, whole["lag_sums"]) and np.array_equal(merged.tail, whole["lag_tail"])
 
 
+def test_hip_lags_at_and_beyond_the_series_length(eng):
+    """70 shuffles with lags 69 (one pair per strategy), 70, 71 and 65 535 (none): the sums kernel's loop starts at
+    ``max(r0, valid_from + lag)`` beyond the chunk, the carry is 65 535 rows deep and head / tail are the whole range.
+
+    A shuffle of the 64-strategy grid at two seats takes 3 840 bytes of workspace, so its 70 shuffles fit one chunk even of the
+    smallest workspace (1 MiB holds 273); that run is compared all the same, and the carry across chunks is driven by the first
+    1 024 strategies of the default grid, whose 70 shuffles take at least five chunks there."""
+    from oracle_engine_stub import Engine as StubEngine
+
+    from bench import grid64
+    from farkle_ii_amd.rng_lags import LagSummary
+    from test_rng_lags_cpu import BEYOND_LAGS as lags, BEYOND_SHUFFLES as n_sh
+    from tools.time_config import table_for
+
+    stub = StubEngine()
+    t64, t1024 = grid64(), table_for(1024)
+    want = stub.tournament_lags(t64, 2, 42, 0, n_sh, lags)
+    want_wide = stub.tournament_lags(t1024, 2, 5, 0, n_sh, lags)
+    for w in (want, want_wide):
+        assert np.all(w["lag_sums"][:, 1, 0] == 1) and not w["lag_sums"][:, 2:].any() and len(w["lag_head"]) == n_sh
+    _same(eng.tournament_lags(t64, 2, 42, 0, n_sh, lags), want)
+    _same(eng.tournament_lags(t1024, 2, 5, 0, n_sh, lags), want_wide)
+    eng.set_option("chunk_bytes", 1 << 20)
+    try:
+        small = eng.tournament_lags(t64, 2, 42, 0, n_sh, lags)
+        print("play launches, 64 strategies:", eng.timing()["play_launches"])
+        wide = eng.tournament_lags(t1024, 2, 5, 0, n_sh, lags)
+        print("play launches, 1 024 strategies:", eng.timing()["play_launches"])
+        assert eng.timing()["play_launches"] >= 3
+    finally:
+        eng.set_option("chunk_bytes", 48 << 30)
+    _same(small, want)
+    _same(wide, want_wide)
+    for table, seed, w in ((t64, 42, want), (t1024, 5, want_wide)):  # two calls, each shorter than every lag but the first
+        a, b = (LagSummary.from_engine(eng.tournament_lags(table, 2, seed, lo, hi, lags), lags) for lo, hi in ((0, 30), (30, n_sh)))
+        merged = a.merge(b)
+        assert merged.n == n_sh and np.array_equal(merged.sums, w["lag_sums"])
+        assert np.array_equal(merged.head, w["lag_head"]) and np.array_equal(merged.tail, w["lag_tail"])
+
+
 def test_lag_request_validation(eng):
     from bench import grid64
     from farkle_ii_amd.backend import FarkleHipError
