@@ -119,7 +119,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin"]
 _libs: dict = {}
 
 
@@ -893,6 +893,21 @@ class Engine:
         out = np.zeros((len(coords), int(n_draws)), dtype=np.uint32)
         self._check(self._lib.fk_debug_bounded_draws(self._ctx, C.c_int64(len(coords)), _p(coords), C.c_uint64(int(bound)),
                                                      C.c_int32(int(n_draws)), _p(out)))
+        return out
+
+    def debug_perm_from_draws(self, S: int, draws: np.ndarray, path: int, out: np.ndarray | None = None, n_sh: int | None = None) -> np.ndarray:
+        """``fk_debug_perm_from_draws``: int32 ``[n_sh][S]``, the Fisher-Yates result of every row of uint16 ``draws [n_sh][S - 1]``
+        (draw ``n`` is the ``j`` of step ``S - 1 - n``, so ``draws[:, n] <= S - 1 - n``) by the swap-chain kernel (``path`` 1) or the
+        chain-free kernel (``path`` 2).  ``out``: the caller's result array (a refused call leaves it as it was); ``n_sh``: the shuffle
+        count handed to the entry when it is not ``len(draws)`` (refusal tests)."""
+        draws = np.ascontiguousarray(draws, dtype=np.uint16)
+        if n_sh is None:
+            n_sh = len(draws) if draws.ndim == 2 else draws.size // max(int(S) - 1, 1)
+        if out is None:
+            out = np.zeros((max(int(n_sh), 0), max(int(S), 0)), dtype=np.int32)
+        assert out.dtype == np.int32 and out.flags.c_contiguous
+        assert n_sh < 1 or S < 1 or (out.size == n_sh * S and draws.size == n_sh * (S - 1)), "draws [n_sh][S - 1] and out [n_sh][S]"
+        self._check(self._lib.fk_debug_perm_from_draws(self._ctx, C.c_int32(int(S)), C.c_int64(int(n_sh)), _p(draws), C.c_int32(int(path)), _p(out)))
         return out
 
     def performance_bootstrap(self, root_seed: int, ks, wins, exposures, replicate_begin: int, replicate_end: int, top_n: int,

@@ -1068,15 +1068,27 @@ int play_block_passes(fk_ctx *c, size_t n_passes, const LaunchPlan &plan, uint64
     return FK_OK;
 }
 
-// The permutation kernels of shuffles [d.sh0, d.sh0 + d.n_sh) into cs.perm (blocked layout, perm_at()) on `st`; the caller has
-// ensured cs.perm.  Shared by the tournament chunks and the roll census (fk_tournament_run_census).
-int launch_perm_kernels(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &d) {
-    const int32_t S = (int32_t)d.S;
-    const uint32_t n_sh = d.n_sh, slots = d.slots;
-    const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
-    const SeedPool perm_prefix = seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k);
-    int rc;
-    const size_t perm_lds = (size_t)slots * S * 2;
+// The accepted Fisher-Yates draws of a split launch as they lie in cs.draws: groups of eight 16-bit draws in one uint4, draw n of a
+// shuffle = the j of step S - 1 - n (so draws[n] <= S - 1 - n), oldest in the low half; a last partial group is right-aligned in the top
+// halves, behind the draws before it.  Group g of shuffle sh is the uint4 at g * g_stride + sh * sh_stride:
+//   path 1 (fk_perm_apply_kernel, the swap chains): group-major, g_stride = n_sh rounded up to 64;
+//   path 2 (fk_perm_parallel_kernel + fk_perm_block_kernel): one row of groups + 1 uint4 per shuffle (a row also takes the S results).
+struct DrawLayout {
+    uint32_t groups, g_stride, sh_stride;
+    size_t bytes;
+};
+
+DrawLayout draw_layout(int path, uint32_t S, uint32_t n_sh) {
+    const uint32_t groups = (S - 1u + 7u) / 8u;
+    if (path == 2) return DrawLayout{groups, 1u, groups + 1u, (size_t)n_sh * (groups + 1u) * 16};
+    const uint32_t n_sh_pad = (n_sh + 63u) & ~63u;
+    return DrawLayout{groups, n_sh_pad, 1u, (size_t)groups * n_sh_pad * 16};
+}
+
+// the chain-free kernel holds a shuffle in 14 B of LDS per strategy (+ its static words)
+bool perm_parallel_fits(int32_t S) { return (size_t)S * 14 <= LDS_LIMIT - 1024; }
+
+int configure_perm_kernels(fk_ctx *c) {
     static int perm_configured = -1; // per device (a second context may sit on another GPU of this process)
     if (perm_configured != c->device) {
         HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_perm_kernel),
@@ -1087,46 +1099,65 @@ int launch_perm_kernels(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(LDS_LIMIT - 1024))); // + its static words
         perm_configured = c->device;
     }
+    return FK_OK;
+}
+
+// First step of a split launch: the draws of shuffles [d.sh0, d.sh0 + d.n_sh) into cs.draws (ensured here) in layout `dl`.  A wave per
+// shuffle while the launch is small (fk_perm_wave.h: ~20 us instead of the thread-per-shuffle kernel's 1 ms latency), a thread per
+// shuffle when there are enough shuffles to fill the chip with them.
+int launch_perm_draws(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &d, const DrawLayout &dl) {
+    const uint32_t n_sh = d.n_sh;
+    const SeedPool perm_prefix = seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k);
+    const bool wave_draw = c->perm_draw_wave == 1 || (c->perm_draw_wave < 0 && n_sh <= WAVE_DRAW_MAX_SH);
+    const int rc = ensure(c, cs.draws, dl.bytes);
+    if (rc) return rc;
+    if (wave_draw)
+        hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
+                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, static_cast<uint4 *>(cs.draws.p));
+    else
+        hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
+                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, static_cast<uint4 *>(cs.draws.p));
+    return FK_OK;
+}
+
+// Second step: the permutations of n_sh shuffles from the draws in cs.draws (layout `dl` of `path`) into cs.perm (blocked layout); the
+// caller has ensured both buffers.  Shared with fk_debug_perm_from_draws, which uploads the draws instead of drawing them.
+void launch_perm_consumers(ChunkSet &cs, hipStream_t st, int path, const DrawLayout &dl, uint32_t n_sh, uint32_t S, uint32_t slots) {
+    const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
+    if (path == 2) {
+        hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), (size_t)S * 14, st,
+                           static_cast<uint4 *>(cs.draws.p), dl.sh_stride, n_sh, S);
+        hipLaunchKernelGGL(fk_perm_block_kernel, dim3((S + 255u) / 256u, perm_blocks), dim3(256), 0, st,
+                           static_cast<const uint16_t *>(cs.draws.p), dl.sh_stride * 8u, n_sh, S, slots,
+                           static_cast<uint16_t *>(cs.perm.p));
+    } else {
+        hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st,
+                           static_cast<const uint4 *>(cs.draws.p), dl.g_stride, n_sh, S, slots,
+                           static_cast<uint16_t *>(cs.perm.p));
+    }
+}
+
+// The permutation kernels of shuffles [d.sh0, d.sh0 + d.n_sh) into cs.perm (blocked layout, perm_at()) on `st`; the caller has
+// ensured cs.perm.  Shared by the tournament chunks and the roll census (fk_tournament_run_census).
+int launch_perm_kernels(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &d) {
+    const int32_t S = (int32_t)d.S;
+    const uint32_t n_sh = d.n_sh, slots = d.slots;
+    int rc = configure_perm_kernels(c);
+    if (rc) return rc;
     // large tables: the draws at full occupancy first (fk_perm_draw_kernel); then either the chain-free
     // permutation (fk_perm_parallel_kernel, one workgroup per shuffle, 14 B of LDS per strategy) or, for tables
     // beyond its LDS reach, the bare swap chains over LDS arrays (fk_perm_apply_kernel)
     const bool split = c->perm_split >= 1 || (c->perm_split < 0 && S >= 1024 && n_sh >= 256);
-    const size_t pp_lds = (size_t)S * 14;
-    const bool parallel = split && c->perm_split != 1 && pp_lds <= LDS_LIMIT - 1024;
-    // the draws: a wave per shuffle while the launch is small (fk_perm_wave.h: ~20 us instead of the thread-per-shuffle kernel's
-    // 1 ms latency), a thread per shuffle when there are enough shuffles to fill the chip with them
-    const bool wave_draw = c->perm_draw_wave == 1 || (c->perm_draw_wave < 0 && n_sh <= WAVE_DRAW_MAX_SH);
-    if (parallel) {
-        const uint32_t groups = ((uint32_t)S - 1u + 7u) / 8u, row_u4 = groups + 1u; // a row also holds the S results
-        rc = ensure(c, cs.draws, (size_t)n_sh * row_u4 * 16);
-        if (rc) return rc;
-        if (wave_draw)
-            hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
-                               perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
-        else
-            hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
-                               perm_prefix, d.sh0, n_sh, (uint32_t)S, 1u, row_u4, static_cast<uint4 *>(cs.draws.p));
-        hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), pp_lds, st,
-                           static_cast<uint4 *>(cs.draws.p), row_u4, n_sh, (uint32_t)S);
-        hipLaunchKernelGGL(fk_perm_block_kernel, dim3(((uint32_t)S + 255u) / 256u, perm_blocks), dim3(256), 0, st,
-                           static_cast<const uint16_t *>(cs.draws.p), row_u4 * 8u, n_sh, (uint32_t)S, slots,
-                           static_cast<uint16_t *>(cs.perm.p));
-    } else if (split) {
-        const uint32_t n_sh_pad = (n_sh + 63u) & ~63u, groups = ((uint32_t)S - 1u + 7u) / 8u;
-        rc = ensure(c, cs.draws, (size_t)groups * n_sh_pad * 16);
-        if (rc) return rc;
-        if (wave_draw)
-            hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
-                               perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
-        else
-            hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
-                               perm_prefix, d.sh0, n_sh, (uint32_t)S, n_sh_pad, 1u, static_cast<uint4 *>(cs.draws.p));
-        hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
-                           static_cast<const uint4 *>(cs.draws.p), n_sh_pad, n_sh, (uint32_t)S, slots,
-                           static_cast<uint16_t *>(cs.perm.p));
+    if (split) {
+        const int path = (c->perm_split != 1 && perm_parallel_fits(S)) ? 2 : 1;
+        const DrawLayout dl = draw_layout(path, d.S, n_sh);
+        if ((rc = launch_perm_draws(c, cs, st, d, dl))) return rc;
+        launch_perm_consumers(cs, st, path, dl, n_sh, d.S, slots);
     } else {
-        hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), perm_lds, st,
-                           perm_prefix, d.sh0, n_sh, (uint32_t)S, slots, static_cast<uint16_t *>(cs.perm.p));
+        const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
+        hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st,
+                           seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k), d.sh0, n_sh, d.S, slots,
+                           static_cast<uint16_t *>(cs.perm.p));
     }
     HIPCHK(c, hipGetLastError());
     return FK_OK;
@@ -3739,6 +3770,52 @@ int fk_debug_bounded_draws(fk_ctx *c, int64_t n, const fk_coord *coords, uint64_
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, c->dbg[2].p, (size_t)n * n_draws * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return FK_OK;
+}
+
+int fk_debug_perm_from_draws(fk_ctx *c, int32_t S, int64_t n_sh, const uint16_t *draws, int32_t path, int32_t *perms) {
+    if (!c) return FK_ERR_ARG;
+    if (S < 1 || S > 65535) return fail(c, FK_ERR_ARG, "S=%d: a table has 1 to 65535 strategies", S);
+    if (n_sh < 1 || (uint64_t)n_sh * (uint64_t)S > ((uint64_t)1 << 28)) return fail(c, FK_ERR_ARG, "1 shuffle at least, 2^28 entries at most in one probe");
+    if (path != 1 && path != 2) return fail(c, FK_ERR_ARG, "path %d: 1 = the swap chains, 2 = the chain-free kernel", (int)path);
+    if (path == 2 && !perm_parallel_fits(S)) return fail(c, FK_ERR_ARG, "S=%d is beyond the chain-free kernel's LDS reach", S);
+    if (!perms || (S > 1 && !draws)) return fail(c, FK_ERR_ARG, "draws and perms are required");
+    const uint32_t N = (uint32_t)S - 1u, full = N & ~7u, tail = N & 7u, n = (uint32_t)n_sh;
+    // the kernels index LDS with the draws: one beyond its step's bound never reaches the device
+    for (uint32_t sh = 0; sh < n; ++sh)
+        for (uint32_t p = 0; p < N; ++p)
+            if (draws[(size_t)sh * N + p] > N - p)
+                return fail(c, FK_ERR_ARG, "shuffle %u, draw %u: %u is beyond its step's bound %u", sh, p, (unsigned)draws[(size_t)sh * N + p], N - p);
+    HIPCHK(c, hipSetDevice(c->device));
+    const DrawLayout dl = draw_layout(path, (uint32_t)S, n);
+    std::vector<uint16_t> packed(dl.bytes / 2, (uint16_t)0);
+    for (uint32_t sh = 0; sh < n; ++sh) {
+        uint16_t *const row = packed.data() + (size_t)sh * dl.sh_stride * 8u;
+        const size_t group_u16 = (size_t)dl.g_stride * 8u;
+        for (uint32_t p = 0; p < N; ++p) {
+            const uint16_t j = draws[(size_t)sh * N + p];
+            if (p < full) row[(size_t)(p >> 3) * group_u16 + (p & 7u)] = j;
+            if (tail && p + 8u >= N) row[(size_t)(full >> 3) * group_u16 + (p + 8u - N)] = j; // the right-aligned last group
+        }
+    }
+    int rc = configure_perm_kernels(c);
+    if (rc) return rc;
+    // the chunk set no prepared (hinted) tournament chunk sits in; whatever it held is void afterwards
+    ChunkSet &cs = c->sets[c->sets[c->cur].prepared ? c->cur ^ 1 : c->cur];
+    cs.prepared = false;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
+    const uint32_t slots = perm_slots(S), perm_blocks = (n + slots - 1u) / slots;
+    if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2))) return rc;
+    if ((rc = ensure(c, cs.draws, dl.bytes))) return rc;
+    if (dl.bytes) HIPCHK(c, hipMemcpyAsync(cs.draws.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, c->stream));
+    launch_perm_consumers(cs, c->stream, path, dl, n, (uint32_t)S, slots);
+    HIPCHK(c, hipGetLastError());
+    std::vector<uint16_t> perm_host((size_t)perm_blocks * S * slots);
+    HIPCHK(c, hipMemcpyAsync(perm_host.data(), cs.perm.p, perm_host.size() * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (uint32_t s = 0; s < n; ++s)
+        for (int32_t i = 0; i < S; ++i)
+            perms[(size_t)s * S + i] = perm_host[((size_t)(s / slots) * S + i) * slots + s % slots];
     return FK_OK;
 }
 

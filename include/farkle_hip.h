@@ -629,6 +629,18 @@ int fk_debug_dice_keys(fk_ctx *ctx, int64_t n, const uint64_t *state, int32_t n_
  * draws nothing from the stream (every result 0).  A bound such as 2^31 + 1 rejects about half the draws, which no batch count does. */
 int fk_debug_bounded_draws(fk_ctx *ctx, int64_t n, const fk_coord *coords, uint64_t bound, int32_t n_draws, uint32_t *out);
 
+/* The two consumers of a shuffle's accepted Fisher-Yates draws, driven by a draw list of the caller instead of the generator:
+ * perms[sh * S + e] (n_sh x S, int32) = the result of  a = arange(S); for n = 0 .. S - 2: i = S - 1 - n, swap(a[i], a[draws[sh][n]])
+ * from host draws[n_sh][S - 1] (uint16; draw n is the j of step S - 1 - n).  path 1: fk_perm_apply_kernel (the swap chains), path 2:
+ * fk_perm_parallel_kernel + fk_perm_block_kernel (bucket sort + pointer jumping), each launched exactly as a tournament chunk launches
+ * it.  The host packs the draws into the path's device layout — groups of eight 16-bit draws per 16 bytes, a last partial group
+ * right-aligned in the top halves behind the draws before it; path 1 group-major over n_sh rounded up to 64, path 2 one row of
+ * ceil((S - 1) / 8) + 1 groups per shuffle — and reads the blocked result back as fk_tournament_run does for `perms`.
+ * Precondition, checked on the host before anything is launched: draws[sh][n] <= S - 1 - n (the kernels index LDS with the draws).
+ * FK_ERR_ARG, with perms untouched: S outside [1, 65535], n_sh < 1, a path other than 1 or 2, path 2 at an S beyond the chain-free
+ * kernel's LDS reach (14 S bytes > the launch limit less 1 KiB), a draw beyond its bound. */
+int fk_debug_perm_from_draws(fk_ctx *ctx, int32_t S, int64_t n_sh, const uint16_t *draws, int32_t path, int32_t *perms);
+
 /* The performance stage's joint deterministic-batch bootstrap (analysis/performance.py: _BootstrapRangeWriter.__call__ :838-928,
  * _reduce_bootstrap_ranges :1013-1111; _joint_batch_resampling :715-833) for replicates [replicate_begin, replicate_end).
  * Inputs: n_k player counts in the caller's (ascending) order; per player count i its k = ks[i], its ELIGIBLE batches

@@ -360,7 +360,8 @@ def test_permutation_kernels_agree_with_numpy_semantics(eng, po, S, k):
     restatement of NumPy's loop, permutations and tallies; shuffle counts that leave partial blocks and partial 8-draw groups.
     16 386 / 32 770 / 65 534 strategies (k = 2): the masked draws of a shuffle change bit length between the bounds 16 383 / 16 384 and
     32 767 / 32 768, and 65 534 is the largest table the ABI takes; at these sizes the chain-free kernel's LDS does not fit, so split
-    modes 1 and 2 both run the swap chains."""
+    modes 1 and 2 both run the swap chains.
+    Odd tables, every tail of the last draw group, the LDS seams and synthetic draw lists: test_perm_stage_gpu.py / perm_stage_cases.py."""
     table = _random_valid_table(S, S) if (S <= 96 or S > 5160) else _default_table()[:S]  # 7 140: the reference's largest documented grid
     n_sh = {8: 300, 64: 521, 96: 77, 1290: 70, 5160: 37, 7140: 260, 16386: 5, 32770: 4, 65534: 3}[S]
     ref = po.tournament(table.view(po.STRATEGY_DTYPE), k, 21, 1000, 1000 + n_sh, want_perms=True, max_rounds=3, n_threads=16)
