@@ -1195,6 +1195,37 @@ __host__ __device__ inline Finish2 finish2_50(const LeanCounters &s0, const Lean
     return finish2_50_winner(second ? s1 : s0, second, rounds, final_round);
 }
 
+// ---- the guard bands of the two-seat lean instances since round 12: tested every RG_SAMPLE_TRIPS-th trip and where a game ends ----
+// roll_guards50 tests the three u16 bands (n_rolls, sf_dice, so_dice) in every roll: three half-rate compares per trip for fields that
+// grow by one roll, or at most six dice, per roll and whose bands leave 1 535 (rolls) and 2 535 (dice) below 65 535.  These instances
+// keep the roll limit and the turn-score band in the roll (roll_guards50_turn) and test the three fields
+//   - at a SAMPLE POINT: every RG_SAMPLE_TRIPS-th trip of the wave, on BOTH records of every playing lane (sampled_overflow50), and
+//   - where a GAME ENDS, in front of its hand-over, on both records, highest_turn included (game_end_overflow50).
+// Why no field wraps unseen and every game beyond a band is reported: a lane makes at most one roll per trip, so between two tests of a
+// record a field grows by at most RG_SAMPLE_TRIPS rolls or 6 x RG_SAMPLE_TRIPS dice; a record that passed a test held at most the band,
+// so it holds at most band + 6 x RG_SAMPLE_TRIPS < 65 535 at the next one (the static_assert below): it has not wrapped, and a value
+// beyond the band is seen there.  A game that ends between two sample points is tested at its end, before its records are read for the
+// results and before its lane is given another game, whose fields start at zero.  The error then names the game as before; which roll
+// raises it is not part of the ABI (after an error the call's outputs are unspecified).
+// The turn-score band stays in the roll: a banked turn is ADDED into cE's low half, next to the flags and the strategy index, and the
+// launch plan leaves exactly one turn of RG_TURN50 above the largest target (LEAN_MAX_TARGET50), so a turn that ran on past the band for
+// some trips could carry into them.  highest_turn (cB's low half) is therefore at most RG_TURN50 where a game ends; the game-end test
+// restates it.  tests/native/guard_sampling_host_check.hip drives these pieces around every band.
+constexpr uint32_t RG_SAMPLE_TRIPS = 32u;
+static_assert((RG_SAMPLE_TRIPS & (RG_SAMPLE_TRIPS - 1u)) == 0u && RG_SAMPLE_TRIPS <= 32u, "a power of two, at most 32");
+static_assert(RG_N_ROLLS + RG_SAMPLE_TRIPS <= 65535u && RG_DICE + 6u * RG_SAMPLE_TRIPS <= 65535u, "no field wraps between two tests");
+
+__host__ __device__ inline uint32_t roll_guards50_turn(uint32_t rolls_before, const RollRegs &r) { // the per-roll half
+    const bool limit = rolls_before >= RG_TURN_ROLLS, overflow = r.turn_score >= (int32_t)(RG_TURN50 + 1u);
+    return limit ? (uint32_t)RG_ROLL_LIMIT : overflow ? (uint32_t)RG_OVERFLOW : (uint32_t)RG_NONE;
+}
+__host__ __device__ inline bool sampled_overflow50(uint32_t cA, uint32_t cC, uint32_t cD) { // the three bands of one record (roll_overflow50's compares)
+    return ((uint16_t)cA >= (uint16_t)(RG_N_ROLLS + 1u)) | (cC >= ((RG_DICE + 1u) << 16)) | (cD >= ((RG_DICE + 1u) << 16));
+}
+__host__ __device__ inline bool game_end_overflow50(const LeanCounters &s0, const LeanCounters &s1) {
+    return sampled_overflow50(s0.cA, s0.cC, s0.cD) | sampled_overflow50(s1.cA, s1.cC, s1.cD) | ((s0.cB & 0xffffu) > RG_TURN50) | ((s1.cB & 0xffffu) > RG_TURN50);
+}
+
 // The tally's sums of squares.  Eight of the ten metrics are 16-bit fields of the record (m[2], m[3], m[5..9]) or the round count (m[1] <=
 // max_rounds <= 65 535, checked where a call enters the library): value <= 65 535, square <= 65 535^2 = 4 294 836 225 < 2^32, so one 24-bit
 // multiply gives the whole square and the addend's high half is zero.  The two point-valued metrics (m[0], m[4]: a 16-bit field times 50,

@@ -839,6 +839,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     // two-player lean instances (KC = 2; not state-store): the packed strategies of both seats stay in registers for the game,
     // so a turn start is one increment load instead of LDS read -> index -> strategy load
     constexpr bool PK2 = (KC == 2) && LEAN && !GS;
+    // Round 12, the two-seat lean instances (the batched-H2H one too: config 5 gains with them, profiles/r12_ab_roll_per_trip.txt): the u16
+    // guard bands are sampled (fk_device.h: RG_SAMPLE_TRIPS), has_buf is written back as a toggle ...
+    constexpr bool GUARD_SAMPLED = PK2, HB_TOGGLE = PK2;
+    // ... and both seats' PCG increments stay in registers: the owner's and the xor of the two, so that a turn start is four v_xor where it
+    // was a 16-byte load (and every trip of the wave opened with the wait for it: some lane starts a turn in almost every trip)
+    constexpr bool INC_REGS = PK2;
+    uint64_t inc_delta_lo = 0, inc_delta_hi = 0;
     // Layout of these words, and of `own_bits` while such an instance plays (init_game re-packs the table's entry): .x = thr50;
     // .y = flags [15:8] as in the table | dice threshold SIGN-EXTENDED in [31:16], low byte 0 — so the threshold is one full-rate
     // arithmetic shift per roll.  Strat50's two-argument constructor (threshold in the low byte) must not be given such a word:
@@ -941,7 +948,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         }
         if (PK2) {
             own_rec = lds_addr(__umul24(s, SEAT_STRIDE) + lane_base);
-            own_inc_at = (uint64_t)(uintptr_t)&a.inc[(size_t)seed_slot * K + s];
+            if (INC_REGS) {
+                const uint4 other = a.inc[(size_t)seed_slot * K + (s ^ 1u)];
+                inc_delta_lo = own_inc_lo ^ ((uint64_t)other.x | ((uint64_t)other.y << 32));
+                inc_delta_hi = own_inc_hi ^ ((uint64_t)other.z | ((uint64_t)other.w << 32));
+            } else {
+                own_inc_at = (uint64_t)(uintptr_t)&a.inc[(size_t)seed_slot * K + s];
+            }
         }
         dice = 6;
         turn_score = 0;
@@ -1138,10 +1151,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             own_rec = (lds_addr(lane_base) + lds_addr(lane_base + SEAT_STRIDE)) - own_rec; // the sum of the two records' addresses less this one
             own_thr ^= (int32_t)pk_delta.x;
             own_bits ^= pk_delta.y;
-            own_inc_at ^= 16u;
-            const u32x4 inc = *(global_u4 *)own_inc_at; // the new owner's increment: the one memory request of a turn start
-            own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
-            own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
+            if constexpr (INC_REGS) {
+                own_inc_lo ^= inc_delta_lo, own_inc_hi ^= inc_delta_hi;
+            } else {
+                own_inc_at ^= 16u;
+                const u32x4 inc = *(global_u4 *)own_inc_at; // the new owner's increment: the one memory request of a turn start
+                own_inc_lo = (uint64_t)inc.x | ((uint64_t)inc.y << 32);
+                own_inc_hi = (uint64_t)inc.z | ((uint64_t)inc.w << 32);
+            }
             dice = 6u;
             turn_score = 0;
             rolls_this_turn = 0u;
@@ -1173,6 +1190,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const uint32_t n = dice;
         bool detour;
         uint32_t key = roll_key_fast(rng, n, detour); // 4 x the score table's key
+        // has_buf as a toggle (round 12): a roll of n dice consumes n 32-bit words, so the flag flips iff n is odd — its bit of cE is one
+        // xor away, where extracting, adding, masking and merging took six instructions.  (A replayed roll may draw more words: below.)
+        uint32_t hb_flip = (n << CE_HAS_BUF_SHIFT) & CE_HAS_BUF;
         if (detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
             asm volatile("" ::: "memory"); // really re-read it: values forwarded from the loads above would stay live across the whole roll
             if (PK2) { // (F_LO0 ... F_BUF are the first five dwords of a lean record)
@@ -1187,6 +1207,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             }
             rng.has_buf = (cE & CE_HAS_BUF) ? 1u : 0u;
             key = 4u * roll_counts_sequential<3>(rng, n, nullptr);
+            hb_flip = (rng.has_buf << CE_HAS_BUF_SHIFT) ^ (cE & CE_HAS_BUF); // rejected words were drawn too
         }
         rolls_this_turn += 1u;
         int32_t dthr = PK2 ? ((int32_t)own_bits >> 16) : (int32_t)(int8_t)(own_bits & 0xffu);
@@ -1200,12 +1221,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const bool over = roll_back_end50w<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
         cA = rg.cA, cB = rg.cB, cC = rg.cC, cD = rg.cD, cE = rg.cE, score = rg.score, dice = rg.dice, turn_score = rg.turn_score;
         // one rare exit for all error conditions: the roll limit, then the u16 guard bands (fk_device.h: roll_guards50; `overflow` is its second half)
-        const uint32_t guard = roll_guards50(rolls_before, rg);
+        // (GUARD_SAMPLED instances: the roll limit and the turn-score band here, the three counter bands in sample_guards and end_guards below)
+        const uint32_t guard = GUARD_SAMPLED ? roll_guards50_turn(rolls_before, rg) : roll_guards50(rolls_before, rg);
         if (guard != RG_NONE) {
             raise(guard == RG_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
             return;
         }
-        cE = (cE & ~CE_HAS_BUF) | (rng.has_buf << CE_HAS_BUF_SHIFT); // has_buf is 0 / 1 (fk_device.h): a shift, no compare and select
+        if (HB_TOGGLE) cE ^= hb_flip;
+        else cE = (cE & ~CE_HAS_BUF) | (rng.has_buf << CE_HAS_BUF_SHIFT); // has_buf is 0 / 1 (fk_device.h): a shift, no compare and select
         if (GS) {
             if (over) { // the turn is over: the record goes back to the state store, the next seat's comes in
                 uint4 *g = reinterpret_cast<uint4 *>(G(s));
@@ -1301,6 +1324,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const uint32_t soff = slot * (2u * st_rec);
         const u32x4 s0 = ld4(st_base, soff), s1 = ld4(st_base, soff + st_rec);
         const u32x4 inc = ld4(inc_base, slot * 32u);
+        u32x4 inc1 = inc;
+        if constexpr (INC_REGS) inc1 = ld4(inc_base, slot * 32u + 16u); // seat 1's, with seat 0's
         // index plane: seats 0 and 1 are the halves of one dword (read twice: one address form for both sources); full state records:
         // one dword each
         const uint32_t ioff = (ho & HO_IDX_STATE) ? soff : slot * 4u;
@@ -1338,7 +1363,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         own_thr = (int32_t)pk0.x;
         own_bits = pk0.y;
         own_rec = lds_addr(lane_base);
-        own_inc_at = inc_base + (uint64_t)(slot * 32u);
+        if constexpr (INC_REGS) {
+            inc_delta_lo = own_inc_lo ^ ((uint64_t)inc1.x | ((uint64_t)inc1.y << 32));
+            inc_delta_hi = own_inc_hi ^ ((uint64_t)inc1.z | ((uint64_t)inc1.w << 32));
+        } else {
+            own_inc_at = inc_base + (uint64_t)(slot * 32u);
+        }
         dice = 6;
         turn_score = 0;
         rolls_this_turn = 0;
@@ -1411,10 +1441,32 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     uint32_t cnt_handovers = 0, cnt_served = 0, cnt_trips = 0, cnt_waiting = 0, cnt_rolling = 0;
 #endif
 
+    // ---- the sampled guard bands (GUARD_SAMPLED; fk_device.h states the argument): both lean records of the lane's game ----
+    auto lane_counters = [&](uint32_t s) __attribute__((always_inline)) -> LeanCounters {
+        const uint32_t *w = lds + s * SEAT_STRIDE + lane_base;
+        return LeanCounters{w[5], w[6], w[7], w[8], w[9]};
+    };
+    auto sample_guards = [&]() __attribute__((always_inline)) { // every RG_SAMPLE_TRIPS-th trip, the playing lanes
+        // (the empty asm keeps this block behind the wave-uniform scalar branch of its caller: without it the compiler folds the sample
+        // test into the lane test below, one v_cmp and an exec-mask region in every trip)
+        asm volatile("");
+        const LeanCounters c0 = lane_counters(0u), c1 = lane_counters(1u); // a lane that does not play reads its own slots and is not heard
+        const bool over = sampled_overflow50(c0.cA, c0.cC, c0.cD) | sampled_overflow50(c1.cA, c1.cC, c1.cD);
+        if (over && st == ST_ACTIVE) raise(FK_ERR_COUNTER_OVERFLOW);
+    };
+    auto end_guards = [&]() __attribute__((always_inline)) { // in front of a hand-over, the lanes whose game has ended
+        if (st == ST_ENDED && game_end_overflow50(lane_counters(0u), lane_counters(1u))) raise(FK_ERR_COUNTER_OVERFLOW);
+    };
+    uint32_t guard_trips = 0; // wave-uniform: trips of the roll loop since the wave started
+
     // ---- wave-level hand-over: finish ended games, deal new tickets ----
     // (`flat`: std::true_type in the loop of a launch that takes the flat path — the choice is made once, around the whole loop nest, see below)
     auto handover = [&](uint64_t waiting, auto flat) {
         constexpr bool FLAT = decltype(flat)::value;
+        if constexpr (GUARD_SAMPLED) { // a lane that raises is done: it neither finishes its game nor takes a ticket
+            end_guards();
+            waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
+        }
         const bool mine = (st == ST_FRESH || st == ST_ENDED);
         if (st == ST_ENDED) {
             if constexpr (FLAT) finish_game2();
@@ -1511,6 +1563,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(waiting), cnt_rolling += (uint32_t)__popcll(active);
 #endif
                 if (playing) roll_step();
+                if constexpr (GUARD_SAMPLED) {
+                    guard_trips += 1u;
+                    if ((guard_trips & (RG_SAMPLE_TRIPS - 1u)) == 0u) sample_guards();
+                }
                 playing = st == ST_ACTIVE;
                 waiting = __ballot(st == ST_ENDED);
                 active = __ballot(playing);
