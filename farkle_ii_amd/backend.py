@@ -101,7 +101,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = hip_sources() + [SRC_DIR / "fk_device.h", SRC_DIR / "fk_kernels.h", SRC_DIR / "fk_play_hc.h", SRC_DIR / "fk_plan.h", SRC_DIR / "fk_shard_writer.h", SRC_DIR / "fk_perm_wave.h", SRC_DIR / "fk_row_columns_seats.h", SRC_DIR / "fk_matchups.h", SRC_DIR / "fk_game_stats.h", SRC_DIR / "fk_rare_events.h", SRC_DIR / "fk_bootstrap.h", SRC_DIR / "fk_root_stability.h", SRC_DIR / "fk_seat_analysis.h", SRC_DIR / "fk_trace.h", SRC_DIR / "fk_census.h", SRC_DIR / "fk_round_robin.h", PKG_DIR.parent / "include" / "farkle_hip.h"]
+    deps = sorted(p for p in SRC_DIR.iterdir() if p.is_file()) + [PKG_DIR.parent / "include" / "farkle_hip.h"]  # (a new header cannot be forgotten)
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *({**VARIANTS, **TOOL_VARIANTS}[variant] if variant else []), "-o", str(out),

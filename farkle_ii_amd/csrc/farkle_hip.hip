@@ -18,6 +18,8 @@
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
 #include "fk_round_robin.h"    // device side: head-to-head round robin (window tables by unranking, generation planner, apply, summary)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
+#include "fk_layouts.h"        // host side: the composite device buffers' layouts
+#include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
 
 #include <dlfcn.h>
 #include <rccl/rccl.h> // TYPES ONLY (ncclConfig_t, result codes): the library itself is bound with dlopen on first use
@@ -42,16 +44,12 @@
 #include <vector>
 
 using namespace fk;
+static_assert(fkl::GAME_COUNTS == fkg::N_COUNTS, "fk_layouts.h states the game-stats count columns on its own");
 
 // ========================================================================================
 // host side
 // ========================================================================================
 constexpr int FK_ROWS_EVENTS = 4; // completion events of async rows calls: a ring (a caller may have this many calls' images not yet awaited)
-
-struct DevBuf {
-    void *p = nullptr;
-    size_t cap = 0;
-};
 
 // Everything a chunk's preparation (permutations, schedule, seat seeding) writes and its game kernel reads.  There are two
 // sets: the next chunk (of this call, or — after fk_tournament_hint_next — of the next call) is prepared into the other set
@@ -73,8 +71,20 @@ struct ChunkDesc {
 };
 
 struct ChunkSet {
-    DevBuf perm, draws, state, inc, seat_idx, order, classes, misc, pools;
-    DevBuf blocks, game_block, game_row; // batched H2H: the pass's block table and game -> block / table-row maps
+    Dev<uint16_t> perm, seat_idx;
+    Dev<uint8_t> draws; // a split launch's draws (DrawLayout: uint4 groups, read as 16-bit values by fk_perm_block_kernel); free again after the
+                        // permutations, the post-passes keep the chunk's inverse permutations (16-bit) in it
+    uint4 *draw_groups() const { return draws.as<uint4>(); }
+    uint16_t *draws16() const { return draws.as<uint16_t>(); }
+    Dev<uint32_t> state, order, classes;
+    Dev<uint4> inc, pools;
+    Dev<uint8_t> misc; // 512 bytes, zeroed per chunk: the words below
+    uint32_t *ticket() const { return misc.as<uint32_t>(0); }      // ticket counter (hammered by atomics)
+    int32_t *err() const { return misc.as<int32_t>(16); }          // error record of the game kernel
+    ull *hcount() const { return misc.as<ull>(128); }              // (measuring build) six hand-over counts
+    uint32_t *sched_ctr() const { return misc.as<uint32_t>(256); } // schedule class cursors of the seed kernel
+    Dev<DevBlock> blocks;                 // batched H2H: the pass's block table ...
+    Dev<uint32_t> game_block, game_row;   // ... and game -> block / table-row maps
     hipEvent_t ready = nullptr;                       // recorded behind the preparation kernels
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr}; // permutation begin / end, seeding begin / end (timing)
     bool prepared = false;
@@ -173,8 +183,19 @@ struct fk_ctx {
         hipEvent_t a, b;
     };
     std::vector<PendingTimer> pending; // kernel timers recorded on the stream, read after the chunk's one sync
-    DevBuf strat, recs, rec0, tally, rows, ov, seatlist, coords, inv, slow, score_lut, discard_lut, block_out, stats, ratios, digest,
-        dbg[6];
+    Dev<uint2> strat;
+    Dev<uint32_t> recs, rec0, inv, score_lut;
+    Dev<ull> tally, block_out;
+    Dev<uint8_t> rows, slow, discard_lut; // (discard_lut: the byte table and, behind it, the wide one)
+    Dev<DevOverride> ov;
+    Dev<int32_t> seatlist;
+    Dev<fk_coord> coords;
+    Dev<long long> stats;
+    Dev<double> ratios;
+    Dev<uint4> digest;
+    Dev<uint8_t> seeds; // fkl::Fingerprints: the game / shuffle seeds of a rows-mode call (fk_game_seeds: its game seeds)
+    Dev<uint8_t> cub;   // hipcub's scratch (FK_CUB)
+    ProbeBufs dbg;
     std::vector<uint2> strat_host;   // the packed table currently resident in `strat` (uploaded once per table)
     int32_t longest_first = 1;
     int32_t blocks_per_cu = 0; // 0 = as many as fit
@@ -200,26 +221,32 @@ struct fk_ctx {
     int32_t use_lds_tally = -1;
     int32_t block = 0;
     int32_t hc = -1;           // hot / cold game kernel (fk_play_hc.h): -1 auto, 0 never, 1 whenever the table allows it
-    DevBuf lds_tables;         // their LDS image (fk_play_hc.h)
-    DevBuf cold;
+    Dev<uint8_t> lds_tables;   // their LDS image (fk_play_hc.h)
+    Dev<uint4> cold;
     int32_t clock_stamps = 0;  // option "clock_stamps": every game-kernel block stamps s_memtime / s_memrealtime at both ends
-    DevBuf clk;                // [grid][4] stamps of the last game kernel
+    Dev<ull> clk;              // [grid][4] stamps of the last game kernel
     int clk_grid = 0;
-    DevBuf lag_v, lag_out, lag_lags, lag_edge, lag_tmp; // fk_tournament_run_lags: value matrix, sums, lag list, head / tail rows
-    DevBuf m_ids, m_dig, m_seat, m_rnd;  // fk_tournament_run_matchups: strategy IDs, one chunk's game records
-    DevBuf mr[36];                       // fk_matchup_reduce: records, sort keys / values, segments, selection, hipcub scratch
+    Dev<uint16_t> lag_v, lag_edge, lag_tmp; // fk_tournament_run_lags: value matrix, head / tail rows, the carry's scratch copy
+    Dev<long long> lag_out;                 // ... its sums
+    Dev<int32_t> lag_lags, m_ids;           // ... its lag list; fk_tournament_run_matchups: strategy IDs
+    Dev<ull> m_dig;                         // ... and one chunk's game records
+    Dev<uint16_t> m_seat, m_rnd;
+    MatchupReduceBufs mr;
     uint64_t matchup_sort_mask = ~0ull;  // option "matchup_sort_key_mask": the bits of the digest the reduce sorts by (tests)
-    DevBuf g_rec, g_out;                 // fk_tournament_run_game_stats: one chunk's game records; the call's histograms + spill list
+    Dev<uint4> g_rec;                    // fk_tournament_run_game_stats: one chunk's game records
+    Dev<uint8_t> g_out;                  // ... the call's histograms + spill list (fkl::GameStatsOut)
     int64_t game_stats_window = 0;       // option "game_stats_window": > 0 caps both histogram windows (tests drive the spill path)
-    DevBuf r_sec, r_out, r_blk, r_base, r_head, r_seats; // one chunk's second scores; second histograms + event total; workgroup counts / bases; the event list
-    DevBuf sa_counts, sa[16];            // fk_tournament_run_seat_counts: its counts; id ranks, the call's mirror records (keys / payloads, both sort buffers), indicators, sums, segments, pair rows
-    DevBuf tr[8];                        // fk_trace_games: strategies in points, seat workspace, event counts / begins, rows, error word, events, hipcub scratch
-    DevBuf cn[3];                        // fk_census_games / fk_tournament_run_census: strategies in points, seat workspace, the four tables + error word
+    Dev<uint32_t> r_sec, r_blk;          // fk_tournament_run_rare_events: one chunk's second scores; workgroup counts ...
+    Dev<ull> r_base, r_out;              // ... and bases; second histograms + event total (fkl::RareOut)
+    Dev<uint4> r_head;                   // the event list
+    Dev<uint16_t> r_seats;
+    SeatBufs sa;
+    TraceBufs tr;
+    CensusBufs cn;
     int64_t census_chunk_games = 0;      // option "census_chunk_games": > 0 caps the games of one census chunk (tests drive the chunk loop)
-    DevBuf rr[12];                       // fk_h2h_round_robin: table (packed, patience), window states, needs, offsets, flags, playing index, playing rows, error record, pass bounds, hipcub scratch, summary
+    RoundRobinBufs rr;
     int64_t rr_window_blocks = (int64_t)1 << 22; // option "rr_window_blocks": blocks of one round-robin window (even, 2 .. 2^22; scheduling only)
-    DevBuf rootb[4];                     // fk_root_stability_bootstrap (beside boot[0..4], boot[7]): weights + observed / expected, maxima, membership, counters
-    DevBuf boot[8];                      // fk_performance_bootstrap: matrices (wins, exposures), descriptors, multiplicities, scores, counters, contrasts + controls, flag
+    BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
@@ -232,14 +259,14 @@ struct fk_ctx {
     bool comm_timeout_set = false;    // "comm_timeout_ms" was set explicitly: the environment default no longer applies
     int32_t comm_timeout_ms = 120000; // option "comm_timeout_ms" (FK_COMM_TIMEOUT_MS): deadline of communicator creation and of each
                                       // collective; 0 = the blocking calls of round 3 (no deadline)
-    DevBuf comm_buf;
+    Dev<uint8_t> comm_buf;
     // resident tally (option "resident_tally"): every tournament call adds its [n_batches][S][26] tally to this device
     // accumulator; fk_tally_resident_reduce sums it over the communicator on the device (the tally never leaves HBM before
     // the reduce; one D2H, on the root)
     // rows mode: the device row buffer exists twice and a copy stream moves chunk i's rows to the host while chunk i + 1 plays
-    DevBuf rows_alt;
+    Dev<uint8_t> rows_alt;
     // fk_tournament_run_columns: the rows buffer receives per-shuffle column images (fk_row_columns_kernel); the strategy ids they name
-    DevBuf ids;
+    Dev<int32_t> ids;
     hipStream_t copy_stream = nullptr;
     hipEvent_t ev_rows[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};
     // option "rows_async": a rows call returns when its last copy to the host is QUEUED, not done; fk_rows_wait(slot) waits for it.  The caller
@@ -258,7 +285,7 @@ struct fk_ctx {
     int64_t rows_chunk_games = 4000000; // rows mode plays in chunks of about this many games (overlap granularity)
     int32_t resident = 0;
     size_t last_tally_bytes = 0; // bytes of the last successful tournament call's tally in `tally`
-    DevBuf acc;
+    Dev<ull> acc;
     size_t acc_n = 0;
 };
 
@@ -282,40 +309,53 @@ int fail(fk_ctx *c, int code, const char *fmt, ...) {
         if (e_ != hipSuccess) return fail((c), FK_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
-int ensure(fk_ctx *c, DevBuf &b, size_t bytes) {
-    if (bytes <= b.cap) return FK_OK;
-    if (b.p) HIPCHK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+// ensure()'s slow path: a buffer that holds `cap` bytes at `p` gives them back and gets `bytes` (256 at least)
+int grow(fk_ctx *c, void *&p, size_t &cap, size_t bytes) {
+    if (p) HIPCHK(c, hipFree(p));
+    g_device_bytes_held -= (int64_t)cap;
+    p = nullptr;
+    cap = 0;
     size_t want = std::max<size_t>(bytes, 256);
-    const hipError_t e = hipMalloc(&b.p, want);
+    const hipError_t e = hipMalloc(&p, want);
     if (e == hipErrorOutOfMemory) {
         c->oom = true;
-        b.p = nullptr;
+        p = nullptr;
         (void)hipGetLastError(); // (the sticky error would fail the next, unrelated call)
         return fail(c, FK_ERR_HIP, "hipMalloc(%zu bytes) failed: out of memory", want);
     }
     HIPCHK(c, e);
-    b.cap = want;
+    cap = want;
+    g_device_bytes_held += (int64_t)want;
     return FK_OK;
 }
 
-void release(DevBuf &b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
+// room for `count` elements
+template <class T>
+inline int ensure(fk_ctx *c, Dev<T> &b, size_t count) {
+    if (count * sizeof(T) <= b.cap) return FK_OK;
+    void *p = b.p;
+    const int rc = grow(c, p, b.cap, count * sizeof(T));
+    b.p = static_cast<T *>(p);
+    return rc;
+}
+
+// ensure() for (buffer, count) pairs in their order; the first failure ends it
+template <class T, class... Rest>
+int ensure_all(fk_ctx *c, Dev<T> &b, size_t count, Rest &&...rest) {
+    if (const int rc = ensure(c, b, count)) return rc;
+    if constexpr (sizeof...(rest) > 0) return ensure_all(c, rest...);
+    else return FK_OK;
 }
 
 // per-chunk buffers: what workspace_budget counts as this context's own and release_workspace gives back
-static std::vector<DevBuf *> workspace_buffers(fk_ctx *c) {
-    std::vector<DevBuf *> out;
-    for (auto &cs : c->sets)
-        for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks,
-                          &cs.game_block, &cs.game_row})
-            out.push_back(b);
+template <class F>
+static void for_workspace_buffers(fk_ctx *c, F f) {
+    for (auto &cs : c->sets) {
+        f(cs.perm), f(cs.draws), f(cs.state), f(cs.inc), f(cs.seat_idx), f(cs.order), f(cs.classes), f(cs.misc), f(cs.pools), f(cs.blocks);
+        f(cs.game_block), f(cs.game_row);
+    }
     // (only buffers that every call sizes and ensures per chunk: c->slow — the patience table upload_strategies fills once per TABLE — is not one)
-    for (DevBuf *b : {&c->recs, &c->rec0, &c->rows, &c->rows_alt, &c->digest, &c->inv, &c->lag_v, &c->lag_tmp, &c->cn[1]}) out.push_back(b);
-    return out;
+    f(c->recs), f(c->rec0), f(c->rows), f(c->rows_alt), f(c->digest), f(c->inv), f(c->lag_v), f(c->lag_tmp), f(c->cn.ws);
 }
 
 // bytes one buffer set of a call may plan for (see fk_ctx::workspace_percent)
@@ -324,7 +364,7 @@ static int64_t workspace_budget(fk_ctx *c) {
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
         size_t held = 0;
-        for (DevBuf *b : workspace_buffers(c)) held += b->cap;
+        for_workspace_buffers(c, [&](auto &b) { held += b.cap; });
         const double have = (double)free_b + (double)held;
         budget = std::min<int64_t>(budget, std::max<int64_t>((int64_t)(have * (double)c->workspace_percent / 100.0 / 2.0), (int64_t)32 << 20));
     } else {
@@ -338,7 +378,7 @@ static int64_t workspace_budget(fk_ctx *c) {
 static void release_workspace(fk_ctx *c) {
     (void)hipDeviceSynchronize();
     (void)hipGetLastError();
-    for (DevBuf *b : workspace_buffers(c)) release(*b);
+    for_workspace_buffers(c, [](auto &b) { b.release(); });
     for (auto &cs : c->sets) cs.prepared = false;
     c->hint_valid = false;
 }
@@ -387,7 +427,7 @@ int upload_strategies(fk_ctx *c, const fk_strategy *s, int64_t S) {
     c->table_epoch += 1; // anything prepared for the previous table is void
     for (auto &cs : c->sets) cs.prepared = false;
     if (c->prep_stream) HIPCHK(c, hipStreamSynchronize(c->prep_stream));
-    rc = ensure(c, c->strat, sizeof(uint2) * (size_t)S);
+    rc = ensure(c, c->strat, (size_t)S);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->strat.p, packed.data(), sizeof(uint2) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     uint32_t f_and = 0xff00u, f_or = 0u;
@@ -683,10 +723,10 @@ uint32_t perm_slots(int32_t S) { return (uint32_t)std::max<size_t>(1, std::min<s
 // the fields every game-kernel launch fills from the context and the call
 PlayArgs table_args(const fk_ctx *c, int32_t target_score, int32_t max_rounds) {
     PlayArgs pa{};
-    pa.strat = static_cast<const uint2 *>(c->strat.p);
-    pa.score_lut = static_cast<const uint32_t *>(c->score_lut.p);
-    pa.discard_lut = static_cast<const uint8_t *>(c->discard_lut.p);
-    pa.lds_tables = static_cast<const uint8_t *>(c->lds_tables.p);
+    pa.strat = c->strat.p;
+    pa.score_lut = c->score_lut.p;
+    pa.discard_lut = c->discard_lut.p;
+    pa.lds_tables = c->lds_tables.p;
     pa.target50 = ceil_div50(target_score);
     pa.beat50 = floor_div50(target_score);
     pa.max_rounds = (uint32_t)max_rounds;
@@ -733,7 +773,7 @@ int map_overrides(fk_ctx *c, const fk_override *ov, int32_t n_ov, uint32_t &n_de
     n_dev = (uint32_t)dov.size();
     if (dov.empty()) return FK_OK;
     std::sort(dov.begin(), dov.end(), [](const DevOverride &x, const DevOverride &y) { return x.game < y.game; });
-    int rc = ensure(c, c->ov, dov.size() * sizeof(DevOverride));
+    int rc = ensure(c, c->ov, dov.size());
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ov.p, dov.data(), dov.size() * sizeof(DevOverride), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -777,21 +817,16 @@ int replay_on_oom(fk_ctx *c, Run run) {
 int seed_stage(fk_ctx *c, int si, hipStream_t st, SeedArgs &sa, bool full_state, bool timed) {
     ChunkSet &cs = c->sets[si];
     sa.state_dw = full_state ? STATE_DW : 4u;
-    int rc = ensure(c, cs.state, (size_t)sa.n_games * sa.k * sa.state_dw * 4);
-    if (rc) return rc;
-    rc = ensure(c, cs.inc, (size_t)sa.n_games * sa.k * 16);
-    if (rc) return rc;
-    // misc: [0] ticket counter (hammered by atomics), [16] error record, [256] schedule class cursors of the seed kernel
-    rc = ensure(c, cs.misc, 512);
+    int rc = ensure_all(c, cs.state, (size_t)sa.n_games * sa.k * sa.state_dw, cs.inc, (size_t)sa.n_games * sa.k, cs.misc, 512);
     if (rc) return rc;
     HIPCHK(c, hipMemsetAsync(cs.misc.p, 0, 512, st));
-    sa.state = static_cast<uint32_t *>(cs.state.p);
-    sa.inc = static_cast<uint4 *>(cs.inc.p);
+    sa.state = cs.state.p;
+    sa.inc = cs.inc.p;
     sa.seat_idx = nullptr;
     if (sa.perm_T && !full_state) { // the seats' strategy indices, resolved once by the seed kernel
-        rc = ensure(c, cs.seat_idx, (size_t)sa.n_games * sa.k * 2);
+        rc = ensure(c, cs.seat_idx, (size_t)sa.n_games * sa.k);
         if (rc) return rc;
-        sa.seat_idx = static_cast<uint16_t *>(cs.seat_idx.p);
+        sa.seat_idx = cs.seat_idx.p;
     }
     if (sa.blocks) { // batched H2H: game -> block map first (the schedule classes and the seed kernel read it)
         hipLaunchKernelGGL(fk_block_map_kernel, dim3((sa.n_games + 255u) / 256u), dim3(256), 0, st, sa.blocks, sa.n_blocks,
@@ -799,15 +834,15 @@ int seed_stage(fk_ctx *c, int si, hipStream_t st, SeedArgs &sa, bool full_state,
         HIPCHK(c, hipGetLastError());
     }
     if ((sa.perm_T || sa.blocks) && c->longest_first) {
-        rc = ensure(c, cs.order, (size_t)sa.n_games * 4);
+        rc = ensure(c, cs.order, (size_t)sa.n_games);
         if (rc) return rc;
-        sa.sched = static_cast<uint32_t *>(cs.order.p);
-        sa.sched_ctr = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(cs.misc.p) + 256);
-        rc = ensure(c, cs.classes, 64);
+        sa.sched = cs.order.p;
+        sa.sched_ctr = cs.sched_ctr();
+        rc = ensure(c, cs.classes, 16);
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(cs.classes.p, 0, 64, st));
-        sa.class_ctr = static_cast<const uint32_t *>(cs.classes.p);
-        sa.patience = static_cast<const uint8_t *>(c->slow.p);
+        sa.class_ctr = cs.classes.p;
+        sa.patience = c->slow.p;
     } else {
         sa.sched = nullptr;
     }
@@ -815,16 +850,14 @@ int seed_stage(fk_ctx *c, int si, hipStream_t st, SeedArgs &sa, bool full_state,
     sa.pools = nullptr;
     if (!sa.coords) { // the pool every game of a shuffle / of a block starts from
         const uint32_t n = sa.blocks ? sa.n_blocks : (sa.gps ? (sa.n_games + sa.gps - 1u) / sa.gps : 1u);
-        rc = ensure(c, cs.pools, (size_t)n * 16);
+        rc = ensure(c, cs.pools, (size_t)n);
         if (rc) return rc;
-        sa.pools = static_cast<const uint4 *>(cs.pools.p);
-        hipLaunchKernelGGL(fk_pool_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, sa.prefix, sa.shuffle0, sa.pair, sa.order, sa.blocks, n,
-                           static_cast<uint4 *>(cs.pools.p));
+        sa.pools = cs.pools.p;
+        hipLaunchKernelGGL(fk_pool_kernel, dim3((n + 255u) / 256u), dim3(256), 0, st, sa.prefix, sa.shuffle0, sa.pair, sa.order, sa.blocks, n, cs.pools.p);
     }
     if (sa.sched) // class sizes first: a game's ticket is class offset + rank
-        hipLaunchKernelGGL(fk_class_count_kernel, dim3(std::min<uint32_t>((sa.n_games + SEED_BLOCK - 1u) / SEED_BLOCK, 1024u)), dim3(SEED_BLOCK), 0,
-                           st, sa.perm_T, sa.perm_slots, sa.S, sa.k, sa.n_sh, sa.n_games, sa.patience,
-                           sa.blocks ? sa.game_row : nullptr, static_cast<uint32_t *>(cs.classes.p));
+        hipLaunchKernelGGL(fk_class_count_kernel, dim3(std::min<uint32_t>((sa.n_games + SEED_BLOCK - 1u) / SEED_BLOCK, 1024u)), dim3(SEED_BLOCK), 0, st,
+                           sa.perm_T, sa.perm_slots, sa.S, sa.k, sa.n_sh, sa.n_games, sa.patience, sa.blocks ? sa.game_row : nullptr, cs.classes.p);
     hipLaunchKernelGGL(fk_seed_kernel, dim3((sa.n_games + SEED_BLOCK - 1u) / SEED_BLOCK), dim3(SEED_BLOCK), 0, st, sa);
     if (timed) (void)hipEventRecord(cs.ev[3], st);
     HIPCHK(c, hipGetLastError());
@@ -844,11 +877,11 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
     ChunkSet &cs = CSET(c);
     int rc;
     if (want_rec0) {
-        rc = ensure(c, c->rec0, (size_t)sa.n_games * 4);
+        rc = ensure(c, c->rec0, (size_t)sa.n_games);
         if (rc) return rc;
     }
     if (want_recs) {
-        rc = ensure(c, c->recs, (size_t)sa.n_games * REC_DW * 4);
+        rc = ensure(c, c->recs, (size_t)sa.n_games * REC_DW);
         if (rc) return rc;
     }
     pa.sched = sa.sched;
@@ -856,11 +889,11 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
     pa.state = sa.state;
     pa.state_dw = sa.state_dw;
     pa.inc = sa.inc;
-    pa.rec0 = want_rec0 ? static_cast<uint32_t *>(c->rec0.p) : nullptr;
-    pa.recs = want_recs ? static_cast<uint32_t *>(c->recs.p) : nullptr;
+    pa.rec0 = want_rec0 ? c->rec0.p : nullptr;
+    pa.recs = want_recs ? c->recs.p : nullptr;
     pa.gs_out = (want_state && !plan.shape().gs) ? 1u : 0u;
-    pa.ticket = static_cast<uint32_t *>(cs.misc.p);
-    pa.err = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(cs.misc.p) + 16);
+    pa.ticket = cs.ticket();
+    pa.err = cs.err();
     // hand-over threshold: the measured optimum is 8 up to eight seats (rounds 1 - 3) and grows with the game length beyond (round 5,
     // 5 160-strategy grid: k = 12 at 16 -1.5 %, k = 10 at 12 -0.6 % kernel time against 8)
     const int auto_thr = sa.k >= 11 ? 16 : sa.k >= 9 ? 12 : 8;
@@ -868,18 +901,18 @@ int launch_play_stage(fk_ctx *c, const SeedArgs &sa, PlayArgs &pa, const LaunchP
     pa.use_lds_tally = plan.lds_tally ? 1u : 0u;
     pa.no_flat = c->flat_handover ? 0u : 1u;
 #ifdef FK_COUNT_HANDOVER // measuring build: the hand-over counts of fk_play_kernel, six zeroed words of the chunk's misc block
-    pa.hcount = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(cs.misc.p) + 128);
+    pa.hcount = cs.hcount();
 #else
     pa.hcount = nullptr;
 #endif
     pa.clk = nullptr;
     c->clk_grid = 0;
     if (c->clock_stamps) {
-        const size_t bytes = (size_t)std::max(plan.grid, 1) * 4 * sizeof(unsigned long long);
-        rc = ensure(c, c->clk, bytes);
+        const size_t bytes = (size_t)std::max(plan.grid, 1) * 4 * sizeof(ull);
+        rc = ensure(c, c->clk, bytes / sizeof(ull));
         if (rc) return rc;
         HIPCHK(c, hipMemsetAsync(c->clk.p, 0, bytes, c->stream));
-        pa.clk = static_cast<unsigned long long *>(c->clk.p);
+        pa.clk = c->clk.p;
     }
     {
         Timer t(c, &c->timing.play_ms, SLOT_PLAY);
@@ -990,20 +1023,20 @@ int play_block_passes(fk_ctx *c, size_t n_passes, const LaunchPlan &plan, uint64
         int rc2 = blocks(i, nullptr, st, nb, games);
         if (rc2) return rc2;
         cs.prepared = false;
-        rc2 = ensure(c, cs.blocks, (size_t)nb * sizeof(DevBlock));
-        if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)games * 4);
-        if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)games * 4);
-        if (!rc2) rc2 = blocks(i, static_cast<DevBlock *>(cs.blocks.p), st, nb, games);
+        rc2 = ensure(c, cs.blocks, (size_t)nb);
+        if (!rc2) rc2 = ensure(c, cs.game_block, (size_t)games);
+        if (!rc2) rc2 = ensure(c, cs.game_row, (size_t)games);
+        if (!rc2) rc2 = blocks(i, cs.blocks.p, st, nb, games);
         if (rc2) return rc2;
         sa = SeedArgs{};
         sa.prefix = seat_prefix;
         sa.gps = 0;
         sa.k = 2;
         sa.n_games = games;
-        sa.blocks = static_cast<const DevBlock *>(cs.blocks.p);
+        sa.blocks = cs.blocks.p;
         sa.n_blocks = nb;
-        sa.game_block = static_cast<const uint32_t *>(cs.game_block.p);
-        sa.game_row = static_cast<const uint32_t *>(cs.game_row.p);
+        sa.game_block = cs.game_block.p;
+        sa.game_row = cs.game_row.p;
         rc2 = seed_stage(c, si, st, sa, false, true);
         if (rc2) return rc2;
         HIPCHK(c, hipEventRecord(cs.ready, st));
@@ -1035,7 +1068,7 @@ int play_block_passes(fk_ctx *c, size_t n_passes, const LaunchPlan &plan, uint64
         }
         PlayArgs pa = table_args(c, target_score, max_rounds);
         pa.game_block = sas[i].game_row; // the kernel wants table rows: seat s of a game plays strategy 2 * row + s
-        pa.ov = overrides ? static_cast<const DevOverride *>(c->ov.p) : nullptr;
+        pa.ov = overrides ? c->ov.p : nullptr;
         pa.n_ov = n_ov;
         pa.mode = MODE_BLOCKS;
         pa.n_games = sas[i].n_games;
@@ -1046,7 +1079,7 @@ int play_block_passes(fk_ctx *c, size_t n_passes, const LaunchPlan &plan, uint64
         HIPCHK(c, hipStreamWaitEvent(c->stream, CSET(c).ready, 0));
         if ((rc = launch_play_stage(c, sas[i], pa, plan, false, true, false))) return rc;
         hipLaunchKernelGGL(fk_h2h_reduce_kernel, dim3((pa.n_games + 256u * H2H_RUN - 1u) / (256u * H2H_RUN)), dim3(256), 0, c->stream,
-                           static_cast<const uint32_t *>(c->rec0.p), pa.n_games, S / 2u, static_cast<unsigned long long *>(c->block_out.p));
+                           c->rec0.p, pa.n_games, S / 2u, c->block_out.p);
         HIPCHK(c, hipGetLastError());
         if (!pipelined) { // (the next pass may re-use the one override buffer)
             if ((rc = finish_play(c, pa, 0, "h2h attempt (pass-local index)"))) return rc;
@@ -1113,10 +1146,10 @@ int launch_perm_draws(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &
     if (rc) return rc;
     if (wave_draw)
         hipLaunchKernelGGL(fk_perm_draw_wave_kernel, dim3((n_sh + WAVE_DRAW_BLOCK / 64 - 1u) / (WAVE_DRAW_BLOCK / 64)), dim3(WAVE_DRAW_BLOCK), 0, st,
-                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, static_cast<uint4 *>(cs.draws.p));
+                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, cs.draw_groups());
     else
         hipLaunchKernelGGL(fk_perm_draw_kernel, dim3((n_sh + DRAW_BLOCK - 1u) / DRAW_BLOCK), dim3(DRAW_BLOCK), 0, st,
-                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, static_cast<uint4 *>(cs.draws.p));
+                           perm_prefix, d.sh0, n_sh, d.S, dl.g_stride, dl.sh_stride, cs.draw_groups());
     return FK_OK;
 }
 
@@ -1125,15 +1158,12 @@ int launch_perm_draws(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc &
 void launch_perm_consumers(ChunkSet &cs, hipStream_t st, int path, const DrawLayout &dl, uint32_t n_sh, uint32_t S, uint32_t slots) {
     const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
     if (path == 2) {
-        hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), (size_t)S * 14, st,
-                           static_cast<uint4 *>(cs.draws.p), dl.sh_stride, n_sh, S);
-        hipLaunchKernelGGL(fk_perm_block_kernel, dim3((S + 255u) / 256u, perm_blocks), dim3(256), 0, st,
-                           static_cast<const uint16_t *>(cs.draws.p), dl.sh_stride * 8u, n_sh, S, slots,
-                           static_cast<uint16_t *>(cs.perm.p));
+        hipLaunchKernelGGL(fk_perm_parallel_kernel, dim3(n_sh), dim3(PP_BLOCK), (size_t)S * 14, st, cs.draw_groups(), dl.sh_stride, n_sh, S);
+        hipLaunchKernelGGL(fk_perm_block_kernel, dim3((S + 255u) / 256u, perm_blocks), dim3(256), 0, st, cs.draws16(), dl.sh_stride * 8u, n_sh, S, slots,
+                           cs.perm.p);
     } else {
-        hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st,
-                           static_cast<const uint4 *>(cs.draws.p), dl.g_stride, n_sh, S, slots,
-                           static_cast<uint16_t *>(cs.perm.p));
+        hipLaunchKernelGGL(fk_perm_apply_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st, cs.draw_groups(), dl.g_stride, n_sh, S, slots,
+                           cs.perm.p);
     }
 }
 
@@ -1155,9 +1185,8 @@ int launch_perm_kernels(fk_ctx *c, ChunkSet &cs, hipStream_t st, const ChunkDesc
         launch_perm_consumers(cs, st, path, dl, n_sh, d.S, slots);
     } else {
         const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
-        hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st,
-                           seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root, (uint64_t)d.k), d.sh0, n_sh, d.S, slots,
-                           static_cast<uint16_t *>(cs.perm.p));
+        hipLaunchKernelGGL(fk_perm_kernel, dim3(perm_blocks), dim3(PERM_BLOCK), (size_t)slots * S * 2, st, seed_prefix(101u /* SHUFFLE_PERMUTATION */, d.root,
+                           (uint64_t)d.k), d.sh0, n_sh, d.S, slots, cs.perm.p);
     }
     HIPCHK(c, hipGetLastError());
     return FK_OK;
@@ -1179,7 +1208,7 @@ int prep_tournament_chunk(fk_ctx *c, int si, hipStream_t st_seed, const ChunkDes
     const int32_t S = (int32_t)d.S;
     const uint32_t n_sh = d.n_sh, slots = d.slots, gps = d.S / d.k;
     const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
-    int rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2);
+    int rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots);
     if (rc) return rc;
     (void)hipEventRecord(cs.ev[0], st);
     if ((rc = launch_perm_kernels(c, cs, st, d))) return rc;
@@ -1191,7 +1220,7 @@ int prep_tournament_chunk(fk_ctx *c, int si, hipStream_t st_seed, const ChunkDes
     sa.gps = gps;
     sa.k = d.k;
     sa.n_games = n_sh * gps;
-    sa.perm_T = static_cast<const uint16_t *>(cs.perm.p);
+    sa.perm_T = cs.perm.p;
     sa.perm_slots = slots;
     sa.S = d.S;
     sa.n_sh = n_sh;
@@ -1211,7 +1240,7 @@ int prep_tournament_chunk(fk_ctx *c, int si, hipStream_t st_seed, const ChunkDes
 // state store + result records of the chunk just played -> rows at `d_rows` (device), game-id order
 int rows_pass(fk_ctx *c, const SeedArgs &sa, bool scheduled, uint32_t n_games, uint32_t gps, uint32_t n_sh, bool perm_mode, uint8_t *d_rows) {
     // `scheduled`: the caller has inverted the schedule into c->inv (fk_invert_sched_kernel)
-    const uint32_t *inv = scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr;
+    const uint32_t *inv = scheduled ? c->inv.p : nullptr;
     const uint32_t row_dw = 1u + 7u * sa.k;
     // rows of a block leave through an LDS tile as whole lines: the largest block whose tile fits 64 KiB
     uint32_t block = 256;
@@ -1223,12 +1252,10 @@ int rows_pass(fk_ctx *c, const SeedArgs &sa, bool scheduled, uint32_t n_games, u
             HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&fk_rows_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
             configured = c->device;
         }
-        hipLaunchKernelGGL(fk_rows_kernel<true>, dim3((n_games + block - 1u) / block), dim3(block), tile, c->stream,
-                           static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p), inv, n_games, gps, n_sh,
-                           sa.k, perm_mode ? 1u : 0u, d_rows);
+        hipLaunchKernelGGL(fk_rows_kernel<true>, dim3((n_games + block - 1u) / block), dim3(block), tile, c->stream, CSET(c).state.p, c->recs.p, inv, n_games,
+                           gps, n_sh, sa.k, perm_mode ? 1u : 0u, d_rows);
     } else { // tables of more than 36 seats: one thread stores its own row
-        hipLaunchKernelGGL(fk_rows_kernel<false>, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
-                           static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p), inv, n_games, gps, n_sh,
+        hipLaunchKernelGGL(fk_rows_kernel<false>, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, CSET(c).state.p, c->recs.p, inv, n_games, gps, n_sh,
                            sa.k, perm_mode ? 1u : 0u, d_rows);
     }
     HIPCHK(c, hipGetLastError());
@@ -1429,7 +1456,7 @@ int fk_init(int device_ordinal, fk_ctx **out) {
         }
     }
     // score table (fk_device.h): 512 KiB, built by one small kernel, read by every roll of the game kernel
-    if (ensure(c, c->score_lut, SCORE_LUT_KEYS * sizeof(uint32_t)) != FK_OK) {
+    if (ensure(c, c->score_lut, SCORE_LUT_KEYS) != FK_OK) {
         fk_destroy(c);
         return FK_ERR_HIP;
     }
@@ -1437,10 +1464,8 @@ int fk_init(int device_ordinal, fk_ctx **out) {
         fk_destroy(c);
         return FK_ERR_HIP;
     }
-    hipLaunchKernelGGL(fk_score_lut_kernel, dim3(SCORE_LUT_KEYS / 256), dim3(256), 0, c->stream,
-                       static_cast<uint32_t *>(c->score_lut.p));
-    hipLaunchKernelGGL(fk_discard_lut_kernel, dim3(DISCARD_LUT_KEYS / 256), dim3(256), 0, c->stream,
-                       static_cast<uint8_t *>(c->discard_lut.p));
+    hipLaunchKernelGGL(fk_score_lut_kernel, dim3(SCORE_LUT_KEYS / 256), dim3(256), 0, c->stream, c->score_lut.p);
+    hipLaunchKernelGGL(fk_discard_lut_kernel, dim3(DISCARD_LUT_KEYS / 256), dim3(256), 0, c->stream, c->discard_lut.p);
     {
         const std::vector<uint8_t> img = build_lds_tables();
         if (ensure(c, c->lds_tables, img.size()) != FK_OK ||
@@ -1466,22 +1491,8 @@ void fk_destroy(fk_ctx *c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)rccl().CommDestroy(c->comm);
     c->comm = nullptr;
-    release(c->comm_buf);
     if (c->prep_stream) (void)hipStreamSynchronize(c->prep_stream);
-    for (DevBuf *b : {&c->strat, &c->recs, &c->rec0, &c->tally, &c->rows, &c->ov, &c->seatlist, &c->coords, &c->inv, &c->slow, &c->digest, &c->score_lut,
-                      &c->discard_lut, &c->block_out, &c->stats, &c->ratios, &c->cold, &c->clk, &c->lds_tables, &c->acc, &c->rows_alt, &c->ids, &c->lag_v, &c->lag_out, &c->lag_lags, &c->lag_edge, &c->lag_tmp,
-                      &c->m_ids, &c->m_dig, &c->m_seat, &c->m_rnd})
-        release(*b);
-    for (DevBuf *b : {&c->r_sec, &c->r_out, &c->r_blk, &c->r_base, &c->r_head, &c->r_seats}) release(*b);
-    for (DevBuf &b : c->mr) release(b);
-    for (DevBuf &b : c->boot) release(b);
-    release(c->sa_counts);
-    for (DevBuf &b : c->sa) release(b);
-    for (DevBuf &b : c->rootb) release(b);
-    for (DevBuf &b : c->tr) release(b);
-    for (DevBuf &b : c->rr) release(b);
     for (auto &cs : c->sets) {
-        for (DevBuf *b : {&cs.perm, &cs.draws, &cs.state, &cs.inc, &cs.seat_idx, &cs.order, &cs.classes, &cs.misc, &cs.pools, &cs.blocks, &cs.game_block, &cs.game_row}) release(*b);
         if (cs.ready) (void)hipEventDestroy(cs.ready);
         for (auto &e : cs.ev)
             if (e) (void)hipEventDestroy(e);
@@ -1500,11 +1511,10 @@ void fk_destroy(fk_ctx *c) {
     if (c->err_host) (void)hipHostFree(c->err_host);
     if (c->mail) (void)hipHostFree(c->mail);
     if (c->prep_stream) (void)hipStreamDestroy(c->prep_stream);
-    for (auto &b : c->dbg) release(b);
     for (auto &e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // (the device is still current) frees every device buffer: each Dev member releases its own
 }
 
 const char *fk_last_error(fk_ctx *c) { return c ? c->err.c_str() : "null context"; }
@@ -1613,6 +1623,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     if (n == "chunk_bytes") *value = c->chunk_bytes;
     else if (n == "workspace_percent") *value = c->workspace_percent;
     else if (n == "last_budget") *value = c->last_budget;
+    else if (n == "device_bytes_held") *value = g_device_bytes_held.load();
     else if (n == "oom_replays") *value = c->oom_replays;
     else if (n == "comm_timeout_ms") *value = effective_comm_timeout_ms(c);
     else if (n == "rows_chunk_games") *value = c->rows_chunk_games;
@@ -1734,9 +1745,8 @@ extern "C++" { // (this part of the file lies inside the C-ABI's extern "C" bloc
 template <int K>
 static void launch_matchup_keys_k(fk_ctx *c, const uint32_t *recs, const uint16_t *perm, uint32_t slots, uint32_t S, uint32_t gps,
                                   uint32_t n_games, uint32_t max_players) {
-    hipLaunchKernelGGL(fkm::fk_matchup_keys_kernel<K>, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, recs, perm, slots, S, gps, n_games,
-                       static_cast<const int32_t *>(c->m_ids.p), max_players, static_cast<unsigned long long *>(c->m_dig.p),
-                       static_cast<uint16_t *>(c->m_seat.p), static_cast<uint16_t *>(c->m_rnd.p));
+    hipLaunchKernelGGL(fkm::fk_matchup_keys_kernel<K>, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, recs, perm, slots, S, gps, n_games, c->m_ids.p,
+                       max_players, c->m_dig.p, c->m_seat.p, c->m_rnd.p);
 }
 } // extern "C++"
 
@@ -1754,14 +1764,26 @@ static int launch_matchup_keys(fk_ctx *c, uint32_t k, const uint32_t *recs, cons
     return FK_OK;
 }
 
-// hipcub device-wide primitives: size query, the context's scratch buffer, the call
-#define FKM_CUB(FN, ...)                                                     \
-    do {                                                                     \
-        size_t tb_ = 0;                                                      \
-        HIPCHK(c, FN(nullptr, tb_, __VA_ARGS__));                            \
-        if ((rc = ensure(c, c->mr[35], std::max<size_t>(tb_, 1)))) return rc; \
-        tb_ = c->mr[35].cap;                                                 \
-        HIPCHK(c, FN(c->mr[35].p, tb_, __VA_ARGS__));                        \
+// hipcub device-wide primitives over the context's one scratch buffer (c->cub), in functions that return `rc` on failure.
+// FK_CUB: size query, ensure, the call.  A loop that must not query sizes takes the two halves apart: FK_CUB_NEED raises `need` to what
+// a call asks for, the caller ensures c->cub once, FK_CUB_SIZED is the call over the scratch as it stands.
+#define FK_CUB_NEED(need, FN, ...)                \
+    do {                                          \
+        size_t tb_ = 0;                           \
+        HIPCHK(c, FN(nullptr, tb_, __VA_ARGS__)); \
+        need = std::max<size_t>(need, tb_);       \
+    } while (0)
+#define FK_CUB_SIZED(FN, ...)                         \
+    do {                                              \
+        size_t tb_ = c->cub.cap;                      \
+        HIPCHK(c, FN(c->cub.p, tb_, __VA_ARGS__));    \
+    } while (0)
+#define FK_CUB(FN, ...)                                  \
+    do {                                                 \
+        size_t need_ = 1;                                \
+        FK_CUB_NEED(need_, FN, __VA_ARGS__);             \
+        if ((rc = ensure(c, c->cub, need_))) return rc;  \
+        FK_CUB_SIZED(FN, __VA_ARGS__);                   \
     } while (0)
 
 int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *digest, const uint16_t *seats, const uint16_t *rounds,
@@ -1781,76 +1803,71 @@ int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *diges
     counts[0] = n_obs;
     if (n == 0) return FK_OK;
     int rc = 0;
-    const size_t sizes[] = {8ul * n, 2ul * n * K, 2ul * n, 8ul * n, 8ul * n, 4ul * n, 4ul * n, 8ul * n, 2ul * n * K, 2ul * n, 4ul * n, 4ul * n,
-                            4ul * n, 4ul * n, 1ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n, 4ul * n};
-    for (int i = 0; i < 21; ++i)
-        if ((rc = ensure(c, c->mr[i], sizes[i]))) return rc;
-    auto U64 = [&](int i) { return static_cast<unsigned long long *>(c->mr[i].p); };
-    auto U32 = [&](int i) { return static_cast<uint32_t *>(c->mr[i].p); };
-    auto U16 = [&](int i) { return static_cast<uint16_t *>(c->mr[i].p); };
+    MatchupReduceBufs &m = c->mr;
+    const size_t nK = (size_t)n * K;
+    if ((rc = ensure_all(c, m.digest, n, m.seats, nK, m.rounds, n, m.key, n, m.key_alt, n, m.idx, n, m.order, n, m.s_digest, n, m.s_seats, nK, m.s_rounds, n,
+                         m.heads, n, m.run_id, n, m.tuple_break, n, m.run_mixed, n, m.mixed_flag, n, m.mixed_pos, n, m.mixed_key, n, m.mixed_key_alt, n,
+                         m.mixed_a, n, m.mixed_b, n, m.order_before, n)))
+        return rc;
     const hipStream_t st = c->stream;
     const dim3 bn((n + 255u) / 256u), b256(256);
-    HIPCHK(c, hipMemcpyAsync(c->mr[0].p, digest, 8ul * n, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->mr[1].p, seats, 2ul * n * K, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->mr[2].p, rounds, 2ul * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(m.digest.p, digest, 8ul * n, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(m.seats.p, seats, 2ul * n * K, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(m.rounds.p, rounds, 2ul * n, hipMemcpyHostToDevice, st));
     // 1. stable radix sort by the (masked) digest: coordinate order is kept inside every run of equal keys
-    hipLaunchKernelGGL(fkm::fkm_key_init, bn, b256, 0, st, U64(0), (unsigned long long)c->matchup_sort_mask, n, U64(3), U32(5));
+    hipLaunchKernelGGL(fkm::fkm_key_init, bn, b256, 0, st, m.digest.p, (ull)c->matchup_sort_mask, n, m.key.p, m.idx.p);
     HIPCHK(c, hipGetLastError());
-    FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(3), U64(4), U32(5), U32(6), (int)n, 0, 64, st);
-    hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, U32(6), U64(0), U16(1), U16(2), n, K, U64(7), U16(8), U16(9));
+    FK_CUB(hipcub::DeviceRadixSort::SortPairs, m.key.p, m.key_alt.p, m.idx.p, m.order.p, (int)n, 0, 64, st);
+    hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, m.order.p, m.digest.p, m.seats.p, m.rounds.p, n, K, m.s_digest.p, m.s_seats.p, m.s_rounds.p);
     // 2. runs of equal sort key that hold more than one tuple (digest collisions): a stable LSD sort of only those elements by
     //    tuple column k-1 .. 0, then by run, puts every tuple of a run together, each still in coordinate order
-    hipLaunchKernelGGL(fkm::fkm_run_heads, bn, b256, 0, st, U64(4), U16(8), n, K, U32(10), U32(12));
-    FKM_CUB(hipcub::DeviceScan::InclusiveSum, U32(10), U32(11), (int)n, st);
-    HIPCHK(c, hipMemsetAsync(c->mr[13].p, 0, 4ul * n, st));
-    hipLaunchKernelGGL(fkm::fkm_mark_mixed, bn, b256, 0, st, U32(11), U32(12), n, U32(13));
-    hipLaunchKernelGGL(fkm::fkm_mixed_flags, bn, b256, 0, st, U32(11), U32(13), n, static_cast<uint8_t *>(c->mr[14].p));
+    hipLaunchKernelGGL(fkm::fkm_run_heads, bn, b256, 0, st, m.key_alt.p, m.s_seats.p, n, K, m.heads.p, m.tuple_break.p);
+    FK_CUB(hipcub::DeviceScan::InclusiveSum, m.heads.p, m.run_id.p, (int)n, st);
+    HIPCHK(c, hipMemsetAsync(m.run_mixed.p, 0, 4ul * n, st));
+    hipLaunchKernelGGL(fkm::fkm_mark_mixed, bn, b256, 0, st, m.run_id.p, m.tuple_break.p, n, m.run_mixed.p);
+    hipLaunchKernelGGL(fkm::fkm_mixed_flags, bn, b256, 0, st, m.run_id.p, m.run_mixed.p, n, m.mixed_flag.p);
     HIPCHK(c, hipGetLastError());
-    if ((rc = ensure(c, c->mr[34], 16))) return rc;
-    uint32_t *d_num = U32(34);
-    FKM_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(c->mr[14].p), U32(15), d_num,
-            (int)n, st);
-    uint32_t m = 0;
-    HIPCHK(c, hipMemcpyAsync(&m, d_num, 4, hipMemcpyDeviceToHost, st));
+    if ((rc = ensure(c, m.num, 4))) return rc;
+    uint32_t *d_num = m.num.p;
+    FK_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(m.mixed_flag.p), m.mixed_pos.p, d_num,
+           (int)n, st);
+    uint32_t n_mixed = 0;
+    HIPCHK(c, hipMemcpyAsync(&n_mixed, d_num, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (m > 0) {
-        const dim3 bm((m + 255u) / 256u);
-        HIPCHK(c, hipMemcpyAsync(c->mr[18].p, c->mr[15].p, 4ul * m, hipMemcpyDeviceToDevice, st)); // values: positions, ascending
-        int a = 18, b = 19;
+    if (n_mixed > 0) {
+        const dim3 bm((n_mixed + 255u) / 256u);
+        HIPCHK(c, hipMemcpyAsync(m.mixed_a.p, m.mixed_pos.p, 4ul * n_mixed, hipMemcpyDeviceToDevice, st)); // values: positions, ascending
+        uint32_t *a = m.mixed_a.p, *b = m.mixed_b.p;
         for (int32_t col = k; col >= 0; --col) { // col = k - 1 .. 0, then the run (col == k is applied LAST: the primary key)
             const uint32_t key_col = col == 0 ? K : (uint32_t)(col - 1);
-            hipLaunchKernelGGL(fkm::fkm_mixed_keys, bm, b256, 0, st, U32(a), U16(8), U32(11), m, K, key_col, U32(16));
+            hipLaunchKernelGGL(fkm::fkm_mixed_keys, bm, b256, 0, st, a, m.s_seats.p, m.run_id.p, n_mixed, K, key_col, m.mixed_key.p);
             HIPCHK(c, hipGetLastError());
-            FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U32(16), U32(17), U32(a), U32(b), (int)m, 0, key_col == K ? 32 : 16, st);
+            FK_CUB(hipcub::DeviceRadixSort::SortPairs, m.mixed_key.p, m.mixed_key_alt.p, a, b, (int)n_mixed, 0, key_col == K ? 32 : 16, st);
             std::swap(a, b);
         }
-        HIPCHK(c, hipMemcpyAsync(c->mr[20].p, c->mr[6].p, 4ul * n, hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(fkm::fkm_mixed_apply, bm, b256, 0, st, U32(15), U32(a), U32(20), m, U32(6));
-        hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, U32(6), U64(0), U16(1), U16(2), n, K, U64(7), U16(8), U16(9));
+        HIPCHK(c, hipMemcpyAsync(m.order_before.p, m.order.p, 4ul * n, hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(fkm::fkm_mixed_apply, bm, b256, 0, st, m.mixed_pos.p, a, m.order_before.p, n_mixed, m.order.p);
+        hipLaunchKernelGGL(fkm::fkm_gather, bn, b256, 0, st, m.order.p, m.digest.p, m.seats.p, m.rounds.p, n, K, m.s_digest.p, m.s_seats.p, m.s_rounds.p);
         HIPCHK(c, hipGetLastError());
     }
     // 3. segments = groups (the tuple changes), their starts, counts, eligibility, priorities, histogram bins
-    hipLaunchKernelGGL(fkm::fkm_seg_heads, bn, b256, 0, st, U16(8), n, K, U32(10));
-    FKM_CUB(hipcub::DeviceScan::InclusiveSum, U32(10), U32(11), (int)n, st);
+    hipLaunchKernelGGL(fkm::fkm_seg_heads, bn, b256, 0, st, m.s_seats.p, n, K, m.heads.p);
+    FK_CUB(hipcub::DeviceScan::InclusiveSum, m.heads.p, m.run_id.p, (int)n, st);
     uint32_t G = 0;
-    HIPCHK(c, hipMemcpyAsync(&G, U32(11) + (n - 1), 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&G, m.run_id.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const size_t gsizes[] = {4ul * (G + 1), 1ul * G, 8ul * G, 4ul * G, 4ul * H, 4ul * G, 4ul * G, 8ul * G};
-    for (int i = 0; i < 8; ++i)
-        if ((rc = ensure(c, c->mr[21 + i], gsizes[i]))) return rc;
-    hipLaunchKernelGGL(fkm::fkm_seg_starts, bn, b256, 0, st, U32(10), U32(11), n, U32(21));
+    if ((rc = ensure_all(c, m.seg_start, (size_t)G + 1, m.eligible, G, m.prio, G, m.bin, G, m.hist, H, m.sel, G, m.sel_sorted, G, m.prio_sorted, G))) return rc;
+    hipLaunchKernelGGL(fkm::fkm_seg_starts, bn, b256, 0, st, m.heads.p, m.run_id.p, n, m.seg_start.p);
     const dim3 bg((G + 255u) / 256u);
-    hipLaunchKernelGGL(fkm::fkm_seg_info, bg, b256, 0, st, U32(21), U64(7), G, K, minimum, static_cast<uint8_t *>(c->mr[22].p), U64(23),
-                       static_cast<int32_t *>(c->mr[24].p));
+    hipLaunchKernelGGL(fkm::fkm_seg_info, bg, b256, 0, st, m.seg_start.p, m.s_digest.p, G, K, minimum, m.eligible.p, m.prio.p, m.bin.p);
     HIPCHK(c, hipGetLastError());
-    FKM_CUB(hipcub::DeviceHistogram::HistogramEven, static_cast<const int32_t *>(c->mr[24].p), U32(25), (int)(H + 1), 0, (int)H, (int)G, st);
+    FK_CUB(hipcub::DeviceHistogram::HistogramEven, static_cast<const int32_t *>(m.bin.p), m.hist.p, (int)(H + 1), 0, (int)H, (int)G, st);
     // 4. selection: the eligible groups by priority (radix sort); the first `cap` and every group tied with the last one kept
-    FKM_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(c->mr[22].p), U32(26), d_num,
-            (int)G, st);
+    FK_CUB(hipcub::DeviceSelect::Flagged, hipcub::CountingInputIterator<uint32_t>(0u), static_cast<const uint8_t *>(m.eligible.p), m.sel.p, d_num, (int)G, st);
     uint32_t E = 0;
     std::vector<uint32_t> hist32(H);
     HIPCHK(c, hipMemcpyAsync(&E, d_num, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hist32.data(), c->mr[25].p, 4ul * H, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hist32.data(), m.hist.p, 4ul * H, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     for (uint32_t i = 0; i < H; ++i) histogram[i] = hist32[i];
     counts[1] = G;
@@ -1858,18 +1875,18 @@ int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *diges
     uint64_t M = E;
     if (E > 0) {
         const dim3 be((E + 255u) / 256u);
-        hipLaunchKernelGGL(fkm::fkm_gather_u64, be, b256, 0, st, U32(26), U64(23), E, U64(4));
+        hipLaunchKernelGGL(fkm::fkm_gather_u64, be, b256, 0, st, m.sel.p, m.prio.p, E, m.key_alt.p);
         HIPCHK(c, hipGetLastError());
-        FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(4), U64(28), U32(26), U32(27), (int)E, 0, 64, st);
+        FK_CUB(hipcub::DeviceRadixSort::SortPairs, m.key_alt.p, m.prio_sorted.p, m.sel.p, m.sel_sorted.p, (int)E, 0, 64, st);
         if (cap > 0 && (uint64_t)cap < E) {
             M = (uint64_t)cap;
-            unsigned long long last = 0;
-            HIPCHK(c, hipMemcpyAsync(&last, U64(28) + (M - 1), 8, hipMemcpyDeviceToHost, st));
+            ull last = 0;
+            HIPCHK(c, hipMemcpyAsync(&last, m.prio_sorted.p + (M - 1), 8, hipMemcpyDeviceToHost, st));
             HIPCHK(c, hipStreamSynchronize(st));
-            std::vector<unsigned long long> more(4096);
+            std::vector<ull> more(4096);
             while (M < E) { // ties on the 64-bit priority: the host breaks them by the rest of the tuple
                 const uint64_t take = std::min<uint64_t>(more.size(), E - M);
-                HIPCHK(c, hipMemcpy(more.data(), U64(28) + M, 8 * take, hipMemcpyDeviceToHost));
+                HIPCHK(c, hipMemcpy(more.data(), m.prio_sorted.p + M, 8 * take, hipMemcpyDeviceToHost));
                 uint64_t j = 0;
                 while (j < take && more[j] == last) ++j;
                 M += j;
@@ -1881,55 +1898,45 @@ int fk_matchup_reduce(fk_ctx *c, int32_t k, int64_t n_obs, const uint64_t *diges
     if ((int64_t)M > out_capacity) return fail(c, FK_ERR_ARG, "fk_matchup_reduce: %llu groups selected, out_capacity is %lld", (unsigned long long)M, (long long)out_capacity);
     if (M == 0) return FK_OK;
     if (!out_digest || !out_seats || !out_count || !out_sums) return fail(c, FK_ERR_ARG, "the output arrays are required");
-    const size_t osizes[] = {8ul * M, 2ul * M * K, 8ul * M, 8ul * M * n_lags * fkm::SUM_COLS, 4ul * n_lags};
-    for (int i = 0; i < 5; ++i)
-        if ((rc = ensure(c, c->mr[29 + i], osizes[i]))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->mr[33].p, lags, 4ul * n_lags, hipMemcpyHostToDevice, st));
+    const size_t n_sums = (size_t)M * n_lags * fkm::SUM_COLS;
+    if ((rc = ensure_all(c, m.out_digest, M, m.out_seats, (size_t)M * K, m.out_count, M, m.out_sums, n_sums, m.lags, (size_t)n_lags))) return rc;
+    HIPCHK(c, hipMemcpyAsync(m.lags.p, lags, 4ul * n_lags, hipMemcpyHostToDevice, st));
     // 5. the lag sums of the selected groups: one wave per group
-    hipLaunchKernelGGL(fkm::fkm_group_sums, dim3((unsigned)((M * 64 + 255) / 256)), b256, 0, st, U32(27), (uint32_t)M, U32(21), U64(7), U16(8),
-                       U16(9), K, static_cast<const int32_t *>(c->mr[33].p), (uint32_t)n_lags, U64(29), U16(30),
-                       static_cast<long long *>(c->mr[31].p), static_cast<long long *>(c->mr[32].p));
+    hipLaunchKernelGGL(fkm::fkm_group_sums, dim3((unsigned)((M * 64 + 255) / 256)), b256, 0, st, m.sel_sorted.p, (uint32_t)M, m.seg_start.p, m.s_digest.p,
+                       m.s_seats.p, m.s_rounds.p, K, m.lags.p, (uint32_t)n_lags, m.out_digest.p, m.out_seats.p, m.out_count.p, m.out_sums.p);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out_digest, c->mr[29].p, osizes[0], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out_seats, c->mr[30].p, osizes[1], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out_count, c->mr[31].p, osizes[2], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(out_sums, c->mr[32].p, osizes[3], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_digest, m.out_digest.p, 8ul * M, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_seats, m.out_seats.p, 2ul * M * K, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_count, m.out_count.p, 8ul * M, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out_sums, m.out_sums.p, 8 * n_sums, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return FK_OK;
 }
-// The pair reduce of fk_tournament_run_seat_counts over the call's n mirror records (c->sa[1] keys, c->sa[3] payloads), on the
-// context's stream with no host round trip: sa[13] = pair ranks [capacity][2], sa[14] = pair sums [capacity][6], sa[15] = the pair count.
+// The pair reduce of fk_tournament_run_seat_counts over the call's n mirror records (c->sa.key, c->sa.val), on the context's stream
+// with no host round trip: pair_rank [capacity][2], pair_sums [capacity][6], pair_count.
 static int mirror_reduce(fk_ctx *c, uint32_t n, uint64_t capacity) {
     int rc = 0;
-    const size_t n1 = (size_t)n + 1;
-    // 5 fr | 6 e_fr | 7 sh | 8 e_sh | 9 ph | 10 e_ph | 11 seg_start | 12 pair_start + seg_diff
-    const size_t sizes[] = {8 * n1, 8 * n1, 8 * n1, 8 * n1, 4 * n1, 4 * n1, 4 * n1, 4 * n1 + 4 * n1};
-    for (int i = 0; i < 8; ++i)
-        if ((rc = ensure(c, c->sa[5 + i], sizes[i]))) return rc;
-    if ((rc = ensure(c, c->sa[13], std::max<size_t>((size_t)capacity, 1) * 4))) return rc;
-    if ((rc = ensure(c, c->sa[14], std::max<size_t>((size_t)capacity, 1) * fksa::PAIR_COLS * 8))) return rc;
-    if ((rc = ensure(c, c->sa[15], 8))) return rc;
-    auto U64 = [&](int i) { return static_cast<unsigned long long *>(c->sa[i].p); };
-    auto U32 = [&](int i) { return static_cast<uint32_t *>(c->sa[i].p); };
+    SeatBufs &s = c->sa;
+    const size_t n1 = (size_t)n + 1, rows = std::max<size_t>((size_t)capacity, 1);
+    if ((rc = ensure_all(c, s.fr, n1, s.e_fr, n1, s.sh, n1, s.e_sh, n1, s.ph, n1, s.e_ph, n1, s.seg_start, n1, s.pair_start, n1, s.seg_diff, n1,
+                         s.pair_rank, rows * 2, s.pair_sums, rows * fksa::PAIR_COLS, s.pair_count, 1)))
+        return rc;
     const hipStream_t st = c->stream;
     const dim3 bn((unsigned)((n1 + 255u) / 256u)), b256(256);
-    FKM_CUB(hipcub::DeviceRadixSort::SortPairs, U64(1), U64(2), U32(3), U32(4), (int)n, 0, 64, st);
-    hipLaunchKernelGGL(fksa::fk_mirror_flags_kernel, bn, b256, 0, st, U64(2), U32(4), n, U64(5), U64(7), U32(9));
+    FK_CUB(hipcub::DeviceRadixSort::SortPairs, s.key.p, s.key_sorted.p, s.val.p, s.val_sorted.p, (int)n, 0, 64, st);
+    hipLaunchKernelGGL(fksa::fk_mirror_flags_kernel, bn, b256, 0, st, s.key_sorted.p, s.val_sorted.p, n, s.fr.p, s.sh.p, s.ph.p);
     HIPCHK(c, hipGetLastError());
-    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U64(5), U64(6), (int)n1, st);
-    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U64(7), U64(8), (int)n1, st);
-    FKM_CUB(hipcub::DeviceScan::ExclusiveSum, U32(9), U32(10), (int)n1, st);
-    uint32_t *pair_start = U32(12);
-    int32_t *seg_diff = reinterpret_cast<int32_t *>(U32(12) + n1);
-    HIPCHK(c, hipMemsetAsync(seg_diff, 0, 4 * n1, st));
-    hipLaunchKernelGGL(fksa::fk_mirror_starts_kernel, bn, b256, 0, st, U64(7), U64(8), U32(9), U32(10), n, U32(11), pair_start);
-    hipLaunchKernelGGL(fksa::fk_mirror_segment_kernel, bn, b256, 0, st, U64(2), U32(4), n, U64(6), U64(8), U32(11), seg_diff);
-    hipLaunchKernelGGL(fksa::fk_mirror_pair_sum_kernel, bn, b256, 0, st, U64(2), U64(6), U64(8), U32(10), n, U32(11), pair_start, seg_diff,
-                       (unsigned long long)capacity, static_cast<uint16_t *>(c->sa[13].p), static_cast<long long *>(c->sa[14].p), U64(15));
+    FK_CUB(hipcub::DeviceScan::ExclusiveSum, s.fr.p, s.e_fr.p, (int)n1, st);
+    FK_CUB(hipcub::DeviceScan::ExclusiveSum, s.sh.p, s.e_sh.p, (int)n1, st);
+    FK_CUB(hipcub::DeviceScan::ExclusiveSum, s.ph.p, s.e_ph.p, (int)n1, st);
+    HIPCHK(c, hipMemsetAsync(s.seg_diff.p, 0, 4 * n1, st));
+    hipLaunchKernelGGL(fksa::fk_mirror_starts_kernel, bn, b256, 0, st, s.sh.p, s.e_sh.p, s.ph.p, s.e_ph.p, n, s.seg_start.p, s.pair_start.p);
+    hipLaunchKernelGGL(fksa::fk_mirror_segment_kernel, bn, b256, 0, st, s.key_sorted.p, s.val_sorted.p, n, s.e_fr.p, s.e_sh.p, s.seg_start.p, s.seg_diff.p);
+    hipLaunchKernelGGL(fksa::fk_mirror_pair_sum_kernel, bn, b256, 0, st, s.key_sorted.p, s.e_fr.p, s.e_sh.p, s.e_ph.p, n, s.seg_start.p, s.pair_start.p,
+                       s.seg_diff.p, (ull)capacity, s.pair_rank.p, s.pair_sums.p, s.pair_count.p);
     HIPCHK(c, hipGetLastError());
     return FK_OK;
 }
-#undef FKM_CUB
 
 // The tournament call path: an entry point checks its own arguments and fills a TournamentCall on its stack; tournament_call plays it
 // through the driver below, once or again on one of its three replays.  Nothing that describes the call in progress is in the context.
@@ -1964,10 +1971,10 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
 
     if ((rc = upload_strategies(c, strategies, S))) return rc;
     if (columns) {
-        if ((rc = ensure(c, c->ids, sizeof(int32_t) * (size_t)S))) return rc;
+        if ((rc = ensure(c, c->ids, (size_t)S))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->ids.p, call.columns_ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = ensure(c, c->tally, tally_bytes))) return rc;
+    if ((rc = ensure(c, c->tally, tally_bytes / 8))) return rc;
     HIPCHK(c, hipMemsetAsync(c->tally.p, 0, tally_bytes, c->stream));
 
     LaunchPlan plan = plan_play(plan_knobs(c), PLAN_TOURNAMENT, k, S, n_batches == 1, target_score);
@@ -1976,7 +1983,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
                     target_score, 50 * LEAN_MAX_TARGET50, (int)k);
     if (plan.shape().hc) c->ran_hc = true;
     if (plan.shape().hc && !plan.shape().cl) { // cold seat records of every lane the grid can seat
-        if ((rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k * 16))) return rc;
+        if ((rc = ensure(c, c->cold, (size_t)plan.grid * (size_t)plan.block * (size_t)k))) return rc;
     }
     const GameStatsReq *gst = call.gstats; // fk_tournament_run_game_stats (null otherwise)
     const RareReq *rare = gst ? call.rare : nullptr; // fk_tournament_run_rare_events
@@ -1985,25 +1992,23 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     const bool want_recs = !plan.lds_tally || want_state || lag != nullptr;
     const size_t stats_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * FK_SEAT_STAT_COLS;
     if (seat_stats) {
-        if ((rc = ensure(c, c->stats, stats_bytes))) return rc;
+        if ((rc = ensure(c, c->stats, stats_bytes / 8))) return rc;
         HIPCHK(c, hipMemsetAsync(c->stats.p, 0, stats_bytes, c->stream));
     }
     const size_t sq_bytes = sizeof(int64_t) * (size_t)n_batches * (size_t)S * (size_t)k * fksa::COUNT_COLS;
     const uint32_t sq_n = sq && sq->id_rank ? (uint32_t)(n_sh_total * gps) : 0u; // mirror records of the call (the entry bounds the range)
     if (sq) {
-        if ((rc = ensure(c, c->sa_counts, sq_bytes))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->sa_counts.p, 0, sq_bytes, c->stream));
+        if ((rc = ensure(c, c->sa.counts, sq_bytes / 8))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->sa.counts.p, 0, sq_bytes, c->stream));
     }
-    if (sq_n) { // 0 id ranks | 1, 2 keys | 3, 4 payloads (two sort buffers each)
+    if (sq_n) { // id ranks, the call's mirror records: keys and payloads, two sort buffers each
         const size_t n = sq_n;
-        const size_t sizes[5] = {2ul * (size_t)S, 8ul * n, 8ul * n, 4ul * n, 4ul * n};
-        for (int i = 0; i < 5; ++i)
-            if ((rc = ensure(c, c->sa[i], sizes[i]))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->sa[0].p, sq->id_rank, 2ul * (size_t)S, hipMemcpyHostToDevice, c->stream));
+        if ((rc = ensure_all(c, c->sa.id_rank, (size_t)S, c->sa.key, n, c->sa.key_sorted, n, c->sa.val, n, c->sa.val_sorted, n))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->sa.id_rank.p, sq->id_rank, 2ul * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
     const size_t ratio_bytes = sizeof(double) * (size_t)n_batches * (size_t)S * FK_SEAT_RATIO_COLS;
     if (seat_ratios) { // running float64 sums, carried from chunk to chunk on the device (all-zero bits = 0.0)
-        if ((rc = ensure(c, c->ratios, ratio_bytes))) return rc;
+        if ((rc = ensure(c, c->ratios, ratio_bytes / 8))) return rc;
         HIPCHK(c, hipMemsetAsync(c->ratios.p, 0, ratio_bytes, c->stream));
     }
 
@@ -2030,53 +2035,43 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     const size_t lag_sum_bytes = lag ? sizeof(int64_t) * (size_t)S * (size_t)lag->n_lags * FK_LAG_COLS : 0;
     uint32_t head_filled = 0;
     if (lag) {
-        if ((rc = ensure(c, c->lag_v, ((size_t)L + chunk_sh) * (size_t)S * 2))) return rc;
-        if ((rc = ensure(c, c->lag_out, lag_sum_bytes))) return rc;
-        if ((rc = ensure(c, c->lag_lags, sizeof(int32_t) * (size_t)lag->n_lags))) return rc;
-        if ((rc = ensure(c, c->lag_edge, 2 * (size_t)std::max<uint32_t>(edge_rows, 1) * (size_t)S * 2))) return rc;
-        if ((rc = ensure(c, c->lag_tmp, (size_t)std::max<uint32_t>(L, 1) * (size_t)S * 2))) return rc;
+        if ((rc = ensure_all(c, c->lag_v, ((size_t)L + chunk_sh) * (size_t)S, c->lag_out, lag_sum_bytes / 8, c->lag_lags, (size_t)lag->n_lags, c->lag_edge,
+                             2 * (size_t)std::max<uint32_t>(edge_rows, 1) * (size_t)S, c->lag_tmp, (size_t)std::max<uint32_t>(L, 1) * (size_t)S)))
+            return rc;
         HIPCHK(c, hipMemsetAsync(c->lag_out.p, 0, lag_sum_bytes, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->lag_lags.p, lag->lags, sizeof(int32_t) * (size_t)lag->n_lags, hipMemcpyHostToDevice, c->stream));
     }
     if (lag && lag->m_digest) { // matchup records of one chunk (copied to the caller's arrays behind it)
-        if ((rc = ensure(c, c->m_ids, sizeof(int32_t) * (size_t)S))) return rc;
-        if ((rc = ensure(c, c->m_dig, (size_t)chunk_sh * gps * 8))) return rc;
-        if ((rc = ensure(c, c->m_seat, (size_t)chunk_sh * gps * 2 * (size_t)k))) return rc;
-        if ((rc = ensure(c, c->m_rnd, (size_t)chunk_sh * gps * 2))) return rc;
+        const size_t n = (size_t)chunk_sh * gps;
+        if ((rc = ensure_all(c, c->m_ids, (size_t)S, c->m_dig, n, c->m_seat, n * (size_t)k, c->m_rnd, n))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->m_ids.p, lag->ids, sizeof(int32_t) * (size_t)S, hipMemcpyHostToDevice, c->stream));
     }
 
-    // game statistics (fk_tournament_run_game_stats): g_out = u64 [S][4] counts | [S][rb] rounds | [S][mb] runner-up | [S][mb] spread |
-    // [4] game counts | [rb] game rounds | [mb] game runner-up | spill count, then the spill entries (int32 [cap][3])
+    // game statistics (fk_tournament_run_game_stats): g_out in the layout `go`
     const uint32_t g_rb = gst ? gst->rounds_bins : 0u, g_mb = gst ? gst->margin_bins : 0u;
     const uint32_t g_wr = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(g_rb, c->game_stats_window) : g_rb;
     const uint32_t g_wm = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(g_mb, c->game_stats_window) : g_mb;
-    const size_t g_sc = 0, g_sr = g_sc + (size_t)S * fkg::N_COUNTS, g_sru = g_sr + (size_t)S * g_rb, g_ssp = g_sru + (size_t)S * g_mb,
-                 g_gc = g_ssp + (size_t)S * g_mb, g_gr = g_gc + fkg::N_COUNTS, g_gru = g_gr + g_rb, g_cnt = g_gru + g_mb, g_u64 = g_cnt + 1;
+    const fkl::GameStatsOut go((size_t)S, g_rb, g_mb);
     fkg::Spill g_spill{};
     if (gst) {
-        if ((rc = ensure(c, c->g_rec, (size_t)chunk_sh * gps * 16))) return rc;
-        if ((rc = ensure(c, c->g_out, g_u64 * 8 + (size_t)std::max<int64_t>(gst->spill_capacity, 1) * 12))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->g_out.p, 0, g_u64 * 8, c->stream));
-        g_spill.count = static_cast<unsigned long long *>(c->g_out.p) + g_cnt;
-        g_spill.entries = reinterpret_cast<int32_t *>(static_cast<unsigned long long *>(c->g_out.p) + g_u64);
+        if ((rc = ensure_all(c, c->g_rec, (size_t)chunk_sh * gps, c->g_out, go.bytes(gst->spill_capacity)))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->g_out.p, 0, go.spill_at(), c->stream));
+        g_spill.count = c->g_out.as<ull>() + go.spill_count;
+        g_spill.entries = c->g_out.as<int32_t>(go.spill_at());
         g_spill.cap = (uint64_t)gst->spill_capacity;
     }
 
-    // rare events (fk_tournament_run_rare_events): r_out = u64 [S][sb] second | [sb] game second | event total
+    // rare events (fk_tournament_run_rare_events): r_out in the layout `ro`
     const uint32_t r_sb = rare ? rare->second_bins : 0u;
     const uint32_t r_ws = c->game_stats_window > 0 ? (uint32_t)std::min<int64_t>(r_sb, c->game_stats_window) : r_sb;
-    const size_t r_gs = (size_t)S * r_sb, r_tot = r_gs + r_sb, r_u64 = r_tot + 1;
+    const fkl::RareOut ro((size_t)S, r_sb);
     if (rare) {
         const size_t max_blocks = ((size_t)chunk_sh * gps + fkre::COUNT_BLOCK - 1) / fkre::COUNT_BLOCK;
-        if ((rc = ensure(c, c->r_sec, (size_t)chunk_sh * gps * 4))) return rc;
-        if ((rc = ensure(c, c->r_out, r_u64 * 8))) return rc;
-        HIPCHK(c, hipMemsetAsync(c->r_out.p, 0, r_u64 * 8, c->stream));
+        if ((rc = ensure_all(c, c->r_sec, (size_t)chunk_sh * gps, c->r_out, ro.n_u64))) return rc;
+        HIPCHK(c, hipMemsetAsync(c->r_out.p, 0, ro.n_u64 * 8, c->stream));
         if (rare->events) {
-            if ((rc = ensure(c, c->r_blk, max_blocks * 4))) return rc;
-            if ((rc = ensure(c, c->r_base, max_blocks * 8))) return rc;
-            if ((rc = ensure(c, c->r_head, (size_t)std::max<int64_t>(rare->event_capacity, 1) * 16))) return rc;
-            if ((rc = ensure(c, c->r_seats, (size_t)std::max<int64_t>(rare->event_capacity, 1) * (size_t)k * 2))) return rc;
+            const size_t room = (size_t)std::max<int64_t>(rare->event_capacity, 1);
+            if ((rc = ensure_all(c, c->r_blk, max_blocks, c->r_base, max_blocks, c->r_head, room, c->r_seats, room * (size_t)k))) return rc;
         }
     }
 
@@ -2137,18 +2132,18 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         if ((rc = map_tournament_overrides(c, ov, n_ov, root_seed, k, sh0, n_sh, gps, n_dov))) return rc;
         // the device row buffers alternate over chunks — and, in async mode, over calls: a one-chunk call's row kernel then has not to wait for the previous call's copy
         const int rb = (int)((done / chunk_sh + (c->rows_async ? c->rows_calls : 0u)) & 1u);
-        DevBuf &row_buf = rb ? c->rows_alt : c->rows;
+        Dev<uint8_t> &row_buf = rb ? c->rows_alt : c->rows;
         if (rows) {
             if ((size_t)n_sh * rows_per_shuffle > row_buf.cap) HIPCHK(c, hipStreamSynchronize(c->copy_stream)); // growing: no copy may be reading it
             if ((rc = ensure(c, row_buf, (size_t)n_sh * rows_per_shuffle))) return rc;
         }
 
         PlayArgs pa = table_args(c, target_score, max_rounds);
-        pa.perm_T = static_cast<const uint16_t *>(CSET(c).perm.p);
+        pa.perm_T = CSET(c).perm.p;
         pa.perm_slots = slots;
         pa.seat_strategy = nullptr;
-        pa.tally = static_cast<unsigned long long *>(c->tally.p);
-        pa.ov = static_cast<const DevOverride *>(c->ov.p);
+        pa.tally = c->tally.p;
+        pa.ov = c->ov.p;
         pa.n_ov = n_dov;
         pa.mode = MODE_PERM;
         pa.n_games = n_games;
@@ -2156,7 +2151,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         pa.n_sh = n_sh;
         pa.k = (uint32_t)k;
         pa.S = (uint32_t)S;
-        pa.cold = static_cast<uint4 *>(c->cold.p);
+        pa.cold = c->cold.p;
 
         // The next chunk (or the hinted next call) is prepared into the other chunk set around this game kernel: its permutations
         // in front of it on the main stream, its schedule + seat seeding on the low-priority stream while it runs.
@@ -2188,56 +2183,51 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             if ((rc = finish_play(c, pa, (int64_t)done * gps, "tournament"))) return rc;
         }
         const bool scheduled = c->longest_first != 0;
-        if (want_state && scheduled) { // game id -> slot of its state records
-            if ((rc = ensure(c, c->inv, (size_t)n_games * 4))) return rc;
-            hipLaunchKernelGGL(fk_invert_sched_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
-                               static_cast<const uint32_t *>(CSET(c).order.p), n_games, static_cast<uint32_t *>(c->inv.p));
+        const uint32_t *inv = nullptr; // game id -> slot of its state records
+        if (want_state && scheduled) {
+            if ((rc = ensure(c, c->inv, (size_t)n_games))) return rc;
+            hipLaunchKernelGGL(fk_invert_sched_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, CSET(c).order.p, n_games, c->inv.p);
+            inv = c->inv.p;
         }
-        if (seat_stats || gst || sq) {
-            rc = ensure(c, CSET(c).draws, (size_t)perm_blocks * S * slots * 2); // the draws buffer is free again: inverse permutations
-            if (rc) return rc;
+        const uint16_t *inv_perm = nullptr;
+        if (seat_stats || gst || sq) { // the draws buffer is free again: inverse permutations
+            if ((rc = ensure(c, CSET(c).draws, (size_t)perm_blocks * S * slots * 2))) return rc;
             const uint32_t cells = perm_blocks * (uint32_t)S * slots;
-            hipLaunchKernelGGL(fk_invert_perm_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, c->stream,
-                               static_cast<const uint16_t *>(CSET(c).perm.p), (uint32_t)S, slots, n_sh, static_cast<uint16_t *>(CSET(c).draws.p));
+            hipLaunchKernelGGL(fk_invert_perm_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, c->stream, CSET(c).perm.p, (uint32_t)S, slots, n_sh,
+                               CSET(c).draws16());
+            inv_perm = CSET(c).draws16();
         }
         if (gst) {
             // phase 1, game-major: one 16-byte record per game + the game-level histograms; phase 2 gathers them per strategy
-            unsigned long long *o = static_cast<unsigned long long *>(c->g_out.p);
+            ull *o = c->g_out.as<ull>();
             const uint32_t rec_grid = std::max<uint32_t>(1u, std::min<uint32_t>((n_games + 255u) / 256u, 2048u));
             hipLaunchKernelGGL(fkg::fk_game_record_kernel, dim3(rec_grid), dim3(256), (size_t)(g_wr + g_wm + fkg::N_COUNTS) * 4, c->stream,
-                               static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
-                               scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr, n_games, gps, n_sh, (uint32_t)k, gst->rare_target,
-                               g_wr, g_wm, static_cast<uint4 *>(c->g_rec.p), o + g_gc, o + g_gr, o + g_gru, g_spill);
+                               CSET(c).state.p, c->recs.p, inv, n_games, gps, n_sh, (uint32_t)k, gst->rare_target, g_wr, g_wm, c->g_rec.p,
+                               o + go.g_counts, o + go.g_rounds, o + go.g_runner, g_spill);
             // (strategy, segment) workgroups: enough of them to fill the chip, at least 256 shuffles (one per lane) per segment
             const uint32_t want_seg = std::max<uint32_t>(1u, (2048u + (uint32_t)S - 1u) / (uint32_t)S);
             const uint32_t rows_per_seg = std::max<uint32_t>(256u, (n_sh + want_seg - 1u) / want_seg);
             const uint32_t n_seg = (n_sh + rows_per_seg - 1u) / rows_per_seg;
             hipLaunchKernelGGL(fkg::fk_game_stats_gather_kernel, dim3((uint32_t)S, n_seg), dim3(256), (size_t)(g_wr + 2 * g_wm + fkg::N_COUNTS) * 4,
-                               c->stream, static_cast<const uint4 *>(c->g_rec.p), static_cast<const uint16_t *>(CSET(c).draws.p), slots,
-                               (uint32_t)S, (uint32_t)k, gps, n_sh, rows_per_seg, g_wr, g_wm, g_rb, g_mb, o + g_sc, o + g_sr, o + g_sru, o + g_ssp,
-                               g_spill);
+                               c->stream, c->g_rec.p, inv_perm, slots, (uint32_t)S, (uint32_t)k, gps, n_sh, rows_per_seg, g_wr, g_wm, g_rb, g_mb,
+                               o + go.s_counts, o + go.s_rounds, o + go.s_runner, o + go.s_spread, g_spill);
             HIPCHK(c, hipGetLastError());
             if (rare) {
-                unsigned long long *ro = static_cast<unsigned long long *>(c->r_out.p);
+                ull *r = c->r_out.p;
                 if (k >= 2) { // one seat has no second score: it contributes nothing
-                    hipLaunchKernelGGL(fkre::fk_second_score_kernel, dim3(rec_grid), dim3(256), (size_t)r_ws * 4, c->stream,
-                                       static_cast<const uint32_t *>(CSET(c).state.p), scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr,
-                                       n_games, gps, n_sh, (uint32_t)k, r_ws, static_cast<uint32_t *>(c->r_sec.p), ro + r_gs, g_spill);
-                    hipLaunchKernelGGL(fkre::fk_second_gather_kernel, dim3((uint32_t)S, n_seg), dim3(256), (size_t)r_ws * 4, c->stream,
-                                       static_cast<const uint32_t *>(c->r_sec.p), static_cast<const uint16_t *>(CSET(c).draws.p), slots, (uint32_t)S,
-                                       (uint32_t)k, gps, n_sh, rows_per_seg, r_ws, r_sb, ro, g_spill);
+                    hipLaunchKernelGGL(fkre::fk_second_score_kernel, dim3(rec_grid), dim3(256), (size_t)r_ws * 4, c->stream, CSET(c).state.p, inv,
+                                       n_games, gps, n_sh, (uint32_t)k, r_ws, c->r_sec.p, r + ro.g_second, g_spill);
+                    hipLaunchKernelGGL(fkre::fk_second_gather_kernel, dim3((uint32_t)S, n_seg), dim3(256), (size_t)r_ws * 4, c->stream, c->r_sec.p,
+                                       inv_perm, slots, (uint32_t)S, (uint32_t)k, gps, n_sh, rows_per_seg, r_ws, r_sb, r + ro.s_second, g_spill);
                 }
                 if (rare->events) { // ordered compaction of the flagged games: count per workgroup, scan from the running total, scatter
                     const uint32_t n_blk = (n_games + fkre::COUNT_BLOCK - 1u) / fkre::COUNT_BLOCK;
-                    hipLaunchKernelGGL(fkre::fk_event_count_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream,
-                                       static_cast<const uint4 *>(c->g_rec.p), n_games, rare->thr, static_cast<uint32_t *>(c->r_blk.p));
-                    hipLaunchKernelGGL(fkre::fk_event_scan_kernel, dim3(1), dim3(fkre::SCAN_BLOCK), 0, c->stream,
-                                       static_cast<const uint32_t *>(c->r_blk.p), n_blk, ro + r_tot, static_cast<unsigned long long *>(c->r_base.p));
-                    hipLaunchKernelGGL(fkre::fk_event_scatter_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream,
-                                       static_cast<const uint4 *>(c->g_rec.p), static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)S,
-                                       (uint32_t)k, gps, n_games, (uint32_t)done, rare->thr, static_cast<const unsigned long long *>(c->r_base.p),
-                                       (unsigned long long)rare->event_capacity, static_cast<uint4 *>(c->r_head.p),
-                                       static_cast<uint16_t *>(c->r_seats.p));
+                    hipLaunchKernelGGL(fkre::fk_event_count_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream, c->g_rec.p, n_games,
+                                       rare->thr, c->r_blk.p);
+                    hipLaunchKernelGGL(fkre::fk_event_scan_kernel, dim3(1), dim3(fkre::SCAN_BLOCK), 0, c->stream, c->r_blk.p, n_blk, r + ro.total, c->r_base.p);
+                    hipLaunchKernelGGL(fkre::fk_event_scatter_kernel, dim3(n_blk), dim3(fkre::COUNT_BLOCK), 0, c->stream, c->g_rec.p, CSET(c).perm.p,
+                                       slots, (uint32_t)S, (uint32_t)k, gps, n_games, (uint32_t)done, rare->thr, c->r_base.p,
+                                       (ull)rare->event_capacity, c->r_head.p, c->r_seats.p);
                 }
                 HIPCHK(c, hipGetLastError());
             }
@@ -2246,14 +2236,12 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             const uint32_t s_blocks = ((uint32_t)S + fksa::COUNT_BLOCK - 1u) / fksa::COUNT_BLOCK;
             const uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(shuffles_per_batch, n_sh) / 8, (4096u + nb * s_blocks - 1u) / (nb * s_blocks)));
             hipLaunchKernelGGL(fksa::fk_seat_counts_kernel, dim3(s_blocks, nb * ppb), dim3(fksa::COUNT_BLOCK),
-                               (size_t)k * fksa::COUNT_COLS * fksa::COUNT_BLOCK * 4, c->stream, static_cast<const uint32_t *>(c->rec0.p),
-                               static_cast<const uint16_t *>(CSET(c).draws.p), slots, (uint32_t)S, (uint32_t)k, gps, n_sh, (uint32_t)done,
-                               shuffles_per_batch, ppb, first_batch, static_cast<long long *>(c->sa_counts.p));
+                               (size_t)k * fksa::COUNT_COLS * fksa::COUNT_BLOCK * 4, c->stream, c->rec0.p, inv_perm, slots, (uint32_t)S, (uint32_t)k, gps,
+                               n_sh, (uint32_t)done, shuffles_per_batch, ppb, first_batch, c->sa.counts.p);
             if (sq_n)
-                hipLaunchKernelGGL(fksa::fk_mirror_record_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
-                                   static_cast<const uint32_t *>(c->rec0.p), static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)S, gps,
-                                   n_games, (uint32_t)done, shuffles_per_batch, static_cast<const uint16_t *>(c->sa[0].p), (uint32_t)(done * gps),
-                                   static_cast<unsigned long long *>(c->sa[1].p), static_cast<uint32_t *>(c->sa[3].p));
+                hipLaunchKernelGGL(fksa::fk_mirror_record_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, c->rec0.p, CSET(c).perm.p,
+                                   slots, (uint32_t)S, gps, n_games, (uint32_t)done, shuffles_per_batch, c->sa.id_rank.p, (uint32_t)(done * gps),
+                                   c->sa.key.p, c->sa.val.p);
             HIPCHK(c, hipGetLastError());
         }
         if (seat_stats) {
@@ -2261,49 +2249,40 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             // enough (strategy block, batch, part) workgroups to fill the chip; a part is at least 8 shuffles
             const uint32_t ppb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(shuffles_per_batch, n_sh) / 8, (4096u + nb * s_blocks - 1u) / (nb * s_blocks)));
             // phase 1, game-major: one 32-byte digest per exposure; phase 2 gathers them per strategy
-            if ((rc = ensure(c, c->digest, (size_t)n_games * k * 32))) return rc;
+            if ((rc = ensure(c, c->digest, (size_t)n_games * k * 2))) return rc;
             const size_t pairs = (size_t)n_games * k;
-            hipLaunchKernelGGL(fk_seat_digest_kernel, dim3((unsigned)((pairs + 255u) / 256u)), dim3(256), 0, c->stream,
-                               static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
-                               scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr, n_games, gps, n_sh, (uint32_t)k,
-                               static_cast<uint4 *>(c->digest.p));
-            hipLaunchKernelGGL(fk_seat_stats_kernel, dim3(s_blocks, nb * ppb), dim3(256), 0, c->stream,
-                               static_cast<const uint4 *>(c->digest.p), static_cast<const uint16_t *>(CSET(c).draws.p),
-                               slots, (uint32_t)S, (uint32_t)k, gps, n_sh, (uint32_t)done, shuffles_per_batch, ppb, first_batch,
-                               static_cast<long long *>(c->stats.p));
+            hipLaunchKernelGGL(fk_seat_digest_kernel, dim3((unsigned)((pairs + 255u) / 256u)), dim3(256), 0, c->stream, CSET(c).state.p, c->recs.p, inv,
+                               n_games, gps, n_sh, (uint32_t)k, c->digest.p);
+            hipLaunchKernelGGL(fk_seat_stats_kernel, dim3(s_blocks, nb * ppb), dim3(256), 0, c->stream, c->digest.p, inv_perm, slots, (uint32_t)S,
+                               (uint32_t)k, gps, n_sh, (uint32_t)done, shuffles_per_batch, ppb, first_batch, c->stats.p);
             if (seat_ratios) // the four float64 sums: one thread per (strategy, batch), the batch's shuffles of this chunk in order
-                hipLaunchKernelGGL(fk_seat_ratio_kernel, dim3(s_blocks, nb), dim3(256), 0, c->stream,
-                                   static_cast<const uint4 *>(c->digest.p), static_cast<const uint16_t *>(CSET(c).draws.p),
-                                   slots, (uint32_t)S, (uint32_t)k, gps, n_sh, (uint32_t)done, shuffles_per_batch, first_batch,
-                                   static_cast<double *>(c->ratios.p));
+                hipLaunchKernelGGL(fk_seat_ratio_kernel, dim3(s_blocks, nb), dim3(256), 0, c->stream, c->digest.p, inv_perm, slots, (uint32_t)S,
+                                   (uint32_t)k, gps, n_sh, (uint32_t)done, shuffles_per_batch, first_batch, c->ratios.p);
             HIPCHK(c, hipGetLastError());
         }
         if (lag) {
-            uint16_t *V = static_cast<uint16_t *>(c->lag_v.p);
+            uint16_t *V = c->lag_v.p;
             const size_t row = (size_t)S; // values per row
             const uint32_t carry = (uint32_t)std::min<uint64_t>(done, L);
-            hipLaunchKernelGGL(fk_lag_values_kernel, dim3((unsigned)(((size_t)n_games * k + 255u) / 256u)), dim3(256), 0, c->stream,
-                               static_cast<const uint32_t *>(c->recs.p), static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)S,
-                               (uint32_t)k, gps, n_games, V + (size_t)L * row);
+            hipLaunchKernelGGL(fk_lag_values_kernel, dim3((unsigned)(((size_t)n_games * k + 255u) / 256u)), dim3(256), 0, c->stream, c->recs.p,
+                               CSET(c).perm.p, slots, (uint32_t)S, (uint32_t)k, gps, n_games, V + (size_t)L * row);
             const uint32_t s_blocks = ((uint32_t)S + 255u) / 256u;
             // enough (strategy block, segment) workgroups to fill the chip, at least 64 rows per segment
             const uint32_t want_seg = std::max<uint32_t>(1u, (2048u + s_blocks - 1u) / s_blocks);
             const uint32_t rows_per_seg = std::max<uint32_t>(64u, (n_sh + want_seg - 1u) / want_seg);
             const uint32_t n_seg = (n_sh + rows_per_seg - 1u) / rows_per_seg;
             hipLaunchKernelGGL(fk_lag_sums_kernel, dim3(s_blocks, n_seg), dim3(256), 0, c->stream, V, (uint32_t)S, L - carry, L, L + n_sh,
-                               rows_per_seg, static_cast<const int32_t *>(c->lag_lags.p), (uint32_t)lag->n_lags,
-                               static_cast<long long *>(c->lag_out.p));
+                               rows_per_seg, c->lag_lags.p, (uint32_t)lag->n_lags, c->lag_out.p);
             HIPCHK(c, hipGetLastError());
             if (lag->m_digest) {
-                rc = launch_matchup_keys(c, (uint32_t)k, static_cast<const uint32_t *>(c->recs.p), static_cast<const uint16_t *>(CSET(c).perm.p),
-                                         slots, (uint32_t)S, gps, n_games, (uint32_t)lag->max_players);
+                rc = launch_matchup_keys(c, (uint32_t)k, c->recs.p, CSET(c).perm.p, slots, (uint32_t)S, gps, n_games, (uint32_t)lag->max_players);
                 if (rc) return rc;
                 const size_t g0 = (size_t)done * gps;
                 HIPCHK(c, hipMemcpyAsync(lag->m_digest + g0, c->m_dig.p, (size_t)n_games * 8, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipMemcpyAsync(lag->m_seats + g0 * k, c->m_seat.p, (size_t)n_games * 2 * k, hipMemcpyDeviceToHost, c->stream));
                 HIPCHK(c, hipMemcpyAsync(lag->m_rounds + g0, c->m_rnd.p, (size_t)n_games * 2, hipMemcpyDeviceToHost, c->stream));
             }
-            uint16_t *edge = static_cast<uint16_t *>(c->lag_edge.p);
+            uint16_t *edge = c->lag_edge.p;
             if (head_filled < edge_rows) { // the first rows of the call's range (they may span chunks shorter than the largest lag)
                 const uint32_t take = std::min<uint32_t>(edge_rows - head_filled, n_sh);
                 HIPCHK(c, hipMemcpyAsync(edge + (size_t)head_filled * row, V + (size_t)L * row, (size_t)take * row * 2, hipMemcpyDeviceToDevice, c->stream));
@@ -2319,7 +2298,6 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         }
         if (!plan.lds_tally) { // result records -> per-batch tallies
             const uint64_t games_per_batch = (uint64_t)shuffles_per_batch * gps;
-            unsigned long long *d_tally = static_cast<unsigned long long *>(c->tally.p);
             if (games_per_batch >= 4096) {
                 // 896 x 22 x 8 B = 154 KiB of LDS: one 1024-thread workgroup per CU, half as many passes over rec0 as two
                 // smaller ones would need
@@ -2334,13 +2312,11 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
                     reduce_configured = c->device;
                 }
                 hipLaunchKernelGGL(fk_tally_reduce_kernel, dim3(ppb * nb, n_slices), dim3(REDUCE_BLOCK), (size_t)slice * RT_COLS * 8, c->stream,
-                                   static_cast<const uint32_t *>(c->rec0.p), static_cast<const uint32_t *>(c->recs.p), n_games, gps,
-                                   (uint32_t)k, (uint32_t)S, static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)done,
-                                   shuffles_per_batch, n_sh, ppb, slice, first_batch, d_tally);
+                                   c->rec0.p, c->recs.p, n_games, gps, (uint32_t)k, (uint32_t)S, CSET(c).perm.p, slots, (uint32_t)done,
+                                   shuffles_per_batch, n_sh, ppb, slice, first_batch, c->tally.p);
             } else {
-                hipLaunchKernelGGL(fk_tally_direct_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
-                                   static_cast<const uint32_t *>(c->recs.p), n_games, gps, (uint32_t)k, (uint32_t)S,
-                                   static_cast<const uint16_t *>(CSET(c).perm.p), slots, (uint32_t)done, shuffles_per_batch, d_tally);
+                hipLaunchKernelGGL(fk_tally_direct_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, c->recs.p, n_games, gps,
+                                   (uint32_t)k, (uint32_t)S, CSET(c).perm.p, slots, (uint32_t)done, shuffles_per_batch, c->tally.p);
             }
             HIPCHK(c, hipGetLastError());
         }
@@ -2349,19 +2325,15 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             // runs beside the next chunk's game kernel.  With a pinned destination (fk_host_alloc) it is one DMA at PCIe rate.
             HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_copy[rb], 0));
             if (columns && k <= 16 && c->columns_by_seat != 0) {
-                hipLaunchKernelGGL(fk_row_columns_seats_kernel, dim3((n_games + 63u) / 64u), dim3(64u * (uint32_t)k), 0, c->stream,
-                                   static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
-                                   scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr, n_games, gps, n_sh, (uint32_t)k, 1u,
-                                   static_cast<const int32_t *>(c->ids.p), static_cast<uint8_t *>(row_buf.p), rows_per_shuffle);
+                hipLaunchKernelGGL(fk_row_columns_seats_kernel, dim3((n_games + 63u) / 64u), dim3(64u * (uint32_t)k), 0, c->stream, CSET(c).state.p,
+                                   c->recs.p, inv, n_games, gps, n_sh, (uint32_t)k, 1u, c->ids.p, row_buf.p, rows_per_shuffle);
                 HIPCHK(c, hipGetLastError());
             } else if (columns) {
-                hipLaunchKernelGGL(fk_row_columns_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream,
-                                   static_cast<const uint32_t *>(CSET(c).state.p), static_cast<const uint32_t *>(c->recs.p),
-                                   scheduled ? static_cast<const uint32_t *>(c->inv.p) : nullptr, n_games, gps, n_sh, (uint32_t)k, 1u,
-                                   static_cast<const int32_t *>(c->ids.p), static_cast<uint8_t *>(row_buf.p), rows_per_shuffle);
+                hipLaunchKernelGGL(fk_row_columns_kernel, dim3((n_games + 255u) / 256u), dim3(256), 0, c->stream, CSET(c).state.p, c->recs.p, inv,
+                                   n_games, gps, n_sh, (uint32_t)k, 1u, c->ids.p, row_buf.p, rows_per_shuffle);
                 HIPCHK(c, hipGetLastError());
             } else {
-                if ((rc = rows_pass(c, sa, scheduled, n_games, gps, n_sh, true, static_cast<uint8_t *>(row_buf.p)))) return rc;
+                if ((rc = rows_pass(c, sa, scheduled, n_games, gps, n_sh, true, row_buf.p))) return rc;
             }
             HIPCHK(c, hipEventRecord(c->ev_rows[rb], c->stream));
             HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_rows[rb], 0));
@@ -2381,8 +2353,8 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
         if ((rc = mirror_reduce(c, sq_n, (uint64_t)std::max<int64_t>(sq->pair_capacity, 0)))) return rc;
     }
     const uint32_t n_rows = (uint32_t)(n_batches * (uint64_t)S);
-    hipLaunchKernelGGL(fk_finalize_tally, dim3((n_rows + 255u) / 256u), dim3(256), 0, c->stream,
-                       static_cast<unsigned long long *>(c->tally.p), n_rows, (uint32_t)S, shuffles_per_batch, n_sh_total, 1u);
+    hipLaunchKernelGGL(fk_finalize_tally, dim3((n_rows + 255u) / 256u), dim3(256), 0, c->stream, c->tally.p, n_rows, (uint32_t)S, shuffles_per_batch,
+                       n_sh_total, 1u);
     HIPCHK(c, hipGetLastError());
     c->last_tally_bytes = tally_bytes; // (fk_tournament_run_stats adds it to the resident accumulator once the call has succeeded)
     HIPCHK(c, hipEventRecord(t1, c->stream));
@@ -2392,50 +2364,49 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
     if (game_seed_bytes + shuffle_seed_bytes) {
         // the fingerprints the row shards carry (game_seed column: ns 102, run_tournament.py:340-350) and their manifest names
         // (shuffle_seed: ns 100 = the same coordinate with game_index 0): with the tally, one host round trip for the launch group
-        const size_t shuffle_at = (game_seed_bytes + 255u) & ~(size_t)255u;
-        if ((rc = ensure(c, c->dbg[5], shuffle_at + shuffle_seed_bytes))) return rc;
-        uint8_t *d_seeds = static_cast<uint8_t *>(c->dbg[5].p);
+        const fkl::Fingerprints fp(game_seed_bytes, shuffle_seed_bytes);
+        if ((rc = ensure(c, c->seeds, fp.bytes))) return rc;
         if (game_seed_bytes) {
             const size_t n = (size_t)n_sh_total * gps;
             hipLaunchKernelGGL(fk_game_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, seed_prefix(102u /* TOURNAMENT_GAME */, root_seed, (uint64_t)k),
-                               shuffle_begin, (uint32_t)n_sh_total, gps, reinterpret_cast<uint32_t *>(d_seeds));
+                               shuffle_begin, (uint32_t)n_sh_total, gps, c->seeds.as<uint32_t>(fp.game_at));
             HIPCHK(c, hipGetLastError());
-            if ((rc = post_d2h(c, call.game_seeds, d_seeds, game_seed_bytes))) return rc;
+            if ((rc = post_d2h(c, call.game_seeds, c->seeds.p + fp.game_at, game_seed_bytes))) return rc;
         }
         if (shuffle_seed_bytes) {
             hipLaunchKernelGGL(fk_game_seed_kernel, dim3((unsigned)((n_sh_total + 255) / 256)), dim3(256), 0, c->stream, seed_prefix(100u /* TOURNAMENT_SHUFFLE */, root_seed, (uint64_t)k),
-                               shuffle_begin, (uint32_t)n_sh_total, 1u, reinterpret_cast<uint32_t *>(d_seeds + shuffle_at));
+                               shuffle_begin, (uint32_t)n_sh_total, 1u, c->seeds.as<uint32_t>(fp.shuffle_at));
             HIPCHK(c, hipGetLastError());
-            if ((rc = post_d2h(c, call.shuffle_seeds, d_seeds + shuffle_at, shuffle_seed_bytes))) return rc;
+            if ((rc = post_d2h(c, call.shuffle_seeds, c->seeds.p + fp.shuffle_at, shuffle_seed_bytes))) return rc;
         }
     }
     if (seat_stats) HIPCHK(c, hipMemcpyAsync(seat_stats, c->stats.p, stats_bytes, hipMemcpyDeviceToHost, c->stream));
     if (seat_ratios) HIPCHK(c, hipMemcpyAsync(seat_ratios, c->ratios.p, ratio_bytes, hipMemcpyDeviceToHost, c->stream));
     int64_t sq_pairs = 0;
-    if (sq) HIPCHK(c, hipMemcpyAsync(sq->counts, c->sa_counts.p, sq_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (sq_n) HIPCHK(c, hipMemcpyAsync(&sq_pairs, c->sa[15].p, 8, hipMemcpyDeviceToHost, c->stream));
+    if (sq) HIPCHK(c, hipMemcpyAsync(sq->counts, c->sa.counts.p, sq_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (sq_n) HIPCHK(c, hipMemcpyAsync(&sq_pairs, c->sa.pair_count.p, 8, hipMemcpyDeviceToHost, c->stream));
     int64_t g_spilled = 0;
     if (gst) {
-        const uint8_t *o = static_cast<const uint8_t *>(c->g_out.p);
-        const std::pair<int64_t *, std::pair<size_t, size_t>> parts[] = {
-            {gst->s_counts, {g_sc, (size_t)S * fkg::N_COUNTS}}, {gst->s_rounds, {g_sr, (size_t)S * g_rb}}, {gst->s_runner, {g_sru, (size_t)S * g_mb}},
-            {gst->s_spread, {g_ssp, (size_t)S * g_mb}}, {gst->g_counts, {g_gc, fkg::N_COUNTS}}, {gst->g_rounds, {g_gr, g_rb}},
-            {gst->g_runner, {g_gru, g_mb}}, {&g_spilled, {g_cnt, 1}}};
+        const ull *o = c->g_out.as<ull>();
+        const std::pair<int64_t *, std::pair<size_t, size_t>> parts[] = { // every part ends where the next begins
+            {gst->s_counts, {go.s_counts, go.s_rounds}}, {gst->s_rounds, {go.s_rounds, go.s_runner}}, {gst->s_runner, {go.s_runner, go.s_spread}},
+            {gst->s_spread, {go.s_spread, go.g_counts}}, {gst->g_counts, {go.g_counts, go.g_rounds}}, {gst->g_rounds, {go.g_rounds, go.g_runner}},
+            {gst->g_runner, {go.g_runner, go.spill_count}}, {&g_spilled, {go.spill_count, go.n_u64}}};
         for (const auto &pt : parts)
-            HIPCHK(c, hipMemcpyAsync(pt.first, o + pt.second.first * 8, pt.second.second * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(pt.first, o + pt.second.first, (pt.second.second - pt.second.first) * 8, hipMemcpyDeviceToHost, c->stream));
     }
     int64_t r_events = 0;
     if (rare) {
-        const uint8_t *o = static_cast<const uint8_t *>(c->r_out.p);
-        HIPCHK(c, hipMemcpyAsync(rare->s_second, o, r_gs * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(rare->g_second, o + r_gs * 8, (size_t)r_sb * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(&r_events, o + r_tot * 8, 8, hipMemcpyDeviceToHost, c->stream));
+        const ull *o = c->r_out.p;
+        HIPCHK(c, hipMemcpyAsync(rare->s_second, o + ro.s_second, ro.g_second * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rare->g_second, o + ro.g_second, (size_t)r_sb * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&r_events, o + ro.total, 8, hipMemcpyDeviceToHost, c->stream));
     }
     if (lag) {
-        const size_t edge_bytes = (size_t)edge_rows * (size_t)S * 2;
+        const size_t edge_cells = (size_t)edge_rows * (size_t)S, edge_bytes = edge_cells * 2;
         HIPCHK(c, hipMemcpyAsync(lag->sums, c->lag_out.p, lag_sum_bytes, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipMemcpyAsync(lag->head, c->lag_edge.p, edge_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(lag->tail, static_cast<uint8_t *>(c->lag_edge.p) + edge_bytes, edge_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(lag->tail, c->lag_edge.p + edge_cells, edge_bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     deliver_mail(c);
@@ -2455,7 +2426,7 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             return fail(c, FK_ERR_ARG, "game statistics: the spill list needs %lld entries, spill_capacity is %lld", (long long)g_spilled,
                         (long long)gst->spill_capacity);
         if (g_spilled)
-            HIPCHK(c, hipMemcpy(gst->spill, static_cast<const unsigned long long *>(c->g_out.p) + g_u64, (size_t)g_spilled * 12, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(gst->spill, c->g_out.p + go.spill_at(), (size_t)g_spilled * 12, hipMemcpyDeviceToHost));
     }
     if (rare) { // the flagged games, in (shuffle, game) order
         if (r_events > rare->event_capacity)
@@ -2472,8 +2443,8 @@ static int tournament_run_impl(fk_ctx *c, const TournamentCall &call) {
             return fail(c, FK_ERR_ARG, "mirrored pairs: the pair list needs %lld rows, pair_capacity is %lld", (long long)sq_pairs,
                         (long long)sq->pair_capacity);
         if (sq_pairs) {
-            HIPCHK(c, hipMemcpy(sq->pair_index, c->sa[13].p, (size_t)sq_pairs * 4, hipMemcpyDeviceToHost));
-            HIPCHK(c, hipMemcpy(sq->pair_sums, c->sa[14].p, (size_t)sq_pairs * fksa::PAIR_COLS * 8, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(sq->pair_index, c->sa.pair_rank.p, (size_t)sq_pairs * 4, hipMemcpyDeviceToHost));
+            HIPCHK(c, hipMemcpy(sq->pair_sums, c->sa.pair_sums.p, (size_t)sq_pairs * fksa::PAIR_COLS * 8, hipMemcpyDeviceToHost));
             std::vector<uint16_t> index_of((size_t)S);
             for (int32_t i = 0; i < S; ++i) index_of[sq->id_rank[i]] = (uint16_t)i;
             for (int64_t i = 0; i < 2 * sq_pairs; ++i) sq->pair_index[i] = index_of[sq->pair_index[i]];
@@ -2503,13 +2474,12 @@ static int tournament_call(fk_ctx *c, const TournamentCall &call) {
         // the overflow that is replayed above included, must not have added anything (shape changes start a new accumulator)
         const size_t tally_bytes = c->last_tally_bytes, n_el = tally_bytes / sizeof(int64_t);
         if (c->acc_n != n_el) {
-            rc = ensure(c, c->acc, tally_bytes);
+            rc = ensure(c, c->acc, n_el);
             if (rc) return rc;
             HIPCHK(c, hipMemsetAsync(c->acc.p, 0, tally_bytes, c->stream));
             c->acc_n = n_el;
         }
-        hipLaunchKernelGGL(fk_add_i64_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, c->stream,
-                           static_cast<unsigned long long *>(c->acc.p), static_cast<const unsigned long long *>(c->tally.p), n_el);
+        hipLaunchKernelGGL(fk_add_i64_kernel, dim3((unsigned)((n_el + 255) / 256)), dim3(256), 0, c->stream, c->acc.p, c->tally.p, n_el);
         HIPCHK(c, hipGetLastError());
     }
     return rc;
@@ -2726,12 +2696,7 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     if (n_games == 0) return FK_OK;
     if ((rc = upload_strategies(c, table, S))) return rc;
     const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
-    rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n_games);
-    if (rc) return rc;
-    rc = ensure(c, c->seatlist, sizeof(int32_t) * (size_t)n_games * k);
-    if (rc) return rc;
-    rc = ensure(c, c->rows, (size_t)n_games * row_bytes);
-    if (rc) return rc;
+    if ((rc = ensure_all(c, c->coords, (size_t)n_games, c->seatlist, (size_t)n_games * k, c->rows, (size_t)n_games * row_bytes))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n_games, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy, sizeof(int32_t) * (size_t)n_games * k, hipMemcpyHostToDevice, c->stream));
 
@@ -2741,13 +2706,13 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
                     target_score, 50 * LEAN_MAX_TARGET50, (int)k);
 
     SeedArgs sa{};
-    sa.coords = static_cast<const fk_coord *>(c->coords.p);
-    sa.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+    sa.coords = c->coords.p;
+    sa.seat_strategy = c->seatlist.p;
     sa.k = (uint32_t)k;
     sa.n_games = (uint32_t)n_games;
 
     PlayArgs pa = table_args(c, target_score, max_rounds);
-    pa.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+    pa.seat_strategy = c->seatlist.p;
     pa.mode = MODE_LIST;
     pa.n_games = (uint32_t)n_games;
     pa.gps = 1;
@@ -2756,7 +2721,7 @@ int fk_play_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_s
     pa.S = (uint32_t)S;
     rc = run_chunk(c, sa, pa, plan, true, true, true, 0, "list");
     if (rc) return rc;
-    rc = rows_pass(c, sa, false, (uint32_t)n_games, 1, 1, false, static_cast<uint8_t *>(c->rows.p));
+    rc = rows_pass(c, sa, false, (uint32_t)n_games, 1, 1, false, c->rows.p);
     if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(rows, c->rows.p, (size_t)n_games * row_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2784,49 +2749,43 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
     const std::vector<int2> packed = strategies_in_points(table, S);
     const uint32_t n = (uint32_t)n_games, n_pad = (n + fktr::TR_BLOCK - 1u) / fktr::TR_BLOCK * fktr::TR_BLOCK;
     const size_t row_bytes = sizeof(fk_row_hdr) + sizeof(fk_seat) * (size_t)k;
-    const size_t sz[6] = {sizeof(int2) * (size_t)S, (size_t)k * fktr::TR_FIELDS * n_pad * 4, 8 * ((size_t)n + 1), 8 * ((size_t)n + 1), (size_t)n * row_bytes, 8};
-    for (int i = 0; i < 6; ++i)
-        if ((rc = ensure(c, c->tr[i], sz[i]))) return rc;
-    if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
-    if ((rc = ensure(c, c->seatlist, sizeof(int32_t) * (size_t)n * k))) return rc;
+    TraceBufs &t = c->tr;
+    const size_t n1 = (size_t)n + 1;
+    if ((rc = ensure_all(c, t.strat, (size_t)S, t.ws, (size_t)k * fktr::TR_FIELDS * n_pad, t.counts, n1, t.begin, n1, t.rows, (size_t)n * row_bytes, t.err, 1,
+                         c->coords, (size_t)n, c->seatlist, (size_t)n * k)))
+        return rc;
     const hipStream_t st = c->stream;
     HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy, sizeof(int32_t) * (size_t)n * k, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(c->tr[0].p, packed.data(), sz[0], hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(c->tr[2].p, 0, sz[2], st));    // (the scan's last input, behind the games' counts)
-    HIPCHK(c, hipMemsetAsync(c->tr[5].p, 0xff, sz[5], st)); // TR_NO_ERROR
+    HIPCHK(c, hipMemcpyAsync(t.strat.p, packed.data(), sizeof(int2) * (size_t)S, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(t.counts.p, 0, 8 * n1, st)); // (the scan's last input, behind the games' counts)
+    HIPCHK(c, hipMemsetAsync(t.err.p, 0xff, 8, st));      // TR_NO_ERROR
     fktr::TraceArgs a{};
-    a.coords = static_cast<const fk_coord *>(c->coords.p);
-    a.strat = static_cast<const int2 *>(c->tr[0].p);
-    a.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+    a.coords = c->coords.p;
+    a.strat = t.strat.p;
+    a.seat_strategy = c->seatlist.p;
     a.n_games = n;
     a.n_pad = n_pad;
     a.k = (uint32_t)k;
     a.target_score = target_score;
     a.max_rounds = (uint32_t)max_rounds;
-    a.ws = static_cast<uint32_t *>(c->tr[1].p);
-    a.rows = static_cast<uint8_t *>(c->tr[4].p);
-    a.counts = static_cast<long long *>(c->tr[2].p);
-    a.begin = static_cast<const long long *>(c->tr[3].p);
-    a.err = static_cast<unsigned long long *>(c->tr[5].p);
+    a.ws = t.ws.p;
+    a.rows = t.rows.p;
+    a.counts = t.counts.p;
+    a.begin = t.begin.p;
+    a.err = t.err.p;
     const dim3 grid(n_pad / fktr::TR_BLOCK), block(fktr::TR_BLOCK);
     {
-        Timer t(c, &c->timing.play_ms, SLOT_PLAY);
+        Timer tm(c, &c->timing.play_ms, SLOT_PLAY);
         hipLaunchKernelGGL(fktr::fk_trace_kernel<false>, grid, block, 0, st, a);
         HIPCHK(c, hipGetLastError());
-        t.stop();
+        tm.stop();
     }
-    {
-        size_t tb = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, a.counts, static_cast<long long *>(c->tr[3].p), (int)(n + 1u), st));
-        if ((rc = ensure(c, c->tr[7], std::max<size_t>(tb, 1)))) return rc;
-        tb = c->tr[7].cap;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->tr[7].p, tb, a.counts, static_cast<long long *>(c->tr[3].p), (int)(n + 1u), st));
-    }
+    FK_CUB(hipcub::DeviceScan::ExclusiveSum, a.counts, t.begin.p, (int)(n + 1u), st);
     unsigned long long err = fktr::TR_NO_ERROR;
-    HIPCHK(c, hipMemcpyAsync(&err, c->tr[5].p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(event_begin, c->tr[3].p, sz[3], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(rows, c->tr[4].p, sz[4], hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&err, t.err.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(event_begin, t.begin.p, 8 * n1, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(rows, t.rows.p, (size_t)n * row_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, collect_timers(c));
     c->timing.play_launches = 1;
@@ -2841,15 +2800,16 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
         return fail(c, FK_ERR_ARG, "event_capacity %lld is too small: the games roll %lld times (call again with that capacity)",
                     (long long)event_capacity, (long long)total);
     if (total == 0) return FK_OK;
-    if ((rc = ensure(c, c->tr[6], sizeof(fk_roll_event) * (size_t)total))) return rc;
-    a.events = static_cast<uint4 *>(c->tr[6].p);
+    static_assert(sizeof(fk_roll_event) == sizeof(uint4), "the trace kernel stores an event as one uint4");
+    if ((rc = ensure(c, t.events, (size_t)total))) return rc;
+    a.events = t.events.p;
     {
-        Timer t(c, &c->timing.play_ms, SLOT_PLAY);
+        Timer tm(c, &c->timing.play_ms, SLOT_PLAY);
         hipLaunchKernelGGL(fktr::fk_trace_kernel<true>, grid, block, 0, st, a);
         HIPCHK(c, hipGetLastError());
-        t.stop();
+        tm.stop();
     }
-    HIPCHK(c, hipMemcpyAsync(events, c->tr[6].p, sizeof(fk_roll_event) * (size_t)total, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(events, t.events.p, sizeof(fk_roll_event) * (size_t)total, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, collect_timers(c));
     c->timing.play_launches = 2;
@@ -2862,7 +2822,7 @@ int fk_trace_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk_
 // last chunk.  Nothing of the call stays in the context but device buffers; a failed call stores nothing in the caller's tables.
 struct CensusCall {
     size_t n_u64[4]; // elements of roll_cells, strategy_dice, strategy_turns, turn_hist
-    size_t off[5];   // their offsets in cn[2] (u64 units, the layout of fkcn::CensusArgs::tables); [4] = the error word
+    size_t off[5];   // their offsets in cn.tables (u64 units, the layout of fkcn::CensusArgs::tables); [4] = the error word
 };
 
 static int census_check_out(fk_ctx *c, const fk_census *out) {
@@ -2887,21 +2847,20 @@ static int census_begin(fk_ctx *c, const fk_strategy *table, int32_t S, int32_t 
     cc.off[2] = fkcn::turns_offset((uint32_t)S);
     cc.off[3] = fkcn::hist_offset((uint32_t)S);
     cc.off[4] = fkcn::err_offset((uint32_t)S, (uint32_t)out->turn_bins);
-    if ((rc = ensure(c, c->cn[0], sizeof(int2) * (size_t)S))) return rc;
-    if ((rc = ensure(c, c->cn[2], 8 * (cc.off[4] + 1)))) return rc;
+    if ((rc = ensure_all(c, c->cn.strat, (size_t)S, c->cn.tables, cc.off[4] + 1))) return rc;
     const hipStream_t st = c->stream;
-    HIPCHK(c, hipMemcpyAsync(c->cn[0].p, packed.data(), sizeof(int2) * (size_t)S, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(c->cn[2].p, 0, 8 * cc.off[4], st));
-    HIPCHK(c, hipMemsetAsync(static_cast<unsigned long long *>(c->cn[2].p) + cc.off[4], 0xff, 8, st)); // TR_NO_ERROR
+    HIPCHK(c, hipMemcpyAsync(c->cn.strat.p, packed.data(), sizeof(int2) * (size_t)S, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->cn.tables.p, 0, 8 * cc.off[4], st));
+    HIPCHK(c, hipMemsetAsync(c->cn.tables.p + cc.off[4], 0xff, 8, st)); // TR_NO_ERROR
     HIPCHK(c, hipStreamSynchronize(st)); // `packed` goes out of scope
     a = fkcn::CensusArgs{};
-    a.strat = static_cast<const int2 *>(c->cn[0].p);
+    a.strat = c->cn.strat.p;
     a.k = (uint32_t)k;
     a.S = (uint32_t)S;
     a.target_score = target_score;
     a.max_rounds = (uint32_t)max_rounds;
     a.turn_bins = (uint32_t)out->turn_bins;
-    a.tables = static_cast<unsigned long long *>(c->cn[2].p);
+    a.tables = c->cn.tables.p;
     return FK_OK;
 }
 
@@ -2918,8 +2877,8 @@ static uint64_t census_chunk_games(fk_ctx *c, int32_t k) {
 static int census_chunk(fk_ctx *c, fkcn::CensusArgs &a, bool list, const char *what) {
     int rc;
     a.n_pad = (a.n_games + fkcn::CN_BLOCK - 1u) / fkcn::CN_BLOCK * fkcn::CN_BLOCK;
-    if ((rc = ensure(c, c->cn[1], (size_t)a.k * fkcn::CN_FIELDS * a.n_pad * 4))) return rc;
-    a.ws = static_cast<uint32_t *>(c->cn[1].p);
+    if ((rc = ensure(c, c->cn.ws, (size_t)a.k * fkcn::CN_FIELDS * a.n_pad))) return rc;
+    a.ws = c->cn.ws.p;
     const dim3 grid(a.n_pad / fkcn::CN_BLOCK), block(fkcn::CN_BLOCK);
     {
         Timer t(c, &c->timing.play_ms, SLOT_PLAY);
@@ -2942,7 +2901,7 @@ static int census_chunk(fk_ctx *c, fkcn::CensusArgs &a, bool list, const char *w
 }
 
 static int census_end(fk_ctx *c, const CensusCall &cc, const fk_census *out) {
-    const unsigned long long *t = static_cast<const unsigned long long *>(c->cn[2].p);
+    const ull *t = c->cn.tables.p;
     uint64_t *dst[4] = {out->roll_cells, out->strategy_dice, out->strategy_turns, out->turn_hist};
     for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemcpyAsync(dst[i], t + cc.off[i], 8 * cc.n_u64[i], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2965,12 +2924,11 @@ int fk_census_games(fk_ctx *c, const fk_coord *coords, int64_t n_games, const fk
     const uint64_t chunk = census_chunk_games(c, k);
     for (uint64_t done = 0; done < (uint64_t)n_games; done += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, (uint64_t)n_games - done);
-        if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
-        if ((rc = ensure(c, c->seatlist, sizeof(int32_t) * (size_t)n * k))) return rc;
+        if ((rc = ensure_all(c, c->coords, (size_t)n, c->seatlist, (size_t)n * k))) return rc;
         HIPCHK(c, hipMemcpyAsync(c->coords.p, coords + done, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->seatlist.p, seat_strategy + done * (uint64_t)k, sizeof(int32_t) * (size_t)n * k, hipMemcpyHostToDevice, c->stream));
-        a.coords = static_cast<const fk_coord *>(c->coords.p);
-        a.seat_strategy = static_cast<const int32_t *>(c->seatlist.p);
+        a.coords = c->coords.p;
+        a.seat_strategy = c->seatlist.p;
         a.n_games = n;
         a.game_base = done;
         if ((rc = census_chunk(c, a, true, "census"))) return rc;
@@ -3009,16 +2967,16 @@ int fk_tournament_run_census(fk_ctx *c, const fk_strategy *strategies, int32_t S
         HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
         const ChunkDesc d{c->table_epoch, root_seed, sh0, n_sh, (uint32_t)S, (uint32_t)k, 0u, 0u, slots};
         const uint32_t perm_blocks = (n_sh + slots - 1u) / slots;
-        if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2))) return rc;
+        if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots))) return rc;
         if ((rc = launch_perm_kernels(c, cs, c->stream, d))) return rc;
         a.coords = nullptr;
         a.seat_strategy = nullptr;
-        a.perm_T = static_cast<const uint16_t *>(cs.perm.p);
+        a.perm_T = cs.perm.p;
         a.perm_slots = slots;
         a.gps = gps;
         a.root_seed = root_seed;
         a.shuffle0 = sh0;
-        a.ov = static_cast<const DevOverride *>(c->ov.p);
+        a.ov = c->ov.p;
         a.n_games = n_sh * gps;
         a.game_base = done * gps;
         if ((rc = census_chunk(c, a, false, "census"))) return rc;
@@ -3075,7 +3033,7 @@ static int h2h_run_blocks_impl(fk_ctx *c, fk_h2h_block *blocks, int64_t n_blocks
         return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
                     50 * LEAN_MAX_TARGET50);
     const uint64_t max_launch = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)workspace_budget(c) / (game_workspace_bytes(2, plan.shape().gs, false, false) + 8), 1u << 30));
-    rc = ensure(c, c->block_out, (size_t)n_blocks * 4 * 8);
+    rc = ensure(c, c->block_out, (size_t)n_blocks * 4);
     if (rc) return rc;
 
     // A GENERATION plays, for every block that still needs games, exactly min(stop - attempted, target - completed) attempts —
@@ -3208,29 +3166,27 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     const uint64_t window_pairs = std::min<uint64_t>((uint64_t)c->rr_window_blocks / 2u, n_pairs_call);
     const uint32_t max_rows = (uint32_t)(window_pairs * 2u);
     const uint64_t max_launch = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)workspace_budget(c) / (game_workspace_bytes(2, plan.shape().gs, false, false) + 8), 1u << 30));
-    const size_t sizes[9] = {sizeof(uint2) * (size_t)n, (size_t)n, (size_t)max_rows * RR_STATE * 4, ((size_t)max_rows + 1) * 8, ((size_t)max_rows + 1) * 8,
-                             ((size_t)max_rows + 1) * 4, ((size_t)max_rows + 1) * 4, (size_t)max_rows * 4, sizeof(RrError)};
+    RoundRobinBufs &r = c->rr;
+    const size_t rows1 = (size_t)max_rows + 1;
     int rc = FK_OK;
-    for (int b = 0; b < 9; ++b)
-        if ((rc = ensure(c, c->rr[b], sizes[b]))) return rc;
-    if (summary && (rc = ensure(c, c->rr[11], (size_t)n * RR_COLS * 8))) return rc;
-    if ((rc = ensure(c, c->strat, sizeof(uint2) * 2 * (size_t)max_rows))) return rc;
-    if ((rc = ensure(c, c->slow, 2 * (size_t)max_rows))) return rc;
-    if ((rc = ensure(c, c->block_out, (size_t)max_rows * 4 * 8))) return rc;
-    uint32_t *d_state = static_cast<uint32_t *>(c->rr[2].p);
-    unsigned long long *d_need = static_cast<unsigned long long *>(c->rr[3].p), *d_off = static_cast<unsigned long long *>(c->rr[4].p);
-    uint32_t *d_flag = static_cast<uint32_t *>(c->rr[5].p), *d_aidx = static_cast<uint32_t *>(c->rr[6].p), *d_act = static_cast<uint32_t *>(c->rr[7].p);
-    RrError *d_err = static_cast<RrError *>(c->rr[8].p);
-    {
-        size_t t64 = 0, t32 = 0;
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t64, d_need, d_off, (int)(max_rows + 1u), c->stream));
-        HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(nullptr, t32, d_flag, d_aidx, (int)(max_rows + 1u), c->stream));
-        if ((rc = ensure(c, c->rr[10], std::max<size_t>(std::max(t64, t32), 1)))) return rc;
+    if ((rc = ensure_all(c, r.table, (size_t)n, r.patience, (size_t)n, r.state, (size_t)max_rows * RR_STATE, r.need, rows1, r.off, rows1, r.flag, rows1,
+                         r.aidx, rows1, r.act, (size_t)max_rows, r.err, 1)))
+        return rc;
+    if (summary && (rc = ensure(c, r.summary, (size_t)n * RR_COLS))) return rc;
+    if ((rc = ensure_all(c, c->strat, 2 * (size_t)max_rows, c->slow, 2 * (size_t)max_rows, c->block_out, (size_t)max_rows * 4))) return rc;
+    uint32_t *d_state = r.state.p, *d_flag = r.flag.p, *d_aidx = r.aidx.p, *d_act = r.act.p;
+    ull *d_need = r.need.p, *d_off = r.off.p;
+    RrError *d_err = r.err.p;
+    { // the scratch of both scans of a generation, sized once for the largest window: no size query inside the window loop
+        size_t need = 1;
+        FK_CUB_NEED(need, hipcub::DeviceScan::ExclusiveSum, d_need, d_off, (int)(max_rows + 1u), c->stream);
+        FK_CUB_NEED(need, hipcub::DeviceScan::ExclusiveSum, d_flag, d_aidx, (int)(max_rows + 1u), c->stream);
+        if ((rc = ensure(c, c->cub, need))) return rc;
     }
-    HIPCHK(c, hipMemcpyAsync(c->rr[0].p, packed.data(), sizes[0], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->rr[1].p, patience.data(), sizes[1], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.table.p, packed.data(), sizeof(uint2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(r.patience.p, patience.data(), (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_err, 0, sizeof(RrError), c->stream));
-    if (summary) HIPCHK(c, hipMemsetAsync(c->rr[11].p, 0, (size_t)n * RR_COLS * 8, c->stream));
+    if (summary) HIPCHK(c, hipMemsetAsync(r.summary.p, 0, (size_t)n * RR_COLS * 8, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream)); // (the host vectors are pageable)
 
     const bool pipelined = c->pipeline != 0;
@@ -3238,18 +3194,14 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     for (uint64_t pair0 = pair_begin; pair0 < pair_end; pair0 += window_pairs) {
         const uint32_t n_pairs = (uint32_t)std::min<uint64_t>(window_pairs, pair_end - pair0), n_rows = 2u * n_pairs;
         const dim3 rows_grid((n_rows + 1u + 255u) / 256u), b256(256);
-        hipLaunchKernelGGL(fk_rr_window_kernel, rows_grid, b256, 0, c->stream, static_cast<const uint2 *>(c->rr[0].p),
-                           static_cast<const uint8_t *>(c->rr[1].p), (uint32_t)n, pair0, n_rows, static_cast<uint2 *>(c->strat.p),
-                           static_cast<uint8_t *>(c->slow.p));
+        hipLaunchKernelGGL(fk_rr_window_kernel, rows_grid, b256, 0, c->stream, r.table.p, r.patience.p, (uint32_t)n, pair0, n_rows, c->strat.p, c->slow.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n_rows * RR_STATE * 4, c->stream)); // every block starts fresh
         while (true) { // generations
             hipLaunchKernelGGL(fk_rr_need_kernel, rows_grid, b256, 0, c->stream, d_state, n_rows, (uint32_t)target, (uint32_t)max_attempts, d_need, d_flag);
             HIPCHK(c, hipGetLastError());
-            size_t tb = c->rr[10].cap;
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->rr[10].p, tb, d_need, d_off, (int)(n_rows + 1u), c->stream));
-            tb = c->rr[10].cap;
-            HIPCHK(c, hipcub::DeviceScan::ExclusiveSum(c->rr[10].p, tb, d_flag, d_aidx, (int)(n_rows + 1u), c->stream));
+            FK_CUB_SIZED(hipcub::DeviceScan::ExclusiveSum, d_need, d_off, (int)(n_rows + 1u), c->stream);
+            FK_CUB_SIZED(hipcub::DeviceScan::ExclusiveSum, d_flag, d_aidx, (int)(n_rows + 1u), c->stream);
             hipLaunchKernelGGL(fk_rr_compact_kernel, rows_grid, b256, 0, c->stream, d_flag, d_aidx, n_rows, d_act);
             HIPCHK(c, hipGetLastError());
             unsigned long long total = 0;
@@ -3267,12 +3219,12 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
                 return fail(c, FK_ERR_ARG, "a generation of %llu games needs more than 2^20 launches of %llu games: raise chunk_bytes or lower rr_window_blocks",
                             total, (unsigned long long)max_launch);
             const uint32_t n_passes = (uint32_t)n_passes64;
-            if ((rc = ensure(c, c->rr[9], (size_t)n_passes * 8))) return rc;
+            if ((rc = ensure(c, r.bounds, (size_t)n_passes * 2))) return rc;
             hipLaunchKernelGGL(fk_rr_pass_bounds_kernel, dim3((n_passes + 255u) / 256u), b256, 0, c->stream, d_off, d_need, d_act, n_act, total,
-                               (unsigned long long)max_launch, n_passes, static_cast<uint32_t *>(c->rr[9].p));
+                               (unsigned long long)max_launch, n_passes, r.bounds.p);
             HIPCHK(c, hipGetLastError());
             bounds.resize((size_t)n_passes * 2);
-            HIPCHK(c, hipMemcpyAsync(bounds.data(), c->rr[9].p, (size_t)n_passes * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(bounds.data(), r.bounds.p, (size_t)n_passes * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipMemsetAsync(c->block_out.p, 0, (size_t)n_rows * 4 * 8, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             auto pass_games = [&](size_t i) { return (uint32_t)(std::min<uint64_t>(total, (uint64_t)(i + 1) * max_launch) - (uint64_t)i * max_launch); };
@@ -3290,13 +3242,12 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
                 return FK_OK;
             };
             if ((rc = play_block_passes(c, n_passes, plan, root_seed, n_rows * 2u, target_score, max_rounds, pipelined, pass_blocks, nullptr))) return rc;
-            hipLaunchKernelGGL(fk_rr_apply_kernel, rows_grid, b256, 0, c->stream, d_state, d_need, static_cast<const unsigned long long *>(c->block_out.p),
-                               n_rows, d_err);
+            hipLaunchKernelGGL(fk_rr_apply_kernel, rows_grid, b256, 0, c->stream, d_state, d_need, c->block_out.p, n_rows, d_err);
             HIPCHK(c, hipGetLastError());
         }
         if (summary) {
             hipLaunchKernelGGL(fk_rr_summary_kernel, dim3((n_pairs + 255u) / 256u), b256, 0, c->stream, d_state, (uint32_t)n, pair0, n_pairs,
-                               (uint32_t)target, static_cast<unsigned long long *>(c->rr[11].p));
+                               (uint32_t)target, r.summary.p);
             HIPCHK(c, hipGetLastError());
         }
         HIPCHK(c, hipMemcpyAsync(block_state + (size_t)(pair0 - pair_begin) * 2 * RR_STATE, d_state, (size_t)n_rows * RR_STATE * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3304,7 +3255,7 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     }
     if (summary) { // added to the caller's buffer only when the whole call has succeeded
         std::vector<int64_t> add((size_t)n * RR_COLS);
-        HIPCHK(c, hipMemcpy(add.data(), c->rr[11].p, add.size() * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(add.data(), r.summary.p, add.size() * 8, hipMemcpyDeviceToHost));
         for (size_t i = 0; i < add.size(); ++i) summary[i] += add[i];
     }
     c->timing.total_ms = c->timing.seed_ms + c->timing.play_ms;
@@ -3582,19 +3533,16 @@ int fk_debug_score(fk_ctx *c, int64_t n, const uint8_t *faces, const int32_t *le
     std::vector<uint2> packed((size_t)n);
     for (int64_t i = 0; i < n; ++i) packed[(size_t)i] = pack_strategy(strategy[i]);
     const size_t sz[5] = {(size_t)n * 6, (size_t)n * 4, (size_t)n * 4, (size_t)n * 8, (size_t)n * 20};
-    for (int i = 0; i < 5; ++i)
-        if ((rc = ensure(c, c->dbg[i], sz[i]))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->dbg[0].p, faces, sz[0], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dbg[1].p, len, sz[1], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dbg[2].p, pre, sz[2], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dbg[3].p, packed.data(), sz[3], hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(fk_dbg_score_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n,
-                       static_cast<const uint8_t *>(c->dbg[0].p), static_cast<const int32_t *>(c->dbg[1].p),
-                       static_cast<const int32_t *>(c->dbg[2].p), static_cast<const uint2 *>(c->dbg[3].p),
-                       static_cast<const uint32_t *>(c->score_lut.p), static_cast<const uint8_t *>(c->discard_lut.p),
-                       static_cast<int32_t *>(c->dbg[4].p));
+    if ((rc = ensure_all(c, c->dbg.a, sz[0], c->dbg.b, sz[1], c->dbg.c, sz[2], c->dbg.d, sz[3], c->dbg.e, sz[4]))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dbg.a.p, faces, sz[0], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dbg.b.p, len, sz[1], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dbg.c.p, pre, sz[2], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dbg.d.p, packed.data(), sz[3], hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fk_dbg_score_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, c->dbg.a.as<const uint8_t>(),
+                       c->dbg.b.as<const int32_t>(), c->dbg.c.as<const int32_t>(), c->dbg.d.as<const uint2>(), c->score_lut.p, c->discard_lut.p,
+                       c->dbg.e.as<int32_t>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->dbg[4].p, sz[4], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->dbg.e.p, sz[4], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3611,15 +3559,13 @@ int fk_debug_should_continue(fk_ctx *c, int64_t n, const int32_t *args, const fk
     std::vector<uint2> packed((size_t)n);
     for (int64_t i = 0; i < n; ++i) packed[(size_t)i] = pack_strategy(strategy[i]);
     const size_t sz[3] = {(size_t)n * 24, (size_t)n * 8, (size_t)n * 4};
-    for (int i = 0; i < 3; ++i)
-        if ((rc = ensure(c, c->dbg[i], sz[i]))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->dbg[0].p, args, sz[0], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dbg[1].p, packed.data(), sz[1], hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(fk_dbg_continue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n,
-                       static_cast<const int32_t *>(c->dbg[0].p), static_cast<const uint2 *>(c->dbg[1].p),
-                       static_cast<int32_t *>(c->dbg[2].p));
+    if ((rc = ensure_all(c, c->dbg.a, sz[0], c->dbg.b, sz[1], c->dbg.c, sz[2]))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dbg.a.p, args, sz[0], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dbg.b.p, packed.data(), sz[1], hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fk_dbg_continue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, c->dbg.a.as<const int32_t>(),
+                       c->dbg.b.as<const uint2>(), c->dbg.c.as<int32_t>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->dbg[2].p, sz[2], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->dbg.c.p, sz[2], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3638,41 +3584,36 @@ static int debug_dice_common(fk_ctx *c, int64_t n, const fk_coord *coords, const
     const uint4 *d_seeds = nullptr, *d_incs = nullptr;
     const uint64_t *d_state = nullptr;
     if (coords) {
-        if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
-        if ((rc = ensure(c, CSET(c).state, (size_t)n * 16))) return rc;
-        if ((rc = ensure(c, CSET(c).inc, (size_t)n * 16))) return rc;
+        if ((rc = ensure_all(c, c->coords, (size_t)n, CSET(c).state, (size_t)n * 4, CSET(c).inc, (size_t)n))) return rc;
         // one 1-seat "game" per coordinate; the seed kernel offsets the seat stream by coords[i].seat_index
         HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
         SeedArgs sa{};
-        sa.coords = static_cast<const fk_coord *>(c->coords.p);
+        sa.coords = c->coords.p;
         sa.k = 1;
         sa.n_games = (uint32_t)n;
-        sa.state = static_cast<uint32_t *>(CSET(c).state.p);
+        sa.state = CSET(c).state.p;
         sa.state_dw = 4;
-        sa.inc = static_cast<uint4 *>(CSET(c).inc.p);
+        sa.inc = CSET(c).inc.p;
         hipLaunchKernelGGL(fk_seed_kernel, dim3((unsigned)((n + SEED_BLOCK - 1) / SEED_BLOCK)), dim3(SEED_BLOCK), 0, c->stream, sa);
         HIPCHK(c, hipGetLastError());
-        d_seeds = static_cast<const uint4 *>(CSET(c).state.p);
+        d_seeds = reinterpret_cast<const uint4 *>(CSET(c).state.p);
         d_incs = sa.inc;
     } else {
         if (!state) return fail(c, FK_ERR_ARG, "state is required");
-        if ((rc = ensure(c, c->dbg[0], (size_t)n * 48))) return rc;
-        HIPCHK(c, hipMemcpyAsync(c->dbg[0].p, state, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-        d_state = static_cast<const uint64_t *>(c->dbg[0].p);
+        if ((rc = ensure(c, c->dbg.a, (size_t)n * 48))) return rc;
+        HIPCHK(c, hipMemcpyAsync(c->dbg.a.p, state, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+        d_state = c->dbg.a.as<const uint64_t>();
     }
-    if ((rc = ensure(c, c->dbg[1], (size_t)n_calls * 4 + 4))) return rc;
-    if ((rc = ensure(c, c->dbg[2], (size_t)n * std::max(total, 1)))) return rc;
-    if ((rc = ensure(c, c->dbg[3], (size_t)n * 32))) return rc;
-    if ((rc = ensure(c, c->dbg[4], (size_t)n * 48))) return rc;
-    if (n_calls) HIPCHK(c, hipMemcpyAsync(c->dbg[1].p, sizes, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ensure_all(c, c->dbg.b, (size_t)n_calls * 4 + 4, c->dbg.c, (size_t)n * std::max(total, 1), c->dbg.d, (size_t)n * 32, c->dbg.e, (size_t)n * 48)))
+        return rc;
+    if (n_calls) HIPCHK(c, hipMemcpyAsync(c->dbg.b.p, sizes, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(fk_dbg_dice_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n, d_seeds, d_incs, d_state, n_calls,
-                       static_cast<const int32_t *>(c->dbg[1].p), total, static_cast<uint8_t *>(c->dbg[2].p),
-                       raw64 ? static_cast<uint64_t *>(c->dbg[3].p) : nullptr,
-                       state_out ? static_cast<uint64_t *>(c->dbg[4].p) : nullptr);
+                       c->dbg.b.as<const int32_t>(), total, c->dbg.c.as<uint8_t>(), raw64 ? c->dbg.d.as<uint64_t>() : nullptr,
+                       state_out ? c->dbg.e.as<uint64_t>() : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (total) HIPCHK(c, hipMemcpyAsync(faces, c->dbg[2].p, (size_t)n * total, hipMemcpyDeviceToHost, c->stream));
-    if (raw64) HIPCHK(c, hipMemcpyAsync(raw64, c->dbg[3].p, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
-    if (state_out) HIPCHK(c, hipMemcpyAsync(state_out, c->dbg[4].p, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
+    if (total) HIPCHK(c, hipMemcpyAsync(faces, c->dbg.c.p, (size_t)n * total, hipMemcpyDeviceToHost, c->stream));
+    if (raw64) HIPCHK(c, hipMemcpyAsync(raw64, c->dbg.d.p, (size_t)n * 32, hipMemcpyDeviceToHost, c->stream));
+    if (state_out) HIPCHK(c, hipMemcpyAsync(state_out, c->dbg.e.p, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3681,17 +3622,14 @@ int fk_coordinate_seeds(fk_ctx *c, int64_t n, const fk_coord *coords, uint32_t *
     if (!c || n < 0 || !coords || (!seed32 && !seed64)) return c ? fail(c, FK_ERR_ARG, "bad arguments") : FK_ERR_ARG;
     if (n == 0) return FK_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n);
+    int rc = ensure_all(c, c->coords, (size_t)n, c->dbg.a, (size_t)n * 4, c->dbg.b, (size_t)n * 8);
     if (rc) return rc;
-    if ((rc = ensure(c, c->dbg[0], (size_t)n * 4))) return rc;
-    if ((rc = ensure(c, c->dbg[1], (size_t)n * 8))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(fk_coordinate_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n,
-                       static_cast<const fk_coord *>(c->coords.p), seed32 ? static_cast<uint32_t *>(c->dbg[0].p) : nullptr,
-                       seed64 ? static_cast<uint64_t *>(c->dbg[1].p) : nullptr);
+    hipLaunchKernelGGL(fk_coordinate_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, n, c->coords.p,
+                       seed32 ? c->dbg.a.as<uint32_t>() : nullptr, seed64 ? c->dbg.b.as<uint64_t>() : nullptr);
     HIPCHK(c, hipGetLastError());
-    if (seed32) HIPCHK(c, hipMemcpyAsync(seed32, c->dbg[0].p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (seed64) HIPCHK(c, hipMemcpyAsync(seed64, c->dbg[1].p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    if (seed32) HIPCHK(c, hipMemcpyAsync(seed32, c->dbg.a.p, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (seed64) HIPCHK(c, hipMemcpyAsync(seed64, c->dbg.b.p, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3706,12 +3644,12 @@ int fk_game_seeds(fk_ctx *c, uint32_t purpose, uint64_t root_seed, uint64_t k, u
     c->letters.clear();
     c->mail_used = 0;
     const size_t n = (size_t)n_shuffles * games_per_shuffle;
-    int rc = ensure(c, c->dbg[5], n * 4);
+    int rc = ensure(c, c->seeds, n * 4);
     if (rc) return rc;
     hipLaunchKernelGGL(fk_game_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, seed_prefix(purpose, root_seed, k),
-                       shuffle_begin, (uint32_t)n_shuffles, games_per_shuffle, static_cast<uint32_t *>(c->dbg[5].p));
+                       shuffle_begin, (uint32_t)n_shuffles, games_per_shuffle, c->seeds.as<uint32_t>());
     HIPCHK(c, hipGetLastError());
-    rc = post_d2h(c, seed32, c->dbg[5].p, n * 4);
+    rc = post_d2h(c, seed32, c->seeds.p, n * 4);
     if (rc) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     deliver_mail(c);
@@ -3738,18 +3676,14 @@ int fk_debug_dice_keys(fk_ctx *c, int64_t n, const uint64_t *state, int32_t n_ca
     if (n == 0) return FK_OK;
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->dbg[0], (size_t)n * 48))) return rc;
-    if ((rc = ensure(c, c->dbg[1], (size_t)n_calls * 4))) return rc;
-    if ((rc = ensure(c, c->dbg[2], (size_t)n * n_calls * 4))) return rc;
-    if ((rc = ensure(c, c->dbg[4], (size_t)n * 48))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->dbg[0].p, state, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->dbg[1].p, sizes, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(fk_dbg_dice_key_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n,
-                       static_cast<const uint64_t *>(c->dbg[0].p), n_calls, static_cast<const int32_t *>(c->dbg[1].p),
-                       static_cast<uint32_t *>(c->dbg[2].p), static_cast<uint64_t *>(c->dbg[4].p));
+    if ((rc = ensure_all(c, c->dbg.a, (size_t)n * 48, c->dbg.b, (size_t)n_calls * 4, c->dbg.c, (size_t)n * n_calls * 4, c->dbg.e, (size_t)n * 48))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->dbg.a.p, state, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->dbg.b.p, sizes, (size_t)n_calls * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fk_dbg_dice_key_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n, c->dbg.a.as<const uint64_t>(), n_calls,
+                       c->dbg.b.as<const int32_t>(), c->dbg.c.as<uint32_t>(), c->dbg.e.as<uint64_t>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(keys, c->dbg[2].p, (size_t)n * n_calls * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(state_out, c->dbg[4].p, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(keys, c->dbg.c.p, (size_t)n * n_calls * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(state_out, c->dbg.e.p, (size_t)n * 48, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3762,13 +3696,13 @@ int fk_debug_bounded_draws(fk_ctx *c, int64_t n, const fk_coord *coords, uint64_
     if ((uint64_t)n * (uint64_t)n_draws > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 draws in one probe");
     HIPCHK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->coords, sizeof(fk_coord) * (size_t)n))) return rc;
-    if ((rc = ensure(c, c->dbg[2], (size_t)n * n_draws * 4))) return rc;
+    if ((rc = ensure(c, c->coords, (size_t)n))) return rc;
+    if ((rc = ensure(c, c->dbg.c, (size_t)n * n_draws * 4))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->coords.p, coords, sizeof(fk_coord) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(fkb::fk_boot_draws_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, n,
-                       static_cast<const fk_coord *>(c->coords.p), (uint32_t)bound, (uint32_t)n_draws, static_cast<uint32_t *>(c->dbg[2].p));
+                       c->coords.p, (uint32_t)bound, (uint32_t)n_draws, c->dbg.c.as<uint32_t>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, c->dbg[2].p, (size_t)n * n_draws * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->dbg.c.p, (size_t)n * n_draws * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
@@ -3805,7 +3739,7 @@ int fk_debug_perm_from_draws(fk_ctx *c, int32_t S, int64_t n_sh, const uint16_t 
     cs.prepared = false;
     HIPCHK(c, hipStreamWaitEvent(c->stream, cs.ready, 0)); // an unused side-stream preparation may still own the set
     const uint32_t slots = perm_slots(S), perm_blocks = (n + slots - 1u) / slots;
-    if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots * 2))) return rc;
+    if ((rc = ensure(c, cs.perm, (size_t)perm_blocks * S * slots))) return rc;
     if ((rc = ensure(c, cs.draws, dl.bytes))) return rc;
     if (dl.bytes) HIPCHK(c, hipMemcpyAsync(cs.draws.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice, c->stream));
     launch_perm_consumers(cs, c->stream, path, dl, n, (uint32_t)S, slots);
@@ -3816,6 +3750,57 @@ int fk_debug_perm_from_draws(fk_ctx *c, int32_t S, int64_t n_sh, const uint16_t 
     for (uint32_t s = 0; s < n; ++s)
         for (int32_t i = 0; i < S; ++i)
             perms[(size_t)s * S + i] = perm_host[((size_t)(s / slots) * S + i) * slots + s % slots];
+    return FK_OK;
+}
+
+// ---- what both bootstrap entries state once (their device code is shared too: fk_bootstrap.h) ----
+// One cell of the stacked matrices (a player count of a root, named `who` in the messages): checks it and appends its descriptor.
+static int boot_add_cell(fk_ctx *c, std::vector<fkb::KDesc> &kd, uint64_t &sum_B, uint64_t root, int32_t k, int64_t n_batches, const int64_t *wins,
+                         const int64_t *exposures, int32_t S, const char *who) {
+    if (n_batches < 1 || n_batches > 0xffffffffll || !wins || !exposures)
+        return fail(c, FK_ERR_ARG, "%s needs 1 to 2^32 - 1 eligible batches and both matrices", who);
+    kd.push_back({root, (uint64_t)k, (uint32_t)n_batches, (uint32_t)sum_B, 1.0 / (double)k});
+    sum_B += (uint64_t)n_batches;
+    if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
+    if (!boot_totals_exact(wins, exposures, (uint64_t)n_batches, (size_t)S))
+        return fail(c, FK_ERR_ARG, "%s: a negative count, or one whose resampled total can pass 2^63", who);
+    return FK_OK;
+}
+
+// both stacked matrices and the descriptors, resident for the call
+static int boot_upload(fk_ctx *c, const std::vector<fkb::KDesc> &kd, const int64_t *const *wins, const int64_t *const *exposures, uint64_t sum_B, int32_t S) {
+    BootBufs &b = c->boot;
+    const size_t cells = (size_t)sum_B * (size_t)S;
+    if (const int rc = ensure_all(c, b.wins, cells, b.exposures, cells, b.kd, kd.size())) return rc;
+    for (int which = 0; which < 2; ++which)
+        for (size_t i = 0; i < kd.size(); ++i)
+            HIPCHK(c, hipMemcpyAsync((which ? b.exposures : b.wins).p + (size_t)kd[i].row0 * (size_t)S, (which ? exposures : wins)[i],
+                                     (size_t)kd[i].B * (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.kd.p, kd.data(), kd.size() * sizeof(fkb::KDesc), hipMemcpyHostToDevice, c->stream));
+    return FK_OK;
+}
+
+// replicates of one device block: what half the workspace budget holds at `per_rep` bytes each (4096 at most; option "bootstrap_block" caps it),
+// in whole groups of `group`, no more than the range needs
+static int64_t boot_block(fk_ctx *c, size_t per_rep, int64_t group, int64_t n_rep) {
+    int64_t block = std::max<int64_t>((int64_t)(workspace_budget(c) / 2 / (int64_t)per_rep), 1);
+    block = std::min<int64_t>(block, 4096);
+    if (c->bootstrap_block > 0) block = std::min(block, c->bootstrap_block);
+    return std::min<int64_t>(std::max<int64_t>(block / group * group, group), (n_rep + group - 1) / group * group);
+}
+
+// one block: its multiplicity rows zeroed, then the draws of `nr` replicates from replicate `rep0`
+static int boot_counts(fk_ctx *c, uint32_t purpose, uint64_t rep0, uint32_t nr, uint32_t nr_pad, uint32_t n_cells, uint32_t sum_B) {
+    HIPCHK(c, hipMemsetAsync(c->boot.counts.p, 0, (size_t)nr_pad * sum_B * 4, c->stream));
+    hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * n_cells + 63) / 64), dim3(64), 0, c->stream, purpose, rep0, nr, n_cells,
+                       c->boot.kd.p, sum_B, c->boot.counts.p);
+    return FK_OK;
+}
+
+// the flag the rate kernels raise on a replicate without complete-support exposure; waits for the stream
+static int boot_read_bad(fk_ctx *c, int32_t &bad) {
+    HIPCHK(c, hipMemcpyAsync(&bad, c->boot.bad.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
 }
 
@@ -3835,85 +3820,55 @@ int fk_performance_bootstrap(fk_ctx *c, uint64_t root_seed, int32_t n_k, const i
         return fail(c, FK_ERR_ARG, "controls need their index list and both accumulators");
     for (int32_t i = 0; i < n_controls; ++i)
         if (controls[i] < 0 || controls[i] >= S) return fail(c, FK_ERR_ARG, "control %d: column %d outside [0, S)", i, controls[i]);
-    std::vector<fkb::KDesc> kd((size_t)n_k);
+    std::vector<fkb::KDesc> kd;
     uint64_t sum_B = 0;
+    int rc;
     for (int32_t i = 0; i < n_k; ++i) {
         if (ks[i] < 1) return fail(c, FK_ERR_ARG, "player count %d: k = %d", i, ks[i]);
-        if (batch_counts[i] < 1 || batch_counts[i] > 0xffffffffll || !wins[i] || !exposures[i])
-            return fail(c, FK_ERR_ARG, "player count %d needs 1 to 2^32 - 1 eligible batches and both matrices", ks[i]);
-        kd[(size_t)i] = {root_seed, (uint64_t)ks[i], (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)ks[i]};
-        sum_B += (uint64_t)batch_counts[i];
-        if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
-        if (!boot_totals_exact(wins[i], exposures[i], (uint64_t)batch_counts[i], (size_t)S))
-            return fail(c, FK_ERR_ARG, "player count %d: a negative count, or one whose resampled total can pass 2^63", ks[i]);
+        char who[48];
+        snprintf(who, sizeof(who), "player count %d", ks[i]);
+        if ((rc = boot_add_cell(c, kd, sum_B, root_seed, ks[i], batch_counts[i], wins[i], exposures[i], S, who))) return rc;
     }
     const int64_t n_rep = replicate_end - replicate_begin;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
     // resident for the call: both stacked matrices, the descriptors, the counters and the contrast accumulators
-    const size_t mat_bytes = (size_t)sum_B * (size_t)S * 8;
-    const size_t counter_bytes = (size_t)4 * S * 8, contrast_bytes = (size_t)2 * n_controls * S * 8;
-    if ((rc = ensure(c, c->boot[0], mat_bytes))) return rc;
-    if ((rc = ensure(c, c->boot[1], mat_bytes))) return rc;
-    if ((rc = ensure(c, c->boot[2], kd.size() * sizeof(fkb::KDesc)))) return rc;
-    if ((rc = ensure(c, c->boot[5], counter_bytes))) return rc;
-    if ((rc = ensure(c, c->boot[6], contrast_bytes + (size_t)n_controls * 4))) return rc;
-    if ((rc = ensure(c, c->boot[7], 4))) return rc;
-    for (int which = 0; which < 2; ++which)
-        for (int32_t i = 0; i < n_k; ++i)
-            HIPCHK(c, hipMemcpyAsync(static_cast<int64_t *>(c->boot[which].p) + (size_t)kd[(size_t)i].row0 * (size_t)S, (which ? exposures : wins)[i],
-                                     (size_t)kd[(size_t)i].B * (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->boot[2].p, kd.data(), kd.size() * sizeof(fkb::KDesc), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->boot[5].p, 0, counter_bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->boot[7].p, 0, 4, c->stream));
-    double *d_contrast = static_cast<double *>(c->boot[6].p);
-    int32_t *d_controls = reinterpret_cast<int32_t *>(static_cast<uint8_t *>(c->boot[6].p) + contrast_bytes);
+    BootBufs &b = c->boot;
+    const size_t n_contrast = (size_t)n_controls * S, contrast_bytes = n_contrast * 8; // of the sums; the squares lie behind them
+    if ((rc = boot_upload(c, kd, wins, exposures, sum_B, S))) return rc;
+    if ((rc = ensure_all(c, b.counters, (size_t)4 * S, b.contrast, 2 * n_contrast, b.controls, (size_t)n_controls, b.bad, 1))) return rc;
+    HIPCHK(c, hipMemsetAsync(b.counters.p, 0, (size_t)4 * S * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.bad.p, 0, 4, c->stream));
     if (n_controls) {
-        HIPCHK(c, hipMemcpyAsync(d_contrast, contrast_sum, contrast_bytes / 2, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_contrast + (size_t)n_controls * S, contrast_square_sum, contrast_bytes / 2, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_controls, controls, (size_t)n_controls * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.contrast.p, contrast_sum, contrast_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.contrast.p + n_contrast, contrast_square_sum, contrast_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.controls.p, controls, (size_t)n_controls * 4, hipMemcpyHostToDevice, c->stream));
     }
     // the replicate range in blocks sized from the workspace budget: per replicate one multiplicity row and one score row
-    const size_t per_rep = (size_t)sum_B * 4 + (size_t)S * 8;
-    int64_t block = std::max<int64_t>((int64_t)(workspace_budget(c) / 2 / (int64_t)per_rep), 1);
-    block = std::min<int64_t>(block, 4096);
-    if (c->bootstrap_block > 0) block = std::min(block, c->bootstrap_block);
-    block = std::min<int64_t>(std::max<int64_t>(block / fkb::RB * fkb::RB, fkb::RB), (n_rep + fkb::RB - 1) / fkb::RB * fkb::RB);
-    if (n_rep > 0) {
-        if ((rc = ensure(c, c->boot[3], (size_t)block * sum_B * 4))) return rc;
-        if ((rc = ensure(c, c->boot[4], (size_t)block * S * 8))) return rc;
-    }
-    const fkb::KDesc *d_kd = static_cast<const fkb::KDesc *>(c->boot[2].p);
-    uint32_t *d_counts = static_cast<uint32_t *>(c->boot[3].p);
-    double *d_scores = static_cast<double *>(c->boot[4].p);
-    int32_t *d_bad = static_cast<int32_t *>(c->boot[7].p);
+    const int64_t block = boot_block(c, (size_t)sum_B * 4 + (size_t)S * 8, fkb::RB, n_rep);
+    if (n_rep > 0 && (rc = ensure_all(c, b.counts, (size_t)block * sum_B, b.scores, (size_t)block * S))) return rc;
     const unsigned s_tiles = (unsigned)((S + fkb::TS - 1) / fkb::TS);
     for (int64_t b0 = 0; b0 < n_rep; b0 += block) {
         const uint32_t nr = (uint32_t)std::min<int64_t>(block, n_rep - b0), nr_pad = (nr + fkb::RB - 1) / fkb::RB * fkb::RB;
-        HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)nr_pad * sum_B * 4, c->stream));
-        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_k + 63) / 64), dim3(64), 0, c->stream, fkb::PURPOSE_BOOTSTRAP,
-                           (uint64_t)(replicate_begin + b0), nr, (uint32_t)n_k, d_kd, (uint32_t)sum_B, d_counts);
+        if ((rc = boot_counts(c, fkb::PURPOSE_BOOTSTRAP, (uint64_t)(replicate_begin + b0), nr, nr_pad, (uint32_t)n_k, (uint32_t)sum_B))) return rc;
         hipLaunchKernelGGL(fkb::fk_boot_score_kernel, dim3(s_tiles, nr_pad / fkb::RB), dim3(fkb::TS), 0, c->stream,
-                           static_cast<const int64_t *>(c->boot[0].p), static_cast<const int64_t *>(c->boot[1].p), d_counts, d_kd,
-                           (uint32_t)n_k, (uint32_t)sum_B, (uint32_t)S, nr, d_scores, d_bad);
-        hipLaunchKernelGGL(fkb::fk_boot_rank_kernel, dim3(s_tiles, (nr + fkb::RC - 1) / fkb::RC), dim3(fkb::TS), 0, c->stream, d_scores,
-                           (uint32_t)S, nr, (uint32_t)top_n, delta, static_cast<unsigned long long *>(c->boot[5].p));
+                           b.wins.p, b.exposures.p, b.counts.p, b.kd.p, (uint32_t)n_k, (uint32_t)sum_B, (uint32_t)S, nr, b.scores.p, b.bad.p);
+        hipLaunchKernelGGL(fkb::fk_boot_rank_kernel, dim3(s_tiles, (nr + fkb::RC - 1) / fkb::RC), dim3(fkb::TS), 0, c->stream, b.scores.p,
+                           (uint32_t)S, nr, (uint32_t)top_n, delta, b.counters.p);
         if (n_controls)
-            hipLaunchKernelGGL(fkb::fk_boot_contrast_kernel, dim3((unsigned)(((size_t)n_controls * S + 255) / 256)), dim3(256), 0, c->stream,
-                               d_scores, (uint32_t)S, nr, d_controls, (uint32_t)n_controls, d_contrast);
+            hipLaunchKernelGGL(fkb::fk_boot_contrast_kernel, dim3((unsigned)((n_contrast + 255) / 256)), dim3(256), 0, c->stream, b.scores.p,
+                               (uint32_t)S, nr, b.controls.p, (uint32_t)n_controls, b.contrast.p);
         HIPCHK(c, hipGetLastError());
-        if (scores) HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * S, d_scores, (size_t)nr * S * 8, hipMemcpyDeviceToHost, c->stream));
+        if (scores) HIPCHK(c, hipMemcpyAsync(scores + (size_t)b0 * S, b.scores.p, (size_t)nr * S * 8, hipMemcpyDeviceToHost, c->stream));
     }
     int32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = boot_read_bad(c, bad))) return rc;
     if (bad) return fail(c, FK_ERR_ARG, "joint batch resampling produced zero complete-support exposure");
     int64_t *outs[4] = {rank_sum, rank_square_sum, top_counts, shortlist_counts};
     for (int i = 0; i < 4; ++i)
-        HIPCHK(c, hipMemcpyAsync(outs[i], static_cast<uint8_t *>(c->boot[5].p) + (size_t)i * S * 8, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(outs[i], b.counters.p + (size_t)i * S, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));
     if (n_controls) {
-        HIPCHK(c, hipMemcpyAsync(contrast_sum, d_contrast, contrast_bytes / 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(contrast_square_sum, d_contrast + (size_t)n_controls * S, contrast_bytes / 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(contrast_sum, b.contrast.p, contrast_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(contrast_square_sum, b.contrast.p + n_contrast, contrast_bytes, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return FK_OK;
@@ -3947,40 +3902,24 @@ int fk_root_stability_bootstrap(fk_ctx *c, const uint64_t *roots, int32_t n_k, c
             if (!std::isfinite(observed_across[j])) return fail(c, FK_ERR_ARG, "across k: observed is not finite");
     }
     const int32_t n_cells = 2 * n_k;
-    std::vector<fkb::KDesc> kd((size_t)n_cells);
+    std::vector<fkb::KDesc> kd;
     uint64_t sum_B = 0;
+    int rc;
     for (int32_t i = 0; i < n_cells; ++i) {
-        const int32_t k = ks[i % n_k];
-        const unsigned long long root = (unsigned long long)roots[i / n_k];
-        if (batch_counts[i] < 1 || batch_counts[i] > 0xffffffffll || !wins[i] || !exposures[i])
-            return fail(c, FK_ERR_ARG, "root %llu, player count %d needs 1 to 2^32 - 1 eligible batches and both matrices", root, k);
-        kd[(size_t)i] = {roots[i / n_k], (uint64_t)k, (uint32_t)batch_counts[i], (uint32_t)sum_B, 1.0 / (double)k};
-        sum_B += (uint64_t)batch_counts[i];
-        if (sum_B > ((uint64_t)1 << 31)) return fail(c, FK_ERR_ARG, "more than 2^31 batches");
-        if (!boot_totals_exact(wins[i], exposures[i], (uint64_t)batch_counts[i], (size_t)S))
-            return fail(c, FK_ERR_ARG, "root %llu, player count %d: a negative count, or one whose resampled total can pass 2^63", root, k);
+        char who[64];
+        snprintf(who, sizeof(who), "root %llu, player count %d", (unsigned long long)roots[i / n_k], ks[i % n_k]);
+        if ((rc = boot_add_cell(c, kd, sum_B, roots[i / n_k], ks[i % n_k], batch_counts[i], wins[i], exposures[i], S, who))) return rc;
     }
     const int64_t n_rep = replicate_end - replicate_begin;
     HIPCHK(c, hipSetDevice(c->device));
-    int rc;
-    // resident for the call: both stacked matrices, the descriptors, weights | observed | expected | across, the counters of both roots
-    const size_t mat_bytes = (size_t)sum_B * (size_t)S * 8;
-    const size_t by_k = (size_t)n_k * (size_t)S;
-    const size_t par_doubles = (size_t)n_k + (joint ? 2 * by_k + 2 * (size_t)S : 0);
-    const size_t counter_bytes = (size_t)2 * 4 * S * 8; // the rank kernel's four counters per root
-    if ((rc = ensure(c, c->boot[0], mat_bytes))) return rc;
-    if ((rc = ensure(c, c->boot[1], mat_bytes))) return rc;
-    if ((rc = ensure(c, c->boot[2], kd.size() * sizeof(fkb::KDesc)))) return rc;
-    if ((rc = ensure(c, c->boot[7], 4))) return rc;
-    if ((rc = ensure(c, c->rootb[0], par_doubles * 8))) return rc;
-    if ((rc = ensure(c, c->rootb[3], counter_bytes))) return rc;
-    for (int which = 0; which < 2; ++which)
-        for (int32_t i = 0; i < n_cells; ++i)
-            HIPCHK(c, hipMemcpyAsync(static_cast<int64_t *>(c->boot[which].p) + (size_t)kd[(size_t)i].row0 * (size_t)S, (which ? exposures : wins)[i],
-                                     (size_t)kd[(size_t)i].B * (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->boot[2].p, kd.data(), kd.size() * sizeof(fkb::KDesc), hipMemcpyHostToDevice, c->stream));
-    double *d_weights = static_cast<double *>(c->rootb[0].p);
-    double *d_observed = d_weights + n_k, *d_expected = d_observed + by_k, *d_observed_across = d_expected + by_k, *d_expected_across = d_observed_across + S;
+    // resident for the call: both stacked matrices, the descriptors, the parameter block, the counters of both roots
+    BootBufs &b = c->boot;
+    const fkl::RootParams par((size_t)n_k, (size_t)S, joint);
+    const size_t by_k = (size_t)n_k * (size_t)S, n_counters = (size_t)2 * 4 * S; // the rank kernel's four counters per root
+    if ((rc = boot_upload(c, kd, wins, exposures, sum_B, S))) return rc;
+    if ((rc = ensure_all(c, b.bad, 1, b.params, par.n, b.root_counters, n_counters))) return rc;
+    double *d_weights = b.params.p + par.weights, *d_observed = b.params.p + par.observed, *d_expected = b.params.p + par.expected;
+    double *d_observed_across = b.params.p + par.observed_across, *d_expected_across = b.params.p + par.expected_across;
     HIPCHK(c, hipMemcpyAsync(d_weights, weights, (size_t)n_k * 8, hipMemcpyHostToDevice, c->stream));
     if (joint) {
         HIPCHK(c, hipMemcpyAsync(d_observed, observed, by_k * 8, hipMemcpyHostToDevice, c->stream));
@@ -3988,36 +3927,27 @@ int fk_root_stability_bootstrap(fk_ctx *c, const uint64_t *roots, int32_t n_k, c
         HIPCHK(c, hipMemcpyAsync(d_observed_across, observed_across, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_expected_across, expected_across, (size_t)S * 8, hipMemcpyHostToDevice, c->stream));
     }
-    HIPCHK(c, hipMemsetAsync(c->rootb[3].p, 0, counter_bytes, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->boot[7].p, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.root_counters.p, 0, n_counters * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.bad.p, 0, 4, c->stream));
     // the replicate range in blocks sized from the workspace budget: per replicate one multiplicity row, one score row per root, one
     // maximum and (when asked for) one membership row per root.  Counts are integers and maxima per replicate: no carried state.
-    const size_t per_rep = (size_t)sum_B * 4 + (size_t)2 * S * 8 + 8 + (membership ? (size_t)2 * S : 0);
-    int64_t block = std::max<int64_t>((int64_t)(workspace_budget(c) / 2 / (int64_t)per_rep), 1);
-    block = std::min<int64_t>(block, 4096);
-    if (c->bootstrap_block > 0) block = std::min(block, c->bootstrap_block);
-    block = std::min<int64_t>(std::max<int64_t>(block / fkr::RRB * fkr::RRB, fkr::RRB), (n_rep + fkr::RRB - 1) / fkr::RRB * fkr::RRB);
+    const int64_t block = boot_block(c, (size_t)sum_B * 4 + (size_t)2 * S * 8 + 8 + (membership ? (size_t)2 * S : 0), fkr::RRB, n_rep);
     if (n_rep > 0) {
-        if ((rc = ensure(c, c->boot[3], (size_t)block * sum_B * 4))) return rc;
-        if ((rc = ensure(c, c->boot[4], (size_t)block * 2 * S * 8))) return rc;
-        if ((rc = ensure(c, c->rootb[1], (size_t)block * 8))) return rc;
-        if (membership && (rc = ensure(c, c->rootb[2], (size_t)block * 2 * S))) return rc;
+        if ((rc = ensure_all(c, b.counts, (size_t)block * sum_B, b.scores, (size_t)block * 2 * S, b.maxima, (size_t)block))) return rc;
+        if (membership && (rc = ensure(c, b.member, (size_t)block * 2 * S))) return rc;
     }
-    const fkb::KDesc *d_kd = static_cast<const fkb::KDesc *>(c->boot[2].p);
-    const int64_t *d_W = static_cast<const int64_t *>(c->boot[0].p), *d_E = static_cast<const int64_t *>(c->boot[1].p);
-    uint32_t *d_counts = static_cast<uint32_t *>(c->boot[3].p);
-    double *d_scores = static_cast<double *>(c->boot[4].p);
-    unsigned long long *d_maxima = static_cast<unsigned long long *>(c->rootb[1].p);
-    uint8_t *d_member = static_cast<uint8_t *>(c->rootb[2].p);
-    unsigned long long *d_counters = static_cast<unsigned long long *>(c->rootb[3].p);
-    int32_t *d_bad = static_cast<int32_t *>(c->boot[7].p);
+    const fkb::KDesc *d_kd = b.kd.p;
+    const int64_t *d_W = b.wins.p, *d_E = b.exposures.p;
+    uint32_t *d_counts = b.counts.p;
+    double *d_scores = b.scores.p;
+    ull *d_maxima = b.maxima.p, *d_counters = b.root_counters.p;
+    uint8_t *d_member = b.member.p;
+    int32_t *d_bad = b.bad.p;
     const unsigned s_tiles = (unsigned)((S + fkb::TS - 1) / fkb::TS);
     for (int64_t b0 = 0; b0 < n_rep; b0 += block) {
         const uint32_t nr = (uint32_t)std::min<int64_t>(block, n_rep - b0), nr_pad = (nr + fkr::RRB - 1) / fkr::RRB * fkr::RRB;
-        HIPCHK(c, hipMemsetAsync(d_counts, 0, (size_t)nr_pad * sum_B * 4, c->stream));
-        hipLaunchKernelGGL(fkb::fk_boot_counts_kernel, dim3((nr * (unsigned)n_cells + 63) / 64), dim3(64), 0, c->stream,
-                           fkb::PURPOSE_ROOT_STABILITY_BOOTSTRAP, (uint64_t)(replicate_begin + b0), nr, (uint32_t)n_cells, d_kd, (uint32_t)sum_B,
-                           d_counts);
+        if ((rc = boot_counts(c, fkb::PURPOSE_ROOT_STABILITY_BOOTSTRAP, (uint64_t)(replicate_begin + b0), nr, nr_pad, (uint32_t)n_cells, (uint32_t)sum_B)))
+            return rc;
         const dim3 rates_grid(s_tiles, nr_pad / fkr::RRB);
         if (joint) {
             HIPCHK(c, hipMemsetAsync(d_maxima, 0, (size_t)nr_pad * 8, c->stream));
@@ -4039,8 +3969,7 @@ int fk_root_stability_bootstrap(fk_ctx *c, const uint64_t *roots, int32_t n_k, c
         if (membership) HIPCHK(c, hipMemcpyAsync(membership + (size_t)b0 * 2 * S, d_member, (size_t)nr * 2 * S, hipMemcpyDeviceToHost, c->stream));
     }
     int32_t bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((rc = boot_read_bad(c, bad))) return rc;
     if (bad) return fail(c, FK_ERR_ARG, "root bootstrap produced zero complete-support exposure");
     for (int root = 0; root < 2; ++root)
         HIPCHK(c, hipMemcpyAsync(top_counts + (size_t)root * S, d_counters + ((size_t)root * 4 + 2) * S, (size_t)S * 8, hipMemcpyDeviceToHost, c->stream));

@@ -1,0 +1,104 @@
+// fk_buffers.h — host side: what a context (farkle_hip.hip: fk_ctx) holds its device memory in.  Dev<T> is one allocation, typed and
+// owning; the structs below group the buffers of the analysis entries, one struct per entry and one named member per role.  Included
+// behind the kernels' headers, whose types the members name.  The layouts of the buffers that hold several parts are in fk_layouts.h.
+#pragma once
+#include <atomic>
+#include <cstddef>
+#include <cstdint>
+
+using ull = unsigned long long;
+
+inline std::atomic<int64_t> g_device_bytes_held{0}; // option "device_bytes_held": `cap` summed over the live buffers of every context of the process
+
+// One device allocation of a context, typed and owning.  ensure() sizes it in elements; `cap` is what it holds in bytes.
+template <class T>
+struct Dev {
+    T *p = nullptr;
+    size_t cap = 0;
+    Dev() = default;
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    ~Dev() { release(); }
+    void release() {
+        if (p) (void)hipFree(p);
+        g_device_bytes_held -= (int64_t)cap;
+        p = nullptr;
+        cap = 0;
+    }
+    // a typed view into a byte buffer that holds more than one type, `byte_off` bytes in
+    template <class U>
+    U *as(size_t byte_off = 0) const {
+        static_assert(sizeof(T) == 1, "views are taken of byte buffers only");
+        return reinterpret_cast<U *>(p + byte_off);
+    }
+};
+
+// ---- the device buffers of the analysis entries, one struct per entry, one member per role ----
+struct MatchupReduceBufs { // fk_matchup_reduce
+    Dev<ull> digest, key, key_alt, s_digest;                 // [n] the records' digests, both sort-key buffers, the sorted digests
+    Dev<uint16_t> seats, rounds, s_seats, s_rounds;          // [n][K] / [n] as given and sorted
+    Dev<uint32_t> idx, order, heads, run_id, tuple_break, run_mixed; // [n] sort payloads (both buffers), run / segment heads and their scan
+    Dev<uint8_t> mixed_flag;                                 // [n] the element lies in a run that holds more than one tuple
+    Dev<uint32_t> mixed_pos, mixed_key, mixed_key_alt, mixed_a, mixed_b, order_before; // the elements of mixed runs and their LSD sort
+    Dev<uint32_t> seg_start;                                 // [G + 1]
+    Dev<uint8_t> eligible;                                   // [G]
+    Dev<ull> prio, prio_sorted;                              // [G]
+    Dev<int32_t> bin;                                        // [G]
+    Dev<uint32_t> hist, sel, sel_sorted;                     // [H], [G] x 2
+    Dev<ull> out_digest;                                     // [M] the selected groups ...
+    Dev<uint16_t> out_seats;                                 // [M][K]
+    Dev<long long> out_count, out_sums;                      // [M], [M][n_lags][SUM_COLS]
+    Dev<int32_t> lags;
+    Dev<uint32_t> num;                                       // hipcub's selected-count word
+};
+struct SeatBufs { // fk_tournament_run_seat_counts
+    Dev<long long> counts;
+    Dev<uint16_t> id_rank;                  // [S]
+    Dev<ull> key, key_sorted;               // the call's mirror records: keys ...
+    Dev<uint32_t> val, val_sorted;          // ... and payloads, two sort buffers each
+    Dev<ull> fr, e_fr, sh, e_sh;            // mirror_reduce: [n + 1] indicators and their exclusive sums
+    Dev<uint32_t> ph, e_ph, seg_start, pair_start;
+    Dev<int32_t> seg_diff;
+    Dev<uint16_t> pair_rank;                // [capacity][2]
+    Dev<long long> pair_sums;               // [capacity][PAIR_COLS]
+    Dev<ull> pair_count;
+};
+struct TraceBufs { // fk_trace_games
+    Dev<int2> strat;       // the strategies in points
+    Dev<uint32_t> ws;      // seat workspace
+    Dev<long long> counts, begin; // [n + 1] events per game and their exclusive scan
+    Dev<uint8_t> rows;
+    Dev<ull> err;
+    Dev<uint4> events;
+};
+struct CensusBufs { // fk_census_games / fk_tournament_run_census
+    Dev<int2> strat;  // the strategies in points
+    Dev<uint32_t> ws; // seat workspace of one chunk
+    Dev<ull> tables;  // the four tables + the error word (fkcn::CensusArgs::tables)
+};
+struct RoundRobinBufs { // fk_h2h_round_robin
+    Dev<uint2> table;      // the n-row table, packed
+    Dev<uint8_t> patience;
+    Dev<uint32_t> state;   // window states
+    Dev<ull> need, off;    // [rows + 1] games each block needs and their scan
+    Dev<uint32_t> flag, aidx, act; // playing flags, their scan, the playing rows
+    Dev<fkrr::RrError> err;
+    Dev<uint32_t> bounds;  // [passes][2]
+    Dev<ull> summary;
+};
+struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
+    Dev<int64_t> wins, exposures; // the stacked matrices
+    Dev<fkb::KDesc> kd;
+    Dev<uint32_t> counts;  // one block's multiplicity rows
+    Dev<double> scores;    // one block's score rows (one per root)
+    Dev<int32_t> bad;      // flag: a replicate without complete-support exposure
+    Dev<ull> counters;     // performance: the rank kernel's four counters
+    Dev<double> contrast;  // performance: [2][n_controls][S] contrast sums and squares
+    Dev<int32_t> controls;
+    Dev<double> params;    // root stability: fkl::RootParams
+    Dev<ull> maxima, root_counters; // root stability: one block's maxima (as ordered bits); four counters per root
+    Dev<uint8_t> member;   // root stability: one block's membership rows
+};
+struct ProbeBufs { // the fk_debug_* probes and fk_coordinate_seeds: the kernel's buffer arguments in their order, bytes
+    Dev<uint8_t> a, b, c, d, e;
+};

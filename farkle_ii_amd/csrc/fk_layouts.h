@@ -1,0 +1,45 @@
+// fk_layouts.h — host side: the composite device buffers of the engine, each as a plain struct that computes its offsets once
+// from its shape.  The same struct serves the buffer's ensure, the kernel arguments and the copies home (farkle_hip.hip).
+// Plain arithmetic, no HIP: tests/native/layouts_host_check.hip evaluates them on the CPU.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace fkl {
+
+constexpr size_t GAME_COUNTS = 4; // = fkg::N_COUNTS (asserted where both are visible)
+
+// fk_tournament_run_game_stats: u64 [S][4] counts | [S][rb] rounds | [S][mb] runner-up | [S][mb] spread | [4] game counts |
+// [rb] game rounds | [mb] game runner-up | spill count, then the spill entries (int32 [cap][3]).  Offsets in u64 units.
+struct GameStatsOut {
+    size_t s_counts, s_rounds, s_runner, s_spread, g_counts, g_rounds, g_runner, spill_count, n_u64;
+    GameStatsOut(size_t S, size_t rb, size_t mb)
+        : s_counts(0), s_rounds(s_counts + S * GAME_COUNTS), s_runner(s_rounds + S * rb), s_spread(s_runner + S * mb), g_counts(s_spread + S * mb),
+          g_rounds(g_counts + GAME_COUNTS), g_runner(g_rounds + rb), spill_count(g_runner + mb), n_u64(spill_count + 1) {}
+    size_t spill_at() const { return n_u64 * 8; } // byte offset of the spill entries
+    size_t bytes(int64_t spill_capacity) const { return spill_at() + (size_t)(spill_capacity > 1 ? spill_capacity : 1) * 12; }
+};
+
+// fk_tournament_run_rare_events: u64 [S][sb] second | [sb] game second | event total.  Offsets in u64 units.
+struct RareOut {
+    size_t s_second, g_second, total, n_u64;
+    RareOut(size_t S, size_t sb) : s_second(0), g_second(S * sb), total(g_second + sb), n_u64(total + 1) {}
+};
+
+// The fingerprints a rows-mode call sends home with its tally: the game seeds, then (256-byte aligned) the shuffle seeds.
+struct Fingerprints {
+    size_t game_at, shuffle_at, bytes;
+    Fingerprints(size_t game_seed_bytes, size_t shuffle_seed_bytes)
+        : game_at(0), shuffle_at((game_seed_bytes + 255u) & ~(size_t)255u), bytes(shuffle_at + shuffle_seed_bytes) {}
+};
+
+// fk_root_stability_bootstrap's parameter block: weights [n_k] and, for the joint family, observed [n_k][S] | expected [n_k][S] |
+// observed across k [S] | expected across k [S].  Offsets in doubles (the joint offsets are stated either way; only n says what exists).
+struct RootParams {
+    size_t weights, observed, expected, observed_across, expected_across, n;
+    RootParams(size_t n_k, size_t S, bool joint)
+        : weights(0), observed(n_k), expected(observed + n_k * S), observed_across(expected + n_k * S), expected_across(observed_across + S),
+          n(n_k + (joint ? 2 * n_k * S + 2 * S : 0)) {}
+};
+
+} // namespace fkl

@@ -179,7 +179,9 @@ int fk_host_free(fk_ctx *ctx, void *p);
 int fk_set_option(fk_ctx *ctx, const char *name, int64_t value);
 /* Read back an option or a figure of the last call: "chunk_bytes", "workspace_percent" (a buffer set's workspace is at most this share of
  * the device memory the context can have — free now + its own per-chunk buffers — halved for the two sets; default 80), "last_budget" (the
- * bytes per buffer set the last tournament / H2H call planned with), "oom_replays" (how often that call met hipErrorOutOfMemory, gave
+ * bytes per buffer set the last tournament / H2H call planned with), "device_bytes_held" (the device memory, in bytes, that the buffers of
+ * every live context of this PROCESS hold right now: it grows where a buffer grows and falls where one is freed, so a destroyed context
+ * leaves it where it was before the context was created; memory held by fk_debug_hold_memory is not counted), "oom_replays" (how often that call met hipErrorOutOfMemory, gave
  * its workspace back and was replayed with half the budget: results are identical), "comm_timeout_ms" (the EFFECTIVE deadline: the option
  * if it was ever set, else a well-formed FK_COMM_TIMEOUT_MS, else 120 000), "rows_chunk_games". */
 int fk_get_option(fk_ctx *ctx, const char *name, int64_t *value);
