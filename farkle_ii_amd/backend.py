@@ -41,6 +41,17 @@ EVENT_DTYPE = np.dtype(
     [("dice", "<u4"), ("turn_score", "<i4"), ("points", "<u2"), ("round", "<u2"), ("seat", "u1"), ("used_left", "u1"),
      ("discards", "u1"), ("flags", "u1")]
 )
+# fk_rr_pair_row, include/farkle_hip.h: one pair of the round-robin inference (fk_rr_inference; frames in farkle_ii_amd/rr_inference.py)
+RR_PAIR_ROW_DTYPE = np.dtype(
+    [("pair_id", "<u8"), ("games_attempted", "<i8"), ("games_completed", "<i8"), ("games_safety_limit", "<i8"), ("n_completed_required", "<i8"),
+     ("n_ab", "<i8"), ("n_ba", "<i8"), ("seat1_a_wins_ab", "<i8"), ("seat1_b_wins_ba", "<i8"), ("seat2_a_wins_ba", "<i8"), ("balanced_a_wins", "<i8"),
+     ("holm_order", "<i8"), ("completion_game_rate", "<f8"), ("q_ab", "<f8"), ("q_ba", "<f8"), ("raw_order_rate_difference", "<f8"), ("d_ab", "<f8"),
+     ("score_null_proportion", "<f8"), ("score_z", "<f8"), ("score_p_value", "<f8"), ("ordinary_d_low", "<f8"), ("ordinary_d_high", "<f8"),
+     ("simultaneous_d_low", "<f8"), ("simultaneous_d_high", "<f8"), ("balanced_a_win_rate", "<f8"), ("holm_adjusted_p", "<f8"),
+     ("strategy_a", "<u4"), ("strategy_b", "<u4"), ("flags", "u1"), ("decision_class", "u1"), ("pad", "u1", (6,))]
+)
+RR_CLASSES = 7         # FK_RR_CLASSES
+RR_STRATEGY_COLS = 12  # FK_RR_STRATEGY_COLS
 TALLY_COLS = 26
 LAG_COLS = 11  # FK_LAG_COLS: pairs | win: sx sy sxx syy sxy | n_rounds: sx sy sxx syy sxy
 SEAT_STAT_COLS = 31
@@ -60,6 +71,12 @@ COMM_ID_BYTES = 128
 def row_dtype(k: int) -> np.dtype:
     """Structured dtype of one game row: 4-byte header + k 28-byte seat records."""
     return np.dtype([("n_rounds", "<u2"), ("status", "u1"), ("winner_seat", "i1"), ("seats", SEAT_DTYPE, (k,))])
+
+
+class _RrInferenceParams(C.Structure):  # fk_rr_inference_params
+    _fields_ = [("family_alpha", C.c_double), ("practical_delta", C.c_double), ("delta_equivalence", C.c_double),
+                ("min_candidate_completion_rate", C.c_double), ("critical_ordinary", C.c_double), ("critical_simultaneous", C.c_double),
+                ("family_pair_count", C.c_uint64)]
 
 
 class _DeviceInfo(C.Structure):
@@ -119,7 +136,8 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin"]
+            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin",
+            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference"]
 _libs: dict = {}
 
 
@@ -269,6 +287,7 @@ class Engine:
     def __init__(self, device: int = 0, variant: str | None = None):
         self._lib = load_library(variant)  # (variant: a test build of the library, backend.VARIANTS)
         self._ctx = C.c_void_p()
+        self._rr_n = 0  # the table size of the resident round-robin pair counts (0: none)
         rc = self._lib.fk_init(C.c_int(device), C.byref(self._ctx))
         if rc != 0:
             self._ctx = C.c_void_p()
@@ -803,6 +822,84 @@ class Engine:
                                                  C.c_uint64(target), C.c_uint64(max_attempts), C.c_int32(target_score), C.c_int32(max_rounds),
                                                  _p(states), _p(summary)))
         return states, summary
+
+    def _rr_range(self, table, pair_begin, pair_end, family_pair_count) -> tuple:
+        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE).reshape(-1)
+        n = len(table)
+        end = n * (n - 1) // 2 if pair_end is None else int(pair_end)
+        begin = int(pair_begin)
+        family = n * (n - 1) // 2 if family_pair_count is None else int(family_pair_count)
+        if min(begin, end, family) < 0:
+            raise ValueError("pair range and family_pair_count must not be negative")
+        return table, n, begin, end, family
+
+    def h2h_round_robin_resident(self, table: np.ndarray, root_seed: int, target: int, max_attempts: int, pair_begin: int = 0,
+                                 pair_end: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
+                                 summary: np.ndarray | None = None, family_pair_count: int | None = None) -> np.ndarray:
+        """``fk_h2h_round_robin_resident``: ``h2h_round_robin`` whose block states stay on the device and are added to the context's pair
+        counts (one call per root; the first fixes table, range and ``family_pair_count`` — default the table's pair count).  Returns the
+        summary, as ``h2h_round_robin`` does."""
+        table, n, begin, end, family = self._rr_range(table, pair_begin, pair_end, family_pair_count)
+        if summary is None:
+            summary = np.zeros((n, 8), dtype=np.int64)
+        elif not (isinstance(summary, np.ndarray) and summary.dtype == np.int64 and summary.shape == (n, 8) and summary.flags.c_contiguous):
+            raise ValueError(f"summary must be a C-contiguous int64 array of shape {(n, 8)}")
+        if min(int(target), int(max_attempts), int(root_seed)) < 0:
+            raise ValueError("target, max_attempts and root_seed must not be negative")
+        self._check(self._lib.fk_h2h_round_robin_resident(self._ctx, _p(table), C.c_int32(n), C.c_uint64(root_seed), C.c_uint64(begin), C.c_uint64(end),
+                                                          C.c_uint64(target), C.c_uint64(max_attempts), C.c_int32(target_score),
+                                                          C.c_int32(max_rounds), _p(summary), C.c_uint64(family)))
+        self._rr_n = n
+        return summary
+
+    def rr_counts_add(self, table: np.ndarray, states: np.ndarray, target: int, max_attempts: int, pair_begin: int = 0,
+                      pair_end: int | None = None, family_pair_count: int | None = None) -> None:
+        """``fk_rr_counts_add``: one root's host-held block states ``[pairs, 2, 5]`` (as ``h2h_round_robin`` returned them for this
+        ``target`` / ``max_attempts``) into the context's pair counts."""
+        table, n, begin, end, family = self._rr_range(table, pair_begin, pair_end, family_pair_count)
+        st = np.asarray(states)
+        if st.shape != (max(end - begin, 0), 2, 5) or st.dtype.kind not in "iu" or (st.size and (int(st.min()) < 0 or int(st.max()) > 0xFFFFFFFF)):
+            raise ValueError(f"states must be unsigned 32-bit counts of shape {(max(end - begin, 0), 2, 5)}")
+        st = np.ascontiguousarray(st, dtype=np.uint32)
+        if min(int(target), int(max_attempts)) < 0:
+            raise ValueError("target and max_attempts must not be negative")
+        self._check(self._lib.fk_rr_counts_add(self._ctx, _p(table), C.c_int32(n), C.c_uint64(begin), C.c_uint64(end), C.c_uint64(target),
+                                               C.c_uint64(max_attempts), _p(st), C.c_uint64(family)))
+        self._rr_n = n
+
+    def rr_counts_reset(self) -> None:
+        """``fk_rr_counts_reset``: forget the resident pair counts."""
+        self._check(self._lib.fk_rr_counts_reset(self._ctx))
+        self._rr_n = 0
+
+    def rr_inference(self, family_alpha: float = 0.02, practical_delta: float = 0.03, delta_equivalence: float | None = None,
+                     min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None,
+                     rows: tuple[int, int] | None = None, want_strategies: bool = True) -> dict:
+        """``fk_rr_inference`` over the resident pair counts (of an ``n``-row table): ``{"class_counts": int64 [7], "strategies": int64
+        [n, 12] or None, "rows": RR_PAIR_ROW_DTYPE [row_end - row_begin] or None}``.  ``rows`` is a pair-id range ``(begin, end)``.  The two
+        critical values are evaluated here, once, with scipy (``norm.isf``), as the reference's ``_score_difference_interval_fallback`` does."""
+        from scipy.stats import norm
+
+        n = self._rr_n  # the table size fixed with the resident counts: it sizes the per-strategy output
+        family = n * (n - 1) // 2 if family_pair_count is None else int(family_pair_count)
+        if family < 0 or family >= 1 << 64:
+            raise ValueError("family_pair_count must fit 64 unsigned bits")
+        alpha = float(family_alpha)
+        ok = 0.0 < alpha < 1.0 and family > 0  # (the entry refuses the others with its own message; isf of them is undefined)
+        par = _RrInferenceParams(alpha, float(practical_delta), float("nan") if delta_equivalence is None else float(delta_equivalence),
+                                 float(min_candidate_completion_rate), float(norm.isf(alpha / 2.0)) if ok else 1.0,
+                                 float(norm.isf(alpha / family / 2.0)) if ok else 1.0, family)
+        out_rows, begin, end = None, 0, 0
+        if rows is not None:
+            begin, end = int(rows[0]), int(rows[1])
+            if begin < 0 or end < 0:
+                raise ValueError("the row range must not be negative")
+            out_rows = np.zeros(max(end - begin, 0), dtype=RR_PAIR_ROW_DTYPE)
+        class_counts = np.zeros(RR_CLASSES, dtype=np.int64)
+        strategies = np.zeros((n, RR_STRATEGY_COLS), dtype=np.int64) if want_strategies else None
+        self._check(self._lib.fk_rr_inference(self._ctx, C.byref(par), _p(out_rows), C.c_uint64(begin), C.c_uint64(end), _p(class_counts),
+                                              _p(strategies)))
+        return {"class_counts": class_counts, "strategies": strategies, "rows": out_rows}
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
     def comm_unique_id(self) -> bytes:

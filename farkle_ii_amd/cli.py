@@ -123,6 +123,14 @@ def build_parser() -> argparse.ArgumentParser:
     rr.add_argument("--out", type=Path, metavar="DIR",
                     help="Write round_robin_pairs.parquet, round_robin_strategies.parquet and round_robin.json under DIR "
                          "(default: <results_root>/h2h_round_robin).  Roots: sim.seed_list")
+    rr.add_argument("--inference", action="store_true",
+                    help="Keep the block states on the GPU (no round_robin_pairs.parquet), run the score test, the score intervals, Holm's "
+                         "adjustment and the decision classes over all roots there, and write round_robin_inference_pairs.parquet, "
+                         "round_robin_inference_strategies.parquet and the class counts into round_robin.json.  Settings: "
+                         "head2head.family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate")
+    rr.add_argument("--rows", metavar="BEGIN:END",
+                    help="With --inference: the pair ids whose rows round_robin_inference_pairs.parquet holds (default: every pair of the "
+                         "range when it has at most 2^22 pairs, none beyond)")
     rr.add_argument("--force", action="store_true", help="Replace the tables of an existing output directory")
     for name in _OUT_OF_SCOPE:
         sub.add_parser(name, help="(reference command outside the simulation path)")
@@ -189,7 +197,7 @@ def main(argv: Sequence[str] | None = None) -> None:
 
         try:
             written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
-                                      out=args.out, force=args.force)
+                                      out=args.out, force=args.force, inference=args.inference, rows=args.rows)
         except (ValueError, FileExistsError) as exc:
             raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})

@@ -104,6 +104,15 @@ class SimConfig:
         return seeds
 
 
+@dataclass(frozen=True)
+class Head2HeadInferenceConfig:
+    """The ``head2head`` fields the round-robin inference reads, with the reference's defaults (config.py ``Head2HeadConfig``)."""
+    family_alpha: float = 0.02
+    practical_delta: float = 0.03
+    delta_equivalence: float | None = None
+    min_candidate_completion_rate: float = 0.99
+
+
 @dataclass
 class AppConfig:
     io: IOConfig = field(default_factory=IOConfig)
@@ -162,6 +171,24 @@ class AppConfig:
 
     def all_player_batch_dir(self, n: int) -> Path | None:
         return self._per_n_dir(self.sim.all_player_batch_dir, n, "all-player-batch-dir")
+
+    @property
+    def head2head(self) -> Head2HeadInferenceConfig:
+        """``head2head.family_alpha`` / ``practical_delta`` / ``delta_equivalence`` / ``min_candidate_completion_rate``; the section is
+        carried opaquely (its other keys belong to the reference's analysis), these four are read from it with the reference's defaults."""
+        section = self.opaque.get("head2head") or {}
+        values = {}
+        for f in fields(Head2HeadInferenceConfig):
+            raw = section.get(f.name, f.default)
+            if isinstance(raw, str):  # a --set override of an opaque section arrives as text
+                raw = _coerce(raw, None)
+            if raw is None and f.name == "delta_equivalence":
+                values[f.name] = None
+                continue
+            if isinstance(raw, bool) or not isinstance(raw, (int, float)):
+                raise ValueError(f"head2head.{f.name} must be a number")
+            values[f.name] = float(raw)
+        return Head2HeadInferenceConfig(**values)
 
     def rng_diagnostic_lags(self) -> tuple[int, ...]:
         """``analysis.rng_diagnostic_lags`` (config.py:335, validated like :1933-1939); the analysis section is carried opaquely."""

@@ -17,6 +17,7 @@
 #include "fk_trace.h"          // device side: roll-level game trace (its own table-free game loop, events at scanned offsets)
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
 #include "fk_round_robin.h"    // device side: head-to-head round robin (window tables by unranking, generation planner, apply, summary)
+#include "fk_rr_inference.h"   // device side: round-robin inference (resident pair counts, score test, intervals, Holm, decision classes)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -246,6 +247,10 @@ struct fk_ctx {
     int64_t census_chunk_games = 0;      // option "census_chunk_games": > 0 caps the games of one census chunk (tests drive the chunk loop)
     RoundRobinBufs rr;
     int64_t rr_window_blocks = (int64_t)1 << 22; // option "rr_window_blocks": blocks of one round-robin window (even, 2 .. 2^22; scheduling only)
+    RrInferenceBufs ri;
+    bool ri_valid = false;               // the accumulator holds counts; what the first adding call fixed with them:
+    int32_t ri_n = 0;
+    uint64_t ri_begin = 0, ri_end = 0, ri_hash = 0, ri_family = 0;
     BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
@@ -3139,8 +3144,8 @@ int fk_h2h_run(fk_ctx *c, const fk_strategy seats[2], uint64_t root_seed, uint64
 // generation's total, the number of playing blocks and the call's error record, then two words per pass; play_block_passes plays them.
 static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end,
                                 uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds, const LaunchPlan &plan,
-                                uint32_t *block_state, int64_t *summary) {
-    using namespace fkrr;
+                                uint32_t *block_state, int64_t *summary, uint32_t *d_staged = nullptr) {
+    using namespace fkrr; // d_staged: the call's states stay on the device, [pair_end - pair_begin][2][RR_STATE] (block_state is null then)
     HIPCHK(c, hipSetDevice(c->device));
     begin_call(c);
     // the n-row table, packed, and its patience classes: uploaded once per call
@@ -3169,12 +3174,12 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     RoundRobinBufs &r = c->rr;
     const size_t rows1 = (size_t)max_rows + 1;
     int rc = FK_OK;
-    if ((rc = ensure_all(c, r.table, (size_t)n, r.patience, (size_t)n, r.state, (size_t)max_rows * RR_STATE, r.need, rows1, r.off, rows1, r.flag, rows1,
+    if ((rc = ensure_all(c, r.table, (size_t)n, r.patience, (size_t)n, r.state, d_staged ? 0 : (size_t)max_rows * RR_STATE, r.need, rows1, r.off, rows1, r.flag, rows1,
                          r.aidx, rows1, r.act, (size_t)max_rows, r.err, 1)))
         return rc;
     if (summary && (rc = ensure(c, r.summary, (size_t)n * RR_COLS))) return rc;
     if ((rc = ensure_all(c, c->strat, 2 * (size_t)max_rows, c->slow, 2 * (size_t)max_rows, c->block_out, (size_t)max_rows * 4))) return rc;
-    uint32_t *d_state = r.state.p, *d_flag = r.flag.p, *d_aidx = r.aidx.p, *d_act = r.act.p;
+    uint32_t *d_flag = r.flag.p, *d_aidx = r.aidx.p, *d_act = r.act.p;
     ull *d_need = r.need.p, *d_off = r.off.p;
     RrError *d_err = r.err.p;
     { // the scratch of both scans of a generation, sized once for the largest window: no size query inside the window loop
@@ -3194,6 +3199,7 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     for (uint64_t pair0 = pair_begin; pair0 < pair_end; pair0 += window_pairs) {
         const uint32_t n_pairs = (uint32_t)std::min<uint64_t>(window_pairs, pair_end - pair0), n_rows = 2u * n_pairs;
         const dim3 rows_grid((n_rows + 1u + 255u) / 256u), b256(256);
+        uint32_t *d_state = d_staged ? d_staged + (size_t)(pair0 - pair_begin) * 2 * RR_STATE : r.state.p;
         hipLaunchKernelGGL(fk_rr_window_kernel, rows_grid, b256, 0, c->stream, r.table.p, r.patience.p, (uint32_t)n, pair0, n_rows, c->strat.p, c->slow.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemsetAsync(d_state, 0, (size_t)n_rows * RR_STATE * 4, c->stream)); // every block starts fresh
@@ -3250,8 +3256,16 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
                                (uint32_t)target, r.summary.p);
             HIPCHK(c, hipGetLastError());
         }
-        HIPCHK(c, hipMemcpyAsync(block_state + (size_t)(pair0 - pair_begin) * 2 * RR_STATE, d_state, (size_t)n_rows * RR_STATE * 4, hipMemcpyDeviceToHost, c->stream));
+        if (!d_staged)
+            HIPCHK(c, hipMemcpyAsync(block_state + (size_t)(pair0 - pair_begin) * 2 * RR_STATE, d_state, (size_t)n_rows * RR_STATE * 4, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream)); // the next window reuses the device buffers
+    }
+    if (d_staged) { // the whole call has succeeded: its states join the resident accumulator (a failed or replayed call has added nothing)
+        const uint64_t n_rows_call = 2u * n_pairs_call;
+        hipLaunchKernelGGL(fkri::fk_ri_add_kernel, dim3((uint32_t)((n_rows_call + 255u) / 256u)), dim3(256), 0, c->stream, d_staged, n_rows_call,
+                           (uint32_t)target, (uint32_t)max_attempts, c->ri.counts.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (summary) { // added to the caller's buffer only when the whole call has succeeded
         std::vector<int64_t> add((size_t)n * RR_COLS);
@@ -3262,9 +3276,9 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
     return FK_OK;
 }
 
-int fk_h2h_round_robin(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
-                       uint64_t max_attempts, int32_t target_score, int32_t max_rounds, uint32_t *block_state, int64_t *summary) {
-    if (!c) return FK_ERR_ARG;
+// what fk_h2h_round_robin and fk_h2h_round_robin_resident refuse alike, before any device work; `plan` is the call's launch plan
+static int round_robin_check(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                             uint64_t max_attempts, int32_t target_score, int32_t max_rounds, LaunchPlan &plan) {
     if (!table) return fail(c, FK_ERR_ARG, "the strategy table is required");
     if (n < 2) return fail(c, FK_ERR_ARG, "a round robin needs at least two strategies, got %d", (int)n);
     const uint64_t all_pairs = (uint64_t)n * (uint64_t)(n - 1) / 2u;
@@ -3275,17 +3289,187 @@ int fk_h2h_round_robin(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t 
         return fail(c, FK_ERR_ARG, "target must be in [1, max_attempts] and max_attempts at most 2^31 - 1");
     int rc = check_max_rounds(c, max_rounds);
     if (rc) return rc;
-    const LaunchPlan plan = plan_play(plan_knobs(c), PLAN_H2H, 2, 4, false, target_score);
+    plan = plan_play(plan_knobs(c), PLAN_H2H, 2, 4, false, target_score);
     if (plan.block == 0)
         return fail(c, FK_ERR_ARG, "target_score %d: batched head-to-head plays with lean records (totals up to %d points)", target_score,
                     50 * LEAN_MAX_TARGET50);
-    if ((rc = validate_strategies(c, table, n))) return rc;
+    return validate_strategies(c, table, n);
+}
+
+int fk_h2h_round_robin(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                       uint64_t max_attempts, int32_t target_score, int32_t max_rounds, uint32_t *block_state, int64_t *summary) {
+    if (!c) return FK_ERR_ARG;
+    LaunchPlan plan{};
+    if (const int rc = round_robin_check(c, table, n, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan)) return rc;
     if (pair_begin == pair_end) return FK_OK; // an empty range touches nothing
     if (!block_state) return fail(c, FK_ERR_ARG, "block_state is required");
     // no in/out state: the replay after an out-of-memory failure is the call again with half the budget
     return replay_on_oom(c, [&] {
         return h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, block_state, summary);
     });
+}
+
+// ---- round-robin inference: resident pair counts and the inference over them (device side: fk_rr_inference.h) ----
+static uint64_t rr_table_hash(const fk_strategy *table, int32_t n) { // FNV-1a over the table's bytes (fk_strategy has no padding)
+    uint64_t h = 0xcbf29ce484222325ull;
+    const unsigned char *b = reinterpret_cast<const unsigned char *>(table);
+    for (size_t i = 0; i < (size_t)n * sizeof(fk_strategy); ++i) h = (h ^ b[i]) * 0x100000001b3ull;
+    return h;
+}
+
+// The first adding call fixes (n, range, table, family); every later one repeats them.  `fresh`: this call is the first.
+static int rr_counts_match(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t family_pair_count,
+                           uint64_t &hash, bool &fresh) {
+    if (pair_begin == pair_end) return fail(c, FK_ERR_ARG, "resident counts need a pair range that is not empty");
+    if (pair_end - pair_begin > 0x7fffffffull) return fail(c, FK_ERR_ARG, "resident counts hold at most 2^31 - 1 pairs");
+    if (family_pair_count < pair_end - pair_begin)
+        return fail(c, FK_ERR_ARG, "family_pair_count %llu is smaller than the %llu pairs of the range", (unsigned long long)family_pair_count,
+                    (unsigned long long)(pair_end - pair_begin));
+    hash = rr_table_hash(table, n);
+    fresh = !c->ri_valid;
+    if (!fresh && (n != c->ri_n || pair_begin != c->ri_begin || pair_end != c->ri_end || hash != c->ri_hash || family_pair_count != c->ri_family))
+        return fail(c, FK_ERR_ARG,
+                    "the resident counts were begun for pairs [%llu, %llu) of a table of %d strategies and a family of %llu pairs: this call's "
+                    "table, range or family differs (fk_rr_counts_reset starts over)",
+                    (unsigned long long)c->ri_begin, (unsigned long long)c->ri_end, (int)c->ri_n, (unsigned long long)c->ri_family);
+    return FK_OK;
+}
+
+// room for the call's states and, on a first call, a zeroed accumulator (it counts as resident only once the call has succeeded)
+static int rr_counts_prepare(fk_ctx *c, uint64_t n_pairs, bool fresh) {
+    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = ensure_all(c, c->ri.counts, (size_t)n_pairs * 2 * fkri::RI_COLS, c->ri.staged, (size_t)n_pairs * 2 * fkrr::RR_STATE)) return rc;
+    if (fresh) HIPCHK(c, hipMemsetAsync(c->ri.counts.p, 0, (size_t)n_pairs * 2 * fkri::RI_COLS * 8, c->stream));
+    return FK_OK;
+}
+
+static void rr_counts_fix(fk_ctx *c, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t hash, uint64_t family_pair_count) {
+    c->ri_valid = true;
+    c->ri_n = n, c->ri_begin = pair_begin, c->ri_end = pair_end, c->ri_hash = hash, c->ri_family = family_pair_count;
+}
+
+int fk_h2h_round_robin_resident(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end,
+                                uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds, int64_t *summary,
+                                uint64_t family_pair_count) {
+    if (!c) return FK_ERR_ARG;
+    LaunchPlan plan{};
+    int rc = round_robin_check(c, table, n, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan);
+    if (rc) return rc;
+    uint64_t hash = 0;
+    bool fresh = false;
+    if ((rc = rr_counts_match(c, table, n, pair_begin, pair_end, family_pair_count, hash, fresh))) return rc;
+    rc = replay_on_oom(c, [&] {
+        if (const int r = rr_counts_prepare(c, pair_end - pair_begin, fresh)) return r;
+        return h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, nullptr, summary,
+                                    c->ri.staged.p);
+    });
+    if (rc == FK_OK) rr_counts_fix(c, n, pair_begin, pair_end, hash, family_pair_count);
+    return rc;
+}
+
+int fk_rr_counts_add(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target, uint64_t max_attempts,
+                     const uint32_t *block_state, uint64_t family_pair_count) {
+    if (!c) return FK_ERR_ARG;
+    if (!table || !block_state) return fail(c, FK_ERR_ARG, "the strategy table and block_state are required");
+    if (n < 2) return fail(c, FK_ERR_ARG, "a round robin needs at least two strategies, got %d", (int)n);
+    const uint64_t all_pairs = (uint64_t)n * (uint64_t)(n - 1) / 2u;
+    if (pair_begin > pair_end || pair_end > all_pairs)
+        return fail(c, FK_ERR_ARG, "pair range [%llu, %llu) is not inside the %llu pairs of %d strategies", (unsigned long long)pair_begin,
+                    (unsigned long long)pair_end, (unsigned long long)all_pairs, (int)n);
+    if (target == 0 || target > max_attempts || max_attempts > 0x7fffffffull)
+        return fail(c, FK_ERR_ARG, "target must be in [1, max_attempts] and max_attempts at most 2^31 - 1");
+    uint64_t hash = 0;
+    bool fresh = false;
+    int rc = rr_counts_match(c, table, n, pair_begin, pair_end, family_pair_count, hash, fresh);
+    if (rc) return rc;
+    const uint64_t n_rows = 2u * (pair_end - pair_begin);
+    for (uint64_t row = 0; row < n_rows; ++row) { // a state no block can end in would poison the sums
+        const uint32_t *s = block_state + row * fkrr::RR_STATE;
+        if (s[0] > max_attempts || s[1] > target || (uint64_t)s[1] + s[2] != s[0] || (uint64_t)s[3] + s[4] != s[1])
+            return fail(c, FK_ERR_ARG, "block_state of pair %llu, order %u is not a state of a block with target %llu and max_attempts %llu",
+                        (unsigned long long)(pair_begin + row / 2u), (unsigned)(row & 1u), (unsigned long long)target, (unsigned long long)max_attempts);
+    }
+    if ((rc = rr_counts_prepare(c, pair_end - pair_begin, fresh))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ri.staged.p, block_state, (size_t)n_rows * fkrr::RR_STATE * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(fkri::fk_ri_add_kernel, dim3((uint32_t)((n_rows + 255u) / 256u)), dim3(256), 0, c->stream, c->ri.staged.p, n_rows, (uint32_t)target,
+                       (uint32_t)max_attempts, c->ri.counts.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    rr_counts_fix(c, n, pair_begin, pair_end, hash, family_pair_count);
+    return FK_OK;
+}
+
+int fk_rr_counts_reset(fk_ctx *c) {
+    if (!c) return FK_ERR_ARG;
+    c->ri_valid = false;
+    return FK_OK;
+}
+
+int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end, int64_t *class_counts,
+                    int64_t *strategy_classes) {
+    using namespace fkri;
+    if (!c) return FK_ERR_ARG;
+    if (!par || !class_counts) return fail(c, FK_ERR_ARG, "params and class_counts are required");
+    if (!c->ri_valid) return fail(c, FK_ERR_ARG, "no resident counts: fk_h2h_round_robin_resident or fk_rr_counts_add comes first");
+    if (rows && (row_begin > row_end || row_begin < c->ri_begin || row_end > c->ri_end))
+        return fail(c, FK_ERR_ARG, "row range [%llu, %llu) is not inside the resident pair range [%llu, %llu)", (unsigned long long)row_begin,
+                    (unsigned long long)row_end, (unsigned long long)c->ri_begin, (unsigned long long)c->ri_end);
+    if (!(par->family_alpha > 0.0 && par->family_alpha < 1.0)) return fail(c, FK_ERR_ARG, "family_alpha must be in (0, 1), got %g", par->family_alpha);
+    if (!(par->practical_delta > 0.0)) return fail(c, FK_ERR_ARG, "practical_delta must be positive, got %g", par->practical_delta);
+    if (!std::isnan(par->delta_equivalence) && !(par->delta_equivalence > 0.0 && par->delta_equivalence < 1.0))
+        return fail(c, FK_ERR_ARG, "delta_equivalence must be in (0, 1) or NaN (off), got %g", par->delta_equivalence);
+    if (!(par->min_candidate_completion_rate >= 0.0 && par->min_candidate_completion_rate <= 1.0))
+        return fail(c, FK_ERR_ARG, "min_candidate_completion_rate must be in [0, 1], got %g", par->min_candidate_completion_rate);
+    const uint64_t n_pairs64 = c->ri_end - c->ri_begin;
+    if (par->family_pair_count < n_pairs64)
+        return fail(c, FK_ERR_ARG, "family_pair_count %llu is smaller than the %llu pairs of the resident range", (unsigned long long)par->family_pair_count,
+                    (unsigned long long)n_pairs64);
+    if (par->family_pair_count != c->ri_family)
+        return fail(c, FK_ERR_ARG, "family_pair_count %llu is not the %llu fixed with the resident counts", (unsigned long long)par->family_pair_count,
+                    (unsigned long long)c->ri_family);
+    if (!(par->critical_ordinary > 0.0 && std::isfinite(par->critical_ordinary) && par->critical_simultaneous > 0.0 && std::isfinite(par->critical_simultaneous)))
+        return fail(c, FK_ERR_ARG, "the critical values must be positive and finite, got %g and %g", par->critical_ordinary, par->critical_simultaneous);
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    RrInferenceBufs &b = c->ri;
+    const uint32_t P = (uint32_t)n_pairs64, n = (uint32_t)c->ri_n;
+    const size_t n_rows_out = rows ? (size_t)(row_end - row_begin) : 0;
+    int rc = FK_OK;
+    if ((rc = ensure_all(c, b.sums, (size_t)n * RI_SUMS, b.strat_flags, (size_t)n, b.key, (size_t)P, b.key_sorted, (size_t)P, b.val, (size_t)P, b.val_sorted,
+                         (size_t)P, b.sim, (size_t)P, b.scaled, (size_t)P, b.running, (size_t)P, b.adjusted, (size_t)P, b.position, (size_t)P, b.class_counts, (size_t)RI_CLASSES,
+                         b.strat_out, (size_t)n * RI_STRAT_COLS, b.rows, n_rows_out)))
+        return rc;
+    Timer device_work(c, &c->timing.play_ms, SLOT_PLAY); // fk_timing: play_ms = total_ms = the entry's device work, copies back excluded
+    HIPCHK(c, hipMemsetAsync(b.sums.p, 0, (size_t)n * RI_SUMS * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.class_counts.p, 0, RI_CLASSES * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.strat_out.p, 0, (size_t)n * RI_STRAT_COLS * 8, c->stream));
+    const dim3 pair_grid((P + 255u) / 256u), b256(256);
+    hipLaunchKernelGGL(fk_ri_pair_kernel, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, par->critical_simultaneous, b.sums.p, b.key.p, b.val.p,
+                       b.sim.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fk_ri_strategy_kernel, dim3((n + 255u) / 256u), b256, 0, c->stream, b.sums.p, n, par->min_candidate_completion_rate, b.strat_flags.p,
+                       b.strat_out.p);
+    HIPCHK(c, hipGetLastError());
+    // Holm: a stable sort of the p-values' bit patterns (ties keep pair order, as argsort(kind="mergesort")), scale, running maximum, scatter
+    FK_CUB(hipcub::DeviceRadixSort::SortPairs, b.key.p, b.key_sorted.p, b.val.p, b.val_sorted.p, (int)P, 0, 64, c->stream);
+    hipLaunchKernelGGL(fk_ri_holm_scale_kernel, pair_grid, b256, 0, c->stream, b.key_sorted.p, P, b.scaled.p);
+    HIPCHK(c, hipGetLastError());
+    FK_CUB(hipcub::DeviceScan::InclusiveScan, b.scaled.p, b.running.p, hipcub::Max(), (int)P, c->stream);
+    hipLaunchKernelGGL(fk_ri_holm_scatter_kernel, pair_grid, b256, 0, c->stream, b.running.p, b.val_sorted.p, P, b.adjusted.p, b.position.p);
+    HIPCHK(c, hipGetLastError());
+    const DecideParams dp{par->family_alpha, par->practical_delta, par->delta_equivalence, par->critical_ordinary};
+    const uint32_t row_first = rows ? (uint32_t)(row_begin - c->ri_begin) : 0u, row_last = rows ? (uint32_t)(row_end - c->ri_begin) : 0u;
+    hipLaunchKernelGGL(fk_ri_decide_kernel, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, dp, b.strat_flags.p, b.sim.p, b.adjusted.p, b.position.p,
+                       b.class_counts.p, b.strat_out.p, row_first, row_last, n_rows_out ? b.rows.p : nullptr);
+    HIPCHK(c, hipGetLastError());
+    device_work.stop();
+    HIPCHK(c, hipMemcpyAsync(class_counts, b.class_counts.p, RI_CLASSES * 8, hipMemcpyDeviceToHost, c->stream));
+    if (strategy_classes) HIPCHK(c, hipMemcpyAsync(strategy_classes, b.strat_out.p, (size_t)n * RI_STRAT_COLS * 8, hipMemcpyDeviceToHost, c->stream));
+    if (n_rows_out) HIPCHK(c, hipMemcpyAsync(rows, b.rows.p, n_rows_out * sizeof(fk_rr_pair_row), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
+    return FK_OK;
 }
 
 // The NEXT fk_tournament_run / _stats call on this context will play shuffles [shuffle_begin, shuffle_end) of the same table,

@@ -86,6 +86,20 @@ struct RoundRobinBufs { // fk_h2h_round_robin
     Dev<uint32_t> bounds;  // [passes][2]
     Dev<ull> summary;
 };
+struct RrInferenceBufs { // fk_h2h_round_robin_resident, fk_rr_counts_add, fk_rr_inference
+    Dev<ull> counts;               // the accumulator: [pairs][2][fkri::RI_COLS], resident between calls
+    Dev<uint32_t> staged;          // one call's states [pairs][2][RR_STATE], added to `counts` when the call has succeeded
+    Dev<ull> sums;                 // [n][fkri::RI_SUMS] per-strategy incident sums
+    Dev<uint8_t> strat_flags;      // [n]
+    Dev<ull> key, key_sorted;      // [pairs] the p-values' bit patterns, both sort buffers
+    Dev<uint32_t> val, val_sorted; // [pairs] pair positions, both sort buffers
+    Dev<double2> sim;              // [pairs] the simultaneous interval's halved bounds
+    Dev<double> scaled, running, adjusted; // [pairs] (count - index) p and its running maximum in Holm's order; adjusted p in pair order
+    Dev<uint32_t> position;        // [pairs] Holm's positions in pair order
+    Dev<ull> class_counts;         // [fkri::RI_CLASSES]
+    Dev<long long> strat_out;      // [n][fkri::RI_STRAT_COLS]
+    Dev<fk_rr_pair_row> rows;      // the asked slice
+};
 struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
     Dev<int64_t> wins, exposures; // the stacked matrices
     Dev<fkb::KDesc> kd;

@@ -7,11 +7,13 @@ the pairs and seats the orders, ``_simulate_block_from_manifest`` :1172-1235 is 
 * ``pair_count`` / ``unrank`` / ``pair_ids`` — the pair numbering, vectorised (``itertools.combinations(range(n), 2)``);
 * ``summary_from_states`` — the host statement of the per-strategy summary the device returns;
 * ``blocks_frame`` / ``pairs_frame`` / ``strategies_frame`` — the tables ``farkle round-robin`` writes;
-* ``run_round_robin`` — the command: one sequence of engine calls per root of ``sim.seed_list``.
+* ``run_round_robin`` — the command: one sequence of engine calls per root of ``sim.seed_list``; with ``--inference`` the states stay
+  on the device and the score test, the score intervals, Holm's adjustment and the decision classes of the reference's
+  ``h2h_inference.py`` run there (``rr_inference.py`` is their host side).
 
-Out of scope: the score test, the intervals and Holm's adjustment of the reference's ``h2h_inference.py`` need ``statsmodels``,
-which this package does not depend on; the reference's power plan, schedule hashes, block ids and sidecars; resuming a partly
-played round robin; several ranks (pair ranges make the split trivial — a later change).
+Out of scope: the library route of the interval (``confint_proportions_2indep``) is not reproduced; the reference's own complete
+inversion is.  Also out of scope: the reference's power plan, schedule hashes, block ids and sidecars; its root-specific diagnostics
+and dominance graph; resuming a partly played round robin; several ranks (pair ranges make the split trivial — a later change).
 """
 from __future__ import annotations
 
@@ -280,10 +282,17 @@ def parse_pair_range(text: str | None, n: int) -> tuple[int, int]:
 
 
 def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
-                    force: bool = False, strategies=None, engine=None, world: int | None = None) -> dict:
+                    force: bool = False, strategies=None, engine=None, world: int | None = None, inference: bool = False,
+                    rows: str | None = None) -> dict:
     """``farkle round-robin``: the grid of ``cfg`` (restricted to the ids of ``strategy_ids_file``), every pair of the range, per root of
     ``sim.seed_list``.  Writes ``round_robin_pairs.parquet``, ``round_robin_strategies.parquet``, ``round_robin.json`` and, with
-    ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths."""
+    ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths.
+
+    With ``inference`` the block states stay on the device (``Engine.h2h_round_robin_resident``, one call per root), the inference runs
+    once over all roots (``Engine.rr_inference`` with the ``head2head`` settings of ``cfg``) and the command writes
+    ``round_robin_inference_pairs.parquet`` (the pairs of ``rows``, ``BEGIN:END`` in pair ids; default every pair of a range of at most
+    2^22 pairs, none beyond), ``round_robin_inference_strategies.parquet``, ``round_robin_strategies.parquet`` and the class counts in
+    ``round_robin.json``; the tables that need the states on the host (``round_robin_pairs.parquet``, ``blocks``) are not written."""
     import os
 
     import pyarrow as pa
@@ -305,6 +314,26 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     ids = [int(s.strategy_id) for s in chosen]
     n = len(chosen)
     begin, end = parse_pair_range(pairs, n)
+    if inference:
+        if blocks:
+            raise ValueError("round-robin: --blocks needs the block states on the host, --inference keeps them on the GPU: choose one")
+        if begin == end:
+            raise ValueError("round-robin: --inference needs a pair range that is not empty")
+        from . import rr_inference as ri
+
+        h2h = cfg.head2head
+        family = pair_count(n)  # the reference's unordered_pair_count: the family is the table's, whatever range this run plays
+        ri.check_params(end - begin, h2h.family_alpha, h2h.practical_delta, h2h.delta_equivalence, h2h.min_candidate_completion_rate, family)
+        if rows is None:
+            row_range = (begin, end) if end - begin <= ri.DEFAULT_ROWS_LIMIT else (begin, begin)
+        else:
+            parts = str(rows).split(":")
+            ok = len(parts) == 2 and all(not p or p.isdigit() for p in parts)
+            row_range = (int(parts[0]) if parts[0] else begin, int(parts[1]) if parts[1] else end) if ok else (0, 0)
+            if not ok or not begin <= row_range[0] <= row_range[1] <= end:
+                raise ValueError(f"round-robin: --rows takes BEGIN:END inside the played pair range [{begin}, {end}), got {rows!r}")
+    elif rows is not None:
+        raise ValueError("round-robin: --rows belongs to --inference")
     roots = [int(r) for r in (cfg.sim.seed_list if cfg.sim.seed_list else [cfg.sim.seed])]
     out_dir = Path(out) if out is not None else cfg.results_root / "h2h_round_robin"
     if out_dir.exists() and not force:
@@ -314,29 +343,52 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     summary = np.zeros((n, len(SUMMARY_COLS)), dtype=np.int64)
     states: list[np.ndarray] = []
     started = time.perf_counter()
-    for root in roots:
+    for root in roots if not inference else ():
         parts = []
         for lo in range(begin, end, CALL_BLOCKS // 2):
             st, _ = eng.h2h_round_robin(table, root, target, max_attempts, pair_begin=lo, pair_end=min(end, lo + CALL_BLOCKS // 2), summary=summary)
             parts.append(st)
         states.append(np.concatenate(parts) if parts else np.zeros((0, 2, len(STATE_COLS)), dtype=np.uint32))
         LOGGER.info("round robin root %d: %d pairs, %d attempts", root, end - begin, int(states[-1][:, :, 0].sum(dtype=np.int64)))
+    if inference:
+        eng.rr_counts_reset()
+        for root in roots:
+            eng.h2h_round_robin_resident(table, root, target, max_attempts, pair_begin=begin, pair_end=end, summary=summary,
+                                         family_pair_count=family)
+            LOGGER.info("round robin root %d: %d pairs, resident", root, end - begin)
+        knobs = dict(family_alpha=h2h.family_alpha, practical_delta=h2h.practical_delta, delta_equivalence=h2h.delta_equivalence,
+                     min_candidate_completion_rate=h2h.min_candidate_completion_rate)
+        result = eng.rr_inference(family_pair_count=family, rows=row_range, **knobs)
+        eng.rr_counts_reset()
     elapsed = time.perf_counter() - started
     out_dir.mkdir(parents=True, exist_ok=True)
-    written = {"pairs": out_dir / "round_robin_pairs.parquet", "strategies": out_dir / "round_robin_strategies.parquet",
-               "json": out_dir / "round_robin.json"}
-    frames = [(pairs_frame(ids, roots, states, target, begin, end), written["pairs"]), (strategies_frame(ids, summary), written["strategies"])]
+    written = {"strategies": out_dir / "round_robin_strategies.parquet", "json": out_dir / "round_robin.json"}
+    frames = [(strategies_frame(ids, summary), written["strategies"])]
+    if inference:
+        written["inference_pairs"] = out_dir / "round_robin_inference_pairs.parquet"
+        written["inference_strategies"] = out_dir / "round_robin_inference_strategies.parquet"
+        frames.append((ri.pairs_frame(result["rows"], ids, family_pair_count=family, **knobs), written["inference_pairs"]))
+        frames.append((ri.strategies_frame(result["strategies"], ids, h2h.min_candidate_completion_rate), written["inference_strategies"]))
+    else:
+        written["pairs"] = out_dir / "round_robin_pairs.parquet"
+        frames.append((pairs_frame(ids, roots, states, target, begin, end), written["pairs"]))
     if blocks:
         written["blocks"] = out_dir / "round_robin_blocks.parquet"
         frames.append((blocks_frame(ids, roots, states, target, max_attempts, begin, end), written["blocks"]))
     for frame, path in frames:
         runner._write_parquet_atomic(pa.Table.from_pandas(frame, preserve_index=False), path)
-    attempted = int(sum(int(st[:, :, 0].sum(dtype=np.int64)) for st in states))
-    completed = int(sum(int(st[:, :, 1].sum(dtype=np.int64)) for st in states))
+    if inference:  # every game of a pair is incident to its two strategies
+        attempted, completed = int(result["strategies"][:, 7].sum()) // 2, int(result["strategies"][:, 8].sum()) // 2
+    else:
+        attempted = int(sum(int(st[:, :, 0].sum(dtype=np.int64)) for st in states))
+        completed = int(sum(int(st[:, :, 1].sum(dtype=np.int64)) for st in states))
     report = {"strategies": n, "strategy_ids_file": None if strategy_ids_file is None else str(strategy_ids_file), "roots": roots,
               "block_games": target, "max_attempt_multiplier": float(multiplier), "max_attempts": max_attempts,
               "target_score": 10_000, "max_rounds": 200, "pair_begin": begin, "pair_end": end, "pairs_total": pair_count(n),
               "blocks": 2 * (end - begin) * len(roots), "games_attempted": attempted, "games_completed": completed,
               "elapsed_seconds": elapsed, "files": sorted(p.name for p in written.values())}
+    if inference:
+        report["inference"] = {"class_counts": {name: int(v) for name, v in zip(ri.DECISION_CLASSES, result["class_counts"])},
+                               "family_pair_count": family, "row_begin": row_range[0], "row_end": row_range[1], **knobs}
     runner._atomic_write_bytes(written["json"], (json.dumps(report, indent=2, sort_keys=True) + "\n").encode("utf-8"))
     return written

@@ -559,6 +559,105 @@ int fk_h2h_round_robin(fk_ctx *ctx, const fk_strategy *table, int32_t n, uint64_
                        uint64_t pair_end, uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds,
                        uint32_t *block_state, int64_t *summary);
 
+/* ---- round-robin inference: the score test, the score intervals, Holm's adjustment and the decision class of every pair of a
+ * resident pair range (src/farkle/analysis/h2h_inference.py), on counts that stay on the device ----
+ *
+ * The context owns ONE accumulator: for every (pair, order) of a pair range [pair_begin, pair_end) of an n-row table the 64-bit
+ * sums over the roots added so far of games_attempted, games_completed, games_safety_limit, wins_seat1, wins_seat2,
+ * n_completed_required (the block's target), max_attempts, the (root, order) cells added and those of them that ended `complete`
+ * (completed == target) — what _combine_within_order (h2h_inference.py:563-635) sums across roots without mixing the orders.
+ * The first adding call after fk_rr_counts_reset (or on a fresh context) fixes (n, pair_begin, pair_end), a hash of the table and
+ * family_pair_count; every later one must repeat them (FK_ERR_ARG otherwise).  A failed call adds nothing.
+ *
+ * fk_h2h_round_robin_resident  fk_h2h_round_robin without block_state: the same windows, generations, passes, apply and summary
+ *                              kernels play the same games; the states stay on the device and are added to the accumulator when the
+ *                              whole call has succeeded (so that a failed or replayed call adds nothing, the summary's rule).
+ *                              An empty range is FK_ERR_ARG here: there is nothing to keep resident.
+ * fk_rr_counts_add             one root's host-held states [pair_end - pair_begin][2][FK_RR_STATE_COLS], as fk_h2h_round_robin
+ *                              returned them for this target / max_attempts (earlier runs, other ranks), into the accumulator
+ * fk_rr_counts_reset           forgets the accumulator's contents and what was fixed with them
+ *
+ * family_pair_count is the reference's unordered_pair_count (:711): it sizes the Bonferroni alpha of the simultaneous interval
+ * (family_alpha / family_pair_count, :715) and is at least the resident range's pair count; a table-wide range passes the table's
+ * pair count.  Holm's family is the resident range itself. */
+int fk_h2h_round_robin_resident(fk_ctx *ctx, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin,
+                                uint64_t pair_end, uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds,
+                                int64_t *summary, uint64_t family_pair_count);
+int fk_rr_counts_add(fk_ctx *ctx, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                     uint64_t max_attempts, const uint32_t *block_state, uint64_t family_pair_count);
+int fk_rr_counts_reset(fk_ctx *ctx);
+
+typedef struct {
+    double family_alpha;                  /* head2head.family_alpha: Holm's level and the ordinary interval's alpha */
+    double practical_delta;               /* > 0 */
+    double delta_equivalence;             /* in (0, 1), or NaN: equivalence is off (the reference's None) */
+    double min_candidate_completion_rate; /* in [0, 1] */
+    double critical_ordinary;             /* norm.isf(family_alpha / 2), evaluated by the caller (:255) */
+    double critical_simultaneous;         /* norm.isf(family_alpha / family_pair_count / 2) */
+    uint64_t family_pair_count;           /* as fixed with the accumulator */
+} fk_rr_inference_params;
+
+/* One pair of _pairwise_estimates' frame (:739-860, :870-913), 224 bytes.  A is table[strategy_a], B is table[strategy_b],
+ * strategy_a < strategy_b.  The counts are written for every pair; the doubles that the reference leaves None for a pair
+ * without a test are NaN.  The d bounds are the halved interval bounds (:851-854). */
+#define FK_RR_FLAG_INFERENTIALLY_VIABLE 1 /* = formal_test_performed */
+#define FK_RR_FLAG_OPERATIONALLY_VIABLE 2
+#define FK_RR_FLAG_CLAIM_ELIGIBLE 4
+#define FK_RR_FLAG_HOLM_REJECT_BEFORE_VIABILITY 8
+#define FK_RR_FLAG_HOLM_REJECT 16
+enum {
+    FK_RR_PRACTICAL_DOMINANCE_A = 0,
+    FK_RR_PRACTICAL_DOMINANCE_B = 1,
+    FK_RR_STATISTICAL_ONLY_ADVANTAGE_A = 2,
+    FK_RR_STATISTICAL_ONLY_ADVANTAGE_B = 3,
+    FK_RR_EQUIVALENT = 4,
+    FK_RR_UNRESOLVED = 5,
+    FK_RR_UNRESOLVED_NONVIABLE = 6
+};
+#define FK_RR_CLASSES 7
+#define FK_RR_STRATEGY_COLS 12
+typedef struct {
+    uint64_t pair_id;
+    int64_t games_attempted, games_completed, games_safety_limit, n_completed_required; /* both orders */
+    int64_t n_ab, n_ba, seat1_a_wins_ab, seat1_b_wins_ba, seat2_a_wins_ba, balanced_a_wins;
+    int64_t holm_order; /* 1-based position in Holm's stable order; 0 = no test performed */
+    double completion_game_rate, q_ab, q_ba, raw_order_rate_difference, d_ab, score_null_proportion, score_z, score_p_value;
+    double ordinary_d_low, ordinary_d_high, simultaneous_d_low, simultaneous_d_high, balanced_a_win_rate, holm_adjusted_p;
+    uint32_t strategy_a, strategy_b; /* table rows */
+    uint8_t flags;                   /* FK_RR_FLAG_* */
+    uint8_t decision_class;          /* FK_RR_PRACTICAL_DOMINANCE_A .. FK_RR_UNRESOLVED_NONVIABLE */
+    uint8_t pad[6];
+} fk_rr_pair_row;
+
+/* The inference over the resident range, in the stages of _viability_status (:638-700) and _pairwise_estimates (:703-915):
+ *   viability   a pair is inferentially viable when every cell of both orders is complete and completed == required; a strategy is
+ *               operationally viable when completed / attempted over its incident pairs (one IEEE division) is at least
+ *               min_candidate_completion_rate, inferentially viable when all its incident pairs are; a pair is claim-eligible
+ *               when it is viable and both its strategies are operationally viable (:754-756)
+ *   score test  two_proportion_score_test (:68-99) on x_ab = A's wins in order 0, x_ba = B's wins in order 1, in the reference's
+ *               statement order without contraction; p = erfc(|z| / sqrt 2)
+ *   intervals   at family_alpha and at family_alpha / family_pair_count: the reference's own complete inversion
+ *               (_score_difference_interval_fallback, :234-277) — the swap for a positive estimate, the dyadic bracket of
+ *               _score_interval_bound (:191-231), a bracketing solver down to a bracket of 2^-44, the symmetric rule; the library
+ *               route of score_difference_interval (confint_proportions_2indep, :118-138) is not reproduced
+ *   Holm        _holm_adjust (:280-295) over ALL pairs of the range, a pair without a test entering as 1.0 (:864-868): a stable
+ *               radix sort of the p-values' bit patterns, (count - index) * p, a running maximum, min(1, .)
+ *   class       the chain of :886-909
+ * Outputs:
+ *   rows              nullable: the pairs [row_begin, row_end) (pair ids, inside the resident range), in order
+ *   class_counts      [FK_RR_CLASSES] pairs of the range per decision class
+ *   strategy_classes  nullable: [n][FK_RR_STRATEGY_COLS] per strategy, over its incident pairs of the range — 0 pairs it wins by
+ *                     practical dominance | 1 loses by it | 2 wins by statistical-only advantage | 3 loses by it | 4 equivalent |
+ *                     5 unresolved | 6 unresolved_nonviable | 7 games_attempted | 8 games_completed | 9 games_safety_limit |
+ *                     10 operationally_viable | 11 inferentially_viable (the completion rate is 8 / 7)
+ * fk_timing: play_ms = total_ms = the entry's device work between two events on the context's stream (the copies back excluded).
+ * FK_ERR_ARG before any device work: no resident counts; a row range outside the resident one (with rows given); family_alpha
+ * outside (0, 1); practical_delta <= 0; delta_equivalence outside (0, 1); min_candidate_completion_rate outside [0, 1];
+ * family_pair_count smaller than the range or other than the one fixed with the counts; a critical value that is not positive
+ * and finite; a range of 2^31 pairs or more. */
+int fk_rr_inference(fk_ctx *ctx, const fk_rr_inference_params *params, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
+                    int64_t *class_counts, int64_t *strategy_classes);
+
 /* ---- multi-GPU: one process per GPU, one context per process, ONE exchange ----
  * The (seed x shuffle x game) space partitions with no data dependency; the only collective of the path is the integer
  * SUM of the per-strategy tally to one rank — the analogue of OutcomeCounter.absorb + _reduce_metric_chunk_payloads
