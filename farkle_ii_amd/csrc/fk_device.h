@@ -1054,9 +1054,14 @@ __host__ __device__ inline uint32_t pk_max_u16(uint32_t a, uint32_t b) {
 //   - highest_turn as a packed 16-bit maximum with the banked turn (its high half is 0: the other half of cB stays).
 // (the part behind the discard entry's decoding: `score50`, `used` = the roll's score / 50 and dice used after the discards; `inc_c`,
 // `inc_d` = the increments of cC and cD)
-template <bool LEAN, uint32_t MIXED>
-__host__ __device__ inline bool roll_back_end50_core(int32_t score50, uint32_t used, uint32_t inc_c, uint32_t inc_d, uint32_t n, const Strat50 &sp,
-                                                     uint32_t uniform_bits, bool final_round, int32_t stb50, RollRegs &r, bool &overflow) {
+// AS_LANES (round 13, the two-seat lean kernels): `over` is returned as the lane mask it is formed as, for the table advance on masks,
+// and `final_round` may arrive as the lane mask those kernels carry (FR = lanes_t: no ballot of a boolean, which costs two vector
+// instructions where the boolean is not a single compare).
+__host__ __device__ inline lanes_t as_lanes(bool p) { return lanes(p); }
+__host__ __device__ inline lanes_t as_lanes(lanes_t m) { return m; }
+template <bool LEAN, uint32_t MIXED, bool AS_LANES = false, class FR = bool>
+__host__ __device__ inline auto roll_back_end50_core(int32_t score50, uint32_t used, uint32_t inc_c, uint32_t inc_d, uint32_t n, const Strat50 &sp,
+                                                     uint32_t uniform_bits, FR final_round, int32_t stb50, RollRegs &r, bool &overflow) {
     const bool farkle = score50 == 0;
     r.cA += 1u + (farkle ? 0x10000u : 0u);
     r.cC += inc_c;
@@ -1068,7 +1073,7 @@ __host__ __device__ inline bool roll_back_end50_core(int32_t score50, uint32_t u
     const bool hot = in_lanes(hot_l);
     if (LEAN) r.cB += hot ? 0x10000u : 0u;
     else r.cE += hot ? 1u : 0u;
-    const lanes_t fr = lanes(final_round), above = lanes(r.score + r.turn_score > stb50);
+    const lanes_t fr = as_lanes(final_round), above = lanes(r.score + r.turn_score > stb50);
     const lanes_t stop = fr & above & ~flag_lanes<MIXED>(sp, uniform_bits, SF_RUN_UP);
     const lanes_t force = fr & ~above;
     const lanes_t entry = lanes((r.cE & BE_HAS_SCORED) == 0u) & lanes(r.turn_score < 10); // 500 points (strategies.py:249)
@@ -1084,7 +1089,8 @@ __host__ __device__ inline bool roll_back_end50_core(int32_t score50, uint32_t u
     if (LEAN) r.cE += banked;
     r.cB = pk_max_u16(r.cB, banked);
     overflow = roll_overflow50(r);
-    return over;
+    if constexpr (AS_LANES) return over_l;
+    else return over;
 }
 
 // ... from the byte table's entry (round 8's form; the host checks' one) ...
@@ -1099,12 +1105,12 @@ __host__ __device__ inline bool roll_back_end50(uint32_t e, uint32_t choice, uin
 }
 
 // ... and from the wide entry (round 9, the game kernels' form): four fields, each one instruction away from its use
-template <bool LEAN, uint32_t MIXED = 0xffffu>
-__host__ __device__ inline bool roll_back_end50w(uint32_t e, uint32_t x, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, bool final_round,
+template <bool LEAN, uint32_t MIXED = 0xffffu, bool AS_LANES = false, class FR = bool>
+__host__ __device__ inline auto roll_back_end50w(uint32_t e, uint32_t x, uint32_t n, const Strat50 &sp, uint32_t uniform_bits, FR final_round,
                                                  int32_t stb50, RollRegs &r, bool &overflow) {
     const int32_t score50 = (int32_t)(e & 63u) - (int32_t)((x >> DW_POINTS_SHIFT) & 0xffu);
     const uint32_t used = ((e >> 6) & 7u) - (x >> DW_DICE_SHIFT);
-    return roll_back_end50_core<LEAN, MIXED>(score50, used, x & DW_INC, (x >> DW_D1_SHIFT) & DW_INC, n, sp, uniform_bits, final_round, stb50, r, overflow);
+    return roll_back_end50_core<LEAN, MIXED, AS_LANES, FR>(score50, used, x & DW_INC, (x >> DW_D1_SHIFT) & DW_INC, n, sp, uniform_bits, final_round, stb50, r, overflow);
 }
 
 // ---- two-seat table advance (engine.py:453-472, 523-550) after a roll: the game-level half of the back end, for every lane of the trip ----
@@ -1131,6 +1137,30 @@ __host__ __device__ inline Advance2 advance2_table50(bool over, int32_t score, i
     const bool sw = over & !ended;
     t.seat ^= sw ? 1u : 0u;
     return Advance2{ended, sw};
+}
+
+// The same rule on flags of any width (round 13).  The two-seat lean kernels carry the final-round flag and the owner's seat across the
+// roll loop as booleans, which the compiler keeps as 64-lane masks in SGPR pairs (one bit per lane), so the advance is mask algebra on
+// the scalar unit and neither flag is compared out of a vector register in every trip.  M = bool: one lane (the kernels' form; on the
+// device that IS the wave's lane mask).  M = lanes_t: 64 games at once, bit l = game l; tests/native/advance2_masks_host_check.hip
+// compares that form with advance2_table50 lane by lane, so the rule holds as pure mask operations (and, or, complement).
+// In: the turn is over; the owner's banked total has reached the target; rounds >= max_rounds; the owner is seat 1; the game is in its
+// final round.  Out: the game has ended; the turn passes (seat1 ^= sw); the first trigger (score_to_beat := score there); the new
+// final-round flag; a normal round closes and another begins (rounds += 1 there).
+template <class M>
+struct Advance2Flags {
+    M ended, sw, trig, in_final, closes;
+};
+__host__ __device__ inline bool flag_not(bool x) { return !x; }
+__host__ __device__ inline lanes_t flag_not(lanes_t x) { return ~x; }
+template <class M>
+__host__ __device__ inline Advance2Flags<M> advance2_flags50(M over, M reached, M at_limit, M seat1, M in_final) {
+    const M normal = over & flag_not(in_final);
+    const M trig = normal & reached;                     // engine.py:462-468
+    const M close = normal & flag_not(reached) & seat1;  // seat 1 closes a normal round
+    const M last = close & at_limit;                     // `while rounds < max_rounds` ends (engine.py:453, 472)
+    const M ended = last | (over & in_final);            // the final round's one turn has been played
+    return Advance2Flags<M>{ended, M(over & flag_not(ended)), trig, M(in_final | trig), M(close & flag_not(last))};
 }
 
 // ---- the end of a two-seat game on lean records (run_tournament.py:375-391, engine.py:477): who won, and the winner's ten metrics ----

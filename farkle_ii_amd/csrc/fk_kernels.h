@@ -821,6 +821,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     enum : uint32_t { ST_FRESH = 0, ST_ACTIVE = 1, ST_ENDED = 2, ST_DONE = 3 };
     uint32_t st = ST_FRESH;
     uint32_t pool_next = 0, pool_end = 0, exhausted = 0; // wave-uniform ticket pool
+    // Round 13, the two-seat lean instances: the per-lane game flags are carried as wave-uniform lane masks in SGPR pairs (bit l = lane l),
+    // not as values in vector registers that every trip compares again.  A lane plays (m_active), holds an ended game that waits for the
+    // hand-over (m_ended), or is done (neither; before the wave's first hand-over every lane is fresh: `fresh`).  m_final: the game is in
+    // its final round; m_seat1: seat 1 owns the turn.  They are written only where control flow is wave-uniform, from ballots of the
+    // lane masks this toolchain forms without a vector instruction: ballots of single compares, combined on the scalar unit (a ballot of
+    // a compound boolean is a v_cndmask and a v_cmp, and a wave-uniform value written under a divergent branch becomes a per-lane
+    // one).  So a roll trip of these instances is run by EVERY lane of the wave, in wave-uniform control flow, and the masks decide what
+    // it may change: a lane that does not play computes a roll from its own last state and stores nothing (roll_step).  Vector
+    // instructions issue per wave, so the idle lanes' arithmetic costs nothing.  The rare places (a hand-over, a sample point) leave a
+    // boolean per lane (lane_raised ... lane_none) and ballot it once.  `st`, `final_round` and `seat` are not carried by these
+    // instances: the hand-over forms the latter two from the masks for the end of a game.
+    // `fresh` is not a lane state: it is one wave-level bit, set until the wave's first hand-over, which serves every lane (none has a game
+    // to finish).  After that hand-over every lane is in exactly one of: m_active, m_ended, neither (done).
+    lanes_t m_active = 0, m_ended = 0, m_final = 0, m_seat1 = 0;
+    uint32_t fresh = 1;
+    bool lane_raised = false, lane_dealt = false, lane_none = false;
 
     // game registers
     uint32_t game_id = 0, seat = 0, rounds = 0, max_rounds = 0, trigger = 0, seed_slot = 0;
@@ -963,12 +979,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
 
     auto raise = [&](int32_t code) {
         if (atomicCAS(&a.err[0], 0, code) == 0) a.err[1] = (int32_t)game_id;
-        st = ST_DONE;
+        // PK2 has no `st`: each of its three callers takes the raising lanes out of the masks itself — roll_step (`raised`, into
+        // advance2), sample_guards (m_active, in the roll loop) and end_guards (m_ended, in handover), the latter two through lane_raised
+        if constexpr (!PK2) st = ST_DONE;
     };
 
     // ---- finished game -> LDS tallies or one result record (run_tournament.py:375-391) ----
     auto finish_game = [&]() {
-        if (PK2 && max_rounds != 0u) seat = own_rec != lds_addr(lane_base) ? 1u : 0u; // the owner of the game's last turn (a game without rounds has none)
+        // (PK2: `seat`, the owner of the game's last turn, and `final_round` come from the lane masks, see handover)
         const bool completed = PK2 ? (final_round != 0u) : (safety == 0u); // two seats: a game ends in its final round or at the round limit
         uint32_t w = 0;
         int32_t best = seat_score(0);
@@ -1131,23 +1149,28 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         }
     };
 
-    // ---- two-player tables (PK2): the table advance as straight-line selects for EVERY lane of the trip ----
+    // ---- two-player tables (PK2): the table advance as straight-line code for EVERY lane of the trip ----
     // Some lane of a 64-lane wave ends its turn in nearly every trip, so `advance` above — an exec-masked region of ~47
     // instructions for the third of the lanes whose turn ended — is paid by the whole wave every trip.  With two seats the
     // rules collapse (engine.py:453-472, 523-550): the next seat is always the other one; a turn played in the final round
-    // is the last of the game; the first score at or above the target starts the final round.  The rules are fk_device.h's
-    // advance2_table50 (plain booleans, which the compiler keeps as lane masks here, and one select per register that changes); only
-    // the change of owner stays under the exec mask: the increment load, and strategy and turn registers switched by xor / constants
-    // (round 8); since round 9 the owner is known by the LDS address of its record (own_rec, toggled there by one subtraction) and the
-    // increment's address by an xor, so no seat number is carried and no record address is formed per roll.  Neither the trigger seat nor the safety flag is carried: both follow from the state a two-seat game ends
-    // in (seat_turns, finish_game; tests/native/roll_back_end_host_check.hip asserts the two relations on advance2_table50), so the
-    // registers `trigger` and `safety` are not touched by these instances after init_game.
-    auto advance2 = [&](bool over, int32_t score) __attribute__((always_inline)) {
-        Table2 t{own_rec != lds_addr(lane_base) ? 1u : 0u, rounds, 0u, final_round, 0u, score_to_beat}; // trigger, safety: not carried (above)
-        const Advance2 adv = advance2_table50(over, score, a.target50, max_rounds, t); // fk_device.h
-        rounds = t.rounds, final_round = t.final_round, score_to_beat = t.score_to_beat;
-        st = adv.ended ? (uint32_t)ST_ENDED : st;
-        if (adv.sw) { // the turn passes (t.seat): the other seat, the other strategy = an xor with the game's difference word, fresh turn
+    // is the last of the game; the first score at or above the target starts the final round.  Since round 13 the rule is
+    // fk_device.h's advance2_flags50 on 64-lane masks (advance2_table50 restated; tests/native/advance2_masks_host_check.hip
+    // compares the two): `over` arrives as the mask of the lanes that played this trip, did not raise and whose turn is over, the
+    // owner's seat and the final round are read from the carried masks m_seat1 / m_final and written back here, on the scalar
+    // unit, in wave-uniform control flow; `raised`: the lanes that raised an error in this trip (they are done).  Only the
+    // change of owner stays under an exec mask: strategy, increment and turn registers switched by xor / constants (rounds
+    // 8 and 12) and the LDS address of the owner's record toggled by one subtraction (round 9: no record address is formed per
+    // roll).  own_rec is an address only: the seat is m_seat1, and the hand-over turns that into `seat` for the end of a game.
+    // Neither the trigger seat nor the safety flag is carried: both follow from the state a two-seat game ends in (seat_turns,
+    // finish_game; tests/native/roll_back_end_host_check.hip asserts the two relations on advance2_table50), so the registers
+    // `trigger` and `safety` are not touched by these instances after init_game.
+    auto advance2 = [&](lanes_t over, lanes_t raised, int32_t score) __attribute__((always_inline)) {
+        const Advance2Flags<lanes_t> adv = advance2_flags50<lanes_t>(over, lanes(score >= a.target50), lanes(rounds >= max_rounds), m_seat1, m_final);
+        rounds += in_lanes(adv.closes) ? 1u : 0u;
+        score_to_beat = in_lanes(adv.trig) ? score : score_to_beat; // engine.py:464
+        m_final = adv.in_final, m_seat1 ^= adv.sw;
+        m_active &= ~(adv.ended | raised), m_ended |= adv.ended;
+        if (in_lanes(adv.sw)) { // the turn passes (t.seat): the other seat, the other strategy = an xor with the game's difference word, fresh turn
             own_rec = (lds_addr(lane_base) + lds_addr(lane_base + SEAT_STRIDE)) - own_rec; // the sum of the two records' addresses less this one
             own_thr ^= (int32_t)pk_delta.x;
             own_bits ^= pk_delta.y;
@@ -1193,7 +1216,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         // has_buf as a toggle (round 12): a roll of n dice consumes n 32-bit words, so the flag flips iff n is odd — its bit of cE is one
         // xor away, where extracting, adding, masking and merging took six instructions.  (A replayed roll may draw more words: below.)
         uint32_t hb_flip = (n << CE_HAS_BUF_SHIFT) & CE_HAS_BUF;
-        if (detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
+        // (PK2, round 13: only a PLAYING lane replays.  The replay holds the roll's one unbounded loop, Lemire's redraw, and a lane that
+        // does not play rolls from whatever its record address holds: a lane that was never dealt a game has increment 0 and reads the
+        // block's first record, which may be LDS nobody has written; state 0 with increment 0 is a fixed point whose output is
+        // rejected every time.  Without the replay such a lane's roll is straight-line code on in-range table keys.)
+        if (PK2 ? in_lanes(lanes(detour) & m_active) : detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
             asm volatile("" ::: "memory"); // really re-read it: values forwarded from the loads above would stay live across the whole roll
             if (PK2) { // (F_LO0 ... F_BUF are the first five dwords of a lean record)
                 const uint32_t *r0 = reinterpret_cast<const uint32_t *>(rec);
@@ -1218,10 +1245,36 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         const uint32_t choice = discard_lookup50w(a.score_lut, reinterpret_cast<const uint32_t *>(a.discard_lut + DISCARD_LUT_KEYS), key, (int32_t)n, turn_score, sp, entry);
         RollRegs rg{cA, cB, cC, cD, cE, score, dice, turn_score};
         bool overflow; // (not read here: roll_guards50 below restates it)
-        const bool over = roll_back_end50w<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
+        auto back_end = [&]() __attribute__((always_inline)) { // (PK2: the final round goes in, and `over` comes back, as lanes)
+            if constexpr (PK2) return roll_back_end50w<LEAN, MIXED, true, lanes_t>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), m_final, score_to_beat, rg, overflow);
+            else return roll_back_end50w<LEAN, MIXED>(entry, choice, n, sp, a.uflags & (0xff00u & ~MIXED), final_round != 0u, score_to_beat, rg, overflow);
+        };
+        const auto over = back_end();
         cA = rg.cA, cB = rg.cB, cC = rg.cC, cD = rg.cD, cE = rg.cE, score = rg.score, dice = rg.dice, turn_score = rg.turn_score;
         // one rare exit for all error conditions: the roll limit, then the u16 guard bands (fk_device.h: roll_guards50; `overflow` is its second half)
         // (GUARD_SAMPLED instances: the roll limit and the turn-score band here, the three counter bands in sample_guards and end_guards below)
+        if constexpr (PK2) {
+            // every lane of the wave has computed a roll (see the masks' declaration): the playing ones that stay inside the roll limit and
+            // the turn-score band (roll_guards50_turn's two compares, as masks) store theirs and advance.  A lane that does not play stores
+            // nothing and changes neither `rounds` nor `score_to_beat` (their masks are cut to the playing lanes); it does run its turn
+            // registers on: dice stays in 1..6 (every roll leaves it there), rolls_this_turn counts up unsigned, and turn_score grows by at
+            // most 60 a trip until a farkle zeroes it (no roll limit stops such a lane: in two's complement it would take 3.5e7 trips without
+            // a farkle to wrap, and the value only feeds clamped table keys and compares whose outcome the masks drop).  All three are set
+            // again where the lane is dealt a game.
+            const lanes_t raised = (lanes(rolls_before >= RG_TURN_ROLLS) | lanes(rg.turn_score >= (int32_t)(RG_TURN50 + 1u))) & m_active;
+            if (in_lanes(raised)) raise(rolls_before >= RG_TURN_ROLLS ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
+            const lanes_t ok = m_active & ~raised;
+            if (in_lanes(ok)) {
+                cE ^= hb_flip;
+                rec[0] = make_uint2((uint32_t)rng.lo, (uint32_t)(rng.lo >> 32));
+                rec[1] = make_uint2((uint32_t)rng.hi, (uint32_t)(rng.hi >> 32));
+                rec[2] = make_uint2(rng.buf, cA);
+                rec[3] = make_uint2(cB, cC);
+                rec[4] = make_uint2(cD, cE);
+            }
+            advance2(over & ok, raised, score);
+            return;
+        }
         const uint32_t guard = GUARD_SAMPLED ? roll_guards50_turn(rolls_before, rg) : roll_guards50(rolls_before, rg);
         if (guard != RG_NONE) {
             raise(guard == RG_ROLL_LIMIT ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
@@ -1261,8 +1314,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             L(F_CD, s) = cD;
             L(F_CE, s) = cE;
         }
-        if (PK2) advance2(over, score);
-        else if (!GS && over) advance(score);
+        if (!GS && over) advance(score);
     };
 
     // ---- the two-seat lean instance of tournament and game-list launches (round 10): a flat hand-over ----
@@ -1374,7 +1426,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         rolls_this_turn = 0;
         const bool none = max_rounds == 0u; // `while rounds < max_rounds` never entered (engine.py:453)
         rounds = none ? 0u : 1u;
-        st = none ? (uint32_t)ST_ENDED : (uint32_t)ST_ACTIVE;
+        lane_none = none; // (handover: such a game has ended where it is dealt)
     };
 
     // the lane's ended game -> LDS tallies, final state records, result record (what finish_game does, for two lean records)
@@ -1392,7 +1444,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         if (ho & HO_GS_OUT) { // final records of both seats -> state store, in its format (R_*): score and n_turns spelled out
             // n_turns (seat_turns): every seat began `rounds` turns, plus the final round's one turn, which the seat that did not trigger
             // it played and still owns; a game without rounds has no owner
-            const uint32_t last = (max_rounds != 0u && own_rec != lds_addr(lane_base)) ? 1u : 0u;
+            const uint32_t last = seat; // (from m_seat1, see handover; clear in a game without rounds)
             const uint32_t t0 = rounds + ((final_round != 0u && last == 0u) ? 1u : 0u), t1 = rounds; // seat s < (last ^ 1): only seat 0, when seat 1 triggered
             const uint2 *r0 = reinterpret_cast<const uint2 *>(w0), *r1 = reinterpret_cast<const uint2 *>(w1);
             const uint2 p0 = r0[0], p1 = r0[1], p2 = r0[2], p3 = r0[3], p4 = r0[4], q0 = r1[0], q1 = r1[1], q2 = r1[2], q3 = r1[3], q4 = r1[4];
@@ -1452,10 +1504,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         asm volatile("");
         const LeanCounters c0 = lane_counters(0u), c1 = lane_counters(1u); // a lane that does not play reads its own slots and is not heard
         const bool over = sampled_overflow50(c0.cA, c0.cC, c0.cD) | sampled_overflow50(c1.cA, c1.cC, c1.cD);
-        if (over && st == ST_ACTIVE) raise(FK_ERR_COUNTER_OVERFLOW);
+        if (over && in_lanes(m_active)) raise(FK_ERR_COUNTER_OVERFLOW), lane_raised = true;
     };
     auto end_guards = [&]() __attribute__((always_inline)) { // in front of a hand-over, the lanes whose game has ended
-        if (st == ST_ENDED && game_end_overflow50(lane_counters(0u), lane_counters(1u))) raise(FK_ERR_COUNTER_OVERFLOW);
+        if (in_lanes(m_ended) && game_end_overflow50(lane_counters(0u), lane_counters(1u))) raise(FK_ERR_COUNTER_OVERFLOW), lane_raised = true;
     };
     uint32_t guard_trips = 0; // wave-uniform: trips of the roll loop since the wave started
 
@@ -1464,11 +1516,18 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     auto handover = [&](uint64_t waiting, auto flat) {
         constexpr bool FLAT = decltype(flat)::value;
         if constexpr (GUARD_SAMPLED) { // a lane that raises is done: it neither finishes its game nor takes a ticket
+            lane_raised = false;
             end_guards();
-            waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
+            const lanes_t raised = lanes(lane_raised);
+            m_ended &= ~raised, waiting &= ~raised;
         }
-        const bool mine = (st == ST_FRESH || st == ST_ENDED);
-        if (st == ST_ENDED) {
+        const bool mine = PK2 ? in_lanes(waiting) : (st == ST_FRESH || st == ST_ENDED);
+        if constexpr (PK2) { // the end of a game reads the two flags per lane: formed here, once per hand-over, from the carried masks
+            seat = in_lanes(m_seat1) ? 1u : 0u;
+            final_round = in_lanes(m_final) ? 1u : 0u;
+            lane_dealt = false, lane_none = false;
+        }
+        if (PK2 ? in_lanes(m_ended) : st == ST_ENDED) {
             if constexpr (FLAT) finish_game2();
             else finish_game();
         }
@@ -1495,9 +1554,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             // and each had its own block of copies of the carried registers
             const uint32_t rank = mbcnt(waiting);
             uint32_t ticket = rank < avail ? pool_next + rank : (rank - avail < new_avail) ? new_base + (rank - avail) : 0xffffffffu;
-            ticket = mine ? ticket : 0xffffffffu;
-            st = (mine && ticket == 0xffffffffu) ? (uint32_t)ST_DONE : st;
-            if (ticket != 0xffffffffu) init_game2(ticket);
+            ticket = mine ? ticket : 0xffffffffu; // (a waiting lane without a ticket is done: it is in no mask below)
+            lane_dealt = ticket != 0xffffffffu;
+            if (lane_dealt) init_game2(ticket);
         } else if (mine) {
             const uint32_t rank = mbcnt(waiting);
             uint32_t ticket = 0xffffffffu;
@@ -1505,9 +1564,15 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             else if (rank - avail < new_avail) ticket = new_base + (rank - avail);
             if (ticket != 0xffffffffu) {
                 init_game(a.sched ? a.sched[ticket] : ticket, ticket);
+                if constexpr (PK2) lane_dealt = true, lane_none = max_rounds == 0u;
             } else {
                 st = ST_DONE;
             }
+        }
+        if constexpr (PK2) { // every waiting lane has been served or is done; a dealt game starts with seat 0, outside its final round
+            const lanes_t dealt = lanes(lane_dealt), none = lanes(lane_none);
+            m_ended = none, m_active |= dealt & ~none, m_final &= ~dealt, m_seat1 &= ~dealt;
+            fresh = 0u;
         }
         if (n <= avail) {
             pool_next += n;
@@ -1540,8 +1605,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
     };
     auto play = [&](auto flat) {
         while (true) {
-            uint64_t waiting = __ballot(st == ST_FRESH || st == ST_ENDED);
-            uint64_t active = __ballot(st == ST_ACTIVE);
+            uint64_t waiting = PK2 ? (fresh ? __ballot(true) : m_ended) : __ballot(st == ST_FRESH || st == ST_ENDED);
+            uint64_t active = PK2 ? m_active : __ballot(st == ST_ACTIVE);
             if (!(waiting | active)) break; // no lane is active and none waits: the wave has drained
             if (handover_due(waiting, active, flat)) {
 #ifdef FK_COUNT_HANDOVER
@@ -1554,22 +1619,35 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 // lane.  A trip in which nobody plays (every dealt game had max_rounds 0, or no ticket was left) costs one ballot.
                 if constexpr (!decltype(flat)::value) continue;
 #ifdef FK_COUNT_HANDOVER // (the first trip's counts are of the lanes as the hand-over left them, as after the general copy's `continue`)
-                waiting = __ballot(st == ST_FRESH || st == ST_ENDED), active = __ballot(st == ST_ACTIVE);
+                if constexpr (PK2) waiting = m_ended, active = m_active;
+                else waiting = __ballot(st == ST_FRESH || st == ST_ENDED), active = __ballot(st == ST_ACTIVE);
 #endif
             }
-            bool playing = st == ST_ACTIVE;
+            bool playing = !PK2 && st == ST_ACTIVE; // (PK2: the masks, not a lane predicate, say who plays)
             do {
 #ifdef FK_COUNT_HANDOVER
                 cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(waiting), cnt_rolling += (uint32_t)__popcll(active);
 #endif
-                if (playing) roll_step();
+                if constexpr (PK2) {
+                    if (m_active) roll_step(); // a scalar branch: the whole wave rolls, the masks say for whom (roll_step)
+                } else if (playing) {
+                    roll_step();
+                }
                 if constexpr (GUARD_SAMPLED) {
                     guard_trips += 1u;
-                    if ((guard_trips & (RG_SAMPLE_TRIPS - 1u)) == 0u) sample_guards();
+                    if ((guard_trips & (RG_SAMPLE_TRIPS - 1u)) == 0u) {
+                        lane_raised = false;
+                        sample_guards();
+                        m_active &= ~lanes(lane_raised);
+                    }
                 }
-                playing = st == ST_ACTIVE;
-                waiting = __ballot(st == ST_ENDED);
-                active = __ballot(playing);
+                if constexpr (PK2) {
+                    waiting = m_ended, active = m_active;
+                } else {
+                    playing = st == ST_ACTIVE;
+                    waiting = __ballot(st == ST_ENDED);
+                    active = __ballot(playing);
+                }
             } while (active && !handover_due(waiting, active, flat));
         }
     };
