@@ -50,6 +50,16 @@ RR_PAIR_ROW_DTYPE = np.dtype(
      ("simultaneous_d_low", "<f8"), ("simultaneous_d_high", "<f8"), ("balanced_a_win_rate", "<f8"), ("holm_adjusted_p", "<f8"),
      ("strategy_a", "<u4"), ("strategy_b", "<u4"), ("flags", "u1"), ("decision_class", "u1"), ("pad", "u1", (6,))]
 )
+# fk_dom_node / fk_dom_extreme, include/farkle_hip.h: the dominance graphs of a round robin (fk_dominance_graph; frames in farkle_ii_amd/dominance.py)
+DOM_NODE_DTYPE = np.dtype(
+    [("component", "<u4", (2,)), ("component_size", "<u4", (2,)), ("front", "<u4", (2,)), ("cycle_length", "<u4", (2,)), ("wins", "<u4", (2,)),
+     ("losses", "<u4", (2,)), ("rate_count", "<u8"), ("rate_mean", "<f8")]
+)
+DOM_EXTREME_DTYPE = np.dtype(
+    [("strongest_winner", "<u4"), ("strongest_loser", "<u4"), ("weakest_winner", "<u4"), ("weakest_loser", "<u4"), ("strongest_distance", "<f8"),
+     ("weakest_distance", "<f8")]
+)
+DOM_MAX_N = 8192       # FK_DOM_MAX_N
 RR_CLASSES = 7         # FK_RR_CLASSES
 RR_STRATEGY_COLS = 12  # FK_RR_STRATEGY_COLS
 TALLY_COLS = 26
@@ -137,7 +147,8 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin",
-            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference"]
+            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference",
+            "fk_dominance_graph", "fk_rr_dominance"]
 _libs: dict = {}
 
 
@@ -872,23 +883,28 @@ class Engine:
         self._check(self._lib.fk_rr_counts_reset(self._ctx))
         self._rr_n = 0
 
+    def _rr_params(self, family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family_pair_count) -> _RrInferenceParams:
+        """``fk_rr_inference_params``; the two critical values are evaluated here, once, with scipy (``norm.isf``)."""
+        from scipy.stats import norm
+
+        n = self._rr_n
+        family = n * (n - 1) // 2 if family_pair_count is None else int(family_pair_count)
+        if family < 0 or family >= 1 << 64:
+            raise ValueError("family_pair_count must fit 64 unsigned bits")
+        alpha = float(family_alpha)
+        ok = 0.0 < alpha < 1.0 and family > 0  # (the entry refuses the others with its own message; isf of them is undefined)
+        return _RrInferenceParams(alpha, float(practical_delta), float("nan") if delta_equivalence is None else float(delta_equivalence),
+                                  float(min_candidate_completion_rate), float(norm.isf(alpha / 2.0)) if ok else 1.0,
+                                  float(norm.isf(alpha / family / 2.0)) if ok else 1.0, family)
+
     def rr_inference(self, family_alpha: float = 0.02, practical_delta: float = 0.03, delta_equivalence: float | None = None,
                      min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None,
                      rows: tuple[int, int] | None = None, want_strategies: bool = True) -> dict:
         """``fk_rr_inference`` over the resident pair counts (of an ``n``-row table): ``{"class_counts": int64 [7], "strategies": int64
         [n, 12] or None, "rows": RR_PAIR_ROW_DTYPE [row_end - row_begin] or None}``.  ``rows`` is a pair-id range ``(begin, end)``.  The two
         critical values are evaluated here, once, with scipy (``norm.isf``), as the reference's ``_score_difference_interval_fallback`` does."""
-        from scipy.stats import norm
-
         n = self._rr_n  # the table size fixed with the resident counts: it sizes the per-strategy output
-        family = n * (n - 1) // 2 if family_pair_count is None else int(family_pair_count)
-        if family < 0 or family >= 1 << 64:
-            raise ValueError("family_pair_count must fit 64 unsigned bits")
-        alpha = float(family_alpha)
-        ok = 0.0 < alpha < 1.0 and family > 0  # (the entry refuses the others with its own message; isf of them is undefined)
-        par = _RrInferenceParams(alpha, float(practical_delta), float("nan") if delta_equivalence is None else float(delta_equivalence),
-                                 float(min_candidate_completion_rate), float(norm.isf(alpha / 2.0)) if ok else 1.0,
-                                 float(norm.isf(alpha / family / 2.0)) if ok else 1.0, family)
+        par = self._rr_params(family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family_pair_count)
         out_rows, begin, end = None, 0, 0
         if rows is not None:
             begin, end = int(rows[0]), int(rows[1])
@@ -900,6 +916,48 @@ class Engine:
         self._check(self._lib.fk_rr_inference(self._ctx, C.byref(par), _p(out_rows), C.c_uint64(begin), C.c_uint64(end), _p(class_counts),
                                               _p(strategies)))
         return {"class_counts": class_counts, "strategies": strategies, "rows": out_rows}
+
+    @staticmethod
+    def _dominance_outputs(n: int, rank, want_adjacency: bool) -> tuple:
+        if rank is not None:
+            rank = np.asarray(rank)
+            if rank.shape != (n,) or rank.dtype.kind not in "iu" or (rank.size and (int(rank.min()) < 0 or int(rank.max()) > 0xFFFFFFFF)):
+                raise ValueError(f"rank must hold {n} unsigned 32-bit positions")
+            rank = np.ascontiguousarray(rank, dtype=np.uint32)
+        nodes = np.zeros(max(n, 0), dtype=DOM_NODE_DTYPE)
+        extremes = np.zeros((2, max(n, 0)), dtype=DOM_EXTREME_DTYPE)
+        adjacency = np.zeros((2, max(n, 0), (max(n, 0) + 63) // 64), dtype=np.uint64) if want_adjacency else None
+        return rank, nodes, extremes, adjacency
+
+    def dominance_graph(self, n: int, decision_class, sim_d_low, sim_d_high, balanced_rate, practical_delta: float = 0.03, rank=None,
+                        want_adjacency: bool = True) -> dict:
+        """``fk_dominance_graph``: the practical (index 0) and statistical (index 1) dominance graphs of an ``n``-row table from its pairs'
+        decision classes, simultaneous d bounds and balanced rates, arrays of ``n (n - 1) / 2`` in pair-id order.  ``rank[row]`` orders the
+        strategies where two internal edges are equally strong (None: table order).  Returns ``{"nodes": DOM_NODE_DTYPE [n], "extremes":
+        DOM_EXTREME_DTYPE [2, n], "adjacency": uint64 [2, n, ceil(n / 64)] or None}``."""
+        n = int(n)
+        n_pairs = max(n * (n - 1) // 2, 0)
+        cls = np.ascontiguousarray(decision_class, dtype=np.uint8).reshape(-1)
+        arrays = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (sim_d_low, sim_d_high, balanced_rate)]
+        if 2 <= n <= DOM_MAX_N and any(len(a) != n_pairs for a in (cls, *arrays)):  # (the entry refuses the other sizes before it reads an array)
+            raise ValueError(f"a table of {n} strategies has {n_pairs} pairs")
+        rank, nodes, extremes, adjacency = self._dominance_outputs(n, rank, want_adjacency)
+        self._check(self._lib.fk_dominance_graph(self._ctx, C.c_int32(n), _p(cls), _p(arrays[0]), _p(arrays[1]), _p(arrays[2]), C.c_double(practical_delta),
+                                                 _p(rank), _p(nodes), _p(extremes), _p(adjacency)))
+        return {"nodes": nodes, "extremes": extremes, "adjacency": adjacency}
+
+    def rr_dominance(self, family_alpha: float = 0.02, practical_delta: float = 0.03, delta_equivalence: float | None = None,
+                     min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None, rank=None,
+                     want_adjacency: bool = True) -> dict:
+        """``fk_rr_dominance``: ``rr_inference`` over the resident pair counts, its classes, bounds and rates fed to the graph kernels of
+        ``dominance_graph`` on the device.  The resident range must be the whole table.  Returns ``dominance_graph``'s dictionary and
+        ``"class_counts"``."""
+        n = self._rr_n
+        par = self._rr_params(family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family_pair_count)
+        rank, nodes, extremes, adjacency = self._dominance_outputs(n, rank, want_adjacency)
+        class_counts = np.zeros(RR_CLASSES, dtype=np.int64)
+        self._check(self._lib.fk_rr_dominance(self._ctx, C.byref(par), _p(rank), _p(nodes), _p(extremes), _p(adjacency), _p(class_counts)))
+        return {"nodes": nodes, "extremes": extremes, "adjacency": adjacency, "class_counts": class_counts}
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
     def comm_unique_id(self) -> bytes:

@@ -131,6 +131,13 @@ def build_parser() -> argparse.ArgumentParser:
     rr.add_argument("--rows", metavar="BEGIN:END",
                     help="With --inference: the pair ids whose rows round_robin_inference_pairs.parquet holds (default: every pair of the "
                          "range when it has at most 2^22 pairs, none beyond)")
+    rr.add_argument("--dominance", action="store_true",
+                    help="With --inference over the whole table: build the practical and the statistical dominance graph on the GPU and write "
+                         "dominance_edges.parquet (when every pair's row is on the host), cycle_groups.parquet, dominance_fronts.parquet and "
+                         "dominance_summary.json")
+    rr.add_argument("--screening-scores", type=Path, metavar="FILE",
+                    help="With --dominance: a JSON object {strategy id: tournament screening score}, the third key of the display order "
+                         "inside a front (default: the column is null)")
     rr.add_argument("--force", action="store_true", help="Replace the tables of an existing output directory")
     for name in _OUT_OF_SCOPE:
         sub.add_parser(name, help="(reference command outside the simulation path)")
@@ -197,7 +204,8 @@ def main(argv: Sequence[str] | None = None) -> None:
 
         try:
             written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
-                                      out=args.out, force=args.force, inference=args.inference, rows=args.rows)
+                                      out=args.out, force=args.force, inference=args.inference, rows=args.rows, dominance=args.dominance,
+                                      screening_scores=args.screening_scores)
         except (ValueError, FileExistsError) as exc:
             raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})

@@ -18,6 +18,7 @@
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
 #include "fk_round_robin.h"    // device side: head-to-head round robin (window tables by unranking, generation planner, apply, summary)
 #include "fk_rr_inference.h"   // device side: round-robin inference (resident pair counts, score test, intervals, Holm, decision classes)
+#include "fk_dominance.h"      // device side: dominance graphs of a round robin (bit matrices, closure, components, fronts, cycles, extremes)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -251,6 +252,7 @@ struct fk_ctx {
     bool ri_valid = false;               // the accumulator holds counts; what the first adding call fixed with them:
     int32_t ri_n = 0;
     uint64_t ri_begin = 0, ri_end = 0, ri_hash = 0, ri_family = 0;
+    DominanceBufs dm;
     BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
@@ -3405,10 +3407,9 @@ int fk_rr_counts_reset(fk_ctx *c) {
     return FK_OK;
 }
 
-int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end, int64_t *class_counts,
-                    int64_t *strategy_classes) {
-    using namespace fkri;
-    if (!c) return FK_ERR_ARG;
+// fk_rr_inference's refusals; fk_rr_dominance makes them too
+static int rr_inference_check(fk_ctx *c, const fk_rr_inference_params *par, const fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
+                              const int64_t *class_counts) {
     if (!par || !class_counts) return fail(c, FK_ERR_ARG, "params and class_counts are required");
     if (!c->ri_valid) return fail(c, FK_ERR_ARG, "no resident counts: fk_h2h_round_robin_resident or fk_rr_counts_add comes first");
     if (rows && (row_begin > row_end || row_begin < c->ri_begin || row_end > c->ri_end))
@@ -3429,8 +3430,15 @@ int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row
                     (unsigned long long)c->ri_family);
     if (!(par->critical_ordinary > 0.0 && std::isfinite(par->critical_ordinary) && par->critical_simultaneous > 0.0 && std::isfinite(par->critical_simultaneous)))
         return fail(c, FK_ERR_ARG, "the critical values must be positive and finite, got %g and %g", par->critical_ordinary, par->critical_simultaneous);
-    HIPCHK(c, hipSetDevice(c->device));
-    begin_call(c);
+    return FK_OK;
+}
+
+// The chain of fk_rr_inference on the context's stream, after begin_call: its device work and the copies home, not yet awaited.
+// `cls_out`, nullable: [pairs] on the device, every pair's class (fk_rr_dominance).
+static int rr_inference_enqueue(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
+                                int64_t *class_counts, int64_t *strategy_classes, uint8_t *cls_out) {
+    using namespace fkri;
+    const uint64_t n_pairs64 = c->ri_end - c->ri_begin;
     RrInferenceBufs &b = c->ri;
     const uint32_t P = (uint32_t)n_pairs64, n = (uint32_t)c->ri_n;
     const size_t n_rows_out = rows ? (size_t)(row_end - row_begin) : 0;
@@ -3460,16 +3468,153 @@ int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row
     const DecideParams dp{par->family_alpha, par->practical_delta, par->delta_equivalence, par->critical_ordinary};
     const uint32_t row_first = rows ? (uint32_t)(row_begin - c->ri_begin) : 0u, row_last = rows ? (uint32_t)(row_end - c->ri_begin) : 0u;
     hipLaunchKernelGGL(fk_ri_decide_kernel, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, dp, b.strat_flags.p, b.sim.p, b.adjusted.p, b.position.p,
-                       b.class_counts.p, b.strat_out.p, row_first, row_last, n_rows_out ? b.rows.p : nullptr);
+                       b.class_counts.p, b.strat_out.p, row_first, row_last, n_rows_out ? b.rows.p : nullptr, cls_out);
     HIPCHK(c, hipGetLastError());
     device_work.stop();
     HIPCHK(c, hipMemcpyAsync(class_counts, b.class_counts.p, RI_CLASSES * 8, hipMemcpyDeviceToHost, c->stream));
     if (strategy_classes) HIPCHK(c, hipMemcpyAsync(strategy_classes, b.strat_out.p, (size_t)n * RI_STRAT_COLS * 8, hipMemcpyDeviceToHost, c->stream));
     if (n_rows_out) HIPCHK(c, hipMemcpyAsync(rows, b.rows.p, n_rows_out * sizeof(fk_rr_pair_row), hipMemcpyDeviceToHost, c->stream));
+    return FK_OK;
+}
+
+int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end, int64_t *class_counts,
+                    int64_t *strategy_classes) {
+    if (!c) return FK_ERR_ARG;
+    if (const int rc = rr_inference_check(c, par, rows, row_begin, row_end, class_counts)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    if (const int rc = rr_inference_enqueue(c, par, rows, row_begin, row_end, class_counts, strategy_classes, nullptr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, collect_timers(c));
     c->timing.total_ms = c->timing.play_ms;
     return FK_OK;
+}
+
+// ---- dominance graphs of a round robin (device side: fk_dominance.h) ----
+static int dominance_check_shape(fk_ctx *c, int64_t n, const uint32_t *rank, const void *nodes, const void *extremes) {
+    if (!nodes || !extremes) return fail(c, FK_ERR_ARG, "nodes and extremes are required");
+    if (n < 2) return fail(c, FK_ERR_ARG, "a dominance graph needs at least two strategies, got %lld", (long long)n);
+    if (n > FK_DOM_MAX_N)
+        return fail(c, FK_ERR_ARG, "a dominance graph holds at most %d strategies (the fronts' in-degrees live in one workgroup's LDS), got %lld", FK_DOM_MAX_N,
+                    (long long)n);
+    if (rank) {
+        std::vector<uint8_t> seen((size_t)n, 0);
+        for (int64_t i = 0; i < n; ++i) {
+            if (rank[i] >= (uint64_t)n || seen[rank[i]]) return fail(c, FK_ERR_ARG, "rank is not a permutation of 0 .. %lld (entry %lld)", (long long)n - 1, (long long)i);
+            seen[rank[i]] = 1;
+        }
+    }
+    return FK_OK;
+}
+
+// The graph stage on the context's stream, classes / bounds / rates on the device; awaits it and copies home.
+static int dominance_run(fk_ctx *c, uint32_t n, const uint8_t *d_cls, const double2 *d_sim, const double *d_rate, double delta, const uint32_t *rank,
+                         fk_dom_node *nodes, fk_dom_extreme *extremes, uint64_t *adjacency) {
+    using namespace fkdm;
+    DominanceBufs &b = c->dm;
+    const uint32_t P = (uint32_t)((uint64_t)n * (n - 1u) / 2u);
+    const fkl::DominanceMats lay(n);
+    const fkl::DominanceKeys keys(n);
+    int rc = FK_OK;
+    if ((rc = ensure_all(c, b.mats, lay.n_u64, b.keys, keys.n_u64, b.comp, (size_t)2 * n, b.comp_deg, (size_t)2 * n, b.rank, (size_t)n, b.unrank, (size_t)n, b.nodes,
+                         (size_t)n, b.extremes, (size_t)2 * n)))
+        return rc;
+    if (rank) {
+        std::vector<uint32_t> inverse(n);
+        for (uint32_t i = 0; i < n; ++i) inverse[rank[i]] = i;
+        HIPCHK(c, hipMemcpyAsync(b.rank.p, rank, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.unrank.p, inverse.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream)); // (`inverse` leaves scope)
+    }
+    const uint32_t W = (uint32_t)lay.W;
+    const Mats m{b.mats.p + lay.adj, b.mats.p + lay.adj_t, b.mats.p + lay.reach, n, W};
+    const ExtremeBufs e{b.keys.p + keys.max_bits, b.keys.p + keys.min_bits, b.keys.p + keys.strong_key, b.keys.p + keys.weak_key};
+    const dim3 pair_grid((P + 255u) / 256u), b256(256);
+    Timer device_work(c, &c->timing.play_ms, SLOT_CALL);
+    Timer edges(c, &c->timing.perm_ms, SLOT_PERM);
+    HIPCHK(c, hipMemsetAsync(b.mats.p, 0, 4 * lay.plane * 8, c->stream)); // adj, adj_t
+    hipLaunchKernelGGL(fk_dm_edges_kernel, pair_grid, b256, 0, c->stream, d_cls, n, P, m);
+    HIPCHK(c, hipGetLastError());
+    edges.stop();
+    Timer closure(c, &c->timing.seed_ms, SLOT_SEED);
+    HIPCHK(c, hipMemcpyAsync(m.reach, m.adj, 4 * lay.plane * 8, hipMemcpyDeviceToDevice, c->stream)); // adj[0], adj[1], adj_t[0], adj_t[1]
+    for (uint32_t kb = 0; kb < W; ++kb) {
+        hipLaunchKernelGGL(fk_dm_panel_kernel, dim3(4), b256, 0, c->stream, m.reach, n, W, kb, b.mats.p + lay.panel, b.mats.p + lay.dstar);
+        hipLaunchKernelGGL(fk_dm_close_kernel, dim3((n + 3u) / 4u, 4), b256, 0, c->stream, m.reach, n, W, kb, b.mats.p + lay.panel, b.mats.p + lay.dstar);
+    }
+    HIPCHK(c, hipGetLastError());
+    closure.stop();
+    HIPCHK(c, hipMemsetAsync(b.comp_deg.p, 0, (size_t)2 * n * 4, c->stream));
+    hipLaunchKernelGGL(fk_dm_component_kernel, dim3((n + 3u) / 4u, 2), b256, 0, c->stream, m, b.nodes.p, b.comp.p, b.comp_deg.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fk_dm_front_kernel, dim3(2), dim3(1024), 0, c->stream, m, b.nodes.p, b.comp.p, b.comp_deg.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fk_dm_mean_kernel, dim3((n + 255u) / 256u), b256, 0, c->stream, d_rate, n, b.nodes.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fk_dm_cycle_kernel, dim3(n, 2), dim3(128), 0, c->stream, m, b.nodes.p);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemsetAsync(e.max_bits, 0, (size_t)2 * n * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(e.min_bits, 0xff, (size_t)6 * n * 8, c->stream)); // min_bits, strong_key, weak_key
+    for (const bool second : {false, true}) {
+        hipLaunchKernelGGL(fk_dm_extreme_kernel, pair_grid, b256, 0, c->stream, d_cls, d_sim, delta, n, P, b.comp.p, rank ? b.rank.p : nullptr, e, second);
+        HIPCHK(c, hipGetLastError());
+    }
+    hipLaunchKernelGGL(fk_dm_extreme_out_kernel, dim3((2u * n + 255u) / 256u), b256, 0, c->stream, n, rank ? b.unrank.p : nullptr, e, b.extremes.p);
+    HIPCHK(c, hipGetLastError());
+    device_work.stop();
+    HIPCHK(c, hipMemcpyAsync(nodes, b.nodes.p, (size_t)n * sizeof(fk_dom_node), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(extremes, b.extremes.p, (size_t)2 * n * sizeof(fk_dom_extreme), hipMemcpyDeviceToHost, c->stream));
+    if (adjacency) HIPCHK(c, hipMemcpyAsync(adjacency, m.adj, 2 * lay.plane * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
+    return FK_OK;
+}
+
+int fk_dominance_graph(fk_ctx *c, int32_t n, const uint8_t *decision_class, const double *sim_d_low, const double *sim_d_high, const double *balanced_rate,
+                       double practical_delta, const uint32_t *rank, fk_dom_node *nodes, fk_dom_extreme *extremes, uint64_t *adjacency) {
+    if (!c) return FK_ERR_ARG;
+    if (const int rc = dominance_check_shape(c, n, rank, nodes, extremes)) return rc;
+    if (!decision_class || !sim_d_low || !sim_d_high || !balanced_rate) return fail(c, FK_ERR_ARG, "the class, bound and rate arrays are required");
+    if (!(practical_delta > 0.0)) return fail(c, FK_ERR_ARG, "practical_delta must be positive, got %g", practical_delta);
+    const size_t P = (size_t)n * (size_t)(n - 1) / 2u;
+    std::vector<double2> sim(P);
+    for (size_t p = 0; p < P; ++p) {
+        const uint8_t cls = decision_class[p];
+        if (cls >= fkri::RI_CLASSES) return fail(c, FK_ERR_ARG, "decision class %u of pair %zu is not one of the %u classes", (unsigned)cls, p, fkri::RI_CLASSES);
+        if (cls < 2u && !std::isfinite(cls == 0u ? sim_d_low[p] : sim_d_high[p]))
+            return fail(c, FK_ERR_ARG, "pair %zu is a practical dominance whose simultaneous bound is not finite", p);
+        sim[p] = make_double2(sim_d_low[p], sim_d_high[p]);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    DominanceBufs &b = c->dm;
+    if (const int rc = ensure_all(c, b.cls, P, b.sim, P, b.rate, P)) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.cls.p, decision_class, P, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.sim.p, sim.data(), P * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.rate.p, balanced_rate, P * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`sim` is pageable memory of this frame)
+    return dominance_run(c, (uint32_t)n, b.cls.p, b.sim.p, b.rate.p, practical_delta, rank, nodes, extremes, adjacency);
+}
+
+int fk_rr_dominance(fk_ctx *c, const fk_rr_inference_params *par, const uint32_t *rank, fk_dom_node *nodes, fk_dom_extreme *extremes, uint64_t *adjacency,
+                    int64_t *class_counts) {
+    if (!c) return FK_ERR_ARG;
+    if (const int rc = rr_inference_check(c, par, nullptr, 0, 0, class_counts)) return rc;
+    const uint64_t all_pairs = (uint64_t)c->ri_n * (uint64_t)(c->ri_n - 1) / 2u;
+    if (c->ri_begin != 0 || c->ri_end != all_pairs)
+        return fail(c, FK_ERR_ARG, "the resident counts hold pairs [%llu, %llu) of the table's %llu: a dominance graph needs the whole family",
+                    (unsigned long long)c->ri_begin, (unsigned long long)c->ri_end, (unsigned long long)all_pairs);
+    if (const int rc = dominance_check_shape(c, c->ri_n, rank, nodes, extremes)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    DominanceBufs &b = c->dm;
+    const uint32_t P = (uint32_t)all_pairs;
+    if (const int rc = ensure_all(c, b.cls, (size_t)P, b.rate, (size_t)P)) return rc;
+    if (const int rc = rr_inference_enqueue(c, par, nullptr, 0, 0, class_counts, nullptr, b.cls.p)) return rc;
+    hipLaunchKernelGGL(fkdm::fk_dm_rate_kernel, dim3((P + 255u) / 256u), dim3(256), 0, c->stream, c->ri.counts.p, P, b.rate.p);
+    HIPCHK(c, hipGetLastError());
+    return dominance_run(c, (uint32_t)c->ri_n, b.cls.p, c->ri.sim.p, b.rate.p, par->practical_delta, rank, nodes, extremes, adjacency);
 }
 
 // The NEXT fk_tournament_run / _stats call on this context will play shuffles [shuffle_begin, shuffle_end) of the same table,

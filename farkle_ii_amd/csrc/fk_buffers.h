@@ -100,6 +100,17 @@ struct RrInferenceBufs { // fk_h2h_round_robin_resident, fk_rr_counts_add, fk_rr
     Dev<long long> strat_out;      // [n][fkri::RI_STRAT_COLS]
     Dev<fk_rr_pair_row> rows;      // the asked slice
 };
+struct DominanceBufs { // fk_dominance_graph, fk_rr_dominance
+    Dev<uint8_t> cls;             // [pairs] decision classes
+    Dev<double2> sim;             // [pairs] the simultaneous bounds handed in (fk_rr_dominance reads RrInferenceBufs::sim)
+    Dev<double> rate;             // [pairs] balanced_a_win_rate
+    Dev<ull> mats;                // fkl::DominanceMats
+    Dev<ull> keys;                // fkl::DominanceKeys
+    Dev<uint32_t> comp, comp_deg; // [2][n] the component of a node; at a component's smallest row, the edges that enter it
+    Dev<uint32_t> rank, unrank;   // [n] the tie-break order and its inverse
+    Dev<fk_dom_node> nodes;       // [n]
+    Dev<fk_dom_extreme> extremes; // [2][n]
+};
 struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
     Dev<int64_t> wins, exposures; // the stacked matrices
     Dev<fkb::KDesc> kd;

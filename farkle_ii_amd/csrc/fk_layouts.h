@@ -42,4 +42,18 @@ struct RootParams {
           n(n_k + (joint ? 2 * n_k * S + 2 * S : 0)) {}
 };
 
+// fk_dominance_graph's bit matrices, rows of W = ceil(n / 64) words: adj [2][n][W] | adj_t [2][n][W] | reach [4][n][W] (the working
+// copies that are closed) | panel [4][64][W] | dstar [4][64].  Offsets in u64 units; adj .. reach is one contiguous run.
+struct DominanceMats {
+    size_t W, plane, adj, adj_t, reach, panel, dstar, n_u64;
+    explicit DominanceMats(size_t n)
+        : W((n + 63) / 64), plane(n * W), adj(0), adj_t(2 * plane), reach(4 * plane), panel(8 * plane), dstar(panel + 4 * 64 * W), n_u64(dstar + 4 * 64) {}
+};
+
+// The keys of the extreme internal edges, [2][n] each: largest distance | smallest distance | strongest (rank, rank) | weakest.
+struct DominanceKeys {
+    size_t max_bits, min_bits, strong_key, weak_key, n_u64;
+    explicit DominanceKeys(size_t n) : max_bits(0), min_bits(2 * n), strong_key(4 * n), weak_key(6 * n), n_u64(8 * n) {}
+};
+
 } // namespace fkl

@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void fk_ri_decide_kernel(const unsigned long l
                                                            const double2 *__restrict__ sim, const double *__restrict__ adjusted,
                                                            const uint32_t *__restrict__ position, unsigned long long *__restrict__ class_counts,
                                                            long long *__restrict__ strat_out, uint32_t row_first, uint32_t row_last,
-                                                           fk_rr_pair_row *__restrict__ rows) {
+                                                           fk_rr_pair_row *__restrict__ rows, uint8_t *__restrict__ cls_out /* nullable: [n_pairs] */) {
 #pragma clang fp contract(off)
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // whole waves
     const bool live = p < n_pairs;
@@ -321,6 +321,7 @@ __global__ __launch_bounds__(256) void fk_ri_decide_kernel(const unsigned long l
         else if (reject) cls = effect > 0.0 ? RI_C_STATISTICAL_A : RI_C_STATISTICAL_B;
         else if (!isnan(par.delta_equivalence) && s.x > -par.delta_equivalence && s.y < par.delta_equivalence) cls = RI_C_EQUIVALENT;
         else cls = RI_C_UNRESOLVED;
+        if (cls_out) cls_out[p] = (uint8_t)cls; // (fk_rr_dominance: the graph kernels read the classes on the device)
         if (rows && p >= row_first && p < row_last) {
             fk_rr_pair_row r;
             r.pair_id = pair0 + p;

@@ -9,11 +9,12 @@ the pairs and seats the orders, ``_simulate_block_from_manifest`` :1172-1235 is 
 * ``blocks_frame`` / ``pairs_frame`` / ``strategies_frame`` — the tables ``farkle round-robin`` writes;
 * ``run_round_robin`` — the command: one sequence of engine calls per root of ``sim.seed_list``; with ``--inference`` the states stay
   on the device and the score test, the score intervals, Holm's adjustment and the decision classes of the reference's
-  ``h2h_inference.py`` run there (``rr_inference.py`` is their host side).
+  ``h2h_inference.py`` run there (``rr_inference.py`` is their host side); with ``--dominance`` on top, the reference's dominance
+  graphs are built there too (``dominance.py`` is their host side).
 
 Out of scope: the library route of the interval (``confint_proportions_2indep``) is not reproduced; the reference's own complete
-inversion is.  Also out of scope: the reference's power plan, schedule hashes, block ids and sidecars; its root-specific diagnostics
-and dominance graph; resuming a partly played round robin; several ranks (pair ranges make the split trivial — a later change).
+inversion is.  Also out of scope: the reference's power plan, schedule hashes, block ids and sidecars; its root-specific diagnostics;
+resuming a partly played round robin; several ranks (pair ranges make the split trivial — a later change).
 """
 from __future__ import annotations
 
@@ -283,7 +284,7 @@ def parse_pair_range(text: str | None, n: int) -> tuple[int, int]:
 
 def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
                     force: bool = False, strategies=None, engine=None, world: int | None = None, inference: bool = False,
-                    rows: str | None = None) -> dict:
+                    rows: str | None = None, dominance: bool = False, screening_scores=None) -> dict:
     """``farkle round-robin``: the grid of ``cfg`` (restricted to the ids of ``strategy_ids_file``), every pair of the range, per root of
     ``sim.seed_list``.  Writes ``round_robin_pairs.parquet``, ``round_robin_strategies.parquet``, ``round_robin.json`` and, with
     ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths.
@@ -292,7 +293,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     once over all roots (``Engine.rr_inference`` with the ``head2head`` settings of ``cfg``) and the command writes
     ``round_robin_inference_pairs.parquet`` (the pairs of ``rows``, ``BEGIN:END`` in pair ids; default every pair of a range of at most
     2^22 pairs, none beyond), ``round_robin_inference_strategies.parquet``, ``round_robin_strategies.parquet`` and the class counts in
-    ``round_robin.json``; the tables that need the states on the host (``round_robin_pairs.parquet``, ``blocks``) are not written."""
+    ``round_robin.json``; the tables that need the states on the host (``round_robin_pairs.parquet``, ``blocks``) are not written.
+
+    With ``dominance`` (and ``inference``, over the whole table) the inference feeds the dominance graphs on the device
+    (``Engine.rr_dominance``) and the command also writes the reference's ``cycle_groups.parquet``, ``dominance_fronts.parquet``,
+    ``dominance_summary.json`` and — when every pair's row is on the host — ``dominance_edges.parquet`` (``dominance.py`` builds the
+    frames; ``round_robin.json`` says when the edges are omitted).  ``screening_scores``: a JSON file ``{strategy id: score}``."""
     import os
 
     import pyarrow as pa
@@ -334,6 +340,23 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
                 raise ValueError(f"round-robin: --rows takes BEGIN:END inside the played pair range [{begin}, {end}), got {rows!r}")
     elif rows is not None:
         raise ValueError("round-robin: --rows belongs to --inference")
+    scores = None
+    if dominance:
+        from . import dominance as dom
+
+        if not inference:
+            raise ValueError("round-robin: --dominance belongs to --inference")
+        if (begin, end) != (0, pair_count(n)):
+            raise ValueError(f"round-robin: --dominance needs every pair of the table, --pairs plays [{begin}, {end}) of {pair_count(n)}")
+        if n > dom.DOM_MAX_N:
+            raise ValueError(f"round-robin: --dominance holds at most {dom.DOM_MAX_N} strategies, got {n}")
+        if screening_scores is not None:
+            scores = {int(k): float(v) for k, v in json.loads(Path(screening_scores).read_text()).items()}
+            missing = sorted(set(ids) - set(scores))
+            if missing:
+                raise ValueError(f"round-robin: {screening_scores} lacks the screening scores of strategies {missing[:10]}")
+    elif screening_scores is not None:
+        raise ValueError("round-robin: --screening-scores belongs to --dominance")
     roots = [int(r) for r in (cfg.sim.seed_list if cfg.sim.seed_list else [cfg.sim.seed])]
     out_dir = Path(out) if out is not None else cfg.results_root / "h2h_round_robin"
     if out_dir.exists() and not force:
@@ -359,6 +382,8 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
         knobs = dict(family_alpha=h2h.family_alpha, practical_delta=h2h.practical_delta, delta_equivalence=h2h.delta_equivalence,
                      min_candidate_completion_rate=h2h.min_candidate_completion_rate)
         result = eng.rr_inference(family_pair_count=family, rows=row_range, **knobs)
+        if dominance:
+            graphs = eng.rr_dominance(family_pair_count=family, rank=dom.rank_of_ids(ids), **knobs)
         eng.rr_counts_reset()
     elapsed = time.perf_counter() - started
     out_dir.mkdir(parents=True, exist_ok=True)
@@ -369,6 +394,18 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
         written["inference_strategies"] = out_dir / "round_robin_inference_strategies.parquet"
         frames.append((ri.pairs_frame(result["rows"], ids, family_pair_count=family, **knobs), written["inference_pairs"]))
         frames.append((ri.strategies_frame(result["strategies"], ids, h2h.min_candidate_completion_rate), written["inference_strategies"]))
+        if dominance:
+            written["dominance_cycles"] = out_dir / "cycle_groups.parquet"
+            written["dominance_fronts"] = out_dir / "dominance_fronts.parquet"
+            written["dominance_summary"] = out_dir / "dominance_summary.json"
+            frames.append((dom.cycles_frame(graphs["nodes"], graphs["extremes"], graphs["adjacency"], ids), written["dominance_cycles"]))
+            frames.append((dom.fronts_frame(graphs["nodes"], result["strategies"], ids, scores), written["dominance_fronts"]))
+            edges_written = row_range == (begin, end)
+            if edges_written:
+                written["dominance_edges"] = out_dir / "dominance_edges.parquet"
+                frames.append((dom.edges_frame(result["rows"], ids, h2h.practical_delta), written["dominance_edges"]))
+            digest = dom.summary(graphs["nodes"], result["strategies"], graphs["class_counts"], ids)
+            runner._atomic_write_bytes(written["dominance_summary"], (json.dumps(digest, indent=2, sort_keys=True) + "\n").encode("utf-8"))
     else:
         written["pairs"] = out_dir / "round_robin_pairs.parquet"
         frames.append((pairs_frame(ids, roots, states, target, begin, end), written["pairs"]))
@@ -390,5 +427,11 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     if inference:
         report["inference"] = {"class_counts": {name: int(v) for name, v in zip(ri.DECISION_CLASSES, result["class_counts"])},
                                "family_pair_count": family, "row_begin": row_range[0], "row_end": row_range[1], **knobs}
+    if dominance:
+        report["dominance"] = {"edges_written": edges_written, "screening_scores": None if screening_scores is None else str(screening_scores),
+                               **{key: digest[key] for key in ("practical_front_count", "statistical_front_count", "practical_cycle_group_count",
+                                                               "statistical_cycle_group_count", "unique_best")}}
+        if not edges_written:
+            report["dominance"]["edges_omitted"] = "dominance_edges.parquet needs the row of every pair on the host (--rows)"
     runner._atomic_write_bytes(written["json"], (json.dumps(report, indent=2, sort_keys=True) + "\n").encode("utf-8"))
     return written

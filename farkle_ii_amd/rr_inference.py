@@ -18,7 +18,8 @@ Left out of the frames (the reference computes them from its power plan, schedul
 does not have): ``family_hash``, ``replacement_attempt_count`` and its per-strategy sums, ``score_test_id``, ``interval_method_id``,
 ``h2h_method_version``, ``planned_target_power_conditional_on_completed_support``,
 ``planned_worst_scenario_power_conditional_on_completed_support``, ``power_support_status``.  Also out of scope:
-``_root_specific_diagnostics``, sidecars and completion stamps, ``dominance.py``'s graph, several ranks, resuming.
+``_root_specific_diagnostics``, sidecars and completion stamps, several ranks, resuming.  The graphs the reference's
+``dominance.py`` builds from these classes are ``Engine.rr_dominance`` and ``farkle_ii_amd/dominance.py``.
 """
 from __future__ import annotations
 

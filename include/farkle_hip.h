@@ -658,6 +658,57 @@ typedef struct {
 int fk_rr_inference(fk_ctx *ctx, const fk_rr_inference_params *params, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
                     int64_t *class_counts, int64_t *strategy_classes);
 
+/* ---- dominance graphs of a round robin: what src/farkle/analysis/dominance.py builds from the pairwise decision classes, for
+ * both of its graphs in one call — index 0 practical (edges of practical_dominance_*), index 1 statistical (edges of every class
+ * ending _a / _b), dominance.py:285-334.  Node ids are table rows; a pair's A is its smaller row.  Device side: fk_dominance.h. ----
+ *
+ * fk_dom_node, per table row (64 bytes), [g] per graph:
+ *   component[g]       the smallest row of the node's strongly connected component ("cycle group" when its size is above 1)
+ *   component_size[g]
+ *   front[g]           1-based layer of the component in the condensation: one more than the largest front among the components
+ *                      with an edge into it (:118-136)
+ *   cycle_length[g]    length of the shortest directed cycle through the node inside its component; 0 for a component of one
+ *   wins[g], losses[g] edges out of and into the node (:386-389)
+ *   rate_count, rate_mean  the pairs of the node with a rate, and the mean over them of balanced_rate (as A) / 1 - balanced_rate
+ *                      (as B), summed in pair-id order from 0.0 and divided once (:357-395); NaN when there is none
+ * fk_dom_extreme, [g][row] (32 bytes): at a component's smallest row the practical edge with both ends inside the component whose
+ *   practical_distance_beyond_threshold (:315-319: simultaneous_d_low - practical_delta for an edge won by A, -simultaneous_d_high -
+ *   practical_delta for one won by B) is largest / smallest, ties to the smallest (rank[winner], rank[loser]) (:504-520).  Winners
+ *   and losers UINT32_MAX and distances NaN at every other row and for a component without such an edge.
+ * adjacency, nullable: [2][n][W] 64-bit words, W = ceil(n / 64); bit j of row i of graph g: i beats j.  Padding bits are zero.
+ *
+ * The closure behind the components is a blocked Warshall over 64-bit words, the fronts are Kahn's rounds in one workgroup's LDS,
+ * the cycle lengths one breadth-first search per node: n is at most FK_DOM_MAX_N. */
+#define FK_DOM_MAX_N 8192
+typedef struct {
+    uint32_t component[2], component_size[2], front[2], cycle_length[2], wins[2], losses[2];
+    uint64_t rate_count;
+    double rate_mean;
+} fk_dom_node;
+typedef struct {
+    uint32_t strongest_winner, strongest_loser, weakest_winner, weakest_loser;
+    double strongest_distance, weakest_distance;
+} fk_dom_extreme;
+
+/* The graph stage alone, on host arrays in pair-id order (P = n (n - 1) / 2): decision_class (FK_RR_PRACTICAL_DOMINANCE_A ..),
+ * the simultaneous d bounds, balanced_a_win_rate (NaN: the pair has none).  rank, nullable: rank[row] = the position of the row's
+ * strategy in the order that breaks ties between equal distances (the reference orders strategies as strings); NULL = table order.
+ * fk_timing: play_ms = total_ms = the device work (copies excluded); perm_ms of it builds the edges, seed_ms closes the matrices.
+ * FK_ERR_ARG before any device work: a null array; n < 2 or n > FK_DOM_MAX_N; a class above 6; a practical class whose bound
+ * (low for _a, high for _b) is not finite; practical_delta that is not positive; rank that is not a permutation of 0 .. n - 1. */
+int fk_dominance_graph(fk_ctx *ctx, int32_t n, const uint8_t *decision_class, const double *sim_d_low, const double *sim_d_high,
+                       const double *balanced_rate, double practical_delta, const uint32_t *rank, fk_dom_node *nodes,
+                       fk_dom_extreme *extremes, uint64_t *adjacency);
+
+/* fk_rr_inference's chain over the resident counts, its classes, simultaneous bounds and rates fed to the same graph kernels on the
+ * device: no pair row comes to the host.  params and class_counts as fk_rr_inference; the other arguments as fk_dominance_graph.
+ * The resident range must be the whole table (pair_begin == 0, pair_end == n (n - 1) / 2): a graph of an incomplete family is
+ * refused, as the reference refuses it (:202-207).  FK_ERR_ARG before any device work: every refusal of fk_rr_inference; a partial
+ * resident range; n > FK_DOM_MAX_N; rank that is not a permutation.  fk_timing: play_ms = total_ms = inference and graph together;
+ * perm_ms and seed_ms as fk_dominance_graph. */
+int fk_rr_dominance(fk_ctx *ctx, const fk_rr_inference_params *params, const uint32_t *rank, fk_dom_node *nodes,
+                    fk_dom_extreme *extremes, uint64_t *adjacency, int64_t *class_counts);
+
 /* ---- multi-GPU: one process per GPU, one context per process, ONE exchange ----
  * The (seed x shuffle x game) space partitions with no data dependency; the only collective of the path is the integer
  * SUM of the per-strategy tally to one rank — the analogue of OutcomeCounter.absorb + _reduce_metric_chunk_payloads
