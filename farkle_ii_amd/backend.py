@@ -50,6 +50,21 @@ RR_PAIR_ROW_DTYPE = np.dtype(
      ("simultaneous_d_low", "<f8"), ("simultaneous_d_high", "<f8"), ("balanced_a_win_rate", "<f8"), ("holm_adjusted_p", "<f8"),
      ("strategy_a", "<u4"), ("strategy_b", "<u4"), ("flags", "u1"), ("decision_class", "u1"), ("pad", "u1", (6,))]
 )
+# fk_rr_root_row / fk_rr_agreement_row, include/farkle_hip.h: one (root, pair) and one pair of the per-root diagnostics
+# (fk_rr_root_diagnostics; frames in farkle_ii_amd/rr_root_diagnostics.py)
+RR_ROOT_ROW_DTYPE = np.dtype(
+    [("pair_id", "<u8"), ("games_attempted", "<i8"), ("games_completed", "<i8"), ("games_safety_limit", "<i8"), ("n_ab", "<i8"), ("n_ba", "<i8"),
+     ("seat1_a_wins_ab", "<i8"), ("seat1_b_wins_ba", "<i8"), ("holm_order", "<i8"), ("completion_game_rate", "<f8"), ("q_ab", "<f8"), ("q_ba", "<f8"),
+     ("d_ab", "<f8"), ("score_null_proportion", "<f8"), ("score_z", "<f8"), ("score_p_value", "<f8"), ("ordinary_d_low", "<f8"),
+     ("ordinary_d_high", "<f8"), ("holm_adjusted_p", "<f8"), ("strategy_a", "<u4"), ("strategy_b", "<u4"), ("flags", "u1"),
+     ("diagnostic_decision", "u1"), ("pad", "u1", (6,))]
+)
+RR_AGREEMENT_ROW_DTYPE = np.dtype(
+    [("pair_id", "<u8"), ("root_a_d_ab", "<f8"), ("root_b_d_ab", "<f8"), ("effect_discrepancy_a_minus_b", "<f8"), ("absolute_effect_discrepancy", "<f8"),
+     ("strategy_a", "<u4"), ("strategy_b", "<u4"), ("root_a_decision", "u1"), ("root_b_decision", "u1"), ("flags", "u1"), ("pad", "u1", (5,))]
+)
+RR_MAX_ROOTS = 2       # FK_RR_MAX_ROOTS
+RR_AGREE_COLS = 12     # FK_RR_AGREE_COLS
 # fk_dom_node / fk_dom_extreme, include/farkle_hip.h: the dominance graphs of a round robin (fk_dominance_graph; frames in farkle_ii_amd/dominance.py)
 DOM_NODE_DTYPE = np.dtype(
     [("component", "<u4", (2,)), ("component_size", "<u4", (2,)), ("front", "<u4", (2,)), ("cycle_length", "<u4", (2,)), ("wins", "<u4", (2,)),
@@ -147,7 +162,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin",
-            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference",
+            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference", "fk_rr_counts_add_root", "fk_rr_root_diagnostics",
             "fk_dominance_graph", "fk_rr_dominance"]
 _libs: dict = {}
 
@@ -864,9 +879,10 @@ class Engine:
         return summary
 
     def rr_counts_add(self, table: np.ndarray, states: np.ndarray, target: int, max_attempts: int, pair_begin: int = 0,
-                      pair_end: int | None = None, family_pair_count: int | None = None) -> None:
+                      pair_end: int | None = None, family_pair_count: int | None = None, root_seed: int | None = None) -> None:
         """``fk_rr_counts_add``: one root's host-held block states ``[pairs, 2, 5]`` (as ``h2h_round_robin`` returned them for this
-        ``target`` / ``max_attempts``) into the context's pair counts."""
+        ``target`` / ``max_attempts``) into the context's pair counts.  With ``root_seed`` it is ``fk_rr_counts_add_root``: under option
+        ``"rr_keep_roots"`` the states are also kept on the device, for ``rr_root_diagnostics``."""
         table, n, begin, end, family = self._rr_range(table, pair_begin, pair_end, family_pair_count)
         st = np.asarray(states)
         if st.shape != (max(end - begin, 0), 2, 5) or st.dtype.kind not in "iu" or (st.size and (int(st.min()) < 0 or int(st.max()) > 0xFFFFFFFF)):
@@ -874,8 +890,14 @@ class Engine:
         st = np.ascontiguousarray(st, dtype=np.uint32)
         if min(int(target), int(max_attempts)) < 0:
             raise ValueError("target and max_attempts must not be negative")
-        self._check(self._lib.fk_rr_counts_add(self._ctx, _p(table), C.c_int32(n), C.c_uint64(begin), C.c_uint64(end), C.c_uint64(target),
-                                               C.c_uint64(max_attempts), _p(st), C.c_uint64(family)))
+        args = (self._ctx, _p(table), C.c_int32(n), C.c_uint64(begin), C.c_uint64(end), C.c_uint64(target), C.c_uint64(max_attempts), _p(st),
+                C.c_uint64(family))
+        if root_seed is None:
+            self._check(self._lib.fk_rr_counts_add(*args))
+        else:
+            if not 0 <= int(root_seed) < 1 << 64:
+                raise ValueError("root_seed must fit 64 unsigned bits")
+            self._check(self._lib.fk_rr_counts_add_root(*args, C.c_uint64(int(root_seed))))
         self._rr_n = n
 
     def rr_counts_reset(self) -> None:
@@ -916,6 +938,33 @@ class Engine:
         self._check(self._lib.fk_rr_inference(self._ctx, C.byref(par), _p(out_rows), C.c_uint64(begin), C.c_uint64(end), _p(class_counts),
                                               _p(strategies)))
         return {"class_counts": class_counts, "strategies": strategies, "rows": out_rows}
+
+    def rr_root_diagnostics(self, family_alpha: float = 0.02, practical_delta: float = 0.03, delta_equivalence: float | None = None,
+                            min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None,
+                            rows: tuple[int, int] | None = None, want_agreement: bool = True) -> dict:
+        """``fk_rr_root_diagnostics`` over the resident pair counts and the root states kept with them (option ``"rr_keep_roots"``):
+        ``{"roots": uint64 [n_roots] ascending, "rows": RR_ROOT_ROW_DTYPE [n_roots, k] or None, "agreement": RR_AGREEMENT_ROW_DTYPE [k] or
+        None, "summary": int64 [12], "max_abs_discrepancy": float}``, ``k`` the pairs of the pair-id range ``rows``.  The parameters are
+        ``rr_inference``'s."""
+        par = self._rr_params(family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family_pair_count)
+        out_rows = agreement = None
+        begin = end = 0
+        if rows is not None:
+            begin, end = int(rows[0]), int(rows[1])
+            if begin < 0 or end < 0:
+                raise ValueError("the row range must not be negative")
+            out_rows = np.zeros((RR_MAX_ROOTS, max(end - begin, 0)), dtype=RR_ROOT_ROW_DTYPE)
+            agreement = np.zeros(max(end - begin, 0), dtype=RR_AGREEMENT_ROW_DTYPE) if want_agreement else None
+        seeds = np.zeros(RR_MAX_ROOTS, dtype=np.uint64)
+        n_roots = C.c_int32(0)
+        summary = np.zeros(RR_AGREE_COLS, dtype=np.int64)
+        largest = C.c_double(float("nan"))
+        self._check(self._lib.fk_rr_root_diagnostics(self._ctx, C.byref(par), _p(seeds), C.byref(n_roots), _p(out_rows), C.c_uint64(begin),
+                                                     C.c_uint64(end), _p(agreement), _p(summary), C.byref(largest)))
+        if out_rows is not None:  # the entry wrote [n_roots][k] at the front of the buffer
+            out_rows = out_rows.reshape(-1)[: n_roots.value * out_rows.shape[1]].reshape(n_roots.value, out_rows.shape[1])
+        return {"roots": seeds[: n_roots.value].copy(), "rows": out_rows, "agreement": agreement, "summary": summary,
+                "max_abs_discrepancy": float(largest.value)}
 
     @staticmethod
     def _dominance_outputs(n: int, rank, want_adjacency: bool) -> tuple:

@@ -131,6 +131,11 @@ def build_parser() -> argparse.ArgumentParser:
     rr.add_argument("--rows", metavar="BEGIN:END",
                     help="With --inference: the pair ids whose rows round_robin_inference_pairs.parquet holds (default: every pair of the "
                          "range when it has at most 2^22 pairs, none beyond)")
+    rr.add_argument("--root-diagnostics", action="store_true",
+                    help="With --inference on one or two roots: keep every root's states on the GPU too, run the score test, Holm's "
+                         "adjustment and the diagnostic decision per root and the agreement between the roots there, and write "
+                         "root_pairwise_diagnostics.parquet and root_decision_agreement.parquet (the pairs of --rows) and the "
+                         "agreement summary into round_robin.json")
     rr.add_argument("--dominance", action="store_true",
                     help="With --inference over the whole table: build the practical and the statistical dominance graph on the GPU and write "
                          "dominance_edges.parquet (when every pair's row is on the host), cycle_groups.parquet, dominance_fronts.parquet and "
@@ -205,7 +210,7 @@ def main(argv: Sequence[str] | None = None) -> None:
         try:
             written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
                                       out=args.out, force=args.force, inference=args.inference, rows=args.rows, dominance=args.dominance,
-                                      screening_scores=args.screening_scores)
+                                      screening_scores=args.screening_scores, root_diagnostics=args.root_diagnostics)
         except (ValueError, FileExistsError) as exc:
             raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})

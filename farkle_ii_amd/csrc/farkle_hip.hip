@@ -18,6 +18,7 @@
 #include "fk_census.h"         // device side: roll census (the trace's game loop, counting instead of recording)
 #include "fk_round_robin.h"    // device side: head-to-head round robin (window tables by unranking, generation planner, apply, summary)
 #include "fk_rr_inference.h"   // device side: round-robin inference (resident pair counts, score test, intervals, Holm, decision classes)
+#include "fk_rr_root_diagnostics.h" // device side: the inference per kept root and the cross-root agreement
 #include "fk_dominance.h"      // device side: dominance graphs of a round robin (bit matrices, closure, components, fronts, cycles, extremes)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
@@ -252,6 +253,10 @@ struct fk_ctx {
     bool ri_valid = false;               // the accumulator holds counts; what the first adding call fixed with them:
     int32_t ri_n = 0;
     uint64_t ri_begin = 0, ri_end = 0, ri_hash = 0, ri_family = 0;
+    bool ri_keep_roots = false;          // option "rr_keep_roots": adding calls keep their states in RrInferenceBufs::root_states
+    bool ri_untracked = false;           // the accumulator holds cells that no root slot holds (fk_rr_counts_add with the option on)
+    int32_t ri_roots = 0;                // root slots in use, in arrival order, and what each was kept with:
+    uint64_t ri_root_seed[FK_RR_MAX_ROOTS] = {0, 0}, ri_root_target[FK_RR_MAX_ROOTS] = {0, 0}, ri_root_cap[FK_RR_MAX_ROOTS] = {0, 0};
     DominanceBufs dm;
     BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
@@ -1638,6 +1643,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "rows_event") *value = c->last_rows_event;
     else if (n == "census_chunk_games") *value = c->census_chunk_games;
     else if (n == "rr_window_blocks") *value = c->rr_window_blocks;
+    else if (n == "rr_keep_roots") *value = c->ri_keep_roots ? 1 : 0;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1682,6 +1688,11 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
         if (value < 2 || value > ((int64_t)1 << 22) || (value & 1))
             return fail(c, FK_ERR_ARG, "rr_window_blocks must be even and in [2, 2^22] (a pair's two blocks share a window)");
         c->rr_window_blocks = value;
+    }
+    else if (n == "rr_keep_roots") {
+        if (value != 0 && value != 1) return fail(c, FK_ERR_ARG, "rr_keep_roots is 0 or 1");
+        if (c->ri_valid) return fail(c, FK_ERR_ARG, "rr_keep_roots cannot change while counts are resident (fk_rr_counts_reset comes first)");
+        c->ri_keep_roots = value != 0;
     }
     else if (n == "block") {
         if (value != 0 && value != 64 && value != 128 && value != 256 && value != 512 && value != 768 && value != 1024)
@@ -3146,8 +3157,9 @@ int fk_h2h_run(fk_ctx *c, const fk_strategy seats[2], uint64_t root_seed, uint64
 // generation's total, the number of playing blocks and the call's error record, then two words per pass; play_block_passes plays them.
 static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t root_seed, uint64_t pair_begin, uint64_t pair_end,
                                 uint64_t target, uint64_t max_attempts, int32_t target_score, int32_t max_rounds, const LaunchPlan &plan,
-                                uint32_t *block_state, int64_t *summary, uint32_t *d_staged = nullptr) {
-    using namespace fkrr; // d_staged: the call's states stay on the device, [pair_end - pair_begin][2][RR_STATE] (block_state is null then)
+                                uint32_t *block_state, int64_t *summary, uint32_t *d_staged = nullptr, uint32_t *d_root_slot = nullptr) {
+    using namespace fkrr; // d_staged: the call's states stay on the device, [pair_end - pair_begin][2][RR_STATE] (block_state is null then);
+                          // d_root_slot, nullable: they are also kept there (option "rr_keep_roots")
     HIPCHK(c, hipSetDevice(c->device));
     begin_call(c);
     // the n-row table, packed, and its patience classes: uploaded once per call
@@ -3267,6 +3279,7 @@ static int h2h_round_robin_impl(fk_ctx *c, const fk_strategy *table, int32_t n, 
         hipLaunchKernelGGL(fkri::fk_ri_add_kernel, dim3((uint32_t)((n_rows_call + 255u) / 256u)), dim3(256), 0, c->stream, d_staged, n_rows_call,
                            (uint32_t)target, (uint32_t)max_attempts, c->ri.counts.p);
         HIPCHK(c, hipGetLastError());
+        if (d_root_slot) HIPCHK(c, hipMemcpyAsync(d_root_slot, d_staged, (size_t)n_rows_call * RR_STATE * 4, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (summary) { // added to the caller's buffer only when the whole call has succeeded
@@ -3337,10 +3350,33 @@ static int rr_counts_match(fk_ctx *c, const fk_strategy *table, int32_t n, uint6
     return FK_OK;
 }
 
-// room for the call's states and, on a first call, a zeroed accumulator (it counts as resident only once the call has succeeded)
-static int rr_counts_prepare(fk_ctx *c, uint64_t n_pairs, bool fresh) {
+// Option "rr_keep_roots": the root slot this adding call's states go to, -1 for none (option off, or the root set is untracked already).
+// Refuses, before any device work, a seed that is kept already and a root beyond the slots.
+static int rr_root_slot(fk_ctx *c, uint64_t root_seed, int &slot) {
+    slot = -1;
+    if (!c->ri_keep_roots || c->ri_untracked) return FK_OK;
+    for (int32_t r = 0; r < c->ri_roots; ++r)
+        if (c->ri_root_seed[r] == root_seed)
+            return fail(c, FK_ERR_ARG, "root_seed %llu is kept already: the kept roots are distinct", (unsigned long long)root_seed);
+    if (c->ri_roots >= FK_RR_MAX_ROOTS)
+        return fail(c, FK_ERR_ARG, "%d roots are kept already: fk_rr_root_diagnostics admits one or two roots", (int)c->ri_roots);
+    slot = c->ri_roots;
+    return FK_OK;
+}
+
+static void rr_root_keep(fk_ctx *c, int slot, uint64_t root_seed, uint64_t target, uint64_t max_attempts) { // the call has succeeded
+    if (slot < 0) return;
+    c->ri_root_seed[slot] = root_seed, c->ri_root_target[slot] = target, c->ri_root_cap[slot] = max_attempts;
+    c->ri_roots = slot + 1;
+}
+
+// room for the call's states (and the root slot they are kept in) and, on a first call, a zeroed accumulator (it counts as resident only
+// once the call has succeeded)
+static int rr_counts_prepare(fk_ctx *c, uint64_t n_pairs, bool fresh, int slot = -1) {
     HIPCHK(c, hipSetDevice(c->device));
     if (const int rc = ensure_all(c, c->ri.counts, (size_t)n_pairs * 2 * fkri::RI_COLS, c->ri.staged, (size_t)n_pairs * 2 * fkrr::RR_STATE)) return rc;
+    if (slot >= 0)
+        if (const int rc = ensure(c, c->ri.root_states[slot], (size_t)n_pairs * 2 * fkrr::RR_STATE)) return rc;
     if (fresh) HIPCHK(c, hipMemsetAsync(c->ri.counts.p, 0, (size_t)n_pairs * 2 * fkri::RI_COLS * 8, c->stream));
     return FK_OK;
 }
@@ -3360,17 +3396,23 @@ int fk_h2h_round_robin_resident(fk_ctx *c, const fk_strategy *table, int32_t n, 
     uint64_t hash = 0;
     bool fresh = false;
     if ((rc = rr_counts_match(c, table, n, pair_begin, pair_end, family_pair_count, hash, fresh))) return rc;
+    int slot = -1;
+    if ((rc = rr_root_slot(c, root_seed, slot))) return rc;
     rc = replay_on_oom(c, [&] {
-        if (const int r = rr_counts_prepare(c, pair_end - pair_begin, fresh)) return r;
+        if (const int r = rr_counts_prepare(c, pair_end - pair_begin, fresh, slot)) return r;
         return h2h_round_robin_impl(c, table, n, root_seed, pair_begin, pair_end, target, max_attempts, target_score, max_rounds, plan, nullptr, summary,
-                                    c->ri.staged.p);
+                                    c->ri.staged.p, slot >= 0 ? c->ri.root_states[slot].p : nullptr);
     });
-    if (rc == FK_OK) rr_counts_fix(c, n, pair_begin, pair_end, hash, family_pair_count);
+    if (rc == FK_OK) {
+        rr_counts_fix(c, n, pair_begin, pair_end, hash, family_pair_count);
+        rr_root_keep(c, slot, root_seed, target, max_attempts);
+    }
     return rc;
 }
 
-int fk_rr_counts_add(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target, uint64_t max_attempts,
-                     const uint32_t *block_state, uint64_t family_pair_count) {
+// fk_rr_counts_add (root_seed null) and fk_rr_counts_add_root
+static int rr_counts_add_impl(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                              uint64_t max_attempts, const uint32_t *block_state, uint64_t family_pair_count, const uint64_t *root_seed) {
     if (!c) return FK_ERR_ARG;
     if (!table || !block_state) return fail(c, FK_ERR_ARG, "the strategy table and block_state are required");
     if (n < 2) return fail(c, FK_ERR_ARG, "a round robin needs at least two strategies, got %d", (int)n);
@@ -3391,24 +3433,41 @@ int fk_rr_counts_add(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pa
             return fail(c, FK_ERR_ARG, "block_state of pair %llu, order %u is not a state of a block with target %llu and max_attempts %llu",
                         (unsigned long long)(pair_begin + row / 2u), (unsigned)(row & 1u), (unsigned long long)target, (unsigned long long)max_attempts);
     }
-    if ((rc = rr_counts_prepare(c, pair_end - pair_begin, fresh))) return rc;
+    int slot = -1;
+    if (root_seed && (rc = rr_root_slot(c, *root_seed, slot))) return rc;
+    if ((rc = rr_counts_prepare(c, pair_end - pair_begin, fresh, slot))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->ri.staged.p, block_state, (size_t)n_rows * fkrr::RR_STATE * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(fkri::fk_ri_add_kernel, dim3((uint32_t)((n_rows + 255u) / 256u)), dim3(256), 0, c->stream, c->ri.staged.p, n_rows, (uint32_t)target,
                        (uint32_t)max_attempts, c->ri.counts.p);
     HIPCHK(c, hipGetLastError());
+    if (slot >= 0)
+        HIPCHK(c, hipMemcpyAsync(c->ri.root_states[slot].p, c->ri.staged.p, (size_t)n_rows * fkrr::RR_STATE * 4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     rr_counts_fix(c, n, pair_begin, pair_end, hash, family_pair_count);
+    if (root_seed) rr_root_keep(c, slot, *root_seed, target, max_attempts);
+    else if (c->ri_keep_roots) c->ri_untracked = true; // the accumulator now holds cells that no slot holds
     return FK_OK;
+}
+
+int fk_rr_counts_add(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target, uint64_t max_attempts,
+                     const uint32_t *block_state, uint64_t family_pair_count) {
+    return rr_counts_add_impl(c, table, n, pair_begin, pair_end, target, max_attempts, block_state, family_pair_count, nullptr);
+}
+
+int fk_rr_counts_add_root(fk_ctx *c, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                          uint64_t max_attempts, const uint32_t *block_state, uint64_t family_pair_count, uint64_t root_seed) {
+    return rr_counts_add_impl(c, table, n, pair_begin, pair_end, target, max_attempts, block_state, family_pair_count, &root_seed);
 }
 
 int fk_rr_counts_reset(fk_ctx *c) {
     if (!c) return FK_ERR_ARG;
     c->ri_valid = false;
+    c->ri_roots = 0, c->ri_untracked = false; // the root slots are forgotten with the accumulator
     return FK_OK;
 }
 
 // fk_rr_inference's refusals; fk_rr_dominance makes them too
-static int rr_inference_check(fk_ctx *c, const fk_rr_inference_params *par, const fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
+static int rr_inference_check(fk_ctx *c, const fk_rr_inference_params *par, bool rows, uint64_t row_begin, uint64_t row_end,
                               const int64_t *class_counts) {
     if (!par || !class_counts) return fail(c, FK_ERR_ARG, "params and class_counts are required");
     if (!c->ri_valid) return fail(c, FK_ERR_ARG, "no resident counts: fk_h2h_round_robin_resident or fk_rr_counts_add comes first");
@@ -3452,8 +3511,8 @@ static int rr_inference_enqueue(fk_ctx *c, const fk_rr_inference_params *par, fk
     HIPCHK(c, hipMemsetAsync(b.class_counts.p, 0, RI_CLASSES * 8, c->stream));
     HIPCHK(c, hipMemsetAsync(b.strat_out.p, 0, (size_t)n * RI_STRAT_COLS * 8, c->stream));
     const dim3 pair_grid((P + 255u) / 256u), b256(256);
-    hipLaunchKernelGGL(fk_ri_pair_kernel, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, par->critical_simultaneous, b.sums.p, b.key.p, b.val.p,
-                       b.sim.p);
+    hipLaunchKernelGGL(fk_ri_pair_kernel<true>, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, par->critical_simultaneous, b.sums.p, b.key.p,
+                       b.val.p, b.sim.p, (uint8_t *)nullptr);
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(fk_ri_strategy_kernel, dim3((n + 255u) / 256u), b256, 0, c->stream, b.sums.p, n, par->min_candidate_completion_rate, b.strat_flags.p,
                        b.strat_out.p);
@@ -3480,13 +3539,91 @@ static int rr_inference_enqueue(fk_ctx *c, const fk_rr_inference_params *par, fk
 int fk_rr_inference(fk_ctx *c, const fk_rr_inference_params *par, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end, int64_t *class_counts,
                     int64_t *strategy_classes) {
     if (!c) return FK_ERR_ARG;
-    if (const int rc = rr_inference_check(c, par, rows, row_begin, row_end, class_counts)) return rc;
+    if (const int rc = rr_inference_check(c, par, rows != nullptr, row_begin, row_end, class_counts)) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     begin_call(c);
     if (const int rc = rr_inference_enqueue(c, par, rows, row_begin, row_end, class_counts, strategy_classes, nullptr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, collect_timers(c));
     c->timing.total_ms = c->timing.play_ms;
+    return FK_OK;
+}
+
+// ---- the inference per kept root and the cross-root agreement (device side: fk_rr_root_diagnostics.h) ----
+int fk_rr_root_diagnostics(fk_ctx *c, const fk_rr_inference_params *par, uint64_t *root_seeds, int32_t *n_roots, fk_rr_root_row *rows, uint64_t row_begin,
+                           uint64_t row_end, fk_rr_agreement_row *agreement, int64_t *summary, double *max_abs_discrepancy) {
+    using namespace fkri;
+    if (!c) return FK_ERR_ARG;
+    if (!par || !root_seeds || !n_roots || !summary) return fail(c, FK_ERR_ARG, "params, root_seeds, n_roots and summary are required");
+    if (const int rc = rr_inference_check(c, par, rows || agreement, row_begin, row_end, summary)) return rc;
+    if (c->ri_untracked)
+        return fail(c, FK_ERR_ARG, "the root set is untracked: fk_rr_counts_add added counts that no root slot holds (fk_rr_counts_add_root keeps them)");
+    if (c->ri_roots == 0) return fail(c, FK_ERR_ARG, "no kept roots: option rr_keep_roots comes before the adding calls");
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    RrInferenceBufs &b = c->ri;
+    const uint32_t P = (uint32_t)(c->ri_end - c->ri_begin), n = (uint32_t)c->ri_n, R = (uint32_t)c->ri_roots;
+    uint32_t slot_of[FK_RR_MAX_ROOTS] = {0u, 1u}; // ascending seed, unsigned
+    if (R == 2u && c->ri_root_seed[1] < c->ri_root_seed[0]) slot_of[0] = 1u, slot_of[1] = 0u;
+    const bool sliced = rows || agreement;
+    const size_t n_rows_out = sliced ? (size_t)(row_end - row_begin) : 0;
+    int rc = FK_OK;
+    if ((rc = ensure_all(c, b.sums, (size_t)n * RI_SUMS, b.strat_flags, (size_t)n, b.strat_out, (size_t)n * RI_STRAT_COLS, b.viable, (size_t)P, b.key, (size_t)P,
+                         b.key_sorted, (size_t)P, b.val, (size_t)P, b.val_sorted, (size_t)P, b.scaled, (size_t)P, b.running, (size_t)P, b.adjusted, (size_t)P,
+                         b.position, (size_t)P, b.root_effect, (size_t)R * P, b.root_decision, (size_t)R * P, b.agree_summary, (size_t)RD_COLS + 1,
+                         b.root_rows, rows ? (size_t)R * n_rows_out : 0, b.agree_rows, agreement ? n_rows_out : 0)))
+        return rc;
+    Timer device_work(c, &c->timing.play_ms, SLOT_PLAY); // fk_timing: play_ms = total_ms = the entry's device work, copies back excluded
+    HIPCHK(c, hipMemsetAsync(b.sums.p, 0, (size_t)n * RI_SUMS * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(b.agree_summary.p, 0, ((size_t)RD_COLS + 1) * 8, c->stream));
+    const dim3 pair_grid((P + 255u) / 256u), b256(256);
+    // 1. the combined viability and the strategies' flags, without the interval
+    hipLaunchKernelGGL(fk_ri_pair_kernel<false>, pair_grid, b256, 0, c->stream, b.counts.p, n, c->ri_begin, P, 0.0, b.sums.p, (unsigned long long *)nullptr,
+                       (uint32_t *)nullptr, (double2 *)nullptr, b.viable.p);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(fk_ri_strategy_kernel, dim3((n + 255u) / 256u), b256, 0, c->stream, b.sums.p, n, par->min_candidate_completion_rate, b.strat_flags.p,
+                       b.strat_out.p);
+    HIPCHK(c, hipGetLastError());
+    const uint32_t row_first = sliced ? (uint32_t)(row_begin - c->ri_begin) : 0u, row_last = sliced ? (uint32_t)(row_end - c->ri_begin) : 0u;
+    // 2. per kept root: the score test, Holm as the combined chain does it, the decisions and the rows
+    for (uint32_t r = 0; r < R; ++r) {
+        const uint32_t *state = b.root_states[slot_of[r]].p;
+        double *effect = b.root_effect.p + (size_t)r * P;
+        hipLaunchKernelGGL(fk_rd_test_kernel, pair_grid, b256, 0, c->stream, state, b.viable.p, P, b.key.p, b.val.p, effect);
+        HIPCHK(c, hipGetLastError());
+        FK_CUB(hipcub::DeviceRadixSort::SortPairs, b.key.p, b.key_sorted.p, b.val.p, b.val_sorted.p, (int)P, 0, 64, c->stream);
+        hipLaunchKernelGGL(fk_ri_holm_scale_kernel, pair_grid, b256, 0, c->stream, b.key_sorted.p, P, b.scaled.p);
+        HIPCHK(c, hipGetLastError());
+        FK_CUB(hipcub::DeviceScan::InclusiveScan, b.scaled.p, b.running.p, hipcub::Max(), (int)P, c->stream);
+        hipLaunchKernelGGL(fk_ri_holm_scatter_kernel, pair_grid, b256, 0, c->stream, b.running.p, b.val_sorted.p, P, b.adjusted.p, b.position.p);
+        HIPCHK(c, hipGetLastError());
+        fk_rr_root_row *d_rows = rows && n_rows_out ? b.root_rows.p + (size_t)r * n_rows_out : nullptr;
+        hipLaunchKernelGGL(d_rows ? fk_rd_decide_kernel<true> : fk_rd_decide_kernel<false>, pair_grid, b256, 0, c->stream, state, b.viable.p, n, c->ri_begin, P,
+                           par->family_alpha, par->critical_ordinary, b.strat_flags.p, effect, b.adjusted.p, b.position.p,
+                           b.agree_summary.p + RD_ROOT0 + (size_t)r * RD_ROOT_COLS, b.root_decision.p + (size_t)r * P, row_first, row_last, d_rows);
+        HIPCHK(c, hipGetLastError());
+    }
+    // 3. the agreement
+    hipLaunchKernelGGL(fk_rd_agree_kernel, pair_grid, b256, 0, c->stream, n, c->ri_begin, P, R, b.root_effect.p, b.root_decision.p, b.agree_summary.p, row_first,
+                       row_last, agreement && n_rows_out ? b.agree_rows.p : nullptr);
+    HIPCHK(c, hipGetLastError());
+    device_work.stop();
+    unsigned long long out[RD_COLS + 1];
+    HIPCHK(c, hipMemcpyAsync(out, b.agree_summary.p, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    if (rows && n_rows_out) HIPCHK(c, hipMemcpyAsync(rows, b.root_rows.p, (size_t)R * n_rows_out * sizeof(fk_rr_root_row), hipMemcpyDeviceToHost, c->stream));
+    if (agreement && n_rows_out)
+        HIPCHK(c, hipMemcpyAsync(agreement, b.agree_rows.p, n_rows_out * sizeof(fk_rr_agreement_row), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
+    for (uint32_t k = 0; k < RD_COLS; ++k) summary[k] = (int64_t)out[k];
+    if (max_abs_discrepancy) {
+        double largest = NAN;
+        if (out[RD_AVAILABLE]) memcpy(&largest, &out[RD_COLS], sizeof(largest));
+        *max_abs_discrepancy = largest;
+    }
+    for (uint32_t r = 0; r < FK_RR_MAX_ROOTS; ++r) root_seeds[r] = r < R ? c->ri_root_seed[slot_of[r]] : 0u;
+    *n_roots = (int32_t)R;
     return FK_OK;
 }
 
@@ -3600,7 +3737,7 @@ int fk_dominance_graph(fk_ctx *c, int32_t n, const uint8_t *decision_class, cons
 int fk_rr_dominance(fk_ctx *c, const fk_rr_inference_params *par, const uint32_t *rank, fk_dom_node *nodes, fk_dom_extreme *extremes, uint64_t *adjacency,
                     int64_t *class_counts) {
     if (!c) return FK_ERR_ARG;
-    if (const int rc = rr_inference_check(c, par, nullptr, 0, 0, class_counts)) return rc;
+    if (const int rc = rr_inference_check(c, par, false, 0, 0, class_counts)) return rc;
     const uint64_t all_pairs = (uint64_t)c->ri_n * (uint64_t)(c->ri_n - 1) / 2u;
     if (c->ri_begin != 0 || c->ri_end != all_pairs)
         return fail(c, FK_ERR_ARG, "the resident counts hold pairs [%llu, %llu) of the table's %llu: a dominance graph needs the whole family",

@@ -86,7 +86,7 @@ struct RoundRobinBufs { // fk_h2h_round_robin
     Dev<uint32_t> bounds;  // [passes][2]
     Dev<ull> summary;
 };
-struct RrInferenceBufs { // fk_h2h_round_robin_resident, fk_rr_counts_add, fk_rr_inference
+struct RrInferenceBufs { // fk_h2h_round_robin_resident, fk_rr_counts_add, fk_rr_inference, fk_rr_root_diagnostics
     Dev<ull> counts;               // the accumulator: [pairs][2][fkri::RI_COLS], resident between calls
     Dev<uint32_t> staged;          // one call's states [pairs][2][RR_STATE], added to `counts` when the call has succeeded
     Dev<ull> sums;                 // [n][fkri::RI_SUMS] per-strategy incident sums
@@ -99,6 +99,14 @@ struct RrInferenceBufs { // fk_h2h_round_robin_resident, fk_rr_counts_add, fk_rr
     Dev<ull> class_counts;         // [fkri::RI_CLASSES]
     Dev<long long> strat_out;      // [n][fkri::RI_STRAT_COLS]
     Dev<fk_rr_pair_row> rows;      // the asked slice
+    // option "rr_keep_roots" and fk_rr_root_diagnostics
+    Dev<uint32_t> root_states[FK_RR_MAX_ROOTS]; // the root slots: one adding call's states each, [pairs][2][RR_STATE], in arrival order
+    Dev<uint8_t> viable;           // [pairs] the combined pair's viability
+    Dev<double> root_effect;       // [roots][pairs] d_ab per root, ascending seed (NaN without a test)
+    Dev<uint8_t> root_decision;    // [roots][pairs] the diagnostic decisions
+    Dev<ull> agree_summary;        // [fkri::RD_COLS] and the largest absolute discrepancy's bits
+    Dev<fk_rr_root_row> root_rows; // [roots][the asked slice]
+    Dev<fk_rr_agreement_row> agree_rows; // the asked slice
 };
 struct DominanceBufs { // fk_dominance_graph, fk_rr_dominance
     Dev<uint8_t> cls;             // [pairs] decision classes

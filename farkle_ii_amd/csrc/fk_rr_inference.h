@@ -11,6 +11,7 @@
 //   fk_ri_add_kernel         one root's block states -> the 64-bit accumulator per (pair, order) (_combine_within_order, :563-635)
 //   fk_ri_pair_kernel        per pair: viability (_viability_status, :638-700), the per-strategy incident sums (a segmented wave
 //                            scan, as fk_rr_summary_kernel), the score test's p as Holm's sort key, the simultaneous interval
+//                            (<false>: viability and sums alone, for fk_rr_root_diagnostics.h)
 //   fk_ri_strategy_kernel    per strategy: completion rate, the two viability flags
 //   fk_ri_holm_scale_kernel  (count - index) * p over the sorted p (_holm_adjust, :280-295); hipcub sorts before and scans (max) after
 //   fk_ri_holm_scatter_kernel min(1, .) and the positions back to pair order
@@ -200,10 +201,12 @@ __global__ void fk_ri_add_kernel(const uint32_t *__restrict__ state, uint64_t n_
 
 // One lane per pair.  The i side of the incident sums leaves through the segmented wave scan of fk_rr_summary_kernel (pair ids ascend
 // with the lane, so the lanes of a wave that share row i are adjacent), the j side with one atomic per lane and column.
+// TESTED = false is the viability pass of fk_rr_root_diagnostics: the sums and the pair's `viable` byte, no test and no interval.
+template <bool TESTED>
 __global__ __launch_bounds__(256) void fk_ri_pair_kernel(const unsigned long long *__restrict__ acc, uint32_t n, uint64_t pair0, uint32_t n_pairs,
                                                          double critical_simultaneous, unsigned long long *__restrict__ sums /* [n][RI_SUMS] */,
                                                          unsigned long long *__restrict__ keys, uint32_t *__restrict__ vals,
-                                                         double2 *__restrict__ sim) {
+                                                         double2 *__restrict__ sim, uint8_t *__restrict__ viable /* [n_pairs], TESTED = false only */) {
 #pragma clang fp contract(off)
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x; // blockDim is a multiple of 64: whole waves
     const bool live = p < n_pairs;
@@ -214,15 +217,19 @@ __global__ __launch_bounds__(256) void fk_ri_pair_kernel(const unsigned long lon
         const PairCounts c = ri_pair_counts(acc + (size_t)p * 2u * RI_COLS);
         v[0] = (unsigned long long)c.attempted, v[1] = (unsigned long long)c.completed, v[2] = (unsigned long long)c.safety;
         v[3] = c.viable ? 0ull : 1ull;
-        double p_value = 1.0, low = NAN, high = NAN; // a pair without a test enters Holm's family as 1.0 (:864-868)
-        if (c.viable) {
-            p_value = ri_score_test(c.x_ab, c.n_ab, c.x_ba, c.n_ba).p;
-            ri_interval(c.x_ab, c.n_ab, c.x_ba, c.n_ba, critical_simultaneous, low, high);
-            low = 0.5 * low, high = 0.5 * high; // :853-854
+        if constexpr (TESTED) {
+            double p_value = 1.0, low = NAN, high = NAN; // a pair without a test enters Holm's family as 1.0 (:864-868)
+            if (c.viable) {
+                p_value = ri_score_test(c.x_ab, c.n_ab, c.x_ba, c.n_ba).p;
+                ri_interval(c.x_ab, c.n_ab, c.x_ba, c.n_ba, critical_simultaneous, low, high);
+                low = 0.5 * low, high = 0.5 * high; // :853-854
+            }
+            keys[p] = (unsigned long long)__double_as_longlong(p_value); // non-negative doubles order as their bit patterns
+            vals[p] = p;
+            sim[p] = make_double2(low, high);
+        } else {
+            viable[p] = c.viable ? 1u : 0u;
         }
-        keys[p] = (unsigned long long)__double_as_longlong(p_value); // non-negative doubles order as their bit patterns
-        vals[p] = p;
-        sim[p] = make_double2(low, high);
     }
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long up_acc[RI_SUMS];

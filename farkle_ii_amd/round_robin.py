@@ -10,10 +10,11 @@ the pairs and seats the orders, ``_simulate_block_from_manifest`` :1172-1235 is 
 * ``run_round_robin`` — the command: one sequence of engine calls per root of ``sim.seed_list``; with ``--inference`` the states stay
   on the device and the score test, the score intervals, Holm's adjustment and the decision classes of the reference's
   ``h2h_inference.py`` run there (``rr_inference.py`` is their host side); with ``--dominance`` on top, the reference's dominance
-  graphs are built there too (``dominance.py`` is their host side).
+  graphs are built there too (``dominance.py`` is their host side); with ``--root-diagnostics`` on top, every root's states are kept
+  there as well and the inference per root and the agreement between the roots run there (``rr_root_diagnostics.py``).
 
 Out of scope: the library route of the interval (``confint_proportions_2indep``) is not reproduced; the reference's own complete
-inversion is.  Also out of scope: the reference's power plan, schedule hashes, block ids and sidecars; its root-specific diagnostics;
+inversion is.  Also out of scope: the reference's power plan, schedule hashes, block ids and sidecars;
 resuming a partly played round robin; several ranks (pair ranges make the split trivial — a later change).
 """
 from __future__ import annotations
@@ -284,7 +285,7 @@ def parse_pair_range(text: str | None, n: int) -> tuple[int, int]:
 
 def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
                     force: bool = False, strategies=None, engine=None, world: int | None = None, inference: bool = False,
-                    rows: str | None = None, dominance: bool = False, screening_scores=None) -> dict:
+                    rows: str | None = None, dominance: bool = False, screening_scores=None, root_diagnostics: bool = False) -> dict:
     """``farkle round-robin``: the grid of ``cfg`` (restricted to the ids of ``strategy_ids_file``), every pair of the range, per root of
     ``sim.seed_list``.  Writes ``round_robin_pairs.parquet``, ``round_robin_strategies.parquet``, ``round_robin.json`` and, with
     ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths.
@@ -298,7 +299,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     With ``dominance`` (and ``inference``, over the whole table) the inference feeds the dominance graphs on the device
     (``Engine.rr_dominance``) and the command also writes the reference's ``cycle_groups.parquet``, ``dominance_fronts.parquet``,
     ``dominance_summary.json`` and — when every pair's row is on the host — ``dominance_edges.parquet`` (``dominance.py`` builds the
-    frames; ``round_robin.json`` says when the edges are omitted).  ``screening_scores``: a JSON file ``{strategy id: score}``."""
+    frames; ``round_robin.json`` says when the edges are omitted).  ``screening_scores``: a JSON file ``{strategy id: score}``.
+
+    With ``root_diagnostics`` (and ``inference``, on one or two distinct roots) the engine's option ``"rr_keep_roots"`` is on for the
+    run, ``Engine.rr_root_diagnostics`` follows the inference and the command also writes the reference's
+    ``root_pairwise_diagnostics.parquet`` and ``root_decision_agreement.parquet`` (the pairs of ``rows``) and the summary under
+    ``"root_diagnostics"`` in ``round_robin.json`` (``rr_root_diagnostics.py`` builds the frames)."""
     import os
 
     import pyarrow as pa
@@ -358,6 +364,15 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     elif screening_scores is not None:
         raise ValueError("round-robin: --screening-scores belongs to --dominance")
     roots = [int(r) for r in (cfg.sim.seed_list if cfg.sim.seed_list else [cfg.sim.seed])]
+    if root_diagnostics:
+        from . import rr_root_diagnostics as rd
+
+        if not inference:
+            raise ValueError("round-robin: --root-diagnostics belongs to --inference")
+        try:
+            rd.check_roots(roots)
+        except ValueError as exc:
+            raise ValueError(f"round-robin: --root-diagnostics: {exc}") from exc
     out_dir = Path(out) if out is not None else cfg.results_root / "h2h_round_robin"
     if out_dir.exists() and not force:
         raise FileExistsError(f"round-robin: {out_dir} exists; pass --force to replace its tables")
@@ -375,16 +390,25 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
         LOGGER.info("round robin root %d: %d pairs, %d attempts", root, end - begin, int(states[-1][:, :, 0].sum(dtype=np.int64)))
     if inference:
         eng.rr_counts_reset()
-        for root in roots:
-            eng.h2h_round_robin_resident(table, root, target, max_attempts, pair_begin=begin, pair_end=end, summary=summary,
-                                         family_pair_count=family)
-            LOGGER.info("round robin root %d: %d pairs, resident", root, end - begin)
-        knobs = dict(family_alpha=h2h.family_alpha, practical_delta=h2h.practical_delta, delta_equivalence=h2h.delta_equivalence,
-                     min_candidate_completion_rate=h2h.min_candidate_completion_rate)
-        result = eng.rr_inference(family_pair_count=family, rows=row_range, **knobs)
-        if dominance:
-            graphs = eng.rr_dominance(family_pair_count=family, rank=dom.rank_of_ids(ids), **knobs)
-        eng.rr_counts_reset()
+        keep_before = eng.get_option("rr_keep_roots") if root_diagnostics else 0
+        if root_diagnostics:
+            eng.set_option("rr_keep_roots", 1)
+        try:
+            for root in roots:
+                eng.h2h_round_robin_resident(table, root, target, max_attempts, pair_begin=begin, pair_end=end, summary=summary,
+                                             family_pair_count=family)
+                LOGGER.info("round robin root %d: %d pairs, resident", root, end - begin)
+            knobs = dict(family_alpha=h2h.family_alpha, practical_delta=h2h.practical_delta, delta_equivalence=h2h.delta_equivalence,
+                         min_candidate_completion_rate=h2h.min_candidate_completion_rate)
+            result = eng.rr_inference(family_pair_count=family, rows=row_range, **knobs)
+            if root_diagnostics:
+                diagnosed = eng.rr_root_diagnostics(family_pair_count=family, rows=row_range, **knobs)
+            if dominance:
+                graphs = eng.rr_dominance(family_pair_count=family, rank=dom.rank_of_ids(ids), **knobs)
+        finally:
+            eng.rr_counts_reset()
+            if root_diagnostics:
+                eng.set_option("rr_keep_roots", keep_before)
     elapsed = time.perf_counter() - started
     out_dir.mkdir(parents=True, exist_ok=True)
     written = {"strategies": out_dir / "round_robin_strategies.parquet", "json": out_dir / "round_robin.json"}
@@ -394,6 +418,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
         written["inference_strategies"] = out_dir / "round_robin_inference_strategies.parquet"
         frames.append((ri.pairs_frame(result["rows"], ids, family_pair_count=family, **knobs), written["inference_pairs"]))
         frames.append((ri.strategies_frame(result["strategies"], ids, h2h.min_candidate_completion_rate), written["inference_strategies"]))
+        if root_diagnostics:
+            written["root_pairs"] = out_dir / "root_pairwise_diagnostics.parquet"
+            written["root_agreement"] = out_dir / "root_decision_agreement.parquet"
+            kept = [int(r) for r in diagnosed["roots"]]
+            frames.append((rd.root_pairs_frame(diagnosed["rows"], kept, ids, family_alpha=h2h.family_alpha), written["root_pairs"]))
+            frames.append((rd.agreement_frame(diagnosed["agreement"], kept, ids), written["root_agreement"]))
         if dominance:
             written["dominance_cycles"] = out_dir / "cycle_groups.parquet"
             written["dominance_fronts"] = out_dir / "dominance_fronts.parquet"
@@ -427,6 +457,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     if inference:
         report["inference"] = {"class_counts": {name: int(v) for name, v in zip(ri.DECISION_CLASSES, result["class_counts"])},
                                "family_pair_count": family, "row_begin": row_range[0], "row_end": row_range[1], **knobs}
+    if root_diagnostics:
+        largest = diagnosed["max_abs_discrepancy"]
+        report["root_diagnostics"] = {"roots": kept, "row_begin": row_range[0], "row_end": row_range[1],
+                                      "summary": {name: int(v) for name, v in zip(rd.SUMMARY_COLS, diagnosed["summary"])},
+                                      "max_abs_discrepancy": None if math.isnan(largest) else float(largest),
+                                      "root_specific_h2h_stability": rd.stability_summary(diagnosed["summary"])}
     if dominance:
         report["dominance"] = {"edges_written": edges_written, "screening_scores": None if screening_scores is None else str(screening_scores),
                                **{key: digest[key] for key in ("practical_front_count", "statistical_front_count", "practical_cycle_group_count",

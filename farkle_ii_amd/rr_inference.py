@@ -17,9 +17,10 @@ The interval is the reference's own complete inversion of the uncorrected constr
 Left out of the frames (the reference computes them from its power plan, schedule hashes and block manifests, which this package
 does not have): ``family_hash``, ``replacement_attempt_count`` and its per-strategy sums, ``score_test_id``, ``interval_method_id``,
 ``h2h_method_version``, ``planned_target_power_conditional_on_completed_support``,
-``planned_worst_scenario_power_conditional_on_completed_support``, ``power_support_status``.  Also out of scope:
-``_root_specific_diagnostics``, sidecars and completion stamps, several ranks, resuming.  The graphs the reference's
-``dominance.py`` builds from these classes are ``Engine.rr_dominance`` and ``farkle_ii_amd/dominance.py``.
+``planned_worst_scenario_power_conditional_on_completed_support``, ``power_support_status``.  Also out of scope: sidecars and
+completion stamps, several ranks, resuming.  The graphs the reference's ``dominance.py`` builds from these classes are
+``Engine.rr_dominance`` and ``farkle_ii_amd/dominance.py``; its ``_root_specific_diagnostics`` (the inference per root and the
+cross-root agreement) is ``Engine.rr_root_diagnostics`` and ``farkle_ii_amd/rr_root_diagnostics.py``.
 """
 from __future__ import annotations
 
@@ -253,6 +254,24 @@ def check_params(n_pairs: int, family_alpha: float, practical_delta: float, delt
         raise ValueError(f"family_pair_count {family_pair_count} is smaller than the {n_pairs} pairs of the range")
 
 
+def viability(n: int, counts: np.ndarray, pair_begin: int, min_candidate_completion_rate: float) -> dict:
+    """``_viability_status`` (:638-700) over ``counts`` (``combine_counts``): the pairs' ids and ``viable`` bits, the per-strategy
+    incident sums ``[n, 4]`` (attempted, completed, safety, nonviable pairs) and the strategies' two flags."""
+    pid, i, j = pair_ids(n, pair_begin, pair_begin + counts.shape[0])
+    ab, ba = counts[:, 0], counts[:, 1]
+    viable = ((ab[:, 7] > 0) & (ab[:, 8] == ab[:, 7]) & (ab[:, 1] == ab[:, 5]) & (ba[:, 7] > 0) & (ba[:, 8] == ba[:, 7]) & (ba[:, 1] == ba[:, 5])
+              & (ab[:, 1] == ba[:, 1]))
+    # incident sums, one division, "all incident pairs viable"
+    sums = np.zeros((n, 4), dtype=np.int64)
+    for idx in (i, j):
+        for c, values in enumerate((ab[:, 0] + ba[:, 0], ab[:, 1] + ba[:, 1], ab[:, 2] + ba[:, 2], (~viable).astype(np.int64))):
+            np.add.at(sums[:, c], idx, values)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rate = sums[:, 1] / sums[:, 0]
+    operational = (sums[:, 0] > 0) & (rate >= float(min_candidate_completion_rate))
+    return {"pair_id": pid, "i": i, "j": j, "viable": viable, "sums": sums, "operational": operational, "inferential": sums[:, 3] == 0}
+
+
 def infer(n: int, counts, pair_begin: int = 0, family_alpha: float = 0.02, practical_delta: float = 0.03,
           delta_equivalence: float | None = None, min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None,
           rows: tuple[int, int] | None = None, intervals: str = "brentq") -> dict:
@@ -267,19 +286,9 @@ def infer(n: int, counts, pair_begin: int = 0, family_alpha: float = 0.02, pract
     n_pairs = counts.shape[0]
     family = pair_count(n) if family_pair_count is None else int(family_pair_count)
     check_params(n_pairs, family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family)
-    pid, i, j = pair_ids(n, begin, begin + n_pairs)
+    status = viability(n, counts, begin, min_candidate_completion_rate)
+    pid, i, j, viable, sums, operational, inferential = (status[k] for k in ("pair_id", "i", "j", "viable", "sums", "operational", "inferential"))
     ab, ba = counts[:, 0], counts[:, 1]
-    viable = ((ab[:, 7] > 0) & (ab[:, 8] == ab[:, 7]) & (ab[:, 1] == ab[:, 5]) & (ba[:, 7] > 0) & (ba[:, 8] == ba[:, 7]) & (ba[:, 1] == ba[:, 5])
-              & (ab[:, 1] == ba[:, 1]))
-    # _viability_status: incident sums, one division, "all incident pairs viable"
-    sums = np.zeros((n, 4), dtype=np.int64)
-    for idx in (i, j):
-        for c, values in enumerate((ab[:, 0] + ba[:, 0], ab[:, 1] + ba[:, 1], ab[:, 2] + ba[:, 2], (~viable).astype(np.int64))):
-            np.add.at(sums[:, c], idx, values)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        rate = sums[:, 1] / sums[:, 0]
-    operational = (sums[:, 0] > 0) & (rate >= float(min_candidate_completion_rate))
-    inferential = sums[:, 3] == 0
     pair_operational = operational[i] & operational[j]
     eligible = viable & pair_operational
 

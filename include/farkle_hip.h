@@ -658,6 +658,75 @@ typedef struct {
 int fk_rr_inference(fk_ctx *ctx, const fk_rr_inference_params *params, fk_rr_pair_row *rows, uint64_t row_begin, uint64_t row_end,
                     int64_t *class_counts, int64_t *strategy_classes);
 
+/* ---- round-robin inference, per root: the fixed-root diagnostics and the cross-root agreement of _root_specific_diagnostics
+ * (h2h_inference.py:918-1059) ----
+ *
+ * The accumulator sums the roots away on arrival.  With option "rr_keep_roots" = 1 (0 / 1, default 0; FK_ERR_ARG while counts are
+ * resident) every adding call that succeeds also keeps its states [pairs][2][FK_RR_STATE_COLS] on the device, in one of
+ * FK_RR_MAX_ROOTS root slots, with (root_seed, target, max_attempts): fk_h2h_round_robin_resident under its own root_seed,
+ * fk_rr_counts_add_root (fk_rr_counts_add plus the slot) under the one it is given.  A failed or replayed call keeps nothing.
+ * FK_ERR_ARG before any device work, accumulator and slots untouched: a root_seed already kept; a root beyond FK_RR_MAX_ROOTS.
+ * Plain fk_rr_counts_add with the option on adds as ever and marks the root set untracked (the accumulator then holds cells that no
+ * slot holds; later calls keep nothing more).  fk_rr_counts_reset forgets the slots.  With the option at 0 nothing is kept and
+ * fk_rr_counts_add_root is fk_rr_counts_add. */
+#define FK_RR_MAX_ROOTS 2
+int fk_rr_counts_add_root(fk_ctx *ctx, const fk_strategy *table, int32_t n, uint64_t pair_begin, uint64_t pair_end, uint64_t target,
+                          uint64_t max_attempts, const uint32_t *block_state, uint64_t family_pair_count, uint64_t root_seed);
+
+/* One (root, pair) of root_pairwise_diagnostics (:957-992), 168 bytes: fk_rr_pair_row's conventions, the counts those of this root
+ * alone.  flags: FK_RR_FLAG_*; the three viability bits are the COMBINED ones (:937-943), the two Holm bits this root's. */
+enum { FK_RR_DIAGNOSTIC_NO_ADJUSTED_REJECTION = 0, FK_RR_DIAGNOSTIC_ADVANTAGE_A = 1, FK_RR_DIAGNOSTIC_ADVANTAGE_B = 2 };
+#define FK_RR_DIAGNOSTIC_NONE 255 /* fk_rr_agreement_row::root_b_decision when there is one root */
+typedef struct {
+    uint64_t pair_id;
+    int64_t games_attempted, games_completed, games_safety_limit; /* both orders, this root */
+    int64_t n_ab, n_ba, seat1_a_wins_ab, seat1_b_wins_ba;
+    int64_t holm_order; /* 1-based position in this root's stable Holm order; 0 = no test performed */
+    double completion_game_rate, q_ab, q_ba, d_ab, score_null_proportion, score_z, score_p_value;
+    double ordinary_d_low, ordinary_d_high, holm_adjusted_p;
+    uint32_t strategy_a, strategy_b; /* table rows */
+    uint8_t flags;
+    uint8_t diagnostic_decision; /* FK_RR_DIAGNOSTIC_* */
+    uint8_t pad[6];
+} fk_rr_root_row;
+
+/* One pair of root_decision_agreement (:1003-1057), 56 bytes.  root_a is the root with the smaller seed (unsigned).  NaN where the
+ * reference leaves None; with one root the root_b half is NaN / FK_RR_DIAGNOSTIC_NONE and no flag is set. */
+#define FK_RR_AGREE_AVAILABLE 1 /* both effects exist */
+#define FK_RR_AGREE_DECISION 2  /* available and the two diagnostic decisions are equal */
+#define FK_RR_AGREE_DIRECTION 4 /* available and int(sign(a)) == int(sign(b)): a zero effect agrees only with another zero */
+typedef struct {
+    uint64_t pair_id;
+    double root_a_d_ab, root_b_d_ab, effect_discrepancy_a_minus_b, absolute_effect_discrepancy;
+    uint32_t strategy_a, strategy_b;
+    uint8_t root_a_decision, root_b_decision; /* FK_RR_DIAGNOSTIC_* */
+    uint8_t flags;                            /* FK_RR_AGREE_* */
+    uint8_t pad[5];
+} fk_rr_agreement_row;
+
+/* The diagnostics over the kept roots, in ascending seed order:
+ *   viability   the COMBINED accumulator's, as fk_rr_inference computes it (a pair that another root's block makes nonviable has no
+ *               test in any root; operational viability is the all-roots completion rate); no simultaneous interval is computed
+ *   per root    the score test on the root's own counts, Holm over all pairs of the range (1.0 without a test), holm_reject =
+ *               performed and adjusted p <= family_alpha and claim-eligible, the diagnostic decision (:945-953), and for the rows of
+ *               the asked slice the ordinary interval
+ *   agreement   per pair, from the two roots' effects and decisions
+ * Outputs:
+ *   root_seeds  [FK_RR_MAX_ROOTS] the kept seeds, ascending as unsigned 64-bit (entries past n_roots are 0); n_roots 1 or 2
+ *   rows        nullable: [n_roots][row_end - row_begin], roots in root_seeds' order
+ *   agreement   nullable: [row_end - row_begin]
+ *   summary     [FK_RR_AGREE_COLS] over the whole resident range: 0 pairs | 1 agreement available | 2 decision agreements |
+ *               3 direction agreements (both over the available pairs) | per root r at 4 + 4 r: pairs without an adjusted rejection,
+ *               with advantage a, with advantage b, tests performed
+ *   max_abs_discrepancy  nullable: the largest absolute_effect_discrepancy over the available pairs, NaN when there is none
+ * fk_timing as fk_rr_inference.  FK_ERR_ARG before any device work: every refusal of fk_rr_inference; no kept roots (the option is
+ * off); an untracked root set; a row range outside the resident one (with rows or agreement given); a null root_seeds, n_roots or
+ * summary. */
+#define FK_RR_AGREE_COLS 12
+int fk_rr_root_diagnostics(fk_ctx *ctx, const fk_rr_inference_params *params, uint64_t *root_seeds, int32_t *n_roots,
+                           fk_rr_root_row *rows, uint64_t row_begin, uint64_t row_end, fk_rr_agreement_row *agreement,
+                           int64_t *summary, double *max_abs_discrepancy);
+
 /* ---- dominance graphs of a round robin: what src/farkle/analysis/dominance.py builds from the pairwise decision classes, for
  * both of its graphs in one call — index 0 practical (edges of practical_dominance_*), index 1 statistical (edges of every class
  * ending _a / _b), dominance.py:285-334.  Node ids are table rows; a pair's A is its smaller row.  Device side: fk_dominance.h. ----
