@@ -76,6 +76,11 @@ DOM_EXTREME_DTYPE = np.dtype(
 )
 DOM_MAX_N = 8192       # FK_DOM_MAX_N
 RR_CLASSES = 7         # FK_RR_CLASSES
+AGREE_COUNTS = 11      # FK_AGREE_COUNTS
+AGREE_NO_RANK = 0      # FK_AGREE_NO_RANK
+CONCORDANCE_COUNTS = 5  # FK_CONCORDANCE_COUNTS
+CONCORDANCE_MAX_M = 65536  # FK_CONCORDANCE_MAX_M
+CONCORDANCE_TILE = 256  # FK_CONCORDANCE_TILE
 RR_STRATEGY_COLS = 12  # FK_RR_STRATEGY_COLS
 TALLY_COLS = 26
 LAG_COLS = 11  # FK_LAG_COLS: pairs | win: sx sy sxx syy sxy | n_rounds: sx sy sxx syy sxy
@@ -163,7 +168,7 @@ _EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_
             "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
             "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin",
             "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference", "fk_rr_counts_add_root", "fk_rr_root_diagnostics",
-            "fk_dominance_graph", "fk_rr_dominance"]
+            "fk_dominance_graph", "fk_rr_dominance", "fk_agreement_pairs", "fk_rr_agreement", "fk_rank_concordance"]
 _libs: dict = {}
 
 
@@ -1007,6 +1012,59 @@ class Engine:
         class_counts = np.zeros(RR_CLASSES, dtype=np.int64)
         self._check(self._lib.fk_rr_dominance(self._ctx, C.byref(par), _p(rank), _p(nodes), _p(extremes), _p(adjacency), _p(class_counts)))
         return {"nodes": nodes, "extremes": extremes, "adjacency": adjacency, "class_counts": class_counts}
+
+    @staticmethod
+    def _int32_array(values, what: str) -> np.ndarray:
+        a = np.asarray(values)
+        if a.ndim != 1 or a.dtype.kind not in "iu" or (a.size and (int(a.min()) < -(1 << 31) or int(a.max()) >= 1 << 31)):
+            raise ValueError(f"{what} must be a one-dimensional array of 32-bit integers")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def _agreement_ranks(self, n: int, win_rate_rank, trueskill_rank, sized: bool = True) -> tuple:
+        win, ts = self._int32_array(win_rate_rank, "win_rate_rank"), self._int32_array(trueskill_rank, "trueskill_rank")
+        if sized and not len(win) == len(ts) == n:  # (the entry refuses the other sizes before it reads an array)
+            raise ValueError(f"the two rank arrays must name the {n} rows of the table")
+        return win, ts
+
+    def agreement_pairs(self, n: int, decision_class, win_rate_rank, trueskill_rank, want_codes: bool = True) -> dict:
+        """``fk_agreement_pairs``: every pair's code byte (bits 0-1 ``h2h_direction``, 2-3 ``win_rate_preference``, 4-5
+        ``trueskill_preference``; 0 none, 1 a, 2 b) and the eleven counts, from the pairs' decision classes in pair-id order and the two
+        ranks of every table row (``AGREE_NO_RANK`` = 0 is null).  Returns ``{"codes": uint8 [pairs] or None, "counts": int64 [11]}``."""
+        n = int(n)
+        n_pairs = max(n * (n - 1) // 2, 0)
+        cls = np.ascontiguousarray(decision_class, dtype=np.uint8).reshape(-1)
+        sized = 2 <= n and n_pairs < 1 << 31
+        win, ts = self._agreement_ranks(n, win_rate_rank, trueskill_rank, sized)
+        if sized and len(cls) != n_pairs:
+            raise ValueError(f"a table of {n} strategies has {n_pairs} pairs")
+        codes = np.zeros(n_pairs if sized else 0, dtype=np.uint8) if want_codes else None
+        counts = np.zeros(AGREE_COUNTS, dtype=np.int64)
+        self._check(self._lib.fk_agreement_pairs(self._ctx, C.c_int32(n), _p(cls), _p(win), _p(ts), _p(codes), _p(counts)))
+        return {"codes": codes, "counts": counts}
+
+    def rr_agreement(self, win_rate_rank, trueskill_rank, family_alpha: float = 0.02, practical_delta: float = 0.03,
+                     delta_equivalence: float | None = None, min_candidate_completion_rate: float = 0.99, family_pair_count: int | None = None,
+                     want_codes: bool = True) -> dict:
+        """``fk_rr_agreement``: ``rr_inference`` over the resident pair counts, its classes fed to the pair kernel of ``agreement_pairs``
+        on the device.  The resident range must be the whole table.  Returns ``agreement_pairs``' dictionary and ``"class_counts"``."""
+        n = self._rr_n
+        par = self._rr_params(family_alpha, practical_delta, delta_equivalence, min_candidate_completion_rate, family_pair_count)
+        win, ts = self._agreement_ranks(n, win_rate_rank, trueskill_rank, n >= 2)  # (n = 0: no resident counts, which the entry refuses)
+        codes = np.zeros(max(n * (n - 1) // 2, 0), dtype=np.uint8) if want_codes else None
+        counts = np.zeros(AGREE_COUNTS, dtype=np.int64)
+        class_counts = np.zeros(RR_CLASSES, dtype=np.int64)
+        self._check(self._lib.fk_rr_agreement(self._ctx, C.byref(par), _p(win), _p(ts), _p(codes), _p(counts), _p(class_counts)))
+        return {"codes": codes, "counts": counts, "class_counts": class_counts}
+
+    def rank_concordance(self, x, y) -> np.ndarray:
+        """``fk_rank_concordance``: Kendall's pair counts of the items with keys ``x``, ``y`` (each at least 1) over all ``i < j``: int64
+        ``[5]`` = concordant, discordant, tied in ``x`` only, tied in ``y`` only, tied in both."""
+        x, y = self._int32_array(x, "x"), self._int32_array(y, "y")
+        if len(x) != len(y):
+            raise ValueError("x and y must have one key per item each")
+        counts = np.zeros(CONCORDANCE_COUNTS, dtype=np.int64)
+        self._check(self._lib.fk_rank_concordance(self._ctx, C.c_int32(min(len(x), (1 << 31) - 1)), _p(x), _p(y), _p(counts)))
+        return counts
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
     def comm_unique_id(self) -> bytes:

@@ -143,6 +143,13 @@ def build_parser() -> argparse.ArgumentParser:
     rr.add_argument("--screening-scores", type=Path, metavar="FILE",
                     help="With --dominance: a JSON object {strategy id: tournament screening score}, the third key of the display order "
                          "inside a front (default: the column is null)")
+    rr.add_argument("--agreement", action="store_true",
+                    help="With --inference over the whole table and --candidate-membership: compare the head-to-head decisions with the "
+                         "win-rate and the TrueSkill screening rank per pair and count Kendall's pairs of the scored population on the GPU, and "
+                         "write agreement_summary.json and (when every pair's row is on the host) selection_conditioned_pairs.parquet")
+    rr.add_argument("--candidate-membership", type=Path, metavar="FILE",
+                    help="With --agreement: the frozen candidate membership (the reference's candidate_family.parquet) whose final family is "
+                         "the strategy table")
     rr.add_argument("--force", action="store_true", help="Replace the tables of an existing output directory")
     for name in _OUT_OF_SCOPE:
         sub.add_parser(name, help="(reference command outside the simulation path)")
@@ -210,7 +217,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         try:
             written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
                                       out=args.out, force=args.force, inference=args.inference, rows=args.rows, dominance=args.dominance,
-                                      screening_scores=args.screening_scores, root_diagnostics=args.root_diagnostics)
+                                      screening_scores=args.screening_scores, root_diagnostics=args.root_diagnostics, agreement=args.agreement,
+                                      candidate_membership=args.candidate_membership)
         except (ValueError, FileExistsError) as exc:
             raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})

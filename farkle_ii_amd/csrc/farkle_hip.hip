@@ -20,6 +20,7 @@
 #include "fk_rr_inference.h"   // device side: round-robin inference (resident pair counts, score test, intervals, Holm, decision classes)
 #include "fk_rr_root_diagnostics.h" // device side: the inference per kept root and the cross-root agreement
 #include "fk_dominance.h"      // device side: dominance graphs of a round robin (bit matrices, closure, components, fronts, cycles, extremes)
+#include "fk_agreement.h"      // device side: method agreement of a round robin (pair codes and their counts, Kendall's pair counts)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -258,6 +259,8 @@ struct fk_ctx {
     int32_t ri_roots = 0;                // root slots in use, in arrival order, and what each was kept with:
     uint64_t ri_root_seed[FK_RR_MAX_ROOTS] = {0, 0}, ri_root_target[FK_RR_MAX_ROOTS] = {0, 0}, ri_root_cap[FK_RR_MAX_ROOTS] = {0, 0};
     DominanceBufs dm;
+    AgreementBufs ag;
+    int64_t agreement_grid = 0;          // option "agreement_grid": > 0 caps the pair kernel's grid lower (tests drive second trips)
     BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
@@ -1644,6 +1647,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "census_chunk_games") *value = c->census_chunk_games;
     else if (n == "rr_window_blocks") *value = c->rr_window_blocks;
     else if (n == "rr_keep_roots") *value = c->ri_keep_roots ? 1 : 0;
+    else if (n == "agreement_grid") *value = c->agreement_grid;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1684,6 +1688,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "game_stats_window") c->game_stats_window = std::max<int64_t>(value, 0);
     else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
     else if (n == "census_chunk_games") c->census_chunk_games = std::max<int64_t>(value, 0);
+    else if (n == "agreement_grid") c->agreement_grid = std::max<int64_t>(value, 0);
     else if (n == "rr_window_blocks") {
         if (value < 2 || value > ((int64_t)1 << 22) || (value & 1))
             return fail(c, FK_ERR_ARG, "rr_window_blocks must be even and in [2, 2^22] (a pair's two blocks share a window)");
@@ -3752,6 +3757,122 @@ int fk_rr_dominance(fk_ctx *c, const fk_rr_inference_params *par, const uint32_t
     hipLaunchKernelGGL(fkdm::fk_dm_rate_kernel, dim3((P + 255u) / 256u), dim3(256), 0, c->stream, c->ri.counts.p, P, b.rate.p);
     HIPCHK(c, hipGetLastError());
     return dominance_run(c, (uint32_t)c->ri_n, b.cls.p, c->ri.sim.p, b.rate.p, par->practical_delta, rank, nodes, extremes, adjacency);
+}
+
+// ---- method agreement of a round robin (device side: fk_agreement.h) ----
+static int agreement_check_ranks(fk_ctx *c, int64_t n, const int32_t *win_rate_rank, const int32_t *trueskill_rank, const void *counts) {
+    if (!win_rate_rank || !trueskill_rank || !counts) return fail(c, FK_ERR_ARG, "win_rate_rank, trueskill_rank and counts are required");
+    for (int64_t i = 0; i < n; ++i)
+        if (win_rate_rank[i] < 0 || trueskill_rank[i] < 0)
+            return fail(c, FK_ERR_ARG, "row %lld has a negative rank (%d, %d): a rank is at least 1, FK_AGREE_NO_RANK = 0 is null", (long long)i,
+                        (int)win_rate_rank[i], (int)trueskill_rank[i]);
+    return FK_OK;
+}
+
+// the rank pairs of the table's rows to the device, awaited: nothing else is on the stream yet
+static int agreement_put_ranks(fk_ctx *c, uint32_t n, const int32_t *win_rate_rank, const int32_t *trueskill_rank) {
+    if (const int rc = ensure(c, c->ag.ranks, (size_t)n)) return rc;
+    std::vector<int2> ranks(n);
+    for (uint32_t i = 0; i < n; ++i) ranks[i] = make_int2(win_rate_rank[i], trueskill_rank[i]);
+    HIPCHK(c, hipMemcpyAsync(c->ag.ranks.p, ranks.data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`ranks` leaves scope)
+    return FK_OK;
+}
+
+// The pair pass on the context's stream, classes and ranks on the device; awaits it and copies home.
+static int agreement_run(fk_ctx *c, uint32_t n, const uint8_t *d_cls, uint8_t *codes, int64_t *counts) {
+    using namespace fkag;
+    AgreementBufs &b = c->ag;
+    const uint32_t P = (uint32_t)((uint64_t)n * (n - 1u) / 2u);
+    if (const int rc = ensure_all(c, b.counts, (size_t)AG_COUNTS, b.codes, codes ? (size_t)P : 0)) return rc;
+    const uint32_t cap = c->agreement_grid > 0 ? (uint32_t)std::min<int64_t>(c->agreement_grid, AG_MAX_GRID) : AG_MAX_GRID;
+    const uint32_t grid = std::min<uint32_t>((P + AG_BLOCK - 1u) / AG_BLOCK, cap);
+    Timer device_work(c, &c->timing.play_ms, SLOT_CALL);
+    Timer pairs(c, &c->timing.perm_ms, SLOT_PERM);
+    HIPCHK(c, hipMemsetAsync(b.counts.p, 0, AG_COUNTS * 8, c->stream));
+    hipLaunchKernelGGL(fk_ag_pairs_kernel, dim3(grid), dim3(AG_BLOCK), 0, c->stream, d_cls, b.ranks.p, n, P, codes ? b.codes.p : nullptr, b.counts.p);
+    HIPCHK(c, hipGetLastError());
+    pairs.stop();
+    device_work.stop();
+    unsigned long long out[AG_COUNTS];
+    HIPCHK(c, hipMemcpyAsync(out, b.counts.p, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    if (codes) HIPCHK(c, hipMemcpyAsync(codes, b.codes.p, (size_t)P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
+    for (uint32_t k = 0; k < AG_COUNTS; ++k) counts[k] = (int64_t)out[k];
+    return FK_OK;
+}
+
+int fk_agreement_pairs(fk_ctx *c, int32_t n, const uint8_t *decision_class, const int32_t *win_rate_rank, const int32_t *trueskill_rank, uint8_t *codes,
+                       int64_t *counts) {
+    if (!c) return FK_ERR_ARG;
+    if (n < 2) return fail(c, FK_ERR_ARG, "pair agreement needs at least two strategies, got %d", (int)n);
+    const uint64_t all_pairs = (uint64_t)n * (uint64_t)(n - 1) / 2u;
+    if (all_pairs > 0x7fffffffull) return fail(c, FK_ERR_ARG, "pair agreement holds at most 2^31 - 1 pairs, %d strategies have %llu", (int)n, (unsigned long long)all_pairs);
+    if (!decision_class) return fail(c, FK_ERR_ARG, "decision_class is required");
+    if (const int rc = agreement_check_ranks(c, n, win_rate_rank, trueskill_rank, counts)) return rc;
+    const size_t P = (size_t)all_pairs;
+    for (size_t p = 0; p < P; ++p)
+        if (decision_class[p] >= fkri::RI_CLASSES)
+            return fail(c, FK_ERR_ARG, "decision class %u of pair %zu is not one of the %u classes", (unsigned)decision_class[p], p, fkri::RI_CLASSES);
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    if (const int rc = ensure(c, c->ag.cls, P)) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->ag.cls.p, decision_class, P, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = agreement_put_ranks(c, (uint32_t)n, win_rate_rank, trueskill_rank)) return rc;
+    return agreement_run(c, (uint32_t)n, c->ag.cls.p, codes, counts);
+}
+
+int fk_rr_agreement(fk_ctx *c, const fk_rr_inference_params *par, const int32_t *win_rate_rank, const int32_t *trueskill_rank, uint8_t *codes, int64_t *counts,
+                    int64_t *class_counts) {
+    if (!c) return FK_ERR_ARG;
+    if (const int rc = rr_inference_check(c, par, false, 0, 0, class_counts)) return rc;
+    const uint64_t all_pairs = (uint64_t)c->ri_n * (uint64_t)(c->ri_n - 1) / 2u;
+    if (c->ri_begin != 0 || c->ri_end != all_pairs)
+        return fail(c, FK_ERR_ARG, "the resident counts hold pairs [%llu, %llu) of the table's %llu: pair agreement needs the whole family",
+                    (unsigned long long)c->ri_begin, (unsigned long long)c->ri_end, (unsigned long long)all_pairs);
+    if (const int rc = agreement_check_ranks(c, c->ri_n, win_rate_rank, trueskill_rank, counts)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    if (const int rc = ensure(c, c->ag.cls, (size_t)all_pairs)) return rc;
+    if (const int rc = agreement_put_ranks(c, (uint32_t)c->ri_n, win_rate_rank, trueskill_rank)) return rc;
+    if (const int rc = rr_inference_enqueue(c, par, nullptr, 0, 0, class_counts, nullptr, c->ag.cls.p)) return rc;
+    return agreement_run(c, (uint32_t)c->ri_n, c->ag.cls.p, codes, counts);
+}
+
+int fk_rank_concordance(fk_ctx *c, int32_t m, const int32_t *x, const int32_t *y, int64_t *counts) {
+    using namespace fkag;
+    if (!c) return FK_ERR_ARG;
+    if (m < 2 || m > FK_CONCORDANCE_MAX_M)
+        return fail(c, FK_ERR_ARG, "rank concordance takes 2 to %d items (one workgroup per tile of the comparison), got %d", FK_CONCORDANCE_MAX_M, (int)m);
+    if (!x || !y || !counts) return fail(c, FK_ERR_ARG, "x, y and counts are required");
+    for (int32_t i = 0; i < m; ++i)
+        if (x[i] < 1 || y[i] < 1) return fail(c, FK_ERR_ARG, "item %d has the keys (%d, %d): a key is at least 1", (int)i, (int)x[i], (int)y[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    AgreementBufs &b = c->ag;
+    if (const int rc = ensure_all(c, b.x, (size_t)m, b.y, (size_t)m, b.concordance, (size_t)CC_COUNTS)) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.x.p, x, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.y.p, y, (size_t)m * 4, hipMemcpyHostToDevice, c->stream));
+    const uint32_t tiles = ((uint32_t)m + CC_TILE - 1u) / CC_TILE;
+    Timer device_work(c, &c->timing.play_ms, SLOT_CALL);
+    HIPCHK(c, hipMemsetAsync(b.concordance.p, 0, CC_COUNTS * 8, c->stream));
+    hipLaunchKernelGGL(fk_ag_concordance_kernel, dim3(tiles * (tiles + 1u) / 2u), dim3(CC_TILE), 0, c->stream, b.x.p, b.y.p, (uint32_t)m, tiles, b.concordance.p);
+    HIPCHK(c, hipGetLastError());
+    device_work.stop();
+    unsigned long long out[CC_COUNTS];
+    HIPCHK(c, hipMemcpyAsync(out, b.concordance.p, sizeof(out), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
+    unsigned long long sum = 0;
+    for (uint32_t k = 0; k < CC_COUNTS; ++k) sum += out[k];
+    const unsigned long long all = (unsigned long long)m * (unsigned long long)(m - 1) / 2u;
+    if (sum != all) // every pair i < j falls into exactly one count
+        return fail(c, FK_ERR_HIP, "rank concordance lost pairs: the five counts sum to %llu, %d items have %llu pairs", sum, (int)m, all);
+    for (uint32_t k = 0; k < CC_COUNTS; ++k) counts[k] = (int64_t)out[k];
+    return FK_OK;
 }
 
 // The NEXT fk_tournament_run / _stats call on this context will play shuffles [shuffle_begin, shuffle_end) of the same table,

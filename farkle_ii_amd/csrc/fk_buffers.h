@@ -119,6 +119,13 @@ struct DominanceBufs { // fk_dominance_graph, fk_rr_dominance
     Dev<fk_dom_node> nodes;       // [n]
     Dev<fk_dom_extreme> extremes; // [2][n]
 };
+struct AgreementBufs { // fk_agreement_pairs, fk_rr_agreement, fk_rank_concordance
+    Dev<uint8_t> cls, codes; // [pairs] decision classes (fk_rr_agreement: written by the inference's chain); the pair codes
+    Dev<int2> ranks;         // [n] (win_rate_rank, trueskill_rank) of every table row
+    Dev<ull> counts;         // [fkag::AG_COUNTS]
+    Dev<int32_t> x, y;       // [m] the keys of fk_rank_concordance
+    Dev<ull> concordance;    // [fkag::CC_COUNTS]
+};
 struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
     Dev<int64_t> wins, exposures; // the stacked matrices
     Dev<fkb::KDesc> kd;

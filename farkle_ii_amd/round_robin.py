@@ -285,7 +285,8 @@ def parse_pair_range(text: str | None, n: int) -> tuple[int, int]:
 
 def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
                     force: bool = False, strategies=None, engine=None, world: int | None = None, inference: bool = False,
-                    rows: str | None = None, dominance: bool = False, screening_scores=None, root_diagnostics: bool = False) -> dict:
+                    rows: str | None = None, dominance: bool = False, screening_scores=None, root_diagnostics: bool = False,
+                    agreement: bool = False, candidate_membership=None) -> dict:
     """``farkle round-robin``: the grid of ``cfg`` (restricted to the ids of ``strategy_ids_file``), every pair of the range, per root of
     ``sim.seed_list``.  Writes ``round_robin_pairs.parquet``, ``round_robin_strategies.parquet``, ``round_robin.json`` and, with
     ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths.
@@ -304,7 +305,14 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     With ``root_diagnostics`` (and ``inference``, on one or two distinct roots) the engine's option ``"rr_keep_roots"`` is on for the
     run, ``Engine.rr_root_diagnostics`` follows the inference and the command also writes the reference's
     ``root_pairwise_diagnostics.parquet`` and ``root_decision_agreement.parquet`` (the pairs of ``rows``) and the summary under
-    ``"root_diagnostics"`` in ``round_robin.json`` (``rr_root_diagnostics.py`` builds the frames)."""
+    ``"root_diagnostics"`` in ``round_robin.json`` (``rr_root_diagnostics.py`` builds the frames).
+
+    With ``agreement`` (and ``inference``, over the whole table) and ``candidate_membership`` — the reference's
+    ``candidate_family.parquet``, whose final family is the table — the inference's classes are compared with the two screening ranks on
+    the device (``Engine.rr_agreement``), Kendall's pair counts of the scored population are taken there (``Engine.rank_concordance``) and
+    the command also writes the reference's ``agreement_summary.json`` and — when every pair's row is on the host —
+    ``selection_conditioned_pairs.parquet`` (``structure_agreement.py`` builds both), and the counts under ``"agreement"`` in
+    ``round_robin.json``.  ``execution_scope`` is ``root_pair`` on two roots and ``single_root`` on one."""
     import os
 
     import pyarrow as pa
@@ -373,6 +381,23 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
             rd.check_roots(roots)
         except ValueError as exc:
             raise ValueError(f"round-robin: --root-diagnostics: {exc}") from exc
+    if agreement:
+        from . import structure_agreement as sa
+
+        if not inference:
+            raise ValueError("round-robin: --agreement belongs to --inference")
+        if candidate_membership is None:
+            raise ValueError("round-robin: --agreement needs --candidate-membership")
+        if (begin, end) != (0, pair_count(n)):
+            raise ValueError(f"round-robin: --agreement needs every pair of the table, --pairs plays [{begin}, {end}) of {pair_count(n)}")
+        if len(roots) not in sa.EXECUTION_SCOPES:
+            raise ValueError(f"round-robin: --agreement runs on one or two roots, got {len(roots)}")
+        try:
+            membership = sa.read_membership(candidate_membership, ids)
+        except ValueError as exc:
+            raise ValueError(f"round-robin: --candidate-membership {candidate_membership}: {exc}") from exc
+    elif candidate_membership is not None:
+        raise ValueError("round-robin: --candidate-membership belongs to --agreement")
     out_dir = Path(out) if out is not None else cfg.results_root / "h2h_round_robin"
     if out_dir.exists() and not force:
         raise FileExistsError(f"round-robin: {out_dir} exists; pass --force to replace its tables")
@@ -405,6 +430,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
                 diagnosed = eng.rr_root_diagnostics(family_pair_count=family, rows=row_range, **knobs)
             if dominance:
                 graphs = eng.rr_dominance(family_pair_count=family, rank=dom.rank_of_ids(ids), **knobs)
+            if agreement:
+                pairs_written = row_range == (begin, end)  # the frame names every pair's class: its row is on the host
+                agreed = eng.rr_agreement(membership["win_rate_rank"], membership["trueskill_rank"], family_pair_count=family,
+                                          want_codes=pairs_written, **knobs)
+                scored = sa.scored_population(membership)
+                concordance = eng.rank_concordance(*scored) if len(scored[0]) >= 2 else None
         finally:
             eng.rr_counts_reset()
             if root_diagnostics:
@@ -436,6 +467,15 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
                 frames.append((dom.edges_frame(result["rows"], ids, h2h.practical_delta), written["dominance_edges"]))
             digest = dom.summary(graphs["nodes"], result["strategies"], graphs["class_counts"], ids)
             runner._atomic_write_bytes(written["dominance_summary"], (json.dumps(digest, indent=2, sort_keys=True) + "\n").encode("utf-8"))
+        if agreement:
+            written["agreement_summary"] = out_dir / "agreement_summary.json"
+            if pairs_written:
+                written["agreement_pairs"] = out_dir / "selection_conditioned_pairs.parquet"
+                frames.append((sa.pairs_frame(agreed["codes"], result["rows"]["decision_class"], ids, membership["family_hash"]),
+                               written["agreement_pairs"]))
+            stability = rd.stability_summary(diagnosed["summary"]) if root_diagnostics else None
+            agreement_digest = sa.summary(membership, agreed["counts"], concordance, stability, sa.EXECUTION_SCOPES[len(roots)])
+            runner._atomic_write_bytes(written["agreement_summary"], (json.dumps(agreement_digest, indent=2, sort_keys=True) + "\n").encode("utf-8"))
     else:
         written["pairs"] = out_dir / "round_robin_pairs.parquet"
         frames.append((pairs_frame(ids, roots, states, target, begin, end), written["pairs"]))
@@ -469,5 +509,13 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
                                                                "statistical_cycle_group_count", "unique_best")}}
         if not edges_written:
             report["dominance"]["edges_omitted"] = "dominance_edges.parquet needs the row of every pair on the host (--rows)"
+    if agreement:
+        report["agreement"] = {"candidate_membership": str(candidate_membership), "family_hash": membership["family_hash"],
+                               "execution_scope": sa.EXECUTION_SCOPES[len(roots)], "pairs_written": pairs_written,
+                               "scored_population": int(len(scored[0])),
+                               "counts": {name: int(v) for name, v in zip(sa.COUNT_NAMES, agreed["counts"])},
+                               "concordance": None if concordance is None else {name: int(v) for name, v in zip(sa.CONCORDANCE_NAMES, concordance)}}
+        if not pairs_written:
+            report["agreement"]["pairs_omitted"] = "selection_conditioned_pairs.parquet needs the row of every pair on the host (--rows)"
     runner._atomic_write_bytes(written["json"], (json.dumps(report, indent=2, sort_keys=True) + "\n").encode("utf-8"))
     return written

@@ -778,6 +778,43 @@ int fk_dominance_graph(fk_ctx *ctx, int32_t n, const uint8_t *decision_class, co
 int fk_rr_dominance(fk_ctx *ctx, const fk_rr_inference_params *params, const uint32_t *rank, fk_dom_node *nodes,
                     fk_dom_extreme *extremes, uint64_t *adjacency, int64_t *class_counts);
 
+/* ---- method agreement of a round robin: what src/farkle/analysis/structure_agreement.py computes per pair (_pair_agreement
+ * :73-125) and over the scored population (kendalltau's pair counts), from the decision classes and the two screening ranks of the
+ * frozen candidate membership.  Device side: fk_agreement.h. ----
+ *
+ * A pair's code, one byte: bits 0-1 h2h_direction, bits 2-3 win_rate_preference, bits 4-5 trueskill_preference, each 0 = none,
+ * 1 = a, 2 = b.  The direction is a for classes 0 and 2, b for 1 and 3, none for 4 .. 6 (:65-70).  A preference is none when either
+ * rank is null (FK_AGREE_NO_RANK) or the two are equal, otherwise a when A's rank is the smaller (:55-62); A is the pair's smaller
+ * table row.  The reference's three agreement tri-states are functions of the code: available when both fields are not none, and
+ * then whether they are equal.
+ * counts [FK_AGREE_COUNTS]: 0 pairs | 1 directional pairs | 2 classes 5 and 6 | 3 class 6 | 4 class 4 | 5, 6 win rate against
+ * TrueSkill: available, agree | 7, 8 H2H against win rate | 9, 10 H2H against TrueSkill. */
+#define FK_AGREE_COUNTS 11
+#define FK_AGREE_NO_RANK 0
+#define FK_CONCORDANCE_COUNTS 5
+#define FK_CONCORDANCE_MAX_M 65536
+#define FK_CONCORDANCE_TILE 256 /* the concordance kernel's tile edge: the item counts at which it changes shape are its multiples */
+
+/* The pair pass alone, on host arrays: decision_class in pair-id order, the ranks per table row (at least 1, or FK_AGREE_NO_RANK).
+ * codes, nullable: every pair's code.  fk_timing: play_ms = total_ms = the device work, perm_ms the pair kernel in it.  FK_ERR_ARG before any device
+ * work: a null required array; n < 2, or 2^31 pairs or more; a class above 6; a negative rank. */
+int fk_agreement_pairs(fk_ctx *ctx, int32_t n, const uint8_t *decision_class /* [n (n - 1) / 2] */, const int32_t *win_rate_rank /* [n] */,
+                       const int32_t *trueskill_rank /* [n] */, uint8_t *codes /* [pairs], nullable */, int64_t *counts);
+
+/* fk_rr_inference's chain over the resident counts, its class array fed to the pair kernel on the device: no pair row comes to the
+ * host.  params and class_counts as fk_rr_inference; the other arguments as fk_agreement_pairs.  The resident range must be the
+ * whole table: the reference refuses an inference whose support differs from the finalists (:82-83).  FK_ERR_ARG before any device
+ * work: every refusal of fk_rr_inference; a partial resident range; a null or negative rank array.  fk_timing: play_ms = total_ms =
+ * inference and pair pass together; perm_ms of it is the pair pass. */
+int fk_rr_agreement(fk_ctx *ctx, const fk_rr_inference_params *params, const int32_t *win_rate_rank, const int32_t *trueskill_rank,
+                    uint8_t *codes /* nullable */, int64_t *counts, int64_t *class_counts);
+
+/* Kendall's pair counts of m items with the keys x, y (each at least 1), over all i < j: counts [FK_CONCORDANCE_COUNTS] = 0
+ * concordant | 1 discordant | 2 tied in x only | 3 tied in y only | 4 tied in both.  They sum to m (m - 1) / 2; the entry checks
+ * that and returns FK_ERR_HIP if the device lost a pair.  fk_timing: play_ms = total_ms = the kernel.  FK_ERR_ARG before any device
+ * work: a null array; m < 2 or m > FK_CONCORDANCE_MAX_M; a key below 1. */
+int fk_rank_concordance(fk_ctx *ctx, int32_t m, const int32_t *x, const int32_t *y, int64_t *counts);
+
 /* ---- multi-GPU: one process per GPU, one context per process, ONE exchange ----
  * The (seed x shuffle x game) space partitions with no data dependency; the only collective of the path is the integer
  * SUM of the per-strategy tally to one rank — the analogue of OutcomeCounter.absorb + _reduce_metric_chunk_payloads
