@@ -6,7 +6,9 @@ library has not been built, or no HIP device is usable, constructing an :class:`
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import re
 import subprocess
 from pathlib import Path
 
@@ -18,6 +20,7 @@ PKG_DIR = Path(__file__).resolve().parent
 # FARKLE_HIP_LIB: load another build of the same C-ABI (A/B timing of kernel variants); the default is the in-tree library
 LIB_PATH = Path(os.environ.get("FARKLE_HIP_LIB", PKG_DIR / "libfarkle_hip.so"))
 SRC_DIR = PKG_DIR / "csrc"
+HEADER = PKG_DIR.parent / "include" / "farkle_hip.h"
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 COORD_DTYPE = np.dtype(
@@ -94,7 +97,7 @@ SEAT_STAT_NAMES = ("exposures", "completed_exposures", "safety_limit_exposures",
 # tally columns (run_tournament.py:109-121, 165-195)
 COL_WINS, COL_ATTEMPTED, COL_COMPLETED, COL_SAFETY, COL_SUMS, COL_SQ_SUMS = 0, 1, 2, 3, 4, 15
 
-FK_ERR_ROLL_LIMIT, FK_ERR_ARG, FK_ERR_COUNTER_OVERFLOW, FK_ERR_HIP, FK_ERR_NO_DEVICE, FK_ERR_COMM = -1, -2, -3, -4, -5, -6
+FK_ERR_ROLL_LIMIT, FK_ERR_ARG, FK_ERR_COUNTER_OVERFLOW, FK_ERR_HIP, FK_ERR_NO_DEVICE, FK_ERR_COMM, FK_ERR_IO = -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
 
 
@@ -148,7 +151,7 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     """Compile the HIP extension for gfx950 in-tree (hipcc cross-compiles without a GPU).  ``variant``: a test build with extra
     definitions (``VARIANTS``), never loaded by the product."""
     out = library_path(variant)
-    deps = sorted(p for p in SRC_DIR.iterdir() if p.is_file()) + [PKG_DIR.parent / "include" / "farkle_hip.h"]  # (a new header cannot be forgotten)
+    deps = sorted(p for p in SRC_DIR.iterdir() if p.is_file()) + [HEADER]  # (a new header cannot be forgotten)
     if out.exists() and not force and all(out.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return out
     cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", *({**VARIANTS, **TOOL_VARIANTS}[variant] if variant else []), "-o", str(out),
@@ -162,13 +165,39 @@ def build_library(force: bool = False, verbose: bool = False, variant: str | Non
     return out
 
 
-_EXPORTS = ["fk_init", "fk_destroy", "fk_last_error", "fk_get_device_info", "fk_get_timing", "fk_set_option",
-            "fk_tournament_run", "fk_tournament_run_stats", "fk_tournament_run_all_player", "fk_tournament_run_game_stats", "fk_tournament_run_rare_events", "fk_tournament_run_lags", "fk_tournament_run_matchups", "fk_matchup_reduce", "fk_tournament_hint_next", "fk_play_games", "fk_h2h_run", "fk_h2h_run_blocks", "fk_coordinate_seeds", "fk_debug_score", "fk_debug_should_continue",
-            "fk_debug_dice", "fk_debug_dice_state", "fk_debug_dice_keys", "fk_comm_unique_id", "fk_comm_init", "fk_reduce_tally", "fk_comm_destroy", "fk_tally_resident_reduce", "fk_comm_ranks", "fk_host_alloc", "fk_host_free", "fk_game_seeds",
-            "fk_tournament_run_columns", "fk_row_columns_bytes", "fk_write_row_shards", "fk_debug_sha256", "fk_get_option", "fk_debug_deadline_handshake", "fk_debug_hold_memory", "fk_rows_wait", "fk_tournament_run_columns_seeds",
-            "fk_last_play_instance", "fk_debug_bounded_draws", "fk_debug_perm_from_draws", "fk_performance_bootstrap", "fk_root_stability_bootstrap", "fk_tournament_run_seat_counts", "fk_trace_games", "fk_census_games", "fk_tournament_run_census", "fk_h2h_round_robin",
-            "fk_h2h_round_robin_resident", "fk_rr_counts_add", "fk_rr_counts_reset", "fk_rr_inference", "fk_rr_counts_add_root", "fk_rr_root_diagnostics",
-            "fk_dominance_graph", "fk_rr_dominance", "fk_agreement_pairs", "fk_rr_agreement", "fk_rank_concordance"]
+_BY_VALUE = {"int": C.c_int, "int32_t": C.c_int32, "uint32_t": C.c_uint32, "int64_t": C.c_int64, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "double": C.c_double}
+_RETURNS = {"int": C.c_int, "void": None, "size_t": C.c_size_t, "const char *": C.c_char_p}
+_PROTOTYPE_START = re.compile(r"^(?:int|void|size_t|const char \*)\s*\*?fk_\w+\(", re.M)
+_PROTOTYPE = re.compile(r"^(int|void|size_t|const char \*)\s*(fk_\w+)\(([^;{}()]*)\);", re.M)
+
+
+def parse_signatures(header_text: str) -> dict:
+    """``{name: (restype, argtypes)}`` of every ``fk_*`` prototype in the text of a header: by-value parameters by ``_BY_VALUE``, ``const char *``
+    as c_char_p, every other pointer or array parameter as c_void_p (which takes ``_p(array)``, ``byref(...)``, string buffers, ctypes arrays and
+    None).  A by-value type without a mapping, or a line that begins like a prototype and is not matched as one, raises: none is skipped."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header_text, flags=re.S)
+    found = {}
+    for ret, name, params in _PROTOTYPE.findall(text):
+        argtypes = []
+        for param in (" ".join(p.split()) for p in params.split(",") if p.strip() not in ("", "void")):
+            if "*" in param or "[" in param:
+                argtypes.append(C.c_char_p if re.fullmatch(r"const char \* ?\w+", param) else C.c_void_p)
+            elif param.rsplit(" ", 1)[0] in _BY_VALUE:
+                argtypes.append(_BY_VALUE[param.rsplit(" ", 1)[0]])
+            else:
+                raise ValueError(f"{name}: no ctypes type for the by-value parameter `{param}`")
+        found[name] = (_RETURNS[ret], argtypes)
+    if len(found) != len(_PROTOTYPE_START.findall(text)):
+        raise ValueError(f"{len(_PROTOTYPE_START.findall(text))} lines begin like a prototype, {len(found)} distinct prototypes were parsed")
+    return found
+
+
+@functools.lru_cache(maxsize=None)
+def signatures() -> dict:
+    """``parse_signatures`` of ``include/farkle_hip.h``: the declared entry points, and what ``load_library`` sets on each."""
+    return parse_signatures(HEADER.read_text())
+
+
 _libs: dict = {}
 
 
@@ -181,14 +210,9 @@ def load_library(variant: str | None = None) -> C.CDLL:
                 f"{path} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback for the simulation path)")
         lib = C.CDLL(str(path))
-        for name in _EXPORTS:
-            getattr(lib, name)  # AttributeError if a declared symbol is not exported
-        lib.fk_last_error.restype = C.c_char_p
-        lib.fk_last_error.argtypes = [C.c_void_p]
-        lib.fk_last_play_instance.restype = C.c_char_p
-        lib.fk_last_play_instance.argtypes = [C.c_void_p]
-        lib.fk_destroy.restype = None
-        lib.fk_destroy.argtypes = [C.c_void_p]
+        for name, (restype, argtypes) in signatures().items():
+            fn = getattr(lib, name)  # AttributeError if a declared symbol is not exported
+            fn.restype, fn.argtypes = restype, argtypes
         _libs[variant] = lib
     return _libs[variant]
 
@@ -215,9 +239,7 @@ def _census_tables(S: int, turn_bins: int) -> tuple[dict, _Census]:
 
 def row_columns_bytes(k: int, games_per_shuffle: int) -> int:
     """``fk_row_columns_bytes``: bytes of one shuffle's column image."""
-    lib = load_library()
-    lib.fk_row_columns_bytes.restype = C.c_size_t
-    return int(lib.fk_row_columns_bytes(C.c_int32(k), C.c_int32(games_per_shuffle)))
+    return int(load_library().fk_row_columns_bytes(k, games_per_shuffle))
 
 
 class _ShardJob(C.Structure):
@@ -276,11 +298,10 @@ def prepare_row_shards_native(row_dir, k: int, root_seed: int, columns: np.ndarr
     sizes = np.zeros(n, dtype=np.int64)
     sha = np.zeros((n, 32), dtype=np.uint8)
     err = C.create_string_buffer(512)
-    lib.fk_write_row_shards.restype = C.c_int
     keep = (columns, sh, seeds, batch, gs, leaf_type, leaf_paths, tpl, sidecar)  # what the job points into
 
     def run() -> dict:
-        rc = lib.fk_write_row_shards(C.byref(job), _p(sizes), _p(sha), _p(side_sha), err, C.c_size_t(len(err)))
+        rc = lib.fk_write_row_shards(C.byref(job), _p(sizes), _p(sha), _p(side_sha), err, len(err))
         if rc != 0:
             raise OSError(f"fk_write_row_shards failed ({rc}): {err.value.decode('utf-8', 'replace')}")
         return {"byte_length": sizes, "sha256": sha, "sidecar_sha256": side_sha}
@@ -319,7 +340,7 @@ class Engine:
         self._lib = load_library(variant)  # (variant: a test build of the library, backend.VARIANTS)
         self._ctx = C.c_void_p()
         self._rr_n = 0  # the table size of the resident round-robin pair counts (0: none)
-        rc = self._lib.fk_init(C.c_int(device), C.byref(self._ctx))
+        rc = self._lib.fk_init(device, C.byref(self._ctx))
         if rc != 0:
             self._ctx = C.c_void_p()
             names = {FK_ERR_NO_DEVICE: "no usable HIP device (this engine has no CPU fallback)", FK_ERR_ARG: "bad device ordinal",
@@ -353,7 +374,7 @@ class Engine:
             raise FarkleHipError(rc, (msg or b"").decode() or f"error {rc}")
 
     def set_option(self, name: str, value: int) -> None:
-        self._check(self._lib.fk_set_option(self._ctx, name.encode(), C.c_int64(int(value))))
+        self._check(self._lib.fk_set_option(self._ctx, name.encode(), int(value)))
 
     def device_info(self) -> dict:
         info = _DeviceInfo()
@@ -387,14 +408,20 @@ class Engine:
 
     def _lead(self, table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally) -> tuple:
         """The thirteen leading arguments of every ``fk_tournament_run*`` entry."""
-        return (self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed), C.c_uint64(shuffle_begin), C.c_uint64(shuffle_end),
-                C.c_uint32(spb), C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)), _p(tally))
+        return self._ctx, _p(table), S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, _p(ov), len(ov), _p(tally)
 
     @staticmethod
     def _game_stat_arrays(S, rb, mb) -> dict:
         """The seven int64 game-stat outputs (the entries take them in the order of ``GAME_STAT_ARRAYS``)."""
         shapes = ((S, 4), (S, rb), (S, mb), (S, mb), 4, rb, mb)
         return {name: np.zeros(shape, np.int64) for name, shape in zip(GAME_STAT_ARRAYS, shapes)}
+
+    @staticmethod
+    def _lag_arrays(lags, S, n_sh) -> tuple:
+        """The lag list as int32, m = min(max lag, n_shuffles), and zeroed ``lag_sums`` / ``lag_head`` / ``lag_tail`` of the lag entries."""
+        lags = np.ascontiguousarray(list(lags), dtype=np.int32)
+        m = min(int(lags.max()) if len(lags) else 0, n_sh)
+        return lags, m, np.zeros((S, len(lags), LAG_COLS), np.int64), np.zeros((max(m, 1), S), np.uint16), np.zeros((max(m, 1), S), np.uint16)
 
     def tournament(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
                    shuffles_per_batch: int | None = None, target_score: int = 10_000, max_rounds: int = 200,
@@ -451,8 +478,8 @@ class Engine:
             spilled = C.c_int64(0)
             rc = self._lib.fk_tournament_run_game_stats(
                 *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
-                None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
-                *(_p(g[name]) for name in GAME_STAT_ARRAYS), C.c_int64(capacity), C.byref(spilled), _p(spill))
+                None, None, _p(stats), _p(ratios), rare_target_score, rb, mb, *(_p(g[name]) for name in GAME_STAT_ARRAYS), capacity,
+                C.byref(spilled), _p(spill))
             if rc == FK_ERR_ARG and spilled.value > capacity:  # more values outside the windows than room: once more with room for all
                 capacity = int(spilled.value)
                 continue
@@ -500,10 +527,9 @@ class Engine:
             seats = np.zeros((max(ev_cap, 1), max(int(k), 1)), dtype=np.uint16) if want_events else None
             rc = self._lib.fk_tournament_run_rare_events(
                 *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
-                None, None, _p(stats), _p(ratios), C.c_int32(rare_target_score), C.c_int32(rb), C.c_int32(mb),
-                *(_p(g[name]) for name in GAME_STAT_ARRAYS), C.c_int64(capacity), C.byref(spilled), _p(spill),
-                C.c_int32(sb), _p(s_second), _p(g_second), C.c_int32(len(thr)), _p(thr) if len(thr) else None,
-                C.c_int64(ev_cap), C.byref(n_events), _p(head), _p(seats))
+                None, None, _p(stats), _p(ratios), rare_target_score, rb, mb, *(_p(g[name]) for name in GAME_STAT_ARRAYS), capacity,
+                C.byref(spilled), _p(spill), sb, _p(s_second), _p(g_second), len(thr), _p(thr) if len(thr) else None, ev_cap,
+                C.byref(n_events), _p(head), _p(seats))
             short = spilled.value > capacity or n_events.value > ev_cap
             if rc == FK_ERR_ARG and short and retry:  # once more with room for all
                 capacity, ev_cap = max(capacity, int(spilled.value)), max(ev_cap, int(n_events.value))
@@ -554,7 +580,7 @@ class Engine:
             sums = np.zeros((max(capacity, 1), 6), dtype=np.int64) if want_mirrored else None
             rc = self._lib.fk_tournament_run_seat_counts(
                 *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
-                _p(counts), _p(rank), C.c_int64(capacity), C.byref(n_pairs) if want_mirrored else None, _p(index), _p(sums))
+                _p(counts), _p(rank), capacity, C.byref(n_pairs) if want_mirrored else None, _p(index), _p(sums))
             if rc == FK_ERR_ARG and want_mirrored and n_pairs.value > capacity and retry and attempts == 1:
                 capacity = int(n_pairs.value)
                 continue
@@ -607,7 +633,7 @@ class Engine:
 
     def rows_wait(self, slot: int) -> None:
         """``fk_rows_wait``: the column images of the ``async_rows`` call that reported ``rows_event == slot`` are in the host buffer."""
-        self._check(self._lib.fk_rows_wait(self._ctx, C.c_int32(slot)))
+        self._check(self._lib.fk_rows_wait(self._ctx, slot))
 
     columns_with_seeds = True  # (tournament_columns takes shuffle_seeds_out / game_seeds_out)
 
@@ -626,14 +652,10 @@ class Engine:
         ``lag_sums [S][n_lags][LAG_COLS]`` int64 and the first / last ``min(max lag, n_shuffles)`` series rows
         (``lag_head`` / ``lag_tail``, uint16 ``n_rounds | won << 15``, ``[m][S]``) that ``rng_lags.LagSummary`` merges ranges with."""
         table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
-        lags = np.ascontiguousarray(list(lags), dtype=np.int32)
-        m = min(int(lags.max()) if len(lags) else 0, n_sh)
-        sums = np.zeros((S, len(lags), LAG_COLS), dtype=np.int64)
-        head = np.zeros((max(m, 1), S), dtype=np.uint16)
-        tail = np.zeros((max(m, 1), S), dtype=np.uint16)
+        lags, m, sums, head, tail = self._lag_arrays(lags, S, n_sh)
         self._check(self._lib.fk_tournament_run_lags(
             *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
-            _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail)))
+            _p(lags), len(lags), _p(sums), _p(head), _p(tail)))
         return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh}
 
     def tournament_matchups(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int, lags, strategy_ids,
@@ -643,22 +665,17 @@ class Engine:
         coordinate order: ``matchups = {"digest": uint64 [n], "seats": uint16 [n][k] (table indices in ascending-ID order),
         "rounds": uint16 [n]}``."""
         table, S, n_sh, spb, n_batches, ov, tally = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
-        lags = np.ascontiguousarray(list(lags), dtype=np.int32)
+        lags, m, sums, head, tail = self._lag_arrays(lags, S, n_sh)
         ids = np.ascontiguousarray(strategy_ids, dtype=np.int32)
         if len(ids) != S or len(np.unique(ids)) != S:
             raise ValueError("strategy_ids must hold one unique ID per strategy of the table")
         n_games = n_sh * (S // k if k > 0 else 0)
-        m = min(int(lags.max()) if len(lags) else 0, n_sh)
-        sums = np.zeros((S, len(lags), LAG_COLS), dtype=np.int64)
-        head = np.zeros((max(m, 1), S), dtype=np.uint16)
-        tail = np.zeros((max(m, 1), S), dtype=np.uint16)
         digest = np.zeros(max(n_games, 1), dtype=np.uint64)
         seats = np.zeros((max(n_games, 1), max(k, 1)), dtype=np.uint16)
         rounds = np.zeros(max(n_games, 1), dtype=np.uint16)
         self._check(self._lib.fk_tournament_run_matchups(
             *self._lead(table, S, k, root_seed, shuffle_begin, shuffle_end, spb, target_score, max_rounds, ov, tally),
-            _p(lags), C.c_int32(len(lags)), _p(sums), _p(head), _p(tail), _p(ids), C.c_int32(max_players),
-            _p(digest), _p(seats), _p(rounds)))
+            _p(lags), len(lags), _p(sums), _p(head), _p(tail), _p(ids), max_players, _p(digest), _p(seats), _p(rounds)))
         return {"tally": tally[:n_batches], "lag_sums": sums, "lag_head": head[:m], "lag_tail": tail[:m], "n_shuffles": n_sh,
                 "matchups": {"digest": digest[:n_games], "seats": seats[:n_games], "rounds": rounds[:n_games]}}
 
@@ -683,9 +700,8 @@ class Engine:
             out_s = np.zeros((max(capacity, 1), max(k, 0)), dtype=np.uint16)
             out_c = np.zeros(max(capacity, 1), dtype=np.int64)
             out_x = np.zeros((max(capacity, 1), len(lags_a), 6), dtype=np.int64)
-            rc = self._lib.fk_matchup_reduce(self._ctx, C.c_int32(k), C.c_int64(n), _p(digest), _p(seats), _p(rounds), _p(lags_a),
-                                             C.c_int32(len(lags_a)), C.c_int64(cap_v), C.c_int64(capacity), _p(counts), _p(hist),
-                                             _p(out_d), _p(out_s), _p(out_c), _p(out_x))
+            rc = self._lib.fk_matchup_reduce(self._ctx, k, n, _p(digest), _p(seats), _p(rounds), _p(lags_a), len(lags_a), cap_v, capacity,
+                                             _p(counts), _p(hist), _p(out_d), _p(out_s), _p(out_c), _p(out_x))
             if rc == FK_ERR_ARG and counts[3] > capacity:  # more priority ties than the slack: once more with room for all
                 capacity = int(counts[3])
                 continue
@@ -705,7 +721,7 @@ class Engine:
     def hold_memory(self, leave_free: int) -> tuple[int, int]:
         """``fk_debug_hold_memory``: take device memory until about ``leave_free`` bytes are free (< 0: give it back); (free, total) after."""
         free, total = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fk_debug_hold_memory(self._ctx, C.c_int64(leave_free), C.byref(free), C.byref(total)))
+        self._check(self._lib.fk_debug_hold_memory(self._ctx, leave_free, C.byref(free), C.byref(total)))
         return int(free.value), int(total.value)
 
     def pinned_empty(self, n: int, dtype) -> np.ndarray:
@@ -716,7 +732,7 @@ class Engine:
         dtype = np.dtype(dtype)
         nbytes = max(int(n) * dtype.itemsize, 1)
         ptr = C.c_void_p()
-        self._check(self._lib.fk_host_alloc(self._ctx, C.c_size_t(nbytes), C.byref(ptr)))
+        self._check(self._lib.fk_host_alloc(self._ctx, nbytes, C.byref(ptr)))
         raw = (C.c_char * nbytes).from_address(ptr.value)
         arr = np.frombuffer(raw, dtype=dtype, count=int(n))
         lib, ctx, addr = self._lib, self._ctx, ptr.value
@@ -726,20 +742,23 @@ class Engine:
     def hint_next(self, shuffle_begin: int, shuffle_end: int, need_state: bool = False) -> None:
         """The call after the next ``tournament`` call will play this shuffle range of the same table, k and root: its
         permutations and seat seeding are then prepared in the drain tail of the next call's game kernel."""
-        self._check(self._lib.fk_tournament_hint_next(self._ctx, C.c_uint64(shuffle_begin), C.c_uint64(shuffle_end),
-                                                      C.c_int32(1 if need_state else 0)))
+        self._check(self._lib.fk_tournament_hint_next(self._ctx, shuffle_begin, shuffle_end, 1 if need_state else 0))
 
-    def play_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
-                   max_rounds: int = 200) -> np.ndarray:
+    @staticmethod
+    def _game_list(coords, table, seat_strategy, k) -> tuple:
+        """What the explicit game-list entries take: the packed coordinates and table, the flat int32 seat strategies and n_games."""
         coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
         table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
         ss = np.ascontiguousarray(seat_strategy, dtype=np.int32).reshape(-1)
-        n = len(coords)
-        if ss.size != n * k:
+        if ss.size != len(coords) * k:
             raise ValueError("seat_strategy must hold n_games * k entries")
+        return coords, table, ss, len(coords)
+
+    def play_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
+                   max_rounds: int = 200) -> np.ndarray:
+        coords, table, ss, n = self._game_list(coords, table, seat_strategy, k)
         rows = np.zeros(n, dtype=row_dtype(k))
-        self._check(self._lib.fk_play_games(self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss),
-                                            C.c_int32(k), C.c_int32(target_score), C.c_int32(max_rounds), _p(rows)))
+        self._check(self._lib.fk_play_games(self._ctx, _p(coords), n, _p(table), len(table), _p(ss), k, target_score, max_rounds, _p(rows)))
         return rows
 
     def trace_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
@@ -747,20 +766,14 @@ class Engine:
         """``fk_trace_games``: the rows ``play_games`` returns for the same arguments, ``event_begin`` (int64 ``[n_games + 1]``) and
         the roll events of every game (``EVENT_DTYPE``; game g owns ``events[event_begin[g]:event_begin[g + 1]]``, in play order).
         A counting call sizes the event list, an exact-size call fills it."""
-        coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        ss = np.ascontiguousarray(seat_strategy, dtype=np.int32).reshape(-1)
-        n = len(coords)
-        if ss.size != n * k:
-            raise ValueError("seat_strategy must hold n_games * k entries")
+        coords, table, ss, n = self._game_list(coords, table, seat_strategy, k)
         rows = np.zeros(n, dtype=row_dtype(k))
         begin = np.zeros(n + 1, dtype=np.int64)
-        lead = (self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss), C.c_int32(k), C.c_int32(target_score),
-                C.c_int32(max_rounds), _p(rows), _p(begin))
-        self._check(self._lib.fk_trace_games(*lead, None, C.c_int64(0)))
+        lead = (self._ctx, _p(coords), n, _p(table), len(table), _p(ss), k, target_score, max_rounds, _p(rows), _p(begin))
+        self._check(self._lib.fk_trace_games(*lead, None, 0))
         events = np.zeros(int(begin[-1]), dtype=EVENT_DTYPE)
         if len(events):
-            self._check(self._lib.fk_trace_games(*lead, _p(events), C.c_int64(len(events))))
+            self._check(self._lib.fk_trace_games(*lead, _p(events), len(events)))
         return rows, begin, events
 
     def census_games(self, coords: np.ndarray, table: np.ndarray, seat_strategy, k: int, target_score: int = 10_000,
@@ -768,15 +781,10 @@ class Engine:
         """``fk_census_games``: the roll census of an explicit game list — int64 ``roll_cells [6][61][7]``, ``strategy_dice [S][6][3]``,
         ``strategy_turns [S][3]``, ``turn_hist [S][turn_bins]`` (``include/farkle_hip.h``: ``fk_census``), equal to
         ``roll_census.RollCensus.from_events`` of what ``trace_games`` returns for the same arguments."""
-        coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
-        table = np.ascontiguousarray(table, dtype=STRATEGY_DTYPE)
-        ss = np.ascontiguousarray(seat_strategy, dtype=np.int32).reshape(-1)
-        n = len(coords)
-        if ss.size != n * k:
-            raise ValueError("seat_strategy must hold n_games * k entries")
+        coords, table, ss, n = self._game_list(coords, table, seat_strategy, k)
         tables, census = _census_tables(len(table), turn_bins)
-        self._check(self._lib.fk_census_games(self._ctx, _p(coords), C.c_int64(n), _p(table), C.c_int32(len(table)), _p(ss), C.c_int32(k),
-                                              C.c_int32(target_score), C.c_int32(max_rounds), C.byref(census)))
+        self._check(self._lib.fk_census_games(self._ctx, _p(coords), n, _p(table), len(table), _p(ss), k, target_score, max_rounds,
+                                              C.byref(census)))
         return tables
 
     def tournament_census(self, table: np.ndarray, k: int, root_seed: int, shuffle_begin: int, shuffle_end: int,
@@ -786,10 +794,8 @@ class Engine:
         range — the same permutations, seat streams and overrides."""
         table, S, n_sh, spb, n_batches, ov, _ = self._setup(table, shuffle_begin, shuffle_end, shuffles_per_batch, overrides)
         tables, census = _census_tables(S, turn_bins)
-        self._check(self._lib.fk_tournament_run_census(self._ctx, _p(table), C.c_int32(S), C.c_int32(k), C.c_uint64(root_seed),
-                                                       C.c_uint64(shuffle_begin), C.c_uint64(max(shuffle_end, shuffle_begin)), C.c_uint32(spb),
-                                                       C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)),
-                                                       C.byref(census)))
+        self._check(self._lib.fk_tournament_run_census(self._ctx, _p(table), S, k, root_seed, shuffle_begin, max(shuffle_end, shuffle_begin),
+                                                       spb, target_score, max_rounds, _p(ov), len(ov), C.byref(census)))
         return tables
 
     def h2h(self, seats: np.ndarray, root_seed: int, pair_id: int, order: int, target: int, max_attempts: int,
@@ -801,9 +807,8 @@ class Engine:
         st = np.zeros(5, dtype=np.uint64) if state is None else np.ascontiguousarray(state, dtype=np.uint64).copy()
         ov = overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE)
         ov = np.ascontiguousarray(ov, dtype=OVERRIDE_DTYPE)
-        self._check(self._lib.fk_h2h_run(self._ctx, _p(seats), C.c_uint64(root_seed), C.c_uint64(pair_id), C.c_uint32(order),
-                                         C.c_uint64(target), C.c_uint64(max_attempts), C.c_uint64(chunk_games),
-                                         C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov)), _p(st)))
+        self._check(self._lib.fk_h2h_run(self._ctx, _p(seats), root_seed, pair_id, order, target, max_attempts, chunk_games, target_score,
+                                         max_rounds, _p(ov), len(ov), _p(st)))
         return st
 
     def h2h_blocks(self, seats: np.ndarray, root_seed: int, pair_ids, orders, target, max_attempts, chunk_games=None,
@@ -826,8 +831,7 @@ class Engine:
         chunk = int(blocks["max_attempts"].max()) if chunk_games is None and n else int(chunk_games or 0)
         ov = overrides if overrides is not None else np.zeros(0, dtype=OVERRIDE_DTYPE)
         ov = np.ascontiguousarray(ov, dtype=OVERRIDE_DTYPE)
-        self._check(self._lib.fk_h2h_run_blocks(self._ctx, _p(blocks), C.c_int64(n), C.c_uint64(root_seed), C.c_uint64(chunk),
-                                                C.c_int32(target_score), C.c_int32(max_rounds), _p(ov), C.c_int32(len(ov))))
+        self._check(self._lib.fk_h2h_run_blocks(self._ctx, _p(blocks), n, root_seed, chunk, target_score, max_rounds, _p(ov), len(ov)))
         return blocks["state"].copy()
 
     def h2h_round_robin(self, table: np.ndarray, root_seed: int, target: int, max_attempts: int, pair_begin: int = 0,
@@ -849,8 +853,7 @@ class Engine:
         if min(begin, end, int(target), int(max_attempts), int(root_seed)) < 0:
             raise ValueError("pair range, target, max_attempts and root_seed must not be negative")
         states = np.zeros((max(end - begin, 0), 2, 5), dtype=np.uint32)
-        self._check(self._lib.fk_h2h_round_robin(self._ctx, _p(table), C.c_int32(n), C.c_uint64(root_seed), C.c_uint64(begin), C.c_uint64(end),
-                                                 C.c_uint64(target), C.c_uint64(max_attempts), C.c_int32(target_score), C.c_int32(max_rounds),
+        self._check(self._lib.fk_h2h_round_robin(self._ctx, _p(table), n, root_seed, begin, end, target, max_attempts, target_score, max_rounds,
                                                  _p(states), _p(summary)))
         return states, summary
 
@@ -877,9 +880,8 @@ class Engine:
             raise ValueError(f"summary must be a C-contiguous int64 array of shape {(n, 8)}")
         if min(int(target), int(max_attempts), int(root_seed)) < 0:
             raise ValueError("target, max_attempts and root_seed must not be negative")
-        self._check(self._lib.fk_h2h_round_robin_resident(self._ctx, _p(table), C.c_int32(n), C.c_uint64(root_seed), C.c_uint64(begin), C.c_uint64(end),
-                                                          C.c_uint64(target), C.c_uint64(max_attempts), C.c_int32(target_score),
-                                                          C.c_int32(max_rounds), _p(summary), C.c_uint64(family)))
+        self._check(self._lib.fk_h2h_round_robin_resident(self._ctx, _p(table), n, root_seed, begin, end, target, max_attempts, target_score,
+                                                          max_rounds, _p(summary), family))
         self._rr_n = n
         return summary
 
@@ -895,14 +897,13 @@ class Engine:
         st = np.ascontiguousarray(st, dtype=np.uint32)
         if min(int(target), int(max_attempts)) < 0:
             raise ValueError("target and max_attempts must not be negative")
-        args = (self._ctx, _p(table), C.c_int32(n), C.c_uint64(begin), C.c_uint64(end), C.c_uint64(target), C.c_uint64(max_attempts), _p(st),
-                C.c_uint64(family))
+        args = (self._ctx, _p(table), n, begin, end, target, max_attempts, _p(st), family)
         if root_seed is None:
             self._check(self._lib.fk_rr_counts_add(*args))
         else:
             if not 0 <= int(root_seed) < 1 << 64:
                 raise ValueError("root_seed must fit 64 unsigned bits")
-            self._check(self._lib.fk_rr_counts_add_root(*args, C.c_uint64(int(root_seed))))
+            self._check(self._lib.fk_rr_counts_add_root(*args, int(root_seed)))
         self._rr_n = n
 
     def rr_counts_reset(self) -> None:
@@ -940,8 +941,7 @@ class Engine:
             out_rows = np.zeros(max(end - begin, 0), dtype=RR_PAIR_ROW_DTYPE)
         class_counts = np.zeros(RR_CLASSES, dtype=np.int64)
         strategies = np.zeros((n, RR_STRATEGY_COLS), dtype=np.int64) if want_strategies else None
-        self._check(self._lib.fk_rr_inference(self._ctx, C.byref(par), _p(out_rows), C.c_uint64(begin), C.c_uint64(end), _p(class_counts),
-                                              _p(strategies)))
+        self._check(self._lib.fk_rr_inference(self._ctx, C.byref(par), _p(out_rows), begin, end, _p(class_counts), _p(strategies)))
         return {"class_counts": class_counts, "strategies": strategies, "rows": out_rows}
 
     def rr_root_diagnostics(self, family_alpha: float = 0.02, practical_delta: float = 0.03, delta_equivalence: float | None = None,
@@ -964,8 +964,8 @@ class Engine:
         n_roots = C.c_int32(0)
         summary = np.zeros(RR_AGREE_COLS, dtype=np.int64)
         largest = C.c_double(float("nan"))
-        self._check(self._lib.fk_rr_root_diagnostics(self._ctx, C.byref(par), _p(seeds), C.byref(n_roots), _p(out_rows), C.c_uint64(begin),
-                                                     C.c_uint64(end), _p(agreement), _p(summary), C.byref(largest)))
+        self._check(self._lib.fk_rr_root_diagnostics(self._ctx, C.byref(par), _p(seeds), C.byref(n_roots), _p(out_rows), begin, end,
+                                                     _p(agreement), _p(summary), C.byref(largest)))
         if out_rows is not None:  # the entry wrote [n_roots][k] at the front of the buffer
             out_rows = out_rows.reshape(-1)[: n_roots.value * out_rows.shape[1]].reshape(n_roots.value, out_rows.shape[1])
         return {"roots": seeds[: n_roots.value].copy(), "rows": out_rows, "agreement": agreement, "summary": summary,
@@ -996,7 +996,7 @@ class Engine:
         if 2 <= n <= DOM_MAX_N and any(len(a) != n_pairs for a in (cls, *arrays)):  # (the entry refuses the other sizes before it reads an array)
             raise ValueError(f"a table of {n} strategies has {n_pairs} pairs")
         rank, nodes, extremes, adjacency = self._dominance_outputs(n, rank, want_adjacency)
-        self._check(self._lib.fk_dominance_graph(self._ctx, C.c_int32(n), _p(cls), _p(arrays[0]), _p(arrays[1]), _p(arrays[2]), C.c_double(practical_delta),
+        self._check(self._lib.fk_dominance_graph(self._ctx, n, _p(cls), _p(arrays[0]), _p(arrays[1]), _p(arrays[2]), practical_delta,
                                                  _p(rank), _p(nodes), _p(extremes), _p(adjacency)))
         return {"nodes": nodes, "extremes": extremes, "adjacency": adjacency}
 
@@ -1039,7 +1039,7 @@ class Engine:
             raise ValueError(f"a table of {n} strategies has {n_pairs} pairs")
         codes = np.zeros(n_pairs if sized else 0, dtype=np.uint8) if want_codes else None
         counts = np.zeros(AGREE_COUNTS, dtype=np.int64)
-        self._check(self._lib.fk_agreement_pairs(self._ctx, C.c_int32(n), _p(cls), _p(win), _p(ts), _p(codes), _p(counts)))
+        self._check(self._lib.fk_agreement_pairs(self._ctx, n, _p(cls), _p(win), _p(ts), _p(codes), _p(counts)))
         return {"codes": codes, "counts": counts}
 
     def rr_agreement(self, win_rate_rank, trueskill_rank, family_alpha: float = 0.02, practical_delta: float = 0.03,
@@ -1063,7 +1063,7 @@ class Engine:
         if len(x) != len(y):
             raise ValueError("x and y must have one key per item each")
         counts = np.zeros(CONCORDANCE_COUNTS, dtype=np.int64)
-        self._check(self._lib.fk_rank_concordance(self._ctx, C.c_int32(min(len(x), (1 << 31) - 1)), _p(x), _p(y), _p(counts)))
+        self._check(self._lib.fk_rank_concordance(self._ctx, min(len(x), (1 << 31) - 1), _p(x), _p(y), _p(counts)))
         return counts
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
@@ -1079,21 +1079,21 @@ class Engine:
         """Collective: every rank joins the communicator on its own GPU."""
         if len(comm_id) != COMM_ID_BYTES:
             raise ValueError("communicator id must be 128 bytes")
-        self._check(self._lib.fk_comm_init(self._ctx, C.create_string_buffer(comm_id, COMM_ID_BYTES), C.c_int32(rank), C.c_int32(world_size)))
+        self._check(self._lib.fk_comm_init(self._ctx, C.create_string_buffer(comm_id, COMM_ID_BYTES), rank, world_size))
         self.comm_world = world_size
         self.comm_rank = rank
 
     def reduce_tally(self, tally: np.ndarray, root: int = 0) -> np.ndarray:
         """Collective: int64 SUM over the communicator; the total on ``root`` (the rank's own tally elsewhere)."""
         t = np.ascontiguousarray(tally, dtype=np.int64).copy()
-        self._check(self._lib.fk_reduce_tally(self._ctx, _p(t), C.c_int64(t.size), C.c_int32(root)))
+        self._check(self._lib.fk_reduce_tally(self._ctx, _p(t), t.size, root))
         return t
 
     def reduce_resident_tally(self, shape, root: int = 0) -> np.ndarray | None:
         """Collective: the device-resident tally accumulator (option ``resident_tally``) summed over the communicator on the
         device; the total on ``root`` (None elsewhere).  Clears the accumulator."""
         out = np.zeros(shape, dtype=np.int64)
-        self._check(self._lib.fk_tally_resident_reduce(self._ctx, _p(out), C.c_int64(out.size), C.c_int32(root)))
+        self._check(self._lib.fk_tally_resident_reduce(self._ctx, _p(out), out.size, root))
         return out if (self.comm_world == 1 or self.comm_rank == root) else None
 
     def comm_ranks(self) -> int:
@@ -1110,15 +1110,14 @@ class Engine:
         n = len(coords)
         s32 = np.zeros(n, dtype=np.uint32) if want32 else None
         s64 = np.zeros(n, dtype=np.uint64) if want64 else None
-        self._check(self._lib.fk_coordinate_seeds(self._ctx, C.c_int64(n), _p(coords), _p(s32), _p(s64)))
+        self._check(self._lib.fk_coordinate_seeds(self._ctx, n, _p(coords), _p(s32), _p(s64)))
         return s32, s64
 
     def game_seeds(self, purpose: int, root_seed: int, k: int, shuffle_begin: int, shuffle_end: int, games_per_shuffle: int) -> np.ndarray:
         """uint32 ``coordinate_seed`` fingerprints ``[n_shuffles][games_per_shuffle]`` of (purpose, root, k, shuffle, game_index)."""
         n_sh = max(int(shuffle_end) - int(shuffle_begin), 0)
         out = np.zeros((n_sh, int(games_per_shuffle)), dtype=np.uint32)
-        self._check(self._lib.fk_game_seeds(self._ctx, C.c_uint32(int(purpose)), C.c_uint64(root_seed), C.c_uint64(k), C.c_uint64(shuffle_begin),
-                                            C.c_uint64(n_sh), C.c_uint32(int(games_per_shuffle)), _p(out)))
+        self._check(self._lib.fk_game_seeds(self._ctx, int(purpose), root_seed, k, shuffle_begin, n_sh, int(games_per_shuffle), _p(out)))
         return out
 
     # -- single-op probes ------------------------------------------------------------------
@@ -1129,14 +1128,14 @@ class Engine:
         pre = np.ascontiguousarray(pre, dtype=np.int32)
         strategies = np.ascontiguousarray(strategies, dtype=STRATEGY_DTYPE)
         out = np.zeros((n, 5), dtype=np.int32)
-        self._check(self._lib.fk_debug_score(self._ctx, C.c_int64(n), _p(faces), _p(lens), _p(pre), _p(strategies), _p(out)))
+        self._check(self._lib.fk_debug_score(self._ctx, n, _p(faces), _p(lens), _p(pre), _p(strategies), _p(out)))
         return out
 
     def debug_should_continue(self, args: np.ndarray, strategies: np.ndarray) -> np.ndarray:
         args = np.ascontiguousarray(args, dtype=np.int32).reshape(-1, 6)
         strategies = np.ascontiguousarray(strategies, dtype=STRATEGY_DTYPE)
         out = np.zeros(len(args), dtype=np.int32)
-        self._check(self._lib.fk_debug_should_continue(self._ctx, C.c_int64(len(args)), _p(args), _p(strategies), _p(out)))
+        self._check(self._lib.fk_debug_should_continue(self._ctx, len(args), _p(args), _p(strategies), _p(out)))
         return out
 
     def debug_dice(self, coords: np.ndarray, sizes, want_raw: bool = True):
@@ -1145,7 +1144,7 @@ class Engine:
         n = len(coords)
         faces = np.zeros((n, int(sizes.sum())), dtype=np.uint8)
         raw = np.zeros((n, 4), dtype=np.uint64) if want_raw else None
-        self._check(self._lib.fk_debug_dice(self._ctx, C.c_int64(n), _p(coords), C.c_int32(len(sizes)), _p(sizes), _p(faces), _p(raw)))
+        self._check(self._lib.fk_debug_dice(self._ctx, n, _p(coords), len(sizes), _p(sizes), _p(faces), _p(raw)))
         return faces, raw
 
     def debug_bounded_draws(self, coords: np.ndarray, bound: int, n_draws: int) -> np.ndarray:
@@ -1153,8 +1152,7 @@ class Engine:
         the bootstrap's own device draw function (1 <= bound <= 2**32 - 1)."""
         coords = np.ascontiguousarray(coords, dtype=COORD_DTYPE)
         out = np.zeros((len(coords), int(n_draws)), dtype=np.uint32)
-        self._check(self._lib.fk_debug_bounded_draws(self._ctx, C.c_int64(len(coords)), _p(coords), C.c_uint64(int(bound)),
-                                                     C.c_int32(int(n_draws)), _p(out)))
+        self._check(self._lib.fk_debug_bounded_draws(self._ctx, len(coords), _p(coords), int(bound), int(n_draws), _p(out)))
         return out
 
     def debug_perm_from_draws(self, S: int, draws: np.ndarray, path: int, out: np.ndarray | None = None, n_sh: int | None = None) -> np.ndarray:
@@ -1169,7 +1167,7 @@ class Engine:
             out = np.zeros((max(int(n_sh), 0), max(int(S), 0)), dtype=np.int32)
         assert out.dtype == np.int32 and out.flags.c_contiguous
         assert n_sh < 1 or S < 1 or (out.size == n_sh * S and draws.size == n_sh * (S - 1)), "draws [n_sh][S - 1] and out [n_sh][S]"
-        self._check(self._lib.fk_debug_perm_from_draws(self._ctx, C.c_int32(int(S)), C.c_int64(int(n_sh)), _p(draws), C.c_int32(int(path)), _p(out)))
+        self._check(self._lib.fk_debug_perm_from_draws(self._ctx, int(S), int(n_sh), _p(draws), int(path), _p(out)))
         return out
 
     def performance_bootstrap(self, root_seed: int, ks, wins, exposures, replicate_begin: int, replicate_end: int, top_n: int,
@@ -1202,9 +1200,9 @@ class Engine:
         w_ptr = (C.c_void_p * n_k)(*[m.ctypes.data for m in W])
         e_ptr = (C.c_void_p * n_k)(*[m.ctypes.data for m in E])
         self._check(self._lib.fk_performance_bootstrap(
-            self._ctx, C.c_uint64(int(root_seed)), C.c_int32(n_k), _p(k_arr), _p(b_arr), w_ptr, e_ptr, C.c_int32(S),
-            C.c_int64(int(replicate_begin)), C.c_int64(int(replicate_end)), C.c_int32(int(top_n)), C.c_double(float(delta)), C.c_int32(n_ctrl),
-            _p(ctrl) if n_ctrl else None, _p(scores), *[_p(a) for a in counters], _p(csum) if n_ctrl else None, _p(csq) if n_ctrl else None))
+            self._ctx, int(root_seed), n_k, _p(k_arr), _p(b_arr), w_ptr, e_ptr, S, int(replicate_begin), int(replicate_end), int(top_n),
+            float(delta), n_ctrl, _p(ctrl) if n_ctrl else None, _p(scores), *[_p(a) for a in counters], _p(csum) if n_ctrl else None,
+            _p(csq) if n_ctrl else None))
         return {"scores": scores, "rank_sum": counters[0], "rank_square_sum": counters[1], "top_counts": counters[2],
                 "shortlist_counts": counters[3], "contrast_sum": csum, "contrast_square_sum": csq}
 
@@ -1246,9 +1244,8 @@ class Engine:
         maxima = np.zeros(R, dtype=np.float64) if joint else None
         membership = np.zeros((R, 2, S), dtype=np.uint8) if want_membership else None
         self._check(self._lib.fk_root_stability_bootstrap(
-            self._ctx, _p(root_arr), C.c_int32(n_k), _p(k_arr), _p(b_arr), w_ptr, e_ptr, C.c_int32(S), _p(w_arr),
-            C.c_int64(int(replicate_begin)), C.c_int64(int(replicate_end)), C.c_int32(int(top_n)), *[_p(v) if joint else None for v in group],
-            _p(top_counts), _p(maxima), _p(membership)))
+            self._ctx, _p(root_arr), n_k, _p(k_arr), _p(b_arr), w_ptr, e_ptr, S, _p(w_arr), int(replicate_begin), int(replicate_end), int(top_n),
+            *[_p(v) if joint else None for v in group], _p(top_counts), _p(maxima), _p(membership)))
         return {"top_counts": top_counts, "maxima": maxima, "membership": membership}
 
     def debug_dice_state(self, state: np.ndarray, sizes):
@@ -1257,7 +1254,7 @@ class Engine:
         n = len(state)
         faces = np.zeros((n, int(sizes.sum())), dtype=np.uint8)
         out = np.zeros((n, 6), dtype=np.uint64)
-        self._check(self._lib.fk_debug_dice_state(self._ctx, C.c_int64(n), _p(state), C.c_int32(len(sizes)), _p(sizes), _p(faces), _p(out)))
+        self._check(self._lib.fk_debug_dice_state(self._ctx, n, _p(state), len(sizes), _p(sizes), _p(faces), _p(out)))
         return faces, out
 
     def debug_dice_keys(self, state: np.ndarray, sizes):
@@ -1268,5 +1265,5 @@ class Engine:
         n = len(state)
         keys = np.zeros((n, len(sizes)), dtype=np.uint32)
         out = np.zeros((n, 6), dtype=np.uint64)
-        self._check(self._lib.fk_debug_dice_keys(self._ctx, C.c_int64(n), _p(state), C.c_int32(len(sizes)), _p(sizes), _p(keys), _p(out)))
+        self._check(self._lib.fk_debug_dice_keys(self._ctx, n, _p(state), len(sizes), _p(sizes), _p(keys), _p(out)))
         return keys, out
