@@ -278,6 +278,9 @@ def test_hot_cold_kernels_in_chunked_hinted_and_unpipelined_calls(eng, po, k):
                     assert _ran_hot_cold(eng, k), eng.timing()
                     if chunk == 1 << 20:
                         assert eng.timing()["play_launches"] >= 5, eng.timing()
+                    if rng == ranges[1]:  # the hinted call: its first chunk was prepared behind the previous call's game kernel, the others behind its own
+                        t = eng.timing()
+                        assert t["prefetched_chunks"] == (t["play_launches"] if pipeline else 0), (k, pipeline, chunk, t)
                     assert np.array_equal(got["tally"], ref[rng]["tally"]), (k, pipeline, chunk, rng)
                     assert got["rows"].tobytes() == ref[rng]["rows"].tobytes(), (k, pipeline, chunk, rng)
                 counts = eng.tournament(table, k, 13, 0, 1500, shuffles_per_batch=250)

@@ -395,11 +395,14 @@ def test_pipelined_preparation_never_changes_results(eng, po):
            for rng in [(0, 600), (600, 1200), (1200, 1500), (77, 300)]}
     ref_other = po.tournament(other.view(po.STRATEGY_DTYPE), 3, 42, 600, 900, n_threads=16)
 
-    def check(rng, **kw):
+    def check(rng, hinted=False, **kw):
         got = eng.tournament(table, 2, 42, rng[0], rng[1], **kw)
         assert np.array_equal(got["tally"], ref[rng]["tally"]), (rng, kw)
         if kw.get("want_rows"):
             assert got["rows"].tobytes() == ref[rng]["rows"].tobytes(), (rng, kw)
+        if hinted:  # the call a right hint was made for: its first chunk was prepared behind the previous call's game kernel, the others behind its own
+            t = eng.timing()
+            assert t["prefetched_chunks"] == (t["play_launches"] if pipeline else 0), (rng, kw, pipeline, chunk, t)
 
     try:
         for pipeline in (1, 0):
@@ -409,8 +412,9 @@ def test_pipelined_preparation_never_changes_results(eng, po):
                 eng.hint_next(600, 1200)            # right hint
                 check((0, 600))
                 eng.hint_next(1200, 1500, need_state=True)
-                check((600, 1200))
-                check((1200, 1500), want_rows=True)
+                check((600, 1200), hinted=True)
+                # (a rows call's chunks are shorter than the plain call's that prepared for it: only a one-chunk call finds its chunk)
+                check((1200, 1500), hinted=chunk == 48 << 30, want_rows=True)
                 eng.hint_next(0, 600)               # wrong hint: another range is played
                 check((77, 300), want_rows=True)
                 check((0, 600))                     # ... and the hinted one after all, a call later
