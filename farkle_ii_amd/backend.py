@@ -85,6 +85,10 @@ CONCORDANCE_COUNTS = 5  # FK_CONCORDANCE_COUNTS
 CONCORDANCE_MAX_M = 65536  # FK_CONCORDANCE_MAX_M
 CONCORDANCE_TILE = 256  # FK_CONCORDANCE_TILE
 RR_STRATEGY_COLS = 12  # FK_RR_STRATEGY_COLS
+# fk_power_cell, include/farkle_hip.h: one (sample size, scenario) cell of fk_score_power_scan (the plan in farkle_ii_amd/h2h_power.py)
+POWER_CELL_DTYPE = np.dtype([("n", "<i4"), ("reserved", "<i4"), ("q_ab", "<f8"), ("q_ba", "<f8")])
+POWER_MAX_N = 1048576  # FK_POWER_MAX_N
+POWER_LDS_MAX_N = 3071  # FK_POWER_LDS_MAX_N
 TALLY_COLS = 26
 LAG_COLS = 11  # FK_LAG_COLS: pairs | win: sx sy sxx syy sxy | n_rounds: sx sy sxx syy sxy
 SEAT_STAT_COLS = 31
@@ -1065,6 +1069,20 @@ class Engine:
         counts = np.zeros(CONCORDANCE_COUNTS, dtype=np.int64)
         self._check(self._lib.fk_rank_concordance(self._ctx, min(len(x), (1 << 31) - 1), _p(x), _p(y), _p(counts)))
         return counts
+
+    def score_power_scan(self, cells, alpha: float) -> np.ndarray:
+        """``fk_score_power_scan``: exact power of the two-sided score test at level ``alpha`` for every cell of ``cells``
+        (``POWER_CELL_DTYPE``: ``n`` completed games per order, ``q_ab``, ``q_ba``; ``h2h_power.make_cells`` builds them), float64
+        ``[cells]`` in the cells' order.  The critical value is evaluated here, once, with scipy (``norm.isf(alpha / 2)``)."""
+        from scipy.stats import norm
+
+        cells = np.ascontiguousarray(cells, dtype=POWER_CELL_DTYPE).reshape(-1)
+        alpha = float(alpha)
+        if not 0.0 < alpha < 1.0:
+            raise ValueError(f"alpha must be in (0, 1), got {alpha}")
+        power = np.zeros(len(cells), dtype=np.float64)
+        self._check(self._lib.fk_score_power_scan(self._ctx, _p(cells), len(cells), float(norm.isf(alpha / 2.0)), _p(power)))
+        return power
 
     # -- multi-GPU: the one exchange of the path, RCCL through the C-ABI ---------------------
     def comm_unique_id(self) -> bytes:

@@ -9,6 +9,7 @@ analysis/orchestration commands of the reference are out of scope and are reject
     python -m farkle_ii_amd --config cfg.yaml watch --players 4 --shuffle 17 --game 3      (replay a tournament game of the config's grid)
     python -m farkle_ii_amd --config cfg.yaml root-stability --root-results data/results_seed_11 --root-results data/results_seed_23
     python -m farkle_ii_amd --config cfg.yaml round-robin --block-games 2191 --strategy-ids family.txt      (every pair, both orders)
+    python -m farkle_ii_amd --config cfg.yaml round-robin --plan-power --strategy-ids family.txt      (the block size from the power plan)
     torchrun --nproc-per-node 8 -m farkle_ii_amd --config cfg.yaml run      (one process per GPU, RCCL tally reduce)
 """
 from __future__ import annotations
@@ -114,9 +115,18 @@ def build_parser() -> argparse.ArgumentParser:
                          "screening.bootstrap_replicates, candidate_contribution_size, practical_delta_by_k, delta_across_k, "
                          "robustness.delta_seed_stability, robustness.joint_discrepancy_alpha, k_aggregation")
     rr = sub.add_parser("round-robin", help="Head-to-head round robin: every pair of the strategy table, both seat orders, per root")
-    rr.add_argument("--block-games", type=int, required=True, metavar="N",
-                    help="Completed games every (pair, root, order) block must reach; a block plays at most "
-                         "ceil(head2head.max_attempt_multiplier x N) attempts (default multiplier 2.0)")
+    size = rr.add_mutually_exclusive_group(required=True)
+    size.add_argument("--block-games", type=int, metavar="N",
+                      help="Completed games every (pair, root, order) block must reach; a block plays at most "
+                           "ceil(head2head.max_attempt_multiplier x N) attempts (default multiplier 2.0)")
+    size.add_argument("--plan-power", action="store_true",
+                      help="Size the blocks by the reference's power plan instead: scan the exact power of the score test over every block "
+                           "size on the GPU and take the first whose worst seat-advantage scenario reaches head2head.target_power at "
+                           "head2head.practical_delta, with the whole table as the family (alpha per pair = family_alpha / pairs) on the "
+                           "configured roots.  Writes h2h_power_plan.json and h2h_power_curve.parquet, then runs what --block-games "
+                           "<planned> would; with --inference the pair table gains the three plan-derived columns.  Settings: "
+                           "head2head.target_power, seat1_advantage_scenarios, sensitivity_deltas, allow_single_root")
+    rr.add_argument("--plan-only", action="store_true", help="With --plan-power: stop after the two plan files; no game is played")
     rr.add_argument("--strategy-ids", type=Path, metavar="FILE", help="Restrict the configuration's grid to these strategy ids (one per line)")
     rr.add_argument("--pairs", metavar="BEGIN:END", help="Play this range of pair ids only (default: every pair of the table)")
     rr.add_argument("--blocks", action="store_true", help="Also write round_robin_blocks.parquet: two rows per pair and root")
@@ -171,7 +181,10 @@ def _maybe_init_distributed() -> None:
 
 
 def main(argv: Sequence[str] | None = None) -> None:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.command == "round-robin" and args.plan_only and not args.plan_power:
+        parser.error("round-robin: --plan-only belongs to --plan-power")
     logging.basicConfig(level=getattr(logging, str(args.log_level).upper(), logging.INFO),
                         format="%(asctime)s %(levelname)s %(name)s: %(message)s")
     if args.command in _OUT_OF_SCOPE:
@@ -212,14 +225,15 @@ def main(argv: Sequence[str] | None = None) -> None:
         print({name: str(path) for name, path in written.items()})
         return
     if args.command == "round-robin":
+        from .h2h_power import PowerPlanError
         from .round_robin import run_round_robin
 
         try:
             written = run_round_robin(cfg, args.block_games, strategy_ids_file=args.strategy_ids, pairs=args.pairs, blocks=args.blocks,
                                       out=args.out, force=args.force, inference=args.inference, rows=args.rows, dominance=args.dominance,
                                       screening_scores=args.screening_scores, root_diagnostics=args.root_diagnostics, agreement=args.agreement,
-                                      candidate_membership=args.candidate_membership)
-        except (ValueError, FileExistsError) as exc:
+                                      candidate_membership=args.candidate_membership, plan_power=args.plan_power, plan_only=args.plan_only)
+        except (ValueError, FileExistsError, PowerPlanError) as exc:
             raise SystemExit(f"farkle round-robin: {exc}") from exc
         print({name: str(path) for name, path in written.items()})
         return

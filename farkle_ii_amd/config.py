@@ -106,11 +106,29 @@ class SimConfig:
 
 @dataclass(frozen=True)
 class Head2HeadInferenceConfig:
-    """The ``head2head`` fields the round-robin inference reads, with the reference's defaults (config.py ``Head2HeadConfig``)."""
+    """The ``head2head`` fields the round-robin inference and its power plan read, with the reference's defaults (config.py
+    ``Head2HeadConfig``)."""
     family_alpha: float = 0.02
     practical_delta: float = 0.03
     delta_equivalence: float | None = None
     min_candidate_completion_rate: float = 0.99
+    target_power: float = 0.80
+    seat1_advantage_scenarios: tuple = (0.0, 0.03, 0.06)
+    sensitivity_deltas: tuple = (0.03, 0.04)
+    allow_single_root: bool = True
+
+    def check_plan(self) -> None:
+        """What the power plan demands of its settings, as the reference validates them (config.py:2049-2066; the seat-advantage
+        scenarios are not locked to the defaults here, and 0.04 need not be among the sensitivity effects)."""
+        if not 0.0 < self.family_alpha < 1.0:
+            raise ValueError("head2head.family_alpha must be between 0 and 1")
+        if not 0.0 < self.target_power < 1.0:
+            raise ValueError("head2head.target_power must be between 0 and 1")
+        if not self.practical_delta > 0.0:
+            raise ValueError("head2head.practical_delta must be positive")
+        deltas = self.sensitivity_deltas
+        if len(set(deltas)) != len(deltas) or any(not d > 0.0 for d in deltas) or self.practical_delta not in deltas:
+            raise ValueError("head2head.sensitivity_deltas must be unique positive values containing the practical delta")
 
 
 @dataclass
@@ -174,16 +192,29 @@ class AppConfig:
 
     @property
     def head2head(self) -> Head2HeadInferenceConfig:
-        """``head2head.family_alpha`` / ``practical_delta`` / ``delta_equivalence`` / ``min_candidate_completion_rate``; the section is
-        carried opaquely (its other keys belong to the reference's analysis), these four are read from it with the reference's defaults."""
+        """``head2head.family_alpha`` / ``practical_delta`` / ``delta_equivalence`` / ``min_candidate_completion_rate`` and the power
+        plan's ``target_power`` / ``seat1_advantage_scenarios`` / ``sensitivity_deltas`` / ``allow_single_root``; the section is carried
+        opaquely (its other keys belong to the reference's analysis), these are read from it with the reference's defaults.  What the
+        power plan demands of its settings is ``Head2HeadInferenceConfig.check_plan``: a run that is handed its block size does not
+        depend on them."""
         section = self.opaque.get("head2head") or {}
         values = {}
         for f in fields(Head2HeadInferenceConfig):
             raw = section.get(f.name, f.default)
             if isinstance(raw, str):  # a --set override of an opaque section arrives as text
-                raw = _coerce(raw, None)
+                raw = _coerce(raw, f.default if f.name == "allow_single_root" else None)
             if raw is None and f.name == "delta_equivalence":
                 values[f.name] = None
+                continue
+            if f.name == "allow_single_root":
+                if not isinstance(raw, bool):
+                    raise ValueError("head2head.allow_single_root must be true or false")
+                values[f.name] = raw
+                continue
+            if f.name in ("seat1_advantage_scenarios", "sensitivity_deltas"):
+                if not isinstance(raw, (list, tuple)) or not raw or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in raw):
+                    raise ValueError(f"head2head.{f.name} must be a list of numbers that is not empty")
+                values[f.name] = tuple(float(v) for v in raw)
                 continue
             if isinstance(raw, bool) or not isinstance(raw, (int, float)):
                 raise ValueError(f"head2head.{f.name} must be a number")

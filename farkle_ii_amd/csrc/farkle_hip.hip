@@ -21,6 +21,7 @@
 #include "fk_rr_root_diagnostics.h" // device side: the inference per kept root and the cross-root agreement
 #include "fk_dominance.h"      // device side: dominance graphs of a round robin (bit matrices, closure, components, fronts, cycles, extremes)
 #include "fk_agreement.h"      // device side: method agreement of a round robin (pair codes and their counts, Kendall's pair counts)
+#include "fk_power_plan.h"     // device side: exact power of the round robin's score test per (sample size, scenario) cell
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -261,6 +262,7 @@ struct fk_ctx {
     DominanceBufs dm;
     AgreementBufs ag;
     int64_t agreement_grid = 0;          // option "agreement_grid": > 0 caps the pair kernel's grid lower (tests drive second trips)
+    PowerPlanBufs pp;
     BootBufs boot;
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
@@ -3872,6 +3874,86 @@ int fk_rank_concordance(fk_ctx *c, int32_t m, const int32_t *x, const int32_t *y
     if (sum != all) // every pair i < j falls into exactly one count
         return fail(c, FK_ERR_HIP, "rank concordance lost pairs: the five counts sum to %llu, %d items have %llu pairs", sum, (int)m, all);
     for (uint32_t k = 0; k < CC_COUNTS; ++k) counts[k] = (int64_t)out[k];
+    return FK_OK;
+}
+
+// ---- exact power of the score test per (sample size, scenario) cell (device side: fk_power_plan.h) ----
+// The context's log-factorial table holds lf[0 .. n_max]: filled on the host, the whole table again when it grows.  An entry is libm's
+// long-double lgamma rounded to fp64, which h2h_power.log_factorials states with the same libm call: a table off by two units in the last place at n = 20 001 (the fp64 lgamma) moves every mass by 5e-11 of itself.
+static int power_plan_table(fk_ctx *c, int32_t n_max) {
+    PowerPlanBufs &b = c->pp;
+    const size_t want = (size_t)n_max + 1u;
+    if (want <= b.lf_n) return FK_OK;
+    const size_t entries = std::max<size_t>(want, std::min<size_t>(2u * b.lf_n, (size_t)FK_POWER_MAX_N + 1u)); // (grown on demand, not cell by cell)
+    b.lf_n = 0;
+    if (const int rc = ensure(c, b.lf, entries)) return rc;
+    std::vector<double> lf(entries);
+    int sign = 0;
+    for (size_t k = 0; k < entries; ++k) lf[k] = k < 2u ? 0.0 : (double)lgammal_r((long double)k + 1.0L, &sign);
+    HIPCHK(c, hipMemcpyAsync(b.lf.p, lf.data(), entries * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`lf` leaves scope)
+    b.lf_n = entries;
+    return FK_OK;
+}
+
+int fk_score_power_scan(fk_ctx *c, const fk_power_cell *cells, int64_t n_cells, double critical_value, double *power) {
+    using namespace fkpp;
+    if (!c) return FK_ERR_ARG;
+    if (n_cells < 0) return fail(c, FK_ERR_ARG, "n_cells must not be negative, got %lld", (long long)n_cells);
+    if (n_cells == 0) return FK_OK;
+    if (!cells || !power) return fail(c, FK_ERR_ARG, "cells and power are required");
+    if (n_cells > 0x7fffffffll) return fail(c, FK_ERR_ARG, "a scan takes at most 2^31 - 1 cells, got %lld", (long long)n_cells);
+    if (!std::isfinite(critical_value) || !(critical_value > 0.0))
+        return fail(c, FK_ERR_ARG, "critical_value must be finite and positive, got %g", critical_value);
+    int32_t n_max = 0;
+    for (int64_t i = 0; i < n_cells; ++i) {
+        const fk_power_cell &cell = cells[i];
+        if (cell.n < 1 || cell.n > FK_POWER_MAX_N)
+            return fail(c, FK_ERR_ARG, "cell %lld: n must be in [1, %d], got %d", (long long)i, FK_POWER_MAX_N, (int)cell.n);
+        for (const double q : {cell.q_ab, cell.q_ba})
+            if (!std::isfinite(q) || !(q > 0.0 && q < 1.0))
+                return fail(c, FK_ERR_ARG, "cell %lld: a probability must lie strictly between 0 and 1, got %g", (long long)i, q);
+        n_max = std::max(n_max, cell.n);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    begin_call(c);
+    PowerPlanBufs &b = c->pp;
+    // largest first (cost is proportional to n); cells of one size keep the caller's order
+    std::vector<uint32_t> order((size_t)n_cells);
+    for (uint32_t i = 0; i < (uint32_t)n_cells; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return cells[x].n > cells[y].n; });
+    std::vector<Cell> sorted((size_t)n_cells);
+    uint32_t beyond = 0; // cells whose tails do not fit LDS: the head of the order
+    for (size_t at = 0; at < sorted.size(); ++at) {
+        const fk_power_cell &cell = cells[order[at]];
+        sorted[at] = Cell{cell.n, order[at], std::log(cell.q_ab), std::log1p(-cell.q_ab), std::log(cell.q_ba), std::log1p(-cell.q_ba)};
+        beyond += cell.n > FK_POWER_LDS_MAX_N ? 1u : 0u;
+    }
+    // the workspace: one slot per workgroup of the global kernel, at most PW_WORKSPACE_BYTES in all and one slot at least
+    constexpr size_t PW_WORKSPACE_BYTES = (size_t)256 << 20;
+    constexpr uint32_t PW_MAX_GRID = 1024;
+    const uint64_t slot_entries = beyond ? (uint64_t)n_max + 1u : 0u;
+    const uint32_t beyond_grid =
+        beyond ? (uint32_t)std::min<uint64_t>(beyond, std::clamp<uint64_t>(PW_WORKSPACE_BYTES / (16u * slot_entries), 1u, PW_MAX_GRID)) : 0u;
+    if (const int rc = power_plan_table(c, n_max)) return rc;
+    if (const int rc = ensure_all(c, b.cells, (size_t)n_cells, b.power, (size_t)n_cells, b.workspace, (size_t)(2u * slot_entries * beyond_grid))) return rc;
+    HIPCHK(c, hipMemcpyAsync(b.cells.p, sorted.data(), sorted.size() * sizeof(Cell), hipMemcpyHostToDevice, c->stream));
+    volatile double two = 2.0; // libm's pow itself, which the reference's `critical ** 2` calls: not folded into a product
+    const double critical_squared = std::pow(critical_value, two);
+    Timer device_work(c, &c->timing.play_ms, SLOT_CALL);
+    if (beyond)
+        hipLaunchKernelGGL(fk_pp_scan_kernel<false>, dim3(beyond_grid), dim3(PW_BLOCK), 0, c->stream, b.cells.p, beyond, b.lf.p, critical_squared,
+                           b.workspace.p, slot_entries, b.power.p);
+    const uint32_t within = (uint32_t)n_cells - beyond;
+    if (within)
+        hipLaunchKernelGGL(fk_pp_scan_kernel<true>, dim3(within), dim3(PW_BLOCK), 0, c->stream, b.cells.p + beyond, within, b.lf.p, critical_squared,
+                           (double *)nullptr, (uint64_t)0, b.power.p);
+    HIPCHK(c, hipGetLastError());
+    device_work.stop();
+    HIPCHK(c, hipMemcpyAsync(power, b.power.p, (size_t)n_cells * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream)); // (`sorted` leaves scope)
+    HIPCHK(c, collect_timers(c));
+    c->timing.total_ms = c->timing.play_ms;
     return FK_OK;
 }
 

@@ -126,6 +126,13 @@ struct AgreementBufs { // fk_agreement_pairs, fk_rr_agreement, fk_rank_concordan
     Dev<int32_t> x, y;       // [m] the keys of fk_rank_concordance
     Dev<ull> concordance;    // [fkag::CC_COUNTS]
 };
+struct PowerPlanBufs { // fk_score_power_scan
+    Dev<double> lf;         // log-factorial table: lf[k] = log k! (long-double lgamma, rounded), k = 0 .. lf_n - 1; filled once, grown with the largest n seen
+    size_t lf_n = 0;        // entries of `lf` that are filled
+    Dev<fkpp::Cell> cells;  // the call's cells, largest n first
+    Dev<double> power;      // [n_cells] in the caller's order
+    Dev<double> workspace;  // the tails of the cells beyond LDS: one slot of 2 (n_max + 1) doubles per workgroup
+};
 struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
     Dev<int64_t> wins, exposures; // the stacked matrices
     Dev<fkb::KDesc> kd;

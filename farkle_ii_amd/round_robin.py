@@ -283,10 +283,10 @@ def parse_pair_range(text: str | None, n: int) -> tuple[int, int]:
     return begin, end
 
 
-def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
+def run_round_robin(cfg, block_games: int | None, *, strategy_ids_file=None, pairs: str | None = None, blocks: bool = False, out=None,
                     force: bool = False, strategies=None, engine=None, world: int | None = None, inference: bool = False,
                     rows: str | None = None, dominance: bool = False, screening_scores=None, root_diagnostics: bool = False,
-                    agreement: bool = False, candidate_membership=None) -> dict:
+                    agreement: bool = False, candidate_membership=None, plan_power: bool = False, plan_only: bool = False) -> dict:
     """``farkle round-robin``: the grid of ``cfg`` (restricted to the ids of ``strategy_ids_file``), every pair of the range, per root of
     ``sim.seed_list``.  Writes ``round_robin_pairs.parquet``, ``round_robin_strategies.parquet``, ``round_robin.json`` and, with
     ``blocks``, ``round_robin_blocks.parquet`` under ``out`` (default ``<results_root>/h2h_round_robin``).  Returns the written paths.
@@ -312,7 +312,14 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     the device (``Engine.rr_agreement``), Kendall's pair counts of the scored population are taken there (``Engine.rank_concordance``) and
     the command also writes the reference's ``agreement_summary.json`` and — when every pair's row is on the host —
     ``selection_conditioned_pairs.parquet`` (``structure_agreement.py`` builds both), and the counts under ``"agreement"`` in
-    ``round_robin.json``.  ``execution_scope`` is ``root_pair`` on two roots and ``single_root`` on one."""
+    ``round_robin.json``.  ``execution_scope`` is ``root_pair`` on two roots and ``single_root`` on one.
+
+    With ``plan_power`` (and ``block_games`` None) the command sizes its own blocks first: the reference's power plan for the whole table
+    as the family, on the configured roots, from the ``head2head`` settings (``h2h_power.plan_from_config``: the device scans the exact
+    power of every block size, ``Engine.score_power_scan``).  It writes ``h2h_power_plan.json`` and ``h2h_power_curve.parquet`` under
+    ``out`` and then runs what ``block_games`` = the planned size would; ``round_robin.json`` gains ``"power_plan"`` and, with
+    ``inference``, the pair table gains the reference's three plan-derived columns.  ``plan_only`` stops after the two files: no game is
+    played and no strategy table reaches the device."""
     import os
 
     import pyarrow as pa
@@ -325,8 +332,12 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     if world > 1:
         raise ValueError(f"round-robin: runs on one rank, got a world of {world} (split the work with --pairs; several ranks are a later change)")
     multiplier = cfg.opaque.get("head2head", {}).get("max_attempt_multiplier", DEFAULT_MAX_ATTEMPT_MULTIPLIER)
-    max_attempts = max_attempts_for(block_games, multiplier)
-    target = int(block_games)
+    if plan_power == (block_games is not None):
+        raise ValueError("round-robin: exactly one of --block-games and --plan-power sizes the blocks")
+    if plan_only and not plan_power:
+        raise ValueError("round-robin: --plan-only belongs to --plan-power")
+    max_attempts = max_attempts_for(1 if plan_power else block_games, multiplier)  # (a plan: the multiplier's check; the cap follows the plan)
+    target = 0 if plan_power else int(block_games)
     if strategies is None:
         strategies, _ = runner._resolve_strategies(cfg, None)
     wanted = read_strategy_ids(strategy_ids_file) if strategy_ids_file is not None else None
@@ -401,8 +412,24 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
     out_dir = Path(out) if out is not None else cfg.results_root / "h2h_round_robin"
     if out_dir.exists() and not force:
         raise FileExistsError(f"round-robin: {out_dir} exists; pass --force to replace its tables")
-    table = pack_strategies(chosen)
     eng = engine or get_engine()
+    written_plan: dict = {}
+    if plan_power:
+        from . import h2h_power as hp
+
+        planned = hp.plan_from_config(eng, cfg.head2head, n, roots)
+        plan_doc = hp.plan_document(planned, cfg.head2head, multiplier)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        written_plan = {"power_plan": out_dir / "h2h_power_plan.json", "power_curve": out_dir / "h2h_power_curve.parquet"}
+        runner._atomic_write_bytes(written_plan["power_plan"], (json.dumps(plan_doc, indent=2, sort_keys=True) + "\n").encode("utf-8"))
+        runner._write_parquet_atomic(pa.Table.from_pandas(hp.curve_frame(planned), preserve_index=False), written_plan["power_curve"])
+        LOGGER.info("round robin power plan: %d games per (pair, root, order) block, worst-scenario power %.6f (%d sizes scanned)",
+                    planned["block_games"], planned["worst_scenario_achieved_power"], len(planned["curve"]))
+        if plan_only:
+            return written_plan
+        target = int(planned["block_games"])
+        max_attempts = max_attempts_for(target, multiplier)
+    table = pack_strategies(chosen)
     summary = np.zeros((n, len(SUMMARY_COLS)), dtype=np.int64)
     states: list[np.ndarray] = []
     started = time.perf_counter()
@@ -442,12 +469,15 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
                 eng.set_option("rr_keep_roots", keep_before)
     elapsed = time.perf_counter() - started
     out_dir.mkdir(parents=True, exist_ok=True)
-    written = {"strategies": out_dir / "round_robin_strategies.parquet", "json": out_dir / "round_robin.json"}
+    written = {"strategies": out_dir / "round_robin_strategies.parquet", "json": out_dir / "round_robin.json", **written_plan}
     frames = [(strategies_frame(ids, summary), written["strategies"])]
     if inference:
         written["inference_pairs"] = out_dir / "round_robin_inference_pairs.parquet"
         written["inference_strategies"] = out_dir / "round_robin_inference_strategies.parquet"
-        frames.append((ri.pairs_frame(result["rows"], ids, family_pair_count=family, **knobs), written["inference_pairs"]))
+        inference_pairs = ri.pairs_frame(result["rows"], ids, family_pair_count=family, **knobs)
+        if plan_power:
+            inference_pairs = ri.with_plan_columns(inference_pairs, h2h.target_power, planned["worst_scenario_achieved_power"])
+        frames.append((inference_pairs, written["inference_pairs"]))
         frames.append((ri.strategies_frame(result["strategies"], ids, h2h.min_candidate_completion_rate), written["inference_strategies"]))
         if root_diagnostics:
             written["root_pairs"] = out_dir / "root_pairwise_diagnostics.parquet"
@@ -494,6 +524,10 @@ def run_round_robin(cfg, block_games: int, *, strategy_ids_file=None, pairs: str
               "target_score": 10_000, "max_rounds": 200, "pair_begin": begin, "pair_end": end, "pairs_total": pair_count(n),
               "blocks": 2 * (end - begin) * len(roots), "games_attempted": attempted, "games_completed": completed,
               "elapsed_seconds": elapsed, "files": sorted(p.name for p in written.values())}
+    if plan_power:
+        report["power_plan"] = {key: plan_doc[key] for key in ("n_completed_required_per_root_order_block", "target_power", "target_effect", "alpha_per_pair",
+                                                                 "worst_scenario_achieved_power", "previous_equal_block_size_worst_power")}
+        report["power_plan"].update(block_sizes_scanned=int(len(planned["curve"])), host_evaluations=int(planned["host_evaluations"]))
     if inference:
         report["inference"] = {"class_counts": {name: int(v) for name, v in zip(ri.DECISION_CLASSES, result["class_counts"])},
                                "family_pair_count": family, "row_begin": row_range[0], "row_end": row_range[1], **knobs}

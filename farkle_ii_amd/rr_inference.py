@@ -14,10 +14,12 @@ stay on the device (``Engine.h2h_round_robin_resident`` / ``Engine.rr_counts_add
 The interval is the reference's own complete inversion of the uncorrected constrained score statistic
 (``_score_difference_interval_fallback``); the library route of the interval (``confint_proportions_2indep``) is not reproduced.
 
-Left out of the frames (the reference computes them from its power plan, schedule hashes and block manifests, which this package
-does not have): ``family_hash``, ``replacement_attempt_count`` and its per-strategy sums, ``score_test_id``, ``interval_method_id``,
-``h2h_method_version``, ``planned_target_power_conditional_on_completed_support``,
-``planned_worst_scenario_power_conditional_on_completed_support``, ``power_support_status``.  Also out of scope: sidecars and
+Left out of the frames (the reference computes them from its schedule hashes and block manifests, which this package does not have):
+``family_hash``, ``replacement_attempt_count`` and its per-strategy sums, ``score_test_id``, ``interval_method_id``,
+``h2h_method_version``.  The three columns the reference derives from its power plan —
+``planned_target_power_conditional_on_completed_support``, ``planned_worst_scenario_power_conditional_on_completed_support``,
+``power_support_status`` — are added by ``with_plan_columns`` when the run planned its own block size (``farkle round-robin
+--plan-power``, ``farkle_ii_amd/h2h_power.py``); a run that was handed its block size has no plan to quote.  Also out of scope: sidecars and
 completion stamps, several ranks, resuming.  The graphs the reference's ``dominance.py`` builds from these classes are
 ``Engine.rr_dominance`` and ``farkle_ii_amd/dominance.py``; its ``_root_specific_diagnostics`` (the inference per root and the
 cross-root agreement) is ``Engine.rr_root_diagnostics`` and ``farkle_ii_amd/rr_root_diagnostics.py``.
@@ -423,6 +425,18 @@ def pairs_frame(rows: np.ndarray, strategy_ids=None, n: int | None = None, famil
         "decision_class": np.asarray(DECISION_CLASSES, dtype=object)[rows["decision_class"]],
         "multiplicity_method": "holm",
     })
+    return frame
+
+
+def with_plan_columns(frame, target_power: float, worst_scenario_power: float):
+    """``pairs_frame`` with the three columns the reference takes from its power plan (``_pairwise_estimates`` :808-816): the plan's
+    target power, its worst-scenario power at the planned size, and whether the pair reached the completed support both are
+    conditional on (its inferential viability)."""
+    frame = frame.copy()
+    frame["planned_target_power_conditional_on_completed_support"] = float(target_power)
+    frame["planned_worst_scenario_power_conditional_on_completed_support"] = float(worst_scenario_power)
+    frame["power_support_status"] = np.where(frame["pair_inferentially_viable"].to_numpy(dtype=bool), "completed_support_achieved",
+                                             "unresolved_required_completed_support_not_achieved")
     return frame
 
 

@@ -955,6 +955,28 @@ int fk_root_stability_bootstrap(fk_ctx *ctx, const uint64_t *roots, int32_t n_k,
                                 const double *expected, const double *observed_across, const double *expected_across,
                                 int64_t *top_counts, double *maxima, uint8_t *membership);
 
+/* Exact power of the round robin's two-sided score test, the quantity the reference's power plan scans block sizes by
+ * (analysis/h2h_schedule.py: implemented_score_test_power :324-358 over _fixed_first_count_boundary_arrays :273-295, scanned by
+ * _minimum_block_games :393-420).  Per cell: n completed games per order, X1 ~ Bin(n, q_ab) and X2 ~ Bin(n, q_ba) independent;
+ * power[i] = sum over c1 = 0 .. n of pmf(X1 = c1) * [ P(X2 <= lower(c1)) + P(X2 >= upper(c1)) ], clamped to [0, 1], where lower / upper are
+ * the reference's closed-form rejecting count boundaries at critical_value = norm.isf(alpha / 2): the roots of the quadratic in count2,
+ * ceil - 1 and floor + 1 of them, clipped to [-1, n] and [0, n + 1], -1 at c1 = 0 and n + 1 at c1 = n.  The boundaries are NumPy's
+ * integer for integer (the same fp64 operations in the same order, never fused); the probabilities are fp64 from a log-factorial table
+ * the context keeps, the lower tail a prefix sum and the upper tail a suffix sum of the probability masses.  The conditional-Fisher
+ * cross-check the reference adds at n <= 64 is not made.  A cell's result does not depend on the other cells or on their order.
+ * Cells of n <= FK_POWER_LDS_MAX_N keep their tails in LDS, larger ones in a workspace of the context.
+ * FK_ERR_ARG, with power untouched: n < 1 or n > FK_POWER_MAX_N, a q outside (0, 1) or not finite, a critical_value that is not finite
+ * and positive, n_cells < 0, a null pointer with n_cells > 0.  n_cells = 0 succeeds and touches nothing. */
+#define FK_POWER_MAX_N 1048576
+#define FK_POWER_LDS_MAX_N 3071
+typedef struct fk_power_cell {
+    int32_t n;        /* completed games per order */
+    int32_t reserved; /* 0 */
+    double q_ab;      /* P(seat 1 wins) in order a-b */
+    double q_ba;      /* ... and in order b-a */
+} fk_power_cell;
+int fk_score_power_scan(fk_ctx *ctx, const fk_power_cell *cells, int64_t n_cells, double critical_value, double *power);
+
 #ifdef __cplusplus
 }
 #endif
