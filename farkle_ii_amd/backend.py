@@ -1266,6 +1266,45 @@ class Engine:
             *[_p(v) if joint else None for v in group], _p(top_counts), _p(maxima), _p(membership)))
         return {"top_counts": top_counts, "maxima": maxima, "membership": membership}
 
+    def performance_by_k(self, k: int, wins, exposures, completed, safety, B: int | None = None, S: int | None = None) -> dict:
+        """``fk_performance_by_k``: the per-k point estimates' sums over ALL batches of one player count.  Four int64 ``[B][S]``
+        matrices (rows in ascending batch id, columns in ascending strategy id; cells without an exposure allowed).  Returns int64
+        ``[S]`` ``wins``, ``exposures``, ``completed``, ``safety``, ``losses``, ``positive_batches`` and float64 ``[S]`` ``rate_sum``,
+        ``ssd`` (NumPy's summation order, ``performance.host_by_k`` bit for bit).  ``B`` / ``S``: the shape handed to the entry when
+        it is not the matrices' (refusal tests)."""
+        mats = [np.ascontiguousarray(m, dtype=np.int64) for m in (wins, exposures, completed, safety)]
+        if mats[0].ndim != 2 or any(m.shape != mats[0].shape for m in mats):
+            raise ValueError("wins, exposures, completed and safety are [batches][S] matrices of one shape")
+        B = mats[0].shape[0] if B is None else int(B)
+        S = mats[0].shape[1] if S is None else int(S)
+        names = ("wins", "exposures", "completed", "safety", "losses", "positive_batches")
+        out = {name: np.zeros(max(S, 0), dtype=np.int64) for name in names}
+        out["rate_sum"], out["ssd"] = np.zeros(max(S, 0), dtype=np.float64), np.zeros(max(S, 0), dtype=np.float64)
+        self._check(self._lib.fk_performance_by_k(self._ctx, int(k), B, S, _p(mats[0]), _p(mats[1]), _p(mats[2]), _p(mats[3]), _p(out["wins"]),
+                                                  _p(out["exposures"]), _p(out["completed"]), _p(out["safety"]), _p(out["losses"]),
+                                                  _p(out["positive_batches"]), _p(out["rate_sum"]), _p(out["ssd"])))
+        return out
+
+    def performance_across_k(self, deltas, variances, n: int | None = None, d: int | None = None) -> dict:
+        """``fk_performance_across_k``: float64 ``[n][d]`` chance deltas and variances (``batch_mcse ** 2``, squared by the caller as the
+        reference squares it: ``performance.squared_mcse``) of the complete-support strategies, rows in ascending strategy id.  Returns
+        float64 ``[n]`` ``delta_sum``, ``variance_sum``, ``minimum``, int32 ``worst_index``, bool ``pareto_member`` and ``leader_row``
+        (``performance.host_across_k`` bit for bit).  ``n`` / ``d``: the shape handed to the entry when it is not the arrays'."""
+        deltas = np.ascontiguousarray(deltas, dtype=np.float64)
+        variances = np.ascontiguousarray(variances, dtype=np.float64)
+        if deltas.ndim != 2 or deltas.shape != variances.shape:
+            raise ValueError("deltas and variances are [n][d] arrays of one shape")
+        n = deltas.shape[0] if n is None else int(n)
+        d = deltas.shape[1] if d is None else int(d)
+        rows = max(n, 0)
+        out = {"delta_sum": np.zeros(rows), "variance_sum": np.zeros(rows), "minimum": np.zeros(rows), "worst_index": np.zeros(rows, np.int32)}
+        member = np.zeros(rows, dtype=np.uint8)
+        leader = C.c_int32(-1)
+        self._check(self._lib.fk_performance_across_k(self._ctx, n, d, _p(deltas), _p(variances), _p(out["delta_sum"]), _p(out["variance_sum"]),
+                                                      _p(out["minimum"]), _p(out["worst_index"]), _p(member), C.byref(leader)))
+        out["pareto_member"], out["leader_row"] = member.astype(bool), int(leader.value)
+        return out
+
     def debug_dice_state(self, state: np.ndarray, sizes):
         state = np.ascontiguousarray(state, dtype=np.uint64).reshape(-1, 6)
         sizes = np.ascontiguousarray(sizes, dtype=np.int32)

@@ -74,6 +74,14 @@ def build_parser() -> argparse.ArgumentParser:
                           "last player count across_k/performance_bootstrap.parquet and across_k/performance_control_contrasts.parquet "
                           "(screening.bootstrap_replicates, delta_across_k, candidate_contribution_size, controls).  May be combined "
                           "with --all-player-batches (the same statistics launch).  Not resumable: an interrupted run asks for --force")
+    run.add_argument("--performance", action="store_true",
+                     help="Write the performance stage's point estimates from the device: the batch matrices of --performance-bootstrap "
+                          "(the same statistics launch) and, after the last player count, per player count "
+                          "analysis/03_metrics/by_k/<k>p/performance_by_k.parquet (totals, win rates, Wilson and batch t intervals) and "
+                          "across_k/performance_across_k.parquet (equal_k_score, Pareto membership, maximin leader; "
+                          "screening.practical_delta_by_k and delta_across_k are required).  With --performance-bootstrap also "
+                          "analysis/04_screening/across_k/descriptive_screening.parquet and descriptive_screening.json.  Not "
+                          "resumable: an interrupted run asks for --force")
     run.add_argument("--roll-census", nargs="?", const=0, type=int, default=None, metavar="SHUFFLES",
                      help="After the run, census the rolls of the first SHUFFLES shuffles of every player count's range (default: one "
                           "deterministic batch) on the device and hold them against the exact dice law: diagnostics/"
@@ -265,6 +273,8 @@ def main(argv: Sequence[str] | None = None) -> None:
         cfg.sim.rare_events = True
     if args.performance_bootstrap:
         cfg.sim.performance_bootstrap = True
+    if args.performance:
+        cfg.sim.performance = True
     if args.seat_analysis:
         cfg.sim.seat_analysis = True
     if args.rng_matchup_lags:  # (one lag-mode game pass feeds both families)
@@ -295,7 +305,7 @@ def main(argv: Sequence[str] | None = None) -> None:
     LOGGER.info("Dispatching run command: seed=%s n_players_list=%s results_dir=%s", cfg.sim.seed, cfg.sim.n_players_list,
                 cfg.results_root)
     try:
-        if len(cfg.sim.n_players_list) > 1 or cfg.sim.performance_bootstrap or cfg.sim.rare_events:  # (the bootstrap / the rare-event files follow the sweep's last player count)
+        if len(cfg.sim.n_players_list) > 1 or cfg.sim.performance_bootstrap or cfg.sim.performance or cfg.sim.rare_events:  # (the bootstrap / the rare-event files follow the sweep's last player count)
             out = runner.run_multi(cfg, force=args.force)
         else:
             out = {cfg.sim.n_players_list[0]: runner.run_single_n(cfg, cfg.sim.n_players_list[0], force=args.force)}

@@ -68,6 +68,7 @@ class SimConfig:
     rare_events: bool = False  # with game_stats: the per-game rows of rare_events.parquet / rare_events_details.parquet and the quantile thresholds (rare_events.py)
     seat_analysis: bool = False  # this engine's option: the seat-analysis stage's count tables, seat effects and mirrored pairs without rows (seat_analysis.py)
     performance_bootstrap: bool = False  # this engine's option: the performance stage's batch matrices + joint batch bootstrap (performance_bootstrap.py)
+    performance: bool = False  # this engine's option: the performance stage's by-k / across-k estimates and, with performance_bootstrap, the descriptive screening frame (performance.py)
     per_n: dict = field(default_factory=dict)
     n_jobs: int | None = None
     mp_start_method: str | None = None
@@ -296,6 +297,22 @@ class AppConfig:
     def performance_control_contrasts_path(self) -> Path:
         """config.py:1006-1009."""
         return self.metrics_stage_dir() / "across_k" / "performance_control_contrasts.parquet"
+
+    def performance_by_k_path(self, n: int) -> Path:
+        """The reference's ``performance_by_k_path`` (config.py:986-989), under this engine's file name."""
+        return self.metrics_stage_dir() / "by_k" / f"{n}p" / "performance_by_k.parquet"
+
+    def performance_across_k_path(self) -> Path:
+        """The reference's ``performance_across_k_path`` (config.py:991-994), under this engine's file name."""
+        return self.metrics_stage_dir() / "across_k" / "performance_across_k.parquet"
+
+    def screening_stage_dir(self) -> Path:
+        """The reference's screening stage directory (config.py:841-845) beside the metrics stage."""
+        return self.results_root / self.io.analysis_subdir / "04_screening"
+
+    def screening_path(self, filename: str = "descriptive_screening.parquet") -> Path:
+        """config.py:1298-1301: ``across_k/descriptive_screening.parquet`` (and ``.json``) of the screening stage."""
+        return self.screening_stage_dir() / "across_k" / filename
 
     def seat_batch_counts_path(self, n: int) -> Path:
         """config.py:1098-1101: ``by_k/<k>p/seat_batch_counts.parquet``."""

@@ -22,6 +22,7 @@
 #include "fk_dominance.h"      // device side: dominance graphs of a round robin (bit matrices, closure, components, fronts, cycles, extremes)
 #include "fk_agreement.h"      // device side: method agreement of a round robin (pair codes and their counts, Kendall's pair counts)
 #include "fk_power_plan.h"     // device side: exact power of the round robin's score test per (sample size, scenario) cell
+#include "fk_performance.h"    // device side: performance stage's point estimates (by-k column sums in NumPy's order, across-k sums, Pareto front, maximin)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -264,6 +265,8 @@ struct fk_ctx {
     int64_t agreement_grid = 0;          // option "agreement_grid": > 0 caps the pair kernel's grid lower (tests drive second trips)
     PowerPlanBufs pp;
     BootBufs boot;
+    PerformanceBufs pf;
+    int64_t performance_grid = 0;        // option "performance_grid": > 0 caps the workgroups of the performance kernels (tests drive the grid strides)
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
@@ -1650,6 +1653,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "rr_window_blocks") *value = c->rr_window_blocks;
     else if (n == "rr_keep_roots") *value = c->ri_keep_roots ? 1 : 0;
     else if (n == "agreement_grid") *value = c->agreement_grid;
+    else if (n == "performance_grid") *value = c->performance_grid;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1691,6 +1695,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "bootstrap_block") c->bootstrap_block = std::max<int64_t>(value, 0);
     else if (n == "census_chunk_games") c->census_chunk_games = std::max<int64_t>(value, 0);
     else if (n == "agreement_grid") c->agreement_grid = std::max<int64_t>(value, 0);
+    else if (n == "performance_grid") c->performance_grid = std::max<int64_t>(value, 0);
     else if (n == "rr_window_blocks") {
         if (value < 2 || value > ((int64_t)1 << 22) || (value & 1))
             return fail(c, FK_ERR_ARG, "rr_window_blocks must be even and in [2, 2^22] (a pair's two blocks share a window)");
@@ -4645,6 +4650,112 @@ int fk_root_stability_bootstrap(fk_ctx *c, const uint64_t *roots, int32_t n_k, c
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (!joint && maxima)
         for (int64_t r = 0; r < n_rep; ++r) maxima[r] = 0.0;
+    return FK_OK;
+}
+
+// workgroups of a performance kernel over `blocks` blocks of work: option "performance_grid" caps them, the kernels stride
+static unsigned perf_grid(fk_ctx *c, uint64_t blocks) {
+    uint64_t grid = std::min<uint64_t>(std::max<uint64_t>(blocks, 1), fkp::MAX_GRID);
+    if (c->performance_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)c->performance_grid);
+    return (unsigned)grid;
+}
+
+int fk_performance_by_k(fk_ctx *c, int32_t k, int64_t B, int32_t S, const int64_t *wins, const int64_t *exposures, const int64_t *completed,
+                        const int64_t *safety, int64_t *total_wins, int64_t *total_exposures, int64_t *total_completed, int64_t *total_safety,
+                        int64_t *total_losses, int64_t *positive_batches, double *rate_sum, double *ssd) {
+    if (!c) return FK_ERR_ARG;
+    if (k < 1) return fail(c, FK_ERR_ARG, "player count k = %d", k);
+    if (B < 1 || B > 0x7fffffffll) return fail(c, FK_ERR_ARG, "%dp: B = %lld: a batch matrix has 1 to 2^31 - 1 batches", k, (long long)B);
+    if (S < 1 || S > (1 << 24)) return fail(c, FK_ERR_ARG, "%dp: S must be in [1, 2^24]", k);
+    if (!wins || !exposures || !completed || !safety) return fail(c, FK_ERR_ARG, "%dp: the four count matrices are required", k);
+    if (!total_wins || !total_exposures || !total_completed || !total_safety || !total_losses || !positive_batches || !rate_sum || !ssd)
+        return fail(c, FK_ERR_ARG, "%dp: the eight outputs are required", k);
+    // the reference's matrix checks (_validate_matrix_array :134-160) and its support check (:486-488), before anything is uploaded
+    const size_t cells = (size_t)B * (size_t)S;
+    std::vector<uint64_t> support((size_t)S, 0);
+    const uint64_t limit = (uint64_t)1 << 62;
+    for (size_t b = 0, at = 0; b < (size_t)B; ++b)
+        for (size_t s = 0; s < (size_t)S; ++s, ++at) {
+            const int64_t w = wins[at], e = exposures[at], done = completed[at], f = safety[at];
+            if (w < 0 || e < 0 || done < 0 || f < 0) return fail(c, FK_ERR_ARG, "%dp: a negative count in batch row %zu, column %zu", k, b, s);
+            if (w > done) return fail(c, FK_ERR_ARG, "%dp: wins > completed in batch row %zu, column %zu: impossible win/exposure counts", k, b, s);
+            if ((uint64_t)done + (uint64_t)f != (uint64_t)e)
+                return fail(c, FK_ERR_ARG, "%dp: exposures != completed + safety in batch row %zu, column %zu: attempted exposure conservation", k, b, s);
+            if ((uint64_t)e > limit - support[s]) return fail(c, FK_ERR_ARG, "%dp: the exposure total of column %zu passes 2^62", k, s);
+            support[s] += (uint64_t)e;
+        }
+    for (size_t s = 0; s < (size_t)S; ++s)
+        if (support[s] == 0) return fail(c, FK_ERR_ARG, "%dp: strategies have no positive exposure support: column %zu", k, s);
+    HIPCHK(c, hipSetDevice(c->device));
+    PerformanceBufs &p = c->pf;
+    if (const int rc = ensure_all(c, p.wins, cells, p.exposures, cells, p.completed, cells, p.safety, cells, p.totals, (size_t)6 * S, p.sums, (size_t)2 * S))
+        return rc;
+    const int64_t *host[4] = {wins, exposures, completed, safety};
+    int64_t *dev[4] = {p.wins.p, p.exposures.p, p.completed.p, p.safety.p};
+    for (int i = 0; i < 4; ++i) HIPCHK(c, hipMemcpyAsync(dev[i], host[i], cells * 8, hipMemcpyHostToDevice, c->stream));
+    const unsigned grid = perf_grid(c, ((uint64_t)S + fkp::COLUMN_BLOCK - 1) / fkp::COLUMN_BLOCK);
+    hipLaunchKernelGGL(fkp::fk_perf_by_k_kernel, dim3(grid), dim3(fkp::COLUMN_BLOCK), 0, c->stream, p.wins.p, p.exposures.p, p.completed.p,
+                       p.safety.p, (uint32_t)B, (uint32_t)S, p.totals.p, p.sums.p);
+    HIPCHK(c, hipGetLastError());
+    // into the caller's arrays only once the stream has come through: a failed call leaves them as they were
+    std::vector<long long> totals((size_t)6 * S);
+    std::vector<double> sums((size_t)2 * S);
+    HIPCHK(c, hipMemcpyAsync(totals.data(), p.totals.p, totals.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sums.data(), p.sums.p, sums.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int64_t *outs[6] = {total_wins, total_exposures, total_completed, total_safety, total_losses, positive_batches};
+    for (int i = 0; i < 6; ++i) std::copy(totals.begin() + (size_t)i * S, totals.begin() + (size_t)(i + 1) * S, outs[i]);
+    std::copy(sums.begin(), sums.begin() + S, rate_sum);
+    std::copy(sums.begin() + S, sums.end(), ssd);
+    return FK_OK;
+}
+
+int fk_performance_across_k(fk_ctx *c, int32_t n, int32_t d, const double *deltas, const double *variances, double *delta_sum,
+                            double *variance_sum, double *minimum, int32_t *worst_index, uint8_t *pareto_member, int32_t *leader_row) {
+    if (!c) return FK_ERR_ARG;
+    if (n < 1 || n > (1 << 24)) return fail(c, FK_ERR_ARG, "n = %d: 1 to 2^24 complete-support strategies", n);
+    if (d < 1 || d > (int32_t)fkp::MAX_D) return fail(c, FK_ERR_ARG, "d = %d: 1 to %u required player counts", d, fkp::MAX_D);
+    if (!deltas || !variances) return fail(c, FK_ERR_ARG, "deltas and variances are required");
+    if (!delta_sum || !variance_sum || !minimum || !worst_index || !pareto_member || !leader_row) return fail(c, FK_ERR_ARG, "the six outputs are required");
+    const size_t cells = (size_t)n * (size_t)d;
+    for (size_t i = 0; i < cells; ++i) {
+        if (!std::isfinite(deltas[i])) return fail(c, FK_ERR_ARG, "row %zu, player count %zu: the chance delta is not finite", i / (size_t)d, i % (size_t)d);
+        if (variances[i] < 0.0 || std::isinf(variances[i])) // (NaN: a column with fewer than two positive batches has no mcse)
+            return fail(c, FK_ERR_ARG, "row %zu, player count %zu: the variance is negative or infinite", i / (size_t)d, i % (size_t)d);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    PerformanceBufs &p = c->pf;
+    if (const int rc = ensure_all(c, p.deltas, cells, p.variances, cells, p.stats, (size_t)3 * n, p.worst, (size_t)n, p.member, (size_t)n, p.best, 2))
+        return rc;
+    const ull start[2] = {0ull, (ull)(uint32_t)n}; // the key of no value; no leader yet
+    HIPCHK(c, hipMemcpyAsync(p.best.p, start, 16, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.deltas.p, deltas, cells * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(p.variances.p, variances, cells * 8, hipMemcpyHostToDevice, c->stream));
+    const unsigned row_grid = perf_grid(c, ((uint64_t)n + 63) / 64), pareto_grid = perf_grid(c, ((uint64_t)n + fkp::PARETO_BLOCK - 1) / fkp::PARETO_BLOCK);
+    uint32_t *leader = reinterpret_cast<uint32_t *>(p.best.p + 1);
+    hipLaunchKernelGGL(fkp::fk_perf_rows_kernel, dim3(row_grid), dim3(64), 0, c->stream, p.deltas.p, p.variances.p, (uint32_t)n, (uint32_t)d,
+                       p.stats.p, p.worst.p, p.best.p);
+    hipLaunchKernelGGL(fkp::fk_perf_pareto_kernel, dim3(pareto_grid), dim3(fkp::PARETO_BLOCK), 0, c->stream, p.deltas.p, (uint32_t)n, (uint32_t)d,
+                       p.member.p);
+    hipLaunchKernelGGL(fkp::fk_perf_leader_kernel, dim3(row_grid), dim3(64), 0, c->stream, p.stats.p + 2 * (size_t)n, (uint32_t)n, p.best.p, leader);
+    HIPCHK(c, hipGetLastError());
+    std::vector<double> stats((size_t)3 * n);
+    std::vector<int32_t> worst((size_t)n);
+    std::vector<uint8_t> member((size_t)n);
+    ull best[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(stats.data(), p.stats.p, stats.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(worst.data(), p.worst.p, worst.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(member.data(), p.member.p, member.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(best, p.best.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const uint32_t leader_found = (uint32_t)best[1];
+    if (leader_found >= (uint32_t)n) return fail(c, FK_ERR_HIP, "the maximin reduction found no leader among %d rows", n);
+    std::copy(stats.begin(), stats.begin() + n, delta_sum);
+    std::copy(stats.begin() + n, stats.begin() + 2 * (size_t)n, variance_sum);
+    std::copy(stats.begin() + 2 * (size_t)n, stats.end(), minimum);
+    std::copy(worst.begin(), worst.end(), worst_index);
+    std::copy(member.begin(), member.end(), pareto_member);
+    *leader_row = (int32_t)leader_found;
     return FK_OK;
 }
 

@@ -146,6 +146,16 @@ struct BootBufs { // fk_performance_bootstrap, fk_root_stability_bootstrap
     Dev<ull> maxima, root_counters; // root stability: one block's maxima (as ordered bits); four counters per root
     Dev<uint8_t> member;   // root stability: one block's membership rows
 };
+struct PerformanceBufs { // fk_performance_by_k, fk_performance_across_k
+    Dev<int64_t> wins, exposures, completed, safety; // by k: the four [B][S] matrices
+    Dev<long long> totals;   // by k: [6][S] wins | exposures | completed | safety | losses | positive batches
+    Dev<double> sums;        // by k: [2][S] rate_sum | ssd
+    Dev<double> deltas, variances; // across k: [n][d]
+    Dev<double> stats;       // across k: [3][n] delta_sum | variance_sum | minimum
+    Dev<int32_t> worst;      // across k: [n]
+    Dev<uint8_t> member;     // across k: [n]
+    Dev<ull> best;           // across k: the largest minimum's ordered key; behind it the leader row
+};
 struct ProbeBufs { // the fk_debug_* probes and fk_coordinate_seeds: the kernel's buffer arguments in their order, bytes
     Dev<uint8_t> a, b, c, d, e;
 };

@@ -1217,8 +1217,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
         if cfg.sim.seat_analysis and not cfg.seat_batch_counts_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.seat_batch_counts_path(n).name}: --seat-analysis needs every game of "
                              "the run; use --force to replay it with the seat counts")
-        if cfg.sim.performance_bootstrap and not cfg.performance_batch_matrix_path(n).exists():
-            raise ValueError(f"{n}p is already complete without {cfg.performance_batch_matrix_path(n).name}: --performance-bootstrap needs "
+        if (cfg.sim.performance_bootstrap or cfg.sim.performance) and not cfg.performance_batch_matrix_path(n).exists():
+            raise ValueError(f"{n}p is already complete without {cfg.performance_batch_matrix_path(n).name}: --performance / --performance-bootstrap need "
                              "the statistics of every deterministic batch; use --force to replay it")
         if cfg.sim.rng_matchup_lags and not cfg.rng_matchup_groups_path(n).exists():
             raise ValueError(f"{n}p is already complete without {cfg.rng_matchup_groups_path(n).name}: --rng-matchup-lags needs every "
@@ -1242,7 +1242,8 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
             for path in (ckpt_path, n_dir / f"{n}p_checkpoint.parquet", cfg.metrics_path(n), simulation_done_path(cfg, n),
                          cfg.rng_lag_sums_path(n), cfg.rng_lag_stats_path(n), cfg.rng_matchup_groups_path(n), cfg.game_stats_path(n),
                          cfg.game_stats_sums_path(n), cfg.performance_batch_matrix_path(n), cfg.performance_bootstrap_path(),
-                         cfg.performance_control_contrasts_path(), cfg.seat_batch_counts_path(n), cfg.seat_effects_by_k_path(n),
+                         cfg.performance_control_contrasts_path(), cfg.performance_by_k_path(n), cfg.performance_across_k_path(),
+                         cfg.screening_path(), cfg.screening_path("descriptive_screening.json"), cfg.seat_batch_counts_path(n), cfg.seat_effects_by_k_path(n),
                          cfg.seat_population_by_k_path(n), cfg.seat_standardized_across_k_path(), cfg.seat_exposure_mixture_diagnostic_path(),
                          cfg.seat_selfplay_diagnostic_path(), *((cfg.seat_mirrored_diagnostic_path(),) if n == 2 else ())):
                 path.unlink(missing_ok=True)
@@ -1296,7 +1297,7 @@ def run_single_n(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy] | N
                             rng_lags=cfg.rng_diagnostic_lags() if cfg.sim.rng_lag_sums else None, defer_final_checkpoint=True,
                             packed_table=shared.packed, defer_tail=run_tail if _defer_publish is not None else None,
                             rng_matchups=_matchup_max_players(cfg, n) if cfg.sim.rng_matchup_lags else None, game_stats=cfg.sim.game_stats,
-                            performance_bootstrap=cfg.sim.performance_bootstrap, rare_events=_rare_event_plan(cfg),
+                            performance_bootstrap=cfg.sim.performance_bootstrap or cfg.sim.performance, rare_events=_rare_event_plan(cfg),
                             seat_analysis=cfg.sim.seat_analysis)
     finally:
         if published is not None:
@@ -1591,6 +1592,57 @@ def _publish_performance_bootstrap(cfg: AppConfig, counts: Sequence[int]) -> Non
         _write_parquet_atomic(table, path)
 
 
+def _check_performance(cfg: AppConfig, counts: Sequence[int]) -> None:
+    """What ``--performance`` cannot serve is refused before anything plays (the reference's configuration checks, config.py:2014-2025)."""
+    sc = cfg.screening
+    practical = sc.practical_delta_by_k
+    if not practical:
+        raise ValueError("screening.practical_delta_by_k must explicitly cover every configured player count")
+    if sorted(int(k) for k in practical) != sorted(int(k) for k in counts):
+        raise ValueError("screening.practical_delta_by_k keys must match sim.n_players_list")
+    if any(float(v) <= 0.0 for v in practical.values()):
+        raise ValueError("screening practical thresholds must be positive")
+    if sc.delta_across_k is None or float(sc.delta_across_k) <= 0.0:
+        raise ValueError("screening.delta_across_k must be explicitly configured and positive")
+    if len(counts) > 16:
+        raise ValueError("the across-k estimates take 16 player counts at most")
+
+
+def _publish_performance(cfg: AppConfig, counts: Sequence[int]) -> None:
+    """After the last player count, on the launching thread of rank 0 (the engine serves one call at a time): the point estimates over
+    the batch matrices of the root — ``performance_by_k.parquet`` of every player count, ``performance_across_k.parquet`` and, when
+    the bootstrap table stands beside it, the descriptive screening frame and its report."""
+    import pyarrow.parquet as pq
+
+    from . import performance as pf
+    from . import performance_bootstrap as pb
+
+    sc = cfg.screening
+    practical = {int(k): float(v) for k, v in sc.practical_delta_by_k.items()}
+    engine = get_engine()
+    required = sorted(int(k) for k in counts)
+    tables, estimates = {}, {}
+    for k in required:
+        matrix = pb.BatchMatrix.load(cfg.performance_batch_matrix_path(k), k)
+        tables[k], estimates[k] = pf.by_k_frame(engine, matrix, float(sc.resolution_delta), practical[k])
+    across, _, _ = pf.across_k_frame(engine, estimates, required, float(sc.delta_across_k))
+    written = [(tables[k], cfg.performance_by_k_path(k)) for k in required] + [(across, cfg.performance_across_k_path())]
+    report = None
+    if cfg.sim.performance_bootstrap:
+        screening = pf.screening_frame(across, pq.read_table(cfg.performance_bootstrap_path()), tables, required,
+                                       int(sc.candidate_contribution_size), sc.delta_across_k, practical, sc.controls, sc.mandatory_diagnostics)
+        written.append((screening, cfg.screening_path()))
+        report = pf.screening_payload(screening, required, cfg.screening_path().name)
+    for table, path in written:
+        path.parent.mkdir(parents=True, exist_ok=True)
+        _write_parquet_atomic(table, path)
+    if report is not None:
+        path = cfg.screening_path("descriptive_screening.json")
+        tmp = path.with_name(path.name + ".tmp")
+        tmp.write_text(json.dumps(report, indent=2, sort_keys=True) + "\n")
+        tmp.replace(path)
+
+
 ROOT_STABILITY_FILES = {"root_bootstrap_top_n_inclusion": "root_bootstrap_top_n_inclusion.parquet",
                         "root_discrepancies": "root_discrepancies.parquet", "root_joint_discrepancy": "root_joint_discrepancy.parquet"}
 
@@ -1665,7 +1717,7 @@ def _publish_results(cfg: AppConfig, n: int, strategies: list[ThresholdStrategy]
         _publish_game_stats(cfg, n, strategies, result)
     if cfg.sim.seat_analysis and result.get("seat_analysis") is not None:
         _publish_seat_analysis(cfg, n, strategies, result)
-    if cfg.sim.performance_bootstrap and result.get("performance_matrix") is not None:
+    if (cfg.sim.performance_bootstrap or cfg.sim.performance) and result.get("performance_matrix") is not None:
         result["performance_matrix"].save(cfg.performance_batch_matrix_path(n))  # (the frames follow the LAST player count: run_multi)
     # (A) summary parquet, (B) expanded metrics parquet — column order, types and values as in runner.py:1612-1712, built column by
     # column from the tally (the per-strategy dict loop cost 25 us per strategy and table: 140 ms of a 330-ms config-3 run).  Rows in
@@ -1770,6 +1822,8 @@ def run_multi(cfg: AppConfig, player_counts: Sequence[int] | None = None, *, for
     results: dict[int, int] = {}
     if cfg.sim.performance_bootstrap:
         _check_performance_bootstrap(cfg, strategies)
+    if cfg.sim.performance:
+        _check_performance(cfg, valid)
     # A player count's publishing tail (summary tables, completion stamp: 10 - 20 ms of Python on the 5 160-strategy grid; in rows mode
     # also the count's last launch groups, whose shards are still being written) runs on its own thread under the NEXT player counts'
     # engine calls (ctypes drops the GIL for their duration).  The tails run in order on that one thread; the launching thread joins a
@@ -1813,6 +1867,8 @@ def run_multi(cfg: AppConfig, player_counts: Sequence[int] | None = None, *, for
             _TRACE.clear()
     if cfg.sim.performance_bootstrap and valid and _rank_world()[0] == 0:  # the matrices of every count are reduced on rank 0
         _publish_performance_bootstrap(cfg, valid)
+    if cfg.sim.performance and valid and _rank_world()[0] == 0:  # (behind the bootstrap: the screening frame merges its table)
+        _publish_performance(cfg, valid)
     if cfg.sim.rare_events and valid and _rank_world()[0] == 0:  # the lists of every count, under thresholds resolved across them
         _publish_rare_events(cfg, valid, strategies)
     return results

@@ -977,6 +977,50 @@ typedef struct fk_power_cell {
 } fk_power_cell;
 int fk_score_power_scan(fk_ctx *ctx, const fk_power_cell *cells, int64_t n_cells, double critical_value, double *power);
 
+/* The performance stage's per-k point estimates from one player count's batch matrix (analysis/performance.py:
+ * _estimate_one_k_matrix :425-542), as far as they are sums over batches.
+ * Inputs: k (the player count, named in the messages); four row-major int64 [B][S] matrices wins / exposures / completed / safety
+ * (raw_wins, raw_player_game_exposures, raw_completed_player_game_exposures, raw_safety_limit_player_game_exposures) of ALL B batches in
+ * ascending batch id, S strategy columns in ascending strategy id.  The matrices are unprojected: a cell without an exposure is allowed
+ * and leaves the float sums, as the reference's `exposures > 0` mask does.
+ * Outputs (caller-owned host memory, [S] each, all required):
+ *   total_wins, total_exposures, total_completed, total_safety   int64 column sums; total_losses = total_exposures - total_wins
+ *   positive_batches   int64: rows with exposures > 0 (raw_batches)
+ *   rate_sum           float64: np.add.reduce of r_b = (double)wins / (double)exposures over the positive rows in ascending batch order
+ *   ssd                float64: np.add.reduce of (r_b - mean) * (r_b - mean), mean = rate_sum / positive_batches: what
+ *                      np.std(rates, ddof = 1) sums.  The caller finishes batch_mcse = sqrt(ssd / (count - 1)) / sqrt(count), the t
+ *                      quantile and the Wilson interval (S values each; farkle_ii_amd/performance.py: by_k_frame).
+ * Both float sums run in NumPy's order over the compacted contiguous vector (csrc/fk_performance.h: np_add_reduce: buffers of 8 192,
+ * the pairwise tree down to blocks of 128, eight accumulators per block), every operation a separate IEEE operation, so the caller's
+ * mcse is the reference's bit for bit.  No result depends on the launch shape (option "performance_grid" > 0 caps the workgroups).
+ * FK_ERR_ARG before any device work, with the outputs untouched: k < 1, B < 1 or B > 2^31 - 1, S outside [1, 2^24], a null pointer, a
+ * negative count, wins > completed, exposures != completed + safety, a column total beyond 2^62, a column whose total exposure is <= 0
+ * (the reference's ValueError "strategies have no positive exposure support"). */
+int fk_performance_by_k(fk_ctx *ctx, int32_t k, int64_t B, int32_t S, const int64_t *wins, const int64_t *exposures,
+                        const int64_t *completed, const int64_t *safety, int64_t *total_wins, int64_t *total_exposures,
+                        int64_t *total_completed, int64_t *total_safety, int64_t *total_losses, int64_t *positive_batches,
+                        double *rate_sum, double *ssd);
+
+/* The performance stage's across-k estimates of the complete-support strategies (analysis/performance.py: _across_k_estimates
+ * :575-687, _pareto_membership :547-572).
+ * Inputs: n rows in ascending strategy id, d required player counts (1 <= d <= 16) in the caller's order; two row-major float64 [n][d]
+ * arrays: deltas (chance_delta per player count) and variances (the caller's batch_mcse ** 2, squared on the host as the reference
+ * squares it — Python's float power, i.e. libm's pow, which differs from the IEEE product in about one value in 1 200 — NaN where a
+ * column has fewer than two positive batches).
+ * Outputs (caller-owned host memory, [n] each, all required):
+ *   delta_sum, variance_sum   float64: np.add.reduce over the row's d elements (the caller divides: equal_k_score = delta_sum / d,
+ *                             equal_k_mcse = sqrt(variance_sum / d^2)); d = 8 is where NumPy's eight accumulators start
+ *   minimum, worst_index      float64, int32: the row's smallest delta and its first position (np.argmin)
+ *   pareto_member             uint8: 1 unless another row is >= in every coordinate and > in at least one.  Equal rows do not dominate
+ *                             each other.  This is the set the reference's incremental frontier ends with.
+ *   leader_row                one int32: the smallest row whose minimum lies within 1e-15 of the largest minimum
+ *                             (np.isclose(rtol = 0, atol = 1e-15)): the maximin leader
+ * Every float operation is a separate IEEE operation; no result depends on the launch shape (option "performance_grid").
+ * FK_ERR_ARG before any device work, with the outputs untouched: n < 1 or n > 2^24, d outside [1, 16], a null pointer, a delta that is
+ * not finite, a variance that is negative or infinite. */
+int fk_performance_across_k(fk_ctx *ctx, int32_t n, int32_t d, const double *deltas, const double *variances, double *delta_sum,
+                            double *variance_sum, double *minimum, int32_t *worst_index, uint8_t *pareto_member, int32_t *leader_row);
+
 #ifdef __cplusplus
 }
 #endif
