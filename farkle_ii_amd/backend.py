@@ -89,6 +89,10 @@ RR_STRATEGY_COLS = 12  # FK_RR_STRATEGY_COLS
 POWER_CELL_DTYPE = np.dtype([("n", "<i4"), ("reserved", "<i4"), ("q_ab", "<f8"), ("q_ba", "<f8")])
 POWER_MAX_N = 1048576  # FK_POWER_MAX_N
 POWER_LDS_MAX_N = 3071  # FK_POWER_LDS_MAX_N
+ROOT_WINDOW_MAX_CELLS = 256  # FK_ROOT_WINDOW_MAX_CELLS
+# fk_root_window_estimates: the planes of its two outputs, in their order
+ROOT_WINDOW_TOTALS = ("wins", "exposures", "completed", "safety", "losses", "positive_batches")
+ROOT_WINDOW_SUMS = ("sum_w2", "sum_we", "sum_e2")
 TALLY_COLS = 26
 LAG_COLS = 11  # FK_LAG_COLS: pairs | win: sx sy sxx syy sxy | n_rounds: sx sy sxx syy sxy
 SEAT_STAT_COLS = 31
@@ -1303,6 +1307,36 @@ class Engine:
         self._check(self._lib.fk_performance_across_k(self._ctx, n, d, _p(deltas), _p(variances), _p(out["delta_sum"]), _p(out["variance_sum"]),
                                                       _p(out["minimum"]), _p(out["worst_index"]), _p(member), C.byref(leader)))
         out["pareto_member"], out["leader_row"] = member.astype(bool), int(leader.value)
+        return out
+
+    def root_window_estimates(self, wins, exposures, completed, safety, windows, S: int | None = None, batch_counts=None) -> dict:
+        """``fk_root_window_estimates``: the two-root stability stage's sums over row windows of its cells.  ``wins[c]`` ..
+        ``safety[c]``: the four int64 ``[B_c][S]`` matrices of cell ``c``, unprojected; ``windows``: int64 ``[n][4]`` rows ``(cell,
+        row_begin, row_end, pairwise_begin)`` (``root_stability.window_pairwise_begin``).  Returns int64 ``[n][S]`` ``wins``,
+        ``exposures``, ``completed``, ``safety``, ``losses``, ``positive_batches`` and float64 ``[n][S]`` ``sum_w2``, ``sum_we``,
+        ``sum_e2`` (``root_stability.estimate_windows`` bit for bit).  ``S`` / ``batch_counts``: the shape handed to the entry when it
+        is not the matrices' (refusal tests)."""
+        kinds = [[np.ascontiguousarray(m, dtype=np.int64) for m in group] for group in (wins, exposures, completed, safety)]
+        n_cells = len(kinds[0])
+        if not n_cells or any(len(group) != n_cells for group in kinds):
+            raise ValueError("one wins / exposures / completed / safety matrix per cell")
+        width = int(kinds[0][0].shape[1]) if kinds[0][0].ndim == 2 else -1
+        for cell in range(n_cells):
+            if any(group[cell].ndim != 2 or group[cell].shape != kinds[0][cell].shape or group[cell].shape[1] != width for group in kinds):
+                raise ValueError("every matrix is [batches][S] with one S, the four of a cell of one shape")
+        windows = np.ascontiguousarray(windows, dtype=np.int64)
+        if windows.ndim != 2 or windows.shape[1] != 4:
+            raise ValueError("windows is [n][4]: cell, row_begin, row_end, pairwise_begin")
+        S = width if S is None else int(S)
+        b_arr = np.asarray([len(m) for m in kinds[0]] if batch_counts is None else batch_counts, dtype=np.int64)
+        pointers = [(C.c_void_p * n_cells)(*[m.ctypes.data for m in group]) for group in kinds]
+        n = len(windows)
+        totals = np.zeros((n, len(ROOT_WINDOW_TOTALS), max(S, 0)), dtype=np.int64)
+        sums = np.zeros((n, len(ROOT_WINDOW_SUMS), max(S, 0)), dtype=np.float64)
+        self._check(self._lib.fk_root_window_estimates(self._ctx, n_cells, _p(b_arr), pointers[0], pointers[1], pointers[2], pointers[3], S, n,
+                                                       _p(windows), _p(totals), _p(sums)))
+        out = {name: totals[:, i, :] for i, name in enumerate(ROOT_WINDOW_TOTALS)}
+        out.update({name: sums[:, i, :] for i, name in enumerate(ROOT_WINDOW_SUMS)})
         return out
 
     def debug_dice_state(self, state: np.ndarray, sizes):

@@ -122,6 +122,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "DIR/root_stability/ (default: roots_<a>_<b> beside the first results root).  Settings: "
                          "screening.bootstrap_replicates, candidate_contribution_size, practical_delta_by_k, delta_across_k, "
                          "robustness.delta_seed_stability, robustness.joint_discrepancy_alpha, k_aggregation")
+    rs.add_argument("--diagnostics", action="store_true",
+                    help="Also write the stage's other eight frames beside the three: performance_root_combination_<k>p.parquet per player "
+                         "count, performance_root_combination_across_k, root_rank_stability, root_top_n_stability, root_control_movement, "
+                         "root_shortlist_changes, root_matched_count_convergence and root_half_drift (further settings: screening.controls, "
+                         "robustness.matched_count_fractions, resources.stage_batch_bytes.performance).  All estimates then come from "
+                         "one window call on the device")
     rr = sub.add_parser("round-robin", help="Head-to-head round robin: every pair of the strategy table, both seat orders, per root")
     size = rr.add_mutually_exclusive_group(required=True)
     size.add_argument("--block-games", type=int, metavar="N",
@@ -229,7 +235,7 @@ def main(argv: Sequence[str] | None = None) -> None:
         watch_tournament_game(strategies, cfg.sim.seed, args.players, args.shuffle, args.game)
         return
     if args.command == "root-stability":
-        written = runner.run_root_stability(cfg, args.root_results, out=args.out)
+        written = runner.run_root_stability(cfg, args.root_results, out=args.out, diagnostics=args.diagnostics)
         print({name: str(path) for name, path in written.items()})
         return
     if args.command == "round-robin":

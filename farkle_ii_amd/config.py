@@ -361,6 +361,34 @@ class AppConfig:
         return {"delta_seed_stability": threshold, "joint_discrepancy_alpha": alpha, "k_aggregation_method": method,
                 "declared_k_weights": None if declared is None else {int(k): float(v) for k, v in dict(declared).items()}}
 
+    def root_stability_diagnostic_settings(self) -> dict:
+        """What the stage's eight diagnostic frames read beside ``root_stability_settings``: ``robustness.matched_count_fractions``
+        (config.py:203, default ``(0.25, 0.5, 0.75, 1.0)``, validated like :1982-1992), ``resources.stage_batch_bytes["performance"]``
+        (:435-446: 16 MiB; a configured mapping without the stage falls back to its ``analysis`` entry, as the reference reads it —
+        the budget decides the column chunks and with them the summation order) and ``screening.controls``."""
+        robustness = self.opaque.get("robustness") or {}
+        raw = robustness.get("matched_count_fractions", (0.25, 0.5, 0.75, 1.0))
+        if isinstance(raw, str):  # a --set override of an opaque section arrives as text
+            raw = [part for part in raw.replace("[", " ").replace("]", " ").replace(",", " ").split()]
+        try:
+            fractions = tuple(float(v) for v in raw)
+        except (TypeError, ValueError):
+            fractions = ()
+        if not fractions or any(not 0.0 < f <= 1.0 for f in fractions) or tuple(sorted(set(fractions))) != fractions or fractions[-1] != 1.0:
+            raise ValueError("robustness.matched_count_fractions must be unique increasing values in (0, 1] ending at 1")
+        budgets = (self.opaque.get("resources") or {}).get("stage_batch_bytes")
+        if budgets is None:
+            budget = 16 * 1024 * 1024
+        else:
+            if not isinstance(budgets, dict) or not budgets or any(
+                    not isinstance(stage, str) or not stage or isinstance(value, bool) or not isinstance(value, int) or value < 1
+                    for stage, value in budgets.items()):
+                raise ValueError("resources.stage_batch_bytes must contain positive integer stage budgets")
+            if "performance" not in budgets and "analysis" not in budgets:
+                raise ValueError("resources.stage_batch_bytes names neither the performance nor the analysis stage")
+            budget = int(budgets.get("performance", budgets.get("analysis")))
+        return {"matched_count_fractions": fractions, "stage_batch_bytes": budget, "controls": [int(c) for c in self.screening.controls]}
+
     def game_stats_path(self, n: int) -> Path:
         return self.n_dir(n) / f"{n}p_game_stats.parquet"
 

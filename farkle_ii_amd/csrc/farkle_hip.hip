@@ -23,6 +23,7 @@
 #include "fk_agreement.h"      // device side: method agreement of a round robin (pair codes and their counts, Kendall's pair counts)
 #include "fk_power_plan.h"     // device side: exact power of the round robin's score test per (sample size, scenario) cell
 #include "fk_performance.h"    // device side: performance stage's point estimates (by-k column sums in NumPy's order, across-k sums, Pareto front, maximin)
+#include "fk_root_windows.h"   // device side: two-root stability stage's window estimates (sequential column walk with snapshots, NumPy's pairwise order for width-1 chunks)
 #include "fk_plan.h"           // host side: the game kernel's instance table and launch planner
 #include "fk_layouts.h"        // host side: the composite device buffers' layouts
 #include "fk_buffers.h"        // host side: the typed, owning device buffer and the named buffer groups of the analysis entries
@@ -267,6 +268,8 @@ struct fk_ctx {
     BootBufs boot;
     PerformanceBufs pf;
     int64_t performance_grid = 0;        // option "performance_grid": > 0 caps the workgroups of the performance kernels (tests drive the grid strides)
+    RootWindowBufs rw;
+    int64_t root_windows_grid = 0;       // option "root_windows_grid": > 0 caps the workgroups of the window kernels (tests drive the task strides)
     int64_t bootstrap_block = 0;         // option "bootstrap_block": > 0 caps the replicates of one device block (tests drive the block carry)
     bool ran_hc = false;       // the current tournament call launched the hot / cold kernel
     int32_t perm_split = -1;   // -1 auto, 0 one-kernel Fisher-Yates, 1 draws + serial swap chains, 2 draws + chain-free kernel
@@ -1654,6 +1657,7 @@ int fk_get_option(fk_ctx *c, const char *name, int64_t *value) {
     else if (n == "rr_keep_roots") *value = c->ri_keep_roots ? 1 : 0;
     else if (n == "agreement_grid") *value = c->agreement_grid;
     else if (n == "performance_grid") *value = c->performance_grid;
+    else if (n == "root_windows_grid") *value = c->root_windows_grid;
     else return fail(c, FK_ERR_ARG, "fk_get_option: unknown option %s", name);
     return FK_OK;
 }
@@ -1696,6 +1700,7 @@ int fk_set_option(fk_ctx *c, const char *name, int64_t value) {
     else if (n == "census_chunk_games") c->census_chunk_games = std::max<int64_t>(value, 0);
     else if (n == "agreement_grid") c->agreement_grid = std::max<int64_t>(value, 0);
     else if (n == "performance_grid") c->performance_grid = std::max<int64_t>(value, 0);
+    else if (n == "root_windows_grid") c->root_windows_grid = std::max<int64_t>(value, 0);
     else if (n == "rr_window_blocks") {
         if (value < 2 || value > ((int64_t)1 << 22) || (value & 1))
             return fail(c, FK_ERR_ARG, "rr_window_blocks must be even and in [2, 2^22] (a pair's two blocks share a window)");
@@ -4756,6 +4761,136 @@ int fk_performance_across_k(fk_ctx *c, int32_t n, int32_t d, const double *delta
     std::copy(worst.begin(), worst.end(), worst_index);
     std::copy(member.begin(), member.end(), pareto_member);
     *leader_row = (int32_t)leader_found;
+    return FK_OK;
+}
+
+static_assert(fkl::RootWindowOut::N_TOTALS == fkw::N_TOTALS && fkl::RootWindowOut::N_SUMS == fkw::N_SUMS, "fk_layouts.h and fk_root_windows.h agree");
+
+// workgroups of a window kernel over `tasks` wave tasks: option "root_windows_grid" caps them, the kernels stride
+static unsigned root_windows_grid(fk_ctx *c, uint64_t tasks) {
+    uint64_t grid = std::min<uint64_t>(std::max<uint64_t>(tasks, 1), fkw::MAX_GRID);
+    if (c->root_windows_grid > 0) grid = std::min<uint64_t>(grid, (uint64_t)c->root_windows_grid);
+    return (unsigned)grid;
+}
+
+int fk_root_window_estimates(fk_ctx *c, int32_t n_cells, const int64_t *batch_counts, const int64_t *const *wins, const int64_t *const *exposures,
+                             const int64_t *const *completed, const int64_t *const *safety, int32_t S, int64_t n_windows, const int64_t *windows,
+                             int64_t *totals, double *sums) {
+    if (!c) return FK_ERR_ARG;
+    if (n_cells < 1 || n_cells > FK_ROOT_WINDOW_MAX_CELLS) return fail(c, FK_ERR_ARG, "n_cells = %d: 1 to %d cells", n_cells, FK_ROOT_WINDOW_MAX_CELLS);
+    if (S < 1 || S > (1 << 24)) return fail(c, FK_ERR_ARG, "S must be in [1, 2^24]");
+    if (n_windows < 1 || n_windows > ((int64_t)1 << 24)) return fail(c, FK_ERR_ARG, "n_windows = %lld: 1 to 2^24 windows", (long long)n_windows);
+    if (!batch_counts || !wins || !exposures || !completed || !safety || !windows) return fail(c, FK_ERR_ARG, "the cells' matrices and the windows are required");
+    if (!totals || !sums) return fail(c, FK_ERR_ARG, "totals and sums are required");
+    for (int32_t i = 0; i < n_cells; ++i) {
+        if (batch_counts[i] < 1 || batch_counts[i] > 0x7fffffffll)
+            return fail(c, FK_ERR_ARG, "cell %d: B = %lld: a batch matrix has 1 to 2^31 - 1 batches", i, (long long)batch_counts[i]);
+        if (!wins[i] || !exposures[i] || !completed[i] || !safety[i]) return fail(c, FK_ERR_ARG, "cell %d: the four count matrices are required", i);
+    }
+    const size_t nS = (size_t)S;
+    std::vector<std::vector<int64_t>> bounds((size_t)n_cells); // per cell: the rows at which a window begins or ends
+    for (int64_t i = 0; i < n_windows; ++i) {
+        const int64_t cell = windows[4 * i], begin = windows[4 * i + 1], end = windows[4 * i + 2], pairwise = windows[4 * i + 3];
+        if (cell < 0 || cell >= n_cells) return fail(c, FK_ERR_ARG, "window %lld: cell %lld of %d", (long long)i, (long long)cell, n_cells);
+        if (begin < 0 || end <= begin || end > batch_counts[cell])
+            return fail(c, FK_ERR_ARG, "window %lld: rows [%lld, %lld) of a cell with %lld batches: root stability matrix slice is empty or invalid",
+                        (long long)i, (long long)begin, (long long)end, (long long)batch_counts[cell]);
+        if (pairwise < 0 || pairwise > S) return fail(c, FK_ERR_ARG, "window %lld: pairwise_begin = %lld outside [0, %d]", (long long)i, (long long)pairwise, S);
+        bounds[(size_t)cell].push_back(begin), bounds[(size_t)cell].push_back(end);
+    }
+    // the reference's matrix checks (_validate_matrix_array :134-160) over every cell, and the exposure prefix of every column at every window
+    // boundary: a window's column total is a difference of two of them (the scope's support check, :442-443), before anything is uploaded
+    const uint64_t limit = (uint64_t)1 << 62;
+    std::vector<std::vector<uint64_t>> prefix((size_t)n_cells); // [boundary][S]
+    for (int32_t ci = 0; ci < n_cells; ++ci) {
+        std::vector<int64_t> &bd = bounds[(size_t)ci];
+        std::sort(bd.begin(), bd.end());
+        bd.erase(std::unique(bd.begin(), bd.end()), bd.end());
+        prefix[(size_t)ci].assign(bd.size() * nS, 0);
+        std::vector<uint64_t> support(nS, 0);
+        const int64_t *W = wins[ci], *E = exposures[ci], *D = completed[ci], *F = safety[ci];
+        size_t next = 0, at = 0;
+        for (int64_t b = 0; b <= batch_counts[ci]; ++b) {
+            if (next < bd.size() && bd[next] == b) std::copy(support.begin(), support.end(), prefix[(size_t)ci].begin() + (next++) * nS);
+            if (b == batch_counts[ci]) break;
+            for (size_t s = 0; s < nS; ++s, ++at) {
+                const int64_t w = W[at], e = E[at], done = D[at], f = F[at];
+                if (w < 0 || e < 0 || done < 0 || f < 0) return fail(c, FK_ERR_ARG, "cell %d: a negative count in batch row %lld, column %zu", ci, (long long)b, s);
+                if (w > done)
+                    return fail(c, FK_ERR_ARG, "cell %d: wins > completed in batch row %lld, column %zu: impossible win/exposure counts", ci, (long long)b, s);
+                if ((uint64_t)done + (uint64_t)f != (uint64_t)e)
+                    return fail(c, FK_ERR_ARG, "cell %d: exposures != completed + safety in batch row %lld, column %zu: attempted exposure conservation", ci,
+                                (long long)b, s);
+                if ((uint64_t)e > limit - support[s]) return fail(c, FK_ERR_ARG, "cell %d: the exposure total of column %zu passes 2^62", ci, s);
+                support[s] += (uint64_t)e;
+            }
+        }
+    }
+    for (int64_t i = 0; i < n_windows; ++i) {
+        const size_t ci = (size_t)windows[4 * i];
+        const std::vector<int64_t> &bd = bounds[ci];
+        const size_t lo = (size_t)(std::lower_bound(bd.begin(), bd.end(), windows[4 * i + 1]) - bd.begin());
+        const size_t hi = (size_t)(std::lower_bound(bd.begin(), bd.end(), windows[4 * i + 2]) - bd.begin());
+        const uint64_t *p_lo = prefix[ci].data() + lo * nS, *p_hi = prefix[ci].data() + hi * nS;
+        for (size_t s = 0; s < nS; ++s)
+            if (p_hi[s] == p_lo[s])
+                return fail(c, FK_ERR_ARG, "window %lld: root stability scope contains a strategy without positive exposure: column %zu", (long long)i, s);
+    }
+    // the windows in (cell, row_begin, row_end, position) order: a group per (cell, row_begin), its snapshots ascending
+    std::vector<int64_t> order((size_t)n_windows);
+    for (int64_t i = 0; i < n_windows; ++i) order[(size_t)i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+        for (int j = 0; j < 3; ++j)
+            if (windows[4 * a + j] != windows[4 * b + j]) return windows[4 * a + j] < windows[4 * b + j];
+        return a < b;
+    });
+    std::vector<fkw::Group> groups;
+    std::vector<fkw::Snap> snaps((size_t)n_windows);
+    std::vector<fkw::PairTask> pairs;
+    for (size_t j = 0; j < order.size(); ++j) {
+        const int64_t *w = windows + 4 * order[j];
+        if (groups.empty() || groups.back().cell != (uint32_t)w[0] || groups.back().row_begin != w[1])
+            groups.push_back(fkw::Group{(uint32_t)w[0], (uint32_t)j, 0u, 0u, w[1]});
+        ++groups.back().count;
+        snaps[j] = fkw::Snap{w[2], (uint32_t)order[j], (uint32_t)w[3]};
+        if (w[3] < S) pairs.push_back(fkw::PairTask{(uint32_t)w[0], (uint32_t)order[j], (uint32_t)w[3], 0u, w[1], w[2]});
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    RootWindowBufs &b = c->rw;
+    const fkl::RootWindowCells stacked((size_t)n_cells, batch_counts, nS);
+    const fkl::RootWindowOut out((size_t)n_windows, nS);
+    if (const int rc = ensure_all(c, b.wins, stacked.n_i64, b.exposures, stacked.n_i64, b.completed, stacked.n_i64, b.safety, stacked.n_i64, b.cells,
+                                  (size_t)n_cells, b.groups, groups.size(), b.snaps, snaps.size(), b.pairs, std::max<size_t>(pairs.size(), 1), b.totals,
+                                  out.n_totals, b.sums, out.n_sums))
+        return rc;
+    std::vector<fkw::Cell> cells((size_t)n_cells);
+    for (int32_t ci = 0; ci < n_cells; ++ci) {
+        const size_t at = stacked.cell_at(batch_counts, (size_t)ci), bytes = (size_t)batch_counts[ci] * nS * 8;
+        cells[(size_t)ci] = fkw::Cell{b.wins.p + at, b.exposures.p + at, b.completed.p + at, b.safety.p + at, batch_counts[ci]};
+        HIPCHK(c, hipMemcpyAsync(b.wins.p + at, wins[ci], bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.exposures.p + at, exposures[ci], bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.completed.p + at, completed[ci], bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b.safety.p + at, safety[ci], bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(b.cells.p, cells.data(), cells.size() * sizeof(fkw::Cell), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.groups.p, groups.data(), groups.size() * sizeof(fkw::Group), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(b.snaps.p, snaps.data(), snaps.size() * sizeof(fkw::Snap), hipMemcpyHostToDevice, c->stream));
+    if (!pairs.empty()) HIPCHK(c, hipMemcpyAsync(b.pairs.p, pairs.data(), pairs.size() * sizeof(fkw::PairTask), hipMemcpyHostToDevice, c->stream));
+    const uint64_t column_blocks = ((uint64_t)S + fkw::COLUMN_BLOCK - 1) / fkw::COLUMN_BLOCK;
+    hipLaunchKernelGGL(fkw::fk_rw_walk_kernel, dim3(root_windows_grid(c, groups.size() * column_blocks)), dim3(fkw::COLUMN_BLOCK), 0, c->stream, b.cells.p,
+                       b.groups.p, b.snaps.p, (uint32_t)groups.size(), (uint32_t)S, b.totals.p, b.sums.p);
+    if (!pairs.empty())
+        hipLaunchKernelGGL(fkw::fk_rw_pairwise_kernel, dim3(root_windows_grid(c, pairs.size() * column_blocks)), dim3(fkw::COLUMN_BLOCK), 0, c->stream,
+                           b.cells.p, b.pairs.p, (uint32_t)pairs.size(), (uint32_t)S, b.sums.p);
+    HIPCHK(c, hipGetLastError());
+    // into the caller's arrays only once the stream has come through: a failed call leaves them as they were
+    std::vector<long long> h_totals(out.n_totals);
+    std::vector<double> h_sums(out.n_sums);
+    HIPCHK(c, hipMemcpyAsync(h_totals.data(), b.totals.p, out.n_totals * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_sums.data(), b.sums.p, out.n_sums * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::copy(h_totals.begin(), h_totals.end(), totals);
+    std::copy(h_sums.begin(), h_sums.end(), sums);
     return FK_OK;
 }
 

@@ -156,6 +156,15 @@ struct PerformanceBufs { // fk_performance_by_k, fk_performance_across_k
     Dev<uint8_t> member;     // across k: [n]
     Dev<ull> best;           // across k: the largest minimum's ordered key; behind it the leader row
 };
+struct RootWindowBufs { // fk_root_window_estimates
+    Dev<int64_t> wins, exposures, completed, safety; // the cells' [B][S] matrices, stacked in cell order (fkl::RootWindowCells)
+    Dev<fkw::Cell> cells;       // [n_cells]
+    Dev<fkw::Group> groups;     // the windows grouped by (cell, row_begin)
+    Dev<fkw::Snap> snaps;       // [n_windows] in group order, ascending row_end within a group
+    Dev<fkw::PairTask> pairs;   // the windows with pairwise columns
+    Dev<long long> totals;      // fkl::RootWindowOut: [n_windows][6][S]
+    Dev<double> sums;           // fkl::RootWindowOut: [n_windows][3][S]
+};
 struct ProbeBufs { // the fk_debug_* probes and fk_coordinate_seeds: the kernel's buffer arguments in their order, bytes
     Dev<uint8_t> a, b, c, d, e;
 };

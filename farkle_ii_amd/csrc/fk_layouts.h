@@ -42,6 +42,29 @@ struct RootParams {
           n(n_k + (joint ? 2 * n_k * S + 2 * S : 0)) {}
 };
 
+// fk_root_window_estimates: the cells' [B][S] matrices stacked in cell order (one such buffer per matrix kind).  Offsets in int64 units.
+struct RootWindowCells {
+    size_t n_cells, S, n_i64;
+    RootWindowCells(size_t n_cells, const int64_t *batch_counts, size_t S) : n_cells(n_cells), S(S), n_i64(0) {
+        for (size_t i = 0; i < n_cells; ++i) n_i64 += (size_t)batch_counts[i] * S;
+    }
+    size_t cell_at(const int64_t *batch_counts, size_t cell) const {
+        size_t at = 0;
+        for (size_t i = 0; i < cell; ++i) at += (size_t)batch_counts[i] * S;
+        return at;
+    }
+};
+
+// fk_root_window_estimates' outputs, on the device and at the caller alike: totals int64 [n_windows][6][S] = wins | exposures | completed
+// | safety | losses | positive batches, sums float64 [n_windows][3][S] = sum_w2 | sum_we | sum_e2.  Offsets in elements.
+struct RootWindowOut {
+    static constexpr size_t N_TOTALS = 6, N_SUMS = 3; // = fkw::N_TOTALS, fkw::N_SUMS (asserted where both are visible)
+    size_t S, n_totals, n_sums;
+    RootWindowOut(size_t n_windows, size_t S) : S(S), n_totals(n_windows * N_TOTALS * S), n_sums(n_windows * N_SUMS * S) {}
+    size_t total_at(size_t window, size_t which) const { return (window * N_TOTALS + which) * S; }
+    size_t sum_at(size_t window, size_t which) const { return (window * N_SUMS + which) * S; }
+};
+
 // fk_dominance_graph's bit matrices, rows of W = ceil(n / 64) words: adj [2][n][W] | adj_t [2][n][W] | reach [4][n][W] (the working
 // copies that are closed) | panel [4][64][W] | dstar [4][64].  Offsets in u64 units; adj .. reach is one contiguous run.
 struct DominanceMats {

@@ -1647,11 +1647,16 @@ ROOT_STABILITY_FILES = {"root_bootstrap_top_n_inclusion": "root_bootstrap_top_n_
                         "root_discrepancies": "root_discrepancies.parquet", "root_joint_discrepancy": "root_joint_discrepancy.parquet"}
 
 
-def run_root_stability(cfg: AppConfig, root_results: Sequence, out: Path | None = None, range_size: int | None = None) -> dict:
+def run_root_stability(cfg: AppConfig, root_results: Sequence, out: Path | None = None, range_size: int | None = None,
+                       diagnostics: bool = False, across_k: dict | None = None) -> dict:
     """``farkle root-stability``: the two-root stability stage's bootstrap families over the batch matrices two
     ``farkle run --performance-bootstrap`` trees left (``<results>/analysis/03_metrics/by_k/<k>p/performance_batch_matrix.npy`` for every
     player count of ``sim.n_players_list``): ``root_bootstrap_top_n_inclusion.parquet``, ``root_discrepancies.parquet`` and
-    ``root_joint_discrepancy.parquet`` under ``<out>/root_stability/``.  Returns ``{frame name: path}``."""
+    ``root_joint_discrepancy.parquet`` under ``<out>/root_stability/``.  ``diagnostics`` (``--diagnostics``): the stage's other eight
+    frames beside them — ``performance_root_combination_<k>p.parquet`` per player count, ``performance_root_combination_across_k``,
+    ``root_rank_stability``, ``root_top_n_stability``, ``root_control_movement``, ``root_shortlist_changes``,
+    ``root_matched_count_convergence`` and ``root_half_drift`` — from one ``Engine.root_window_estimates`` call, from which the
+    discrepancy chain then takes its estimates too (``across_k``: ``root_stability.diagnostic_tables``).  Returns ``{frame name: path}``."""
     from . import root_stability as rs
 
     directories = [Path(d) for d in root_results]
@@ -1687,13 +1692,18 @@ def run_root_stability(cfg: AppConfig, root_results: Sequence, out: Path | None 
         raise ValueError(f"two-root stability requires exactly two roots: both --root-results hold root {loaded[0][0]}")
     loaded.sort(key=lambda item: item[0])
     cells = rs.check_cells({(root, k): m for root, matrices in loaded for k, m in matrices.items()}, [root for root, _ in loaded], required)
-    tables = rs.root_stability_tables(get_engine(), cells, int(sc.bootstrap_replicates), int(sc.candidate_contribution_size),
-                                      sc.practical_delta_by_k, sc.delta_across_k, range_size=range_size, **settings)
+    if diagnostics:
+        tables = rs.root_stability_diagnostic_tables(get_engine(), cells, int(sc.bootstrap_replicates), int(sc.candidate_contribution_size),
+                                                     sc.practical_delta_by_k, sc.delta_across_k, range_size=range_size, across_k=across_k,
+                                                     **settings, **cfg.root_stability_diagnostic_settings())
+    else:
+        tables = rs.root_stability_tables(get_engine(), cells, int(sc.bootstrap_replicates), int(sc.candidate_contribution_size),
+                                          sc.practical_delta_by_k, sc.delta_across_k, range_size=range_size, **settings)
     target = (Path(out) if out is not None else directories[0].parent / f"roots_{cells.roots[0]}_{cells.roots[1]}") / "root_stability"
     target.mkdir(parents=True, exist_ok=True)
     written = {}
     for name, table in tables.items():
-        written[name] = target / ROOT_STABILITY_FILES[name]
+        written[name] = target / ROOT_STABILITY_FILES.get(name, f"{name}.parquet")  # (the eight diagnostic frames are named as their files)
         _write_parquet_atomic(table, written[name])
     return written
 

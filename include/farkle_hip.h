@@ -1021,6 +1021,34 @@ int fk_performance_by_k(fk_ctx *ctx, int32_t k, int64_t B, int32_t S, const int6
 int fk_performance_across_k(fk_ctx *ctx, int32_t n, int32_t d, const double *deltas, const double *variances, double *delta_sum,
                             double *variance_sum, double *minimum, int32_t *worst_index, uint8_t *pareto_member, int32_t *leader_row);
 
+/* The two-root stability stage's estimates over row windows of its cells, as far as they are sums over batches
+ * (analysis/root_stability.py: _estimate_matrix_cells :411-433, which _scope_estimates, _matched_count_convergence :1429-1513 and
+ * _half_drift :1516-1628 call for the full cells, for prefixes and for halves).  One call takes all windows of a stage.
+ * Inputs: n_cells cells (1 to FK_ROOT_WINDOW_MAX_CELLS), each with batch_counts[cell] rows and four row-major int64
+ * [batch_counts[cell]][S] matrices wins / exposures / completed / safety, unprojected, as fk_performance_by_k takes them; S strategy
+ * columns, the same for every cell.  windows: int64 [n_windows][4] = (cell, row_begin, row_end, pairwise_begin) per window: rows
+ * [row_begin, row_end) of the cell; pairwise_begin in [0, S] is the first column whose float sums take NumPy's pairwise order, because
+ * the reference's column chunking (chunk = max(1, min(S, max_bytes // max(1, rows * 57)))) leaves it in a chunk of width 1
+ * (farkle_ii_amd/root_stability.py: window_pairwise_begin).  Windows may repeat and overlap in any way.
+ * Outputs (caller-owned host memory, both required):
+ *   totals   int64 [n_windows][6][S]: the column sums of wins, exposures, completed, safety; losses = exposures - wins; positive_batches
+ *            = rows with exposures > 0
+ *   sums     float64 [n_windows][3][S]: sum(w * w), sum(w * e), sum(e * e) over the window's rows, w and e the row's counts as doubles
+ *            (a row without an exposure adds 0.0).  Columns below pairwise_begin: 0.0, then one addition per row in ascending row order
+ *            (np.sum(axis=0) over a chunk of two or more columns).  Columns from pairwise_begin: np.add.reduce over the window's rows as a
+ *            vector (csrc/fk_performance.h: np_add_reduce).  Every product and every addition is a separate IEEE operation.
+ * Windows of one cell with one row_begin share one pass over the rows (snapshots of the running sums), which changes no bit.  No result
+ * depends on the launch shape (option "root_windows_grid" > 0 caps the workgroups).
+ * FK_ERR_ARG before any device work, with the outputs untouched: a null pointer, n_cells outside [1, FK_ROOT_WINDOW_MAX_CELLS], n_windows
+ * < 1, S outside [1, 2^24], a cell with B < 1 or B > 2^31 - 1, a window of an unknown cell, empty or reaching beyond its cell,
+ * pairwise_begin outside [0, S], a negative count, wins > completed, exposures != completed + safety, a column total of a cell beyond 2^62,
+ * a window in which some column's total exposure is <= 0 (the reference's ValueError "root stability scope contains a strategy without
+ * positive exposure"). */
+#define FK_ROOT_WINDOW_MAX_CELLS 256
+int fk_root_window_estimates(fk_ctx *ctx, int32_t n_cells, const int64_t *batch_counts, const int64_t *const *wins,
+                             const int64_t *const *exposures, const int64_t *const *completed, const int64_t *const *safety, int32_t S,
+                             int64_t n_windows, const int64_t *windows, int64_t *totals, double *sums);
+
 #ifdef __cplusplus
 }
 #endif
