@@ -1220,7 +1220,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         // does not play rolls from whatever its record address holds: a lane that was never dealt a game has increment 0 and reads the
         // block's first record, which may be LDS nobody has written; state 0 with increment 0 is a fixed point whose output is
         // rejected every time.  Without the replay such a lane's roll is straight-line code on in-range table keys.)
-        if (PK2 ? in_lanes(lanes(detour) & m_active) : detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
+        // (PK2, round 14: the replay sits behind a wave-uniform, unlikely test of its lane mask, so the compiler places the block — some
+        // 150 lines with its two nested loops — out of line and the trip falls through a scalar branch that is not taken, where it took an
+        // s_cbranch_execz over the block in every trip.  The forced-detour test build is right with the hint and slow, as it is meant to be.)
+        lanes_t replaying = 0;
+        if constexpr (PK2) replaying = lanes(detour) & m_active;
+        if (PK2 ? (__builtin_expect(replaying != 0, 0) && in_lanes(replaying)) : detour) { // a Lemire rejection (once in ~2^30 dice): the generator comes back from the seat record, which is still the roll's input
             asm volatile("" ::: "memory"); // really re-read it: values forwarded from the loads above would stay live across the whole roll
             if (PK2) { // (F_LO0 ... F_BUF are the first five dwords of a lean record)
                 const uint32_t *r0 = reinterpret_cast<const uint32_t *>(rec);
@@ -1262,7 +1267,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
             // a farkle to wrap, and the value only feeds clamped table keys and compares whose outcome the masks drop).  All three are set
             // again where the lane is dealt a game.
             const lanes_t raised = (lanes(rolls_before >= RG_TURN_ROLLS) | lanes(rg.turn_score >= (int32_t)(RG_TURN50 + 1u))) & m_active;
-            if (in_lanes(raised)) raise(rolls_before >= RG_TURN_ROLLS ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
+            if (__builtin_expect(raised != 0, 0)) { // out of line, like the replay: the block holds a global atomic and no trip of a sound call enters it
+                if (in_lanes(raised)) raise(rolls_before >= RG_TURN_ROLLS ? FK_ERR_ROLL_LIMIT : FK_ERR_COUNTER_OVERFLOW);
+            }
             const lanes_t ok = m_active & ~raised;
             if (in_lanes(ok)) {
                 cE ^= hb_flip;
@@ -1603,11 +1610,23 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
         if constexpr (!decltype(flat)::value) return handover_due_general(waiting, active);
         else return waiting && (!active || (uint32_t)__popcll(waiting) >= ho_thr || (exhausted && pool_next != pool_end));
     };
+    // Round 14, the two-seat lean instances: one loop-control decision per trip.  Inside the roll loop the masks change only on a trip in
+    // which a lane's game ended or a lane raised, and every such lane leaves m_active (advance2; the sample point) — so while m_active
+    // equals `tested`, its value at the last full test that found no hand-over due, handover_due has the inputs it had then (m_ended
+    // changes only with m_active; ho_thr, `exhausted` and the ticket pool only in a hand-over) and a trip goes round on one scalar
+    // compare.  The full test runs on a trip that changed m_active, and after the first trip behind a flat hand-over that left ended lanes
+    // (dealt games with max_rounds 0): there `tested` starts as a value m_active cannot take, because that hand-over falls through into
+    // the loop without a test of its own, and the rule has always tested after that trip whatever it changed.  An entry without a hand-over
+    // has just found none due.  The `if (m_active)` in front of every roll is the loop's entry test now: a hand-over after which nobody
+    // plays goes back to the outer loop's head, as it did before after one trip without a roll (guard_trips now counts played trips
+    // only, so a sample point comes every RG_SAMPLE_TRIPS-th PLAYED trip: fk_device.h's argument is about those).  The sampled guards sit
+    // behind an unlikely test, out of line like roll_step's two rare blocks: the hot trip falls through to its one taken branch, the back edge.
     auto play = [&](auto flat) {
         while (true) {
             uint64_t waiting = PK2 ? (fresh ? __ballot(true) : m_ended) : __ballot(st == ST_FRESH || st == ST_ENDED);
             uint64_t active = PK2 ? m_active : __ballot(st == ST_ACTIVE);
             if (!(waiting | active)) break; // no lane is active and none waits: the wave has drained
+            bool flat_handed = false; // (PK2) the flat path has just handed over and falls through: nothing has tested the masks it left
             if (handover_due(waiting, active, flat)) {
 #ifdef FK_COUNT_HANDOVER
                 cnt_handovers += 1u, cnt_served += (uint32_t)__popcll(waiting);
@@ -1618,37 +1637,44 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(WPE))) vo
                 // — eighteen copies in front of the served region, eighteen behind it, thirteen on the edge into the roll loop, for every
                 // lane.  A trip in which nobody plays (every dealt game had max_rounds 0, or no ticket was left) costs one ballot.
                 if constexpr (!decltype(flat)::value) continue;
+                flat_handed = true;
 #ifdef FK_COUNT_HANDOVER // (the first trip's counts are of the lanes as the hand-over left them, as after the general copy's `continue`)
                 if constexpr (PK2) waiting = m_ended, active = m_active;
                 else waiting = __ballot(st == ST_FRESH || st == ST_ENDED), active = __ballot(st == ST_ACTIVE);
 #endif
             }
-            bool playing = !PK2 && st == ST_ACTIVE; // (PK2: the masks, not a lane predicate, say who plays)
-            do {
+            if constexpr (PK2) {
+                lanes_t tested = flat_handed ? (m_active | m_ended) : m_active; // (m_ended and m_active are disjoint)
+                if (m_active) {
+                    do {
 #ifdef FK_COUNT_HANDOVER
-                cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(waiting), cnt_rolling += (uint32_t)__popcll(active);
+                        cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(m_ended), cnt_rolling += (uint32_t)__popcll(m_active);
 #endif
-                if constexpr (PK2) {
-                    if (m_active) roll_step(); // a scalar branch: the whole wave rolls, the masks say for whom (roll_step)
-                } else if (playing) {
-                    roll_step();
-                }
-                if constexpr (GUARD_SAMPLED) {
-                    guard_trips += 1u;
-                    if ((guard_trips & (RG_SAMPLE_TRIPS - 1u)) == 0u) {
-                        lane_raised = false;
-                        sample_guards();
-                        m_active &= ~lanes(lane_raised);
-                    }
-                }
-                if constexpr (PK2) {
-                    waiting = m_ended, active = m_active;
+                        roll_step(); // the whole wave rolls, the masks say for whom (roll_step)
+                        guard_trips += 1u;
+                        if (__builtin_expect((guard_trips & (RG_SAMPLE_TRIPS - 1u)) == 0u, 0)) {
+                            lane_raised = false;
+                            sample_guards();
+                            m_active &= ~lanes(lane_raised);
+                        }
+                    } while (__builtin_expect(m_active == tested, 1) || (m_active && !handover_due(m_ended, m_active, flat) && ((tested = m_active), true)));
                 } else {
+#ifdef FK_COUNT_HANDOVER // (counted as the trip without a roll that it was before round 14)
+                    cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(m_ended);
+#endif
+                }
+            } else {
+                bool playing = st == ST_ACTIVE;
+                do {
+#ifdef FK_COUNT_HANDOVER
+                    cnt_trips += 1u, cnt_waiting += (uint32_t)__popcll(waiting), cnt_rolling += (uint32_t)__popcll(active);
+#endif
+                    if (playing) roll_step();
                     playing = st == ST_ACTIVE;
                     waiting = __ballot(st == ST_ENDED);
                     active = __ballot(playing);
-                }
-            } while (active && !handover_due(waiting, active, flat));
+                } while (active && !handover_due(waiting, active, flat));
+            }
         }
     };
     // The two-seat lean instance holds the loop nest twice, and a launch runs one of them: with the flat hand-over, or — a chunk too large

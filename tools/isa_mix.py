@@ -64,7 +64,9 @@ def roll_loop(body):
         blocks.append((name, ann, ins))
     best, best_n = None, -1
     for h, a, _ in blocks:
-        if "Loop Header: Depth=2" not in a:
+        # (round 14: Depth=2 or deeper — the two-seat block instance's roll loop sits inside a Depth=2 loop of its own full hand-over test;
+        # the rule for what belongs to a loop is unchanged, so the figures stay comparable with the earlier rounds')
+        if not re.search(r"Loop Header: Depth=[2-9]", a):
             continue
         members = [b for b in blocks if b[0] == h or re.search(rf"(Header=|Parent Loop ){h}\b", b[1])]
         ops = Counter(o for b in members for o in b[2])
